@@ -23,13 +23,16 @@ Workload (config.workload names it):
 `python bench.py --gpus N` with N > 1 and no launcher (WORLD_SIZE unset) re-executes itself under torch.distributed.run with
 N ranks on 127.0.0.1, so the driver's command line works for every N.  Before the counted --warmup steps the headline
 kernel is pre-warmed by TIME (launches of this kernel get faster for the first 20-30 ms of back-to-back execution:
-clock / power management settling), reported as `prewarm_ms`.  At N > 1 rank 0 first measures `per_gpu_single`: the SAME
-per-GPU load (131 072 runs) on one GPU with the other ranks idle, so that scaling efficiency compares like with like.
+clock / power management settling), reported as `prewarm_ms`.  With --full at N > 1, rank 0 first measures `per_gpu_single`:
+the SAME per-GPU load (131 072 runs) on one GPU with the other ranks idle, so that scaling efficiency compares like with like.
 
-The JSON line (rank 0) also carries, measured in the same process after the timed region (N = 1 only):
-  roofline             dominant kernel: algorithmic bytes / HIP-event launch time, vs 8 TB/s; `traffic` = HBM bytes per
-                       launch from rocprofv3 PMC passes (WRITE_SIZE, FETCH_SIZE x 2 on gfx950) run live on this build,
-                       or from profiles/pmc_traffic.json when that file carries this build's library hash, else null
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR) and prints the line:
+  roofline             dominant kernel: algorithmic bytes / HIP-event time of the timed launches, vs 8 TB/s; `traffic` = HBM
+                       bytes per launch from profiles/pmc_traffic.json when that file carries this build's library hash, else null
+With --full the line also carries, measured in the same process after the timed region (N = 1 only):
+  roofline.traffic     from rocprofv3 PMC passes (WRITE_SIZE, FETCH_SIZE x 2 on gfx950) run live on this build (--pmc live)
+  headline_again       the K timed steps once more, a few seconds later
+  roofline_asis        the same launches with the other placement of the output planes (roofline_placed after --placement asis)
   configs[]            the other BASELINE configurations as legs: C3 (long_drive @200 Hz, 262 144 runs, stats-only),
                        C4's per-GPU share, C5 fp32, Allan end-to-end (3600 s @ 400 Hz), the mechanisation alone, and C2 in a
                        vibration environment (random; PSD arrays)
@@ -490,6 +493,36 @@ def leg_sim_e2e(workloads):
     return out
 
 
+DUMP_BYTES = 48_000_000      # --dump-outputs: all files together
+DUMP_END_BYTES = 8_000_000   # of which the end-point errors (a seeded sample of the runs beyond this)
+
+
+def dump_outputs(d, job, merged, keep):
+    """What the timed path computed in its last step, as a caller receives it, to d/<name>.npy (float64): the merged end-point
+    statistics of the step (count, mean, std, max|e| of att3 pos3 vel3), the (runs, 9) end-point errors of the batch and, when
+    the series are materialised, accel / gyro / att / pos / vel (k, n, 3) of k runs drawn with a fixed seed.  Run ids are the
+    batch's global ids.  The same arguments give the same inputs and the same sample."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    R, n = job.runs, job.n
+    first = int(job.params.run_offset)
+    out = {'stats_count': np.array([merged.count]), 'stats_mean': merged.mean, 'stats_std': merged.std, 'stats_maxabs': merged.maxabs}
+    end = job.end_errors('free')
+    rows = min(R, DUMP_END_BYTES // (9 * 8))
+    ids = np.arange(R) if rows == R else np.sort(rng.choice(R, rows, replace=False))
+    out['end_errors'], out['end_errors_run_ids'] = end[ids], first + ids
+    if keep:
+        left = DUMP_BYTES - sum(np.asarray(v).size * 8 for v in out.values()) - (1 << 20)
+        k = int(max(1, min(R, left // (8 * (15 * n + 1)))))
+        ids = np.sort(rng.choice(R, k, replace=False))
+        out['series_run_ids'] = first + ids
+        out['accel'], out['gyro'] = job.sensors('accel', ids), job.sensors('gyro', ids)
+        out['att'], out['pos'], out['vel'] = job.trajectories('free', ids)
+    for name, v in out.items():
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -511,16 +544,17 @@ def main():
     ap.add_argument('--ref-frame', type=int, default=1)
     ap.add_argument('--stats-only', action='store_true', help='do not materialise sensors/trajectories')
     ap.add_argument('--precision', choices=['f64', 'f32'], default='f64', help="f32 = BASELINE config 5's single-precision kernel")
-    ap.add_argument('--cpu-baseline-seconds', type=float, default=12.0, help='0 disables the CPU baseline leg')
-    ap.add_argument('--no-legs', action='store_true', help='skip the configs[] legs (C3, C4 share, C5, Allan, mechanisation)')
+    ap.add_argument('--cpu-baseline-seconds', type=float, default=12.0, help='--full: 0 disables the CPU baseline leg')
+    ap.add_argument('--no-legs', action='store_true', help='--full: skip the configs[] legs (C3, C4 share, C5, Allan, mechanisation)')
     ap.add_argument('--placement', choices=['placed', 'asis'], default='placed',
                     help="placed (the library's default, what an unconfigured Sim gets): the materialised series are carved from the "
                          "device's placed arena (ABI 7: stripes cycling through the three classes of physical memory); asis: plain "
                          "hipMalloc, wherever the driver puts the planes.  Either way the line carries BOTH rooflines (N = 1): "
                          "`roofline` for --placement, `roofline_asis` / `roofline_placed` for the other one, same process")
-    ap.add_argument('--no-repeat', action='store_true', help='N = 1: do not time the K steps a second time (headline_again)')
+    ap.add_argument('--no-repeat', action='store_true', help='--full, N = 1: do not time the K steps a second time (headline_again)')
     ap.add_argument('--pmc', choices=['live', 'file', 'off'], default='live',
-                    help='roofline.traffic: rocprofv3 PMC passes of this build (live), the stamped profiles/pmc_traffic.json, or null')
+                    help='roofline.traffic: rocprofv3 PMC passes of this build (live; a run without --full reads the file instead), '
+                         'the stamped profiles/pmc_traffic.json, or null')
     ap.add_argument('--pmc-child', action='store_true', help='internal: the short workload the live PMC passes profile')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend for N > 1 (nccl = RCCL; gloo only for tests)')
     ap.add_argument('--exchange', choices=['abi', 'torch'], default=None,
@@ -531,9 +565,18 @@ def main():
                          'the RCCL code path: communicator set-up, device-tensor all-reduce, non-blocking work handles)')
     ap.add_argument('--shared-device', action='store_true',
                     help='TEST ONLY: every rank uses GPU 0 (exercises the N > 1 control flow on a one-GPU box)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: live PMC passes, the repeated timed region, the other placement, the '
+                         'configs[] legs, the CPU baselines (N = 1) and per_gpu_single (N > 1).  Without it a run sets up, warms '
+                         'up, times the K steps, writes --dump-outputs and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64, at most 48 MB): "
+                         "the merged end-point statistics, the end-point errors of the batch and a fixed, seeded sample of its "
+                         "runs' sensor and trajectory series")
     args = ap.parse_args()
     if args.pmc_child:
         args.steps, args.warmup, args.cpu_baseline_seconds, args.no_legs, args.pmc, args.no_repeat = 3, 1, 0.0, True, 'off', True
+        args.dump_outputs = None
 
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -699,7 +742,7 @@ def main():
     # N > 1: the same per-GPU load on ONE GPU at a time while the other ranks wait -- the reference point scaling efficiency
     # needs, from EVERY rank (a slow GPU shows up here before it shows up as the step time of the whole job)
     single = None
-    if use_dist and world > 1:
+    if use_dist and world > 1 and args.full:
         mine = None
         for turn in range(world):
             fence()
@@ -761,11 +804,13 @@ def main():
 
     kern_ms = [ctx.event_elapsed(2 * (s // stride), 2 * (s // stride) + 1) for s in range(args.warmup, nsteps) if s % stride == 0]
     kern_avg_ms = float(np.mean(kern_ms))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, job, merged, keep)
 
     # The same timed region ONCE MORE in this process, a few seconds later (N = 1): how much of the run-to-run spread of this
     # store-bound kernel is the box and how much is the moment.  `value` stays the first region (the K steps the contract names).
     again = None
-    if world == 1 and not args.pmc_child and not args.no_repeat:
+    if world == 1 and args.full and not args.pmc_child and not args.no_repeat:
         time.sleep(3.0)
         spent, done = 0.0, 0
         while spent < WARM_MS and done < 64:
@@ -788,7 +833,7 @@ def main():
     # The SAME launches with the other placement, same process (N = 1): plain hipMalloc planes when the headline ran placed, placed
     # planes when it ran --placement asis.  K launches back to back after the same time-based pre-warm, HIP events around each.
     other = None
-    if world == 1 and keep and not args.pmc_child and not args.shared_device:
+    if world == 1 and keep and args.full and not args.pmc_child and not args.shared_device:
         want_placed = args.placement == 'asis'
         saved = (ctx.placed_enabled, ctx.placed_note)
         if want_placed:
@@ -849,7 +894,7 @@ def main():
         given_name = 'ginsim::mc_kernel<%d, 1, true, false, 0, false>' % rf
         traffic, traffic_source, pmc = None, None, None
         if world == 1 and args.precision == 'f64' and keep:
-            if args.pmc == 'live':
+            if args.pmc == 'live' and args.full:
                 pmc = pmc_live()
                 traffic = pmc_traffic(pmc, [k for k in (pmc or {}) if 'mc_kernel' in k])
                 traffic_source = 'live: rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE passes of `bench.py --pmc-child` on this build'
@@ -916,7 +961,7 @@ def main():
             out.update(rccl_seen)
         if per_rank is not None:
             out['per_rank'] = per_rank
-        if world == 1 and not args.no_legs:
+        if world == 1 and args.full and not args.no_legs:
             legs = []
 
             if keep and args.precision == 'f64':
@@ -956,7 +1001,7 @@ def main():
             legs.append(leg_allan(ginsim, workloads, ctx, pmc=pmc))
             legs.append(leg_sim_e2e(workloads))
             out['configs'] = legs
-        if world == 1 and args.cpu_baseline_seconds > 0:
+        if world == 1 and args.full and args.cpu_baseline_seconds > 0:
             out['cpu_baseline'] = cpu_baseline(fs, rf, ini, truth, acc, gyr, args.cpu_baseline_seconds)
         print(json.dumps(out), flush=True)
 

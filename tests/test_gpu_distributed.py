@@ -54,7 +54,8 @@ def test_bench_starts_itself_for_n_gt_1():
     """`python bench.py --gpus 2 ...` with NO launcher in front (the form of the driver's command): the script re-executes itself
     under torch.distributed.run with two ranks; the N > 1 line carries per_gpu_single (rank 0 alone on the same per-GPU load)
     and the time-based pre-warm."""
-    common = ['--steps', '3', '--warmup', '1', '--runs-per-gpu', '8192', '--cpu-baseline-seconds', '0', '--no-legs', '--pmc', 'off']
+    common = ['--steps', '3', '--warmup', '1', '--runs-per-gpu', '8192', '--cpu-baseline-seconds', '0', '--no-legs', '--pmc', 'off',
+              '--full']
     two = _bench(2, common + ['--backend', 'gloo', '--shared-device'], launcher=False)
     assert two['n_gpus'] == 2 and two['config']['total_runs_per_step'] == 16384 and two['result']['runs'] == 16384
     s = two['per_gpu_single']
@@ -72,7 +73,7 @@ def test_bench_eight_ranks_without_a_launcher():
     the one GPU of this box over gloo: self-start under torch.distributed.run, sharding by global run id, the per-rank turns of
     per_gpu_single, the exchange, the merge and the per-rank fields of the line all execute with world = 8."""
     d = _bench(8, ['--steps', '2', '--warmup', '1', '--runs-per-gpu', '4096', '--cpu-baseline-seconds', '0', '--no-legs', '--pmc', 'off',
-                   '--backend', 'gloo', '--shared-device'], launcher=False)
+                   '--backend', 'gloo', '--shared-device', '--full'], launcher=False)
     assert d['n_gpus'] == 8 and d['config']['total_runs_per_step'] == 8 * 4096 and d['result']['runs'] == 8 * 4096
     assert len(d['per_rank']['kernel_ms_avg']) == 8 and 0 <= d['per_rank']['argmax'] < 8
     assert len(d['per_gpu_single']['every_rank']['value']) == 8 and d['per_gpu_single']['runs'] == 4096
@@ -82,7 +83,7 @@ def test_bench_eight_ranks_without_a_launcher():
 def test_bench_line_contract():
     """The ONE JSON line the driver reads: every field of the contract, on the C2 workload at its real size (few steps), with
     a short CPU-baseline sample and one leg-free pass; the roofline object must be consistent with itself."""
-    d = _bench(1, ['--steps', '5', '--warmup', '3', '--cpu-baseline-seconds', '1', '--no-legs', '--pmc', 'off'])
+    d = _bench(1, ['--steps', '5', '--warmup', '3', '--cpu-baseline-seconds', '1', '--no-legs', '--pmc', 'off', '--full'])
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
                 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert key in d, key
@@ -106,6 +107,37 @@ def test_bench_line_contract():
     c = d['cpu_baseline']
     assert c['kind'] == 'port' and c['unit'] == 'sample*MC/s' and c['cores'] >= 1 and c['value'] > 0 and 'sample' in c
     assert c['reference_python']['kind'] in ('quoted', 'reference') and c['reference_python']['cores'] == 1
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """Without --full the line is the headline alone; --dump-outputs writes what the last timed step computed (float64, the whole
+    set well under 64 MB), consistent with the line, and the same arguments write the same arrays again."""
+    args = ['--steps', '2', '--warmup', '1', '--runs-per-gpu', '8192']
+    d = _bench(1, args + ['--dump-outputs', str(tmp_path / 'a')])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline', 'result'):
+        assert key in d, key
+    for key in ('configs', 'cpu_baseline', 'headline_again', 'roofline_asis', 'mechanisation_only'):
+        assert key not in d, key
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['dtype'] == 'f64'
+    np.testing.assert_allclose(d['value'], 8192 * 1000 / (d['ms_per_step'] * 1e-3), rtol=1e-6)
+    files = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert files == sorted(n + '.npy' for n in ('stats_count', 'stats_mean', 'stats_std', 'stats_maxabs', 'end_errors',
+                                                'end_errors_run_ids', 'series_run_ids', 'accel', 'gyro', 'att', 'pos', 'vel')), files
+    assert sum((tmp_path / 'a' / f).stat().st_size for f in files) <= 64e6
+    a = {f[:-4]: np.load(str(tmp_path / 'a' / f)) for f in files}
+    assert all(v.dtype == np.float64 for v in a.values())
+    # the last timed step is step 2 (one warm-up + two timed): global run ids 2 * 8192 ..
+    assert a['stats_count'][0] == 8192 and a['end_errors'].shape == (8192, 9)
+    np.testing.assert_array_equal(a['end_errors_run_ids'], 2 * 8192 + np.arange(8192))
+    np.testing.assert_allclose(a['stats_std'], a['end_errors'].std(axis=0), rtol=1e-7, atol=1e-12)
+    np.testing.assert_allclose(a['stats_maxabs'], np.abs(a['end_errors']).max(axis=0), rtol=1e-7, atol=1e-10)
+    np.testing.assert_allclose(a['stats_std'][6:9], d['result']['vel_std_mps'], rtol=1e-12)
+    k = a['series_run_ids'].size
+    assert 1 <= k <= 8192 and all(a[s].shape == (k, 1000, 3) for s in ('accel', 'gyro', 'att', 'pos', 'vel'))
+    assert np.all((a['series_run_ids'] >= 2 * 8192) & (a['series_run_ids'] < 3 * 8192))
+    _bench(1, args + ['--dump-outputs', str(tmp_path / 'b')])
+    for name, v in a.items():
+        np.testing.assert_array_equal(np.load(str(tmp_path / 'b' / (name + '.npy'))), v, err_msg=name)
 
 
 def test_rccl_exchange_executes_on_one_gpu():
@@ -134,7 +166,7 @@ def test_arena_search_then_collectives_with_two_ranks():
     warm-up, timed steps, exchange.  16 384 runs per rank materialise 1.97 GB: placed by default.  The line carries every rank's
     placement and roofline and its own efficiency figure."""
     d = _bench(2, ['--steps', '4', '--warmup', '2', '--runs-per-gpu', '16384', '--cpu-baseline-seconds', '0', '--no-legs', '--pmc', 'off',
-                   '--backend', 'gloo', '--shared-device'], launcher=False)
+                   '--backend', 'gloo', '--shared-device', '--full'], launcher=False)
     assert d['n_gpus'] == 2 and d['result']['runs'] == 2 * 16384
     pl = d['per_rank']['placement']
     assert len(pl) == 2 and all(p['placed'] == ['imu', 'traj_free'] and sum(p['arena_stripes_of_class']) >= 4 for p in pl), pl

@@ -17,9 +17,90 @@ import pytest
 
 from conftest import load_golden, REPO, PKG
 
-REF = '/root/reference'
-need_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'gnss_ins_sim')),
-                              reason='no reference checkout at %s (build container only)' % REF)
+# A stand-in checkout of the reference for the fall-through: the layout of Aceinna/gnss-ins-sim (gnss_ins_sim/<pkg>/<module>.py,
+# demo_algorithms/) with small modules of this test's own under the names the hosted plugin reaches for -- off-path names of a
+# module the drop-in shadows (attitude.quat_update / quat2dcm / dcm2quat, geoparams.ecef2lla) and whole modules it does not have
+# (geomag, psd.time_series_from_psd, demo_algorithms.inclinometer_mahony).  What is tested is the loader, not the reference's
+# arithmetic: the names resolve to the checkout, hot-path names stay the drop-in's, nothing is written into the checkout.
+STAND_IN = {
+    'gnss_ins_sim/__init__.py': '',
+    'gnss_ins_sim/attitude/__init__.py': '',
+    'gnss_ins_sim/attitude/attitude.py': """
+import math
+import numpy as np
+
+
+def quat_update(q, w, dt):
+    \"\"\"q_nb after the body rate w [rad/s] for dt: q * (rotation by w dt), normalised (scalar first).\"\"\"
+    th = math.sqrt(float(np.dot(w, w))) * dt
+    if th == 0.0:
+        return np.array(q, dtype=float)
+    u = np.asarray(w, dtype=float) * (dt / th)
+    p = np.concatenate([[math.cos(0.5 * th)], math.sin(0.5 * th) * u])
+    r = np.array([q[0] * p[0] - np.dot(q[1:], p[1:])] + list(q[0] * p[1:] + p[0] * np.asarray(q[1:]) + np.cross(q[1:], p[1:])))
+    return r / np.linalg.norm(r)
+
+
+def quat2dcm(q):
+    a, b, c, d = q
+    return np.array([[a * a + b * b - c * c - d * d, 2 * (b * c + a * d), 2 * (b * d - a * c)],
+                     [2 * (b * c - a * d), a * a - b * b + c * c - d * d, 2 * (c * d + a * b)],
+                     [2 * (b * d + a * c), 2 * (c * d - a * b), a * a - b * b - c * c + d * d]])
+
+
+def dcm2quat(c):
+    a = 0.5 * math.sqrt(max(0.0, 1.0 + c[0, 0] + c[1, 1] + c[2, 2]))
+    return np.array([a, (c[1, 2] - c[2, 1]) / (4 * a), (c[2, 0] - c[0, 2]) / (4 * a), (c[0, 1] - c[1, 0]) / (4 * a)])
+""",
+    'gnss_ins_sim/geoparams/__init__.py': '',
+    'gnss_ins_sim/geoparams/geoparams.py': """
+import math
+import numpy as np
+
+RE, E2 = 6378137.0, 0.0818191908426215 ** 2
+
+
+def ecef2lla(xyz):
+    x, y, z = (float(v) for v in xyz)
+    p, lat = math.hypot(x, y), math.atan2(z, math.hypot(x, y) * (1.0 - E2))
+    for _ in range(20):
+        rn = RE / math.sqrt(1.0 - E2 * math.sin(lat) ** 2)
+        h = p / math.cos(lat) - rn
+        lat = math.atan2(z, p * (1.0 - E2 * rn / (rn + h)))
+    return np.array([lat, math.atan2(y, x), h])
+""",
+    'gnss_ins_sim/geoparams/geomag.py': """
+class GeoMag(object):
+    def __init__(self, coefficients):
+        self.coefficients = coefficients
+""",
+    'gnss_ins_sim/psd/__init__.py': '',
+    'gnss_ins_sim/psd/time_series_from_psd.py': """
+import numpy as np
+
+
+def time_series_from_psd(psd, fs, n):
+    return np.zeros(n)
+""",
+    'demo_algorithms/__init__.py': '',
+    'demo_algorithms/inclinometer_mahony.py': """
+from gnss_ins_sim.attitude import attitude
+
+
+def step(q, w, dt):
+    return attitude.dcm2quat(attitude.quat2dcm(attitude.quat_update(q, w, dt)))
+""",
+}
+
+
+@pytest.fixture
+def stand_in_checkout(tmp_path):
+    root = tmp_path / 'gnss-ins-sim'
+    for rel, text in STAND_IN.items():
+        f = root / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text(text.lstrip('\n'))
+    return str(root)
 
 
 def test_euler_update_zyx_is_the_references():
@@ -182,16 +263,16 @@ print('OK')
 '''
 
 
-@need_ref
-def test_hosted_plugin_reaches_reference_names_through_the_dropin(tmp_path):
+def test_hosted_plugin_reaches_reference_names_through_the_dropin(tmp_path, stand_in_checkout):
     """With $GNSS_INS_SIM_REFERENCE naming a checkout, a hosted plugin that calls attitude.quat_update (attitude.py:665) and
     attitude.euler_update_zyx (:679) runs inside the drop-in Sim; demo_algorithms.inclinometer_mahony (which calls quat_update /
-    dcm2quat at :115, 151) imports; nothing is written into the checkout."""
+    dcm2quat at :115, 151) imports; nothing is written into the checkout.  The checkout is the stand-in above."""
+    ref = stand_in_checkout
     script = tmp_path / 'hosted.py'
-    script.write_text(_HOSTED % {'pkg': PKG, 'ref': REF})
+    script.write_text(_HOSTED % {'pkg': PKG, 'ref': ref})
     data = tmp_path / 'logged'
     data.mkdir()
-    env = dict(os.environ, GNSS_INS_SIM_REFERENCE=REF, MPLBACKEND='Agg')
+    env = dict(os.environ, GNSS_INS_SIM_REFERENCE=ref, MPLBACKEND='Agg')
     env.pop('PYTHONDONTWRITEBYTECODE', None)             # the loader itself must keep the checkout clean
     out = subprocess.run([sys.executable, str(script), str(data)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     assert out.returncode == 0 and b'OK' in out.stdout, out.stdout.decode()[-4000:]

@@ -15,7 +15,7 @@ sha256sum gnss-ins-sim_amd/lib/libginsim.so | cut -c1-16 > $OUT/lib_sha256.txt
 python -X faulthandler -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log
 cp gpurun_out/parity_margins.json $OUT/ 2>/dev/null
 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; python - <<PY
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))
 print("bench: %.4g %s, %.3f ms/step, kernel %.3f ms, frac %.3f, traffic %s" % (d["value"], d["unit"], d["ms_per_step"],
@@ -26,8 +26,8 @@ for l in d.get("configs", []):
 PY
 cd /tmp && export TMPDIR=/tmp
 B="python $ROOT/bench.py --pmc-child"
-# the default command (200 timed + 30 warm-up steps, all legs) under the kernel trace: per-kernel averages that must agree with the HIP events
-timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_trace -o bench -- python $ROOT/bench.py --cpu-baseline-seconds 0 --pmc off > $OUT/prof_trace.json 2> $OUT/prof_trace.log
+# the full command (200 timed + 30 warm-up steps, all legs) under the kernel trace: per-kernel averages that must agree with the HIP events
+timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_trace -o bench -- python $ROOT/bench.py --full --cpu-baseline-seconds 0 --pmc off > $OUT/prof_trace.json 2> $OUT/prof_trace.log
 timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/prof_pmc_write -o bench -- $B > $OUT/prof_pmc_write.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/prof_pmc_fetch -o bench -- $B > $OUT/prof_pmc_fetch.log 2>&1
 timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace -d $OUT/prof_pmc_sq -o bench -- $B > $OUT/prof_pmc_sq.log 2>&1
