@@ -207,11 +207,12 @@ __device__ __forceinline__ double angle_range_pi_mul(double x) {
 // rounding (clamped at 0 here).  No variant runs the raw form any more: the sums are kept about an error close to the mean,
 // per lane where the registers are there, per launch where they are not (see Proc;
 // tests/test_process_stats.py::test_online_statistics_floor_for_a_constant_error).
-// The attitude error is wrapped to [-pi, pi] only when some lane of the wavefront is outside it (wrap_pi3).
-__device__ __forceinline__ double wrap_pi_lane(double x) { return fabs(x) <= kPi ? x : angle_range_pi_mul(x); }
+// The attitude error is wrapped to (-pi, pi] only when some lane of the wavefront is outside (-pi, pi) (wrap_pi3); exactly -pi
+// takes the wrap, which returns +pi as angle_range_pi does.
+__device__ __forceinline__ double wrap_pi_lane(double x) { return fabs(x) < kPi ? x : angle_range_pi_mul(x); }
 
 __device__ __forceinline__ void wrap_pi3(double (&e)[9]) {
-    const bool out = !(fabs(e[0]) <= kPi) || !(fabs(e[1]) <= kPi) || !(fabs(e[2]) <= kPi);
+    const bool out = !(fabs(e[0]) < kPi) || !(fabs(e[1]) < kPi) || !(fabs(e[2]) < kPi);
     if (__builtin_amdgcn_ballot_w64(out) != 0) {
         e[0] = wrap_pi_lane(e[0]); e[1] = wrap_pi_lane(e[1]); e[2] = wrap_pi_lane(e[2]);
     }
@@ -279,14 +280,17 @@ struct Proc {
             mx[c] = fmax(mx[c], fabs(e[c]));
         }
     }
+    // Non-finite errors as __array_stats has them (np.max / np.average / np.std): add's fmax drops a NaN, but s2 (a sum of
+    // squares) is NaN exactly when some d was, so max|e| is NaN then; s1 carries an infinity into the mean and s2 / cnt - md^2
+    // makes the std NaN.  The std keeps a NaN and clamps a rounding negative to 0.
     __device__ __forceinline__ void store(double* __restrict__ out, int64_t runs, int64_t r, double cnt, uniform_ptr about) const {
 #pragma unroll
         for (int c = 0; c < 9; ++c) {
             const double md = cnt > 0.0 ? s1[c] / cnt : 0.0;
             const double var = cnt > 0.0 ? s2[c] / cnt - md * md : 0.0;
-            out[(0 * 9 + c) * runs + r] = mx[c];
+            out[(0 * 9 + c) * runs + r] = s2[c] != s2[c] ? s2[c] : mx[c];
             out[(1 * 9 + c) * runs + r] = SHIFT == 1 ? e0[c] + md : (SHIFT == 2 ? about[c] + md : md);
-            out[(2 * 9 + c) * runs + r] = var > 0.0 ? sqrt(var) : 0.0;
+            out[(2 * 9 + c) * runs + r] = var < 0.0 ? 0.0 : sqrt(var);
         }
     }
 };

@@ -13,15 +13,24 @@ namespace ginsim {
 
 struct Mom { double n, mean, m2, mx; };
 
+// Non-finite errors follow __array_stats (np.max(np.abs(x)), np.average, np.std): a NaN anywhere makes all three NaN; an
+// infinity makes the mean +-inf (NaN when both signs occur) and the std NaN.  The max of |e| keeps a NaN from either side.
+__host__ __device__ inline double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
+
 __host__ __device__ inline Mom merge(const Mom& a, const Mom& b) {
     const double n = a.n + b.n;
     if (n == 0.0) return Mom{0.0, 0.0, 0.0, 0.0};
-    const double d = b.mean - a.mean;
     Mom o;
     o.n = n;
-    o.mean = a.mean + d * (b.n / n);
-    o.m2 = a.m2 + b.m2 + d * d * (a.n * b.n / n);
-    o.mx = a.mx > b.mx ? a.mx : b.mx;
+    if (__builtin_isfinite(a.mean) && __builtin_isfinite(b.mean)) {
+        const double d = b.mean - a.mean;
+        o.mean = a.mean + d * (b.n / n);
+        o.m2 = a.m2 + b.m2 + d * d * (a.n * b.n / n);
+    } else {                            // inf + finite = inf, inf - inf = NaN, NaN stays: the sign rule of np.average
+        o.mean = a.mean + b.mean;
+        o.m2 = __builtin_nan("");
+    }
+    o.mx = nan_max(a.mx, b.mx);
     return o;
 }
 
@@ -32,20 +41,33 @@ __device__ inline Mom shfl_xor(const Mom& m, int mask) {
 
 constexpr int kStatBlock = 256;
 
+// The end-point reduction runs on x - k, k = the component's first error (0 if that is not finite): a mean and its deviations
+// of the size of the spread instead of the size of the offset.  Without it the running means of data at 1e6 +- 1e-6 are
+// rounded to ulp(1e6) ~ 1e-10 at every update and merge, and the std came out 1e-5 relative off where np.std is 1e-9.
+__device__ __forceinline__ double shift_of(const double* x) {
+    const double k = x[0];
+    return __builtin_isfinite(k) ? k : 0.0;
+}
+
 // grid = (blocks, 9); partial[(comp*blocks + block)] = moments of that block's strided slice
 __global__ void __launch_bounds__(kStatBlock) stats_partial_kernel(const double* __restrict__ e, int64_t runs,
                                                                    Mom* __restrict__ partial) {
     const int comp = blockIdx.y;
     const double* x = e + (int64_t)comp * runs;
+    const double k = shift_of(x);
     Mom m{0.0, 0.0, 0.0, 0.0};
     for (int64_t r = (int64_t)blockIdx.x * kStatBlock + threadIdx.x; r < runs; r += (int64_t)gridDim.x * kStatBlock) {
-        const double v = x[r];
+        const double v = x[r] - k;
         m.n += 1.0;
-        const double d = v - m.mean;
-        m.mean += d / m.n;
-        m.m2 += d * (v - m.mean);
-        const double av = fabs(v);
-        m.mx = av > m.mx ? av : m.mx;
+        if (__builtin_isfinite(v) && __builtin_isfinite(m.mean)) {
+            const double d = v - m.mean;
+            m.mean += d / m.n;
+            m.m2 += d * (v - m.mean);
+        } else {                        // see merge
+            m.mean += v;
+            m.m2 = __builtin_nan("");
+        }
+        m.mx = nan_max(fabs(x[r]), m.mx);
     }
 #pragma unroll
     for (int mask = 32; mask >= 1; mask >>= 1) m = merge(m, shfl_xor(m, mask));
@@ -61,7 +83,8 @@ __global__ void __launch_bounds__(kStatBlock) stats_partial_kernel(const double*
 
 // one 64-lane block per component: lanes fold the block partials they own (stride 64, fixed order), then the same
 // butterfly of Chan merges as above -- deterministic, and ~10x shorter than one lane walking all partials
-__global__ void stats_final_kernel(const Mom* __restrict__ partial, int blocks, ginsim_stats* __restrict__ out) {
+__global__ void stats_final_kernel(const Mom* __restrict__ partial, int blocks, const double* __restrict__ e, int64_t runs,
+                                   ginsim_stats* __restrict__ out) {
     const int c = blockIdx.x;
     Mom t{0.0, 0.0, 0.0, 0.0};
     for (int b = threadIdx.x; b < blocks; b += 64) t = merge(t, partial[c * blocks + b]);
@@ -69,7 +92,7 @@ __global__ void stats_final_kernel(const Mom* __restrict__ partial, int blocks, 
     for (int mask = 32; mask >= 1; mask >>= 1) t = merge(t, shfl_xor(t, mask));
     if (threadIdx.x == 0) {
         if (c == 0) out->count = t.n;
-        out->mean[c] = t.mean;
+        out->mean[c] = shift_of(e + (int64_t)c * runs) + t.mean;
         out->m2[c] = t.m2;
         out->maxabs[c] = t.mx;
     }
@@ -123,26 +146,31 @@ __global__ void __launch_bounds__(64 * kSeg) process_stats_kernel(const T* __res
         const double* row = org.table + 3 * (call < (uint64_t)org.n_ini ? call : 0);
         o3[0] = row[0]; o3[1] = row[1]; o3[2] = row[2];
     }
+    // the error of sample j against the truth
+    auto error = [&](int64_t j, double (&e)[9]) {
+        double x[9], t[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) { x[c] = (double)traj[c * plane + j * runs + r]; t[c] = truth[9 * j + c]; }
+        x[3] += o3[0]; x[4] += o3[1]; x[5] += o3[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {       // wrapped only when outside (-pi, pi), exactly as the online accumulator does (mc_kernel.hip wrap_pi3)
+            const double d = x[c] - t[c];
+            e[c] = fabs(d) < kPi ? d : angle_range_pi_mul(d);
+        }
+        if (pos_ned) {
+            const Vec3 d = lla_error_ned(Vec3{x[3], x[4], x[5]}, Vec3{t[3], t[4], t[5]});
+            e[3] = d.x; e[4] = d.y; e[5] = d.z;
+        } else {
+#pragma unroll
+            for (int c = 3; c < 6; ++c) e[c] = x[c] - t[c];
+        }
+#pragma unroll
+        for (int c = 6; c < 9; ++c) e[c] = x[c] - t[c];
+    };
     if (active) {
         for (int64_t j = jb; j < je; ++j) {
-            double x[9], t[9], e[9];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) { x[c] = (double)traj[c * plane + j * runs + r]; t[c] = truth[9 * j + c]; }
-            x[3] += o3[0]; x[4] += o3[1]; x[5] += o3[2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {       // wrapped only when outside [-pi, pi], exactly as the online accumulator does (mc_kernel.hip wrap_pi3)
-                const double d = x[c] - t[c];
-                e[c] = fabs(d) <= kPi ? d : angle_range_pi_mul(d);
-            }
-            if (pos_ned) {
-                const Vec3 d = lla_error_ned(Vec3{x[3], x[4], x[5]}, Vec3{t[3], t[4], t[5]});
-                e[3] = d.x; e[4] = d.y; e[5] = d.z;
-            } else {
-#pragma unroll
-                for (int c = 3; c < 6; ++c) e[c] = x[c] - t[c];
-            }
-#pragma unroll
-            for (int c = 6; c < 9; ++c) e[c] = x[c] - t[c];
+            double e[9];
+            error(j, e);
             cnt += 1.0;
             const double icnt = rcp_nr(cnt);
 #pragma unroll
@@ -150,9 +178,27 @@ __global__ void __launch_bounds__(64 * kSeg) process_stats_kernel(const T* __res
                 const double d = e[c] - mean[c];
                 mean[c] = __builtin_fma(d, icnt, mean[c]);
                 m2[c] = __builtin_fma(d, e[c] - mean[c], m2[c]);
-                const double a = fabs(e[c]);
-                mx[c] = a > mx[c] ? a : mx[c];
+                mx[c] = nan_max(fabs(e[c]), mx[c]);
             }
+        }
+        // a non-finite error (max|e| is inf or NaN) left the Welford mean NaN even where np.average is +-inf: that segment's
+        // mean is formed again as a plain sum, and its M2 is NaN (see merge).  Once per segment, and only for such a run.
+        bool bad = false;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) bad |= !__builtin_isfinite(mx[c]);
+        if (bad) {
+            double sum[9];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) sum[c] = 0.0;
+            for (int64_t j = jb; j < je; ++j) {
+                double e[9];
+                error(j, e);
+#pragma unroll
+                for (int c = 0; c < 9; ++c) sum[c] += e[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 9; ++c)
+                if (!__builtin_isfinite(mx[c])) { mean[c] = sum[c] / cnt; m2[c] = __builtin_nan(""); }
         }
     }
 #pragma unroll
@@ -204,7 +250,7 @@ hipError_t launch_end_stats(const double* end_err, int64_t runs, void* scratch, 
     Mom* partial = reinterpret_cast<Mom*>(scratch);
     ginsim_stats* out = reinterpret_cast<ginsim_stats*>(partial + 9 * blocks);
     hipLaunchKernelGGL(stats_partial_kernel, dim3(blocks, 9), dim3(kStatBlock), 0, s, end_err, runs, partial);
-    hipLaunchKernelGGL(stats_final_kernel, dim3(9), dim3(64), 0, s, partial, blocks, out);
+    hipLaunchKernelGGL(stats_final_kernel, dim3(9), dim3(64), 0, s, partial, blocks, end_err, runs, out);
     return hipGetLastError();
 }
 

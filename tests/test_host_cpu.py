@@ -177,6 +177,63 @@ def test_stats_merge_host_matches_numpy():
     np.testing.assert_array_equal(m.maxabs, np.abs(e).max(0))
 
 
+def _nonfinite_columns():
+    """(runs, 9) errors whose columns hold the non-finite cases of __array_stats, next to finite ones: clean, one NaN, +inf,
+    -inf, +inf and -inf, NaN and inf, clean, a NaN in the first row, an inf in the last row."""
+    rng = np.random.default_rng(5)
+    e = rng.normal(size=(1000, 9)) * 1e-3 + 0.5
+    e[123, 1] = np.nan
+    e[7, 2] = np.inf
+    e[500, 3] = -np.inf
+    e[10, 4], e[900, 4] = np.inf, -np.inf
+    e[11, 5], e[12, 5] = np.nan, np.inf
+    e[0, 7] = np.nan
+    e[999, 8] = np.inf
+    return e
+
+
+def test_oracle_array_stats_follow_numpy_on_non_finite_errors():
+    """The oracle's __array_stats is np.max(np.abs(x)) / np.average / np.std: NaN anywhere -> NaN for all three; +inf -> max inf,
+    avg inf, std NaN; +inf and -inf -> max inf, avg NaN, std NaN.  Pinned here so that the oracle cannot drift from that rule."""
+    from oracle import ins_np
+    e = _nonfinite_columns()
+    with np.errstate(invalid='ignore'):
+        st = ins_np.array_stats(e)
+    nan, inf = np.nan, np.inf
+    want_max = [None, nan, inf, inf, inf, nan, None, nan, inf]
+    want_avg = [None, nan, inf, -inf, nan, nan, None, nan, inf]
+    for c in range(9):
+        if want_max[c] is None:
+            assert np.isfinite(st['max'][c]) and np.isfinite(st['avg'][c]) and np.isfinite(st['std'][c])
+            continue
+        np.testing.assert_array_equal(st['max'][c], want_max[c])
+        np.testing.assert_array_equal(st['avg'][c], want_avg[c])
+        assert np.isnan(st['std'][c])
+    x = np.array([[1.0], [np.nan]])
+    np.testing.assert_array_equal(ins_np.process_error_stats(x[None, :, :].repeat(3, 2), x[None].repeat(3, 2),
+                                                             x[None].repeat(3, 2), np.zeros((2, 3)), np.zeros((2, 3)),
+                                                             np.zeros((2, 3)), 0)[0], np.full((3, 9), np.nan))
+
+
+@pytest.mark.parametrize('split', [[500], [1, 2], [123, 124], [17, 400, 901], [999]])
+def test_stats_merge_host_non_finite_follows_numpy(split):
+    """ginsim_stats_merge on partials that carry NaN / inf (a shard whose runs went non-finite): the merged record follows
+    __array_stats, whatever side of the merge the non-finite partial is on."""
+    import ginsim
+    from ginsim import distributed
+    from oracle import ins_np
+    e = _nonfinite_columns()
+    with np.errstate(invalid='ignore'):
+        ref = ins_np.array_stats(e)
+        for order in (1, -1):
+            parts = [distributed.stats_from_errors(x) for x in np.array_split(e, split)][::order]
+            m = ginsim.StatsResult.merge(parts)
+            assert m.count == 1000
+            np.testing.assert_array_equal(m.maxabs, ref['max'])
+            np.testing.assert_allclose(m.mean, ref['avg'], rtol=1e-13, equal_nan=True)
+            np.testing.assert_allclose(m.std, ref['std'], rtol=1e-11, equal_nan=True)
+
+
 _WORKER = r'''
 import os, sys
 sys.path[:0] = [%(pkg)r, %(repo)r]
