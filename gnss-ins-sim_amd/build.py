@@ -37,6 +37,7 @@ SOURCES = [
     ('allan.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),
     ('vib_psd.hip', ['--offload-arch=' + ARCH]),
+    ('selftest.hip', ['--offload-arch=' + ARCH]),
     ('ginsim_api.hip', ['--offload-arch=' + ARCH]),
     # host-only truth generator; no fused multiply-adds (see the file header)
     ('pathgen.cpp', ['-x', 'c++', '-ffp-contract=off']),

@@ -49,6 +49,9 @@ hipError_t launch_rng_probe(uint64_t seed, uint64_t run, uint32_t stream, int64_
 hipError_t launch_aos_to_soa(const double* src, double* dst, int64_t R, int64_t n, int C, hipStream_t s);
 hipError_t launch_runs_to_series(const double* in, double* out, int C, int64_t n, int64_t R, hipStream_t s);
 hipError_t launch_normal_transform(const uint32_t* words, int64_t count, double* z0, double* z1, hipStream_t s);
+hipError_t launch_pattern_fill(void* p, uint64_t words, uint32_t tag, hipStream_t s);
+hipError_t launch_pattern_check(const void* p, uint64_t words, uint32_t tag, unsigned long long* out, hipStream_t s);
+hipError_t launch_digest(const void* p, uint64_t words, unsigned long long* out, hipStream_t s);
 hipError_t launch_gather_runs(const double* series, int C, int64_t n, int64_t runs, const int64_t* ids, int nsel,
                               double* out, hipStream_t s);
 hipError_t launch_gather_series(const double* series, int C, int64_t n, const int64_t* ids, int nsel, double* out, hipStream_t s);
@@ -83,6 +86,8 @@ struct ginsim_ctx {
     ginsim_stats* stat_slots = nullptr;                   // pinned host records of ginsim_end_stats_begin/_finish
     hipEvent_t stat_ev[8] = {};
     bool stat_pending[8] = {};
+    unsigned long long* selftest = nullptr;               // device [3]: the results of ginsim_pattern_check / ginsim_digest (kept: a
+                                                          // hipMalloc + hipFree per call would flush stale translations, csrc/placed.hip)
 };
 
 // grow-only scratch owned by the context: avoids a hipMalloc/hipFree pair (~100 us each) per call
@@ -184,6 +189,7 @@ int ginsim_destroy(ginsim_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->stat_slots) (void)hipHostFree(c->stat_slots);
     if (c->allan_host) (void)hipHostFree(c->allan_host);
+    if (c->selftest) (void)hipFree(c->selftest);
     if (c->comm) ginsim::comm_destroy(c->comm);
     if (c->comm_recv) (void)hipFree(c->comm_recv);
     if (c->comm_host) (void)hipHostFree(c->comm_host);
@@ -1006,6 +1012,54 @@ int ginsim_normal_transform(ginsim_ctx* c, const uint32_t* host_words, int64_t c
     HIP_TRY(hipMemcpyAsync(host_z0, z0.p, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(host_z1, z1.p, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
+// ---- ABI 9: memory self-test (csrc/selftest.hip)
+static int selftest_args(ginsim_ctx* c, const void* dptr, size_t bytes, const char* what) {
+    REQUIRE(c && (bytes == 0 || dptr), "%s: bad arguments", what);
+    REQUIRE(bytes % 8 == 0 && ((uintptr_t)dptr & 7) == 0, "%s: the region must be whole, aligned 64-bit words", what);
+    REQUIRE(bytes / 8 < ((uint64_t)1 << 40), "%s: more than 2^40 words", what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->selftest) HIP_TRY(hipMalloc(&c->selftest, 4 * sizeof(unsigned long long)));
+    return GINSIM_OK;
+}
+
+int ginsim_pattern_fill(ginsim_ctx* c, void* dptr, size_t bytes, uint32_t tag) {
+    const int rc = selftest_args(c, dptr, bytes, "pattern_fill");
+    if (rc) return rc;
+    if (bytes) HIP_TRY(launch_pattern_fill(dptr, bytes / 8, tag, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
+int ginsim_pattern_check(ginsim_ctx* c, const void* dptr, size_t bytes, uint32_t tag, int64_t* bad, int64_t* first_bad_offset,
+                         uint64_t* found) {
+    REQUIRE(bad && first_bad_offset && found, "pattern_check: NULL output");
+    const int rc = selftest_args(c, dptr, bytes, "pattern_check");
+    if (rc) return rc;
+    *bad = 0; *first_bad_offset = -1; *found = 0;
+    if (!bytes) return GINSIM_OK;
+    unsigned long long h[3] = {0, 0, 0};
+    HIP_TRY(launch_pattern_check(dptr, bytes / 8, tag, c->selftest, c->stream));
+    HIP_TRY(hipMemcpyAsync(h, c->selftest, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *bad = (int64_t)h[0];
+    if (h[0]) { *first_bad_offset = (int64_t)(h[1] * 8); *found = h[2]; }
+    return GINSIM_OK;
+}
+
+int ginsim_digest(ginsim_ctx* c, const void* dptr, size_t bytes, uint64_t* out) {
+    REQUIRE(out, "digest: NULL output");
+    const int rc = selftest_args(c, dptr, bytes, "digest");
+    if (rc) return rc;
+    *out = 0;
+    if (!bytes) return GINSIM_OK;
+    unsigned long long h = 0;
+    HIP_TRY(launch_digest(dptr, bytes / 8, c->selftest, c->stream));
+    HIP_TRY(hipMemcpyAsync(&h, c->selftest, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = (uint64_t)h;
     return GINSIM_OK;
 }
 

@@ -167,6 +167,10 @@ _SIGS = {
     'ginsim_normal_transform': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64, _PD, _PD]),
     'ginsim_rng_normals': (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int64, _PD, _PD,
                                      C.POINTER(C.c_uint32)]),
+    'ginsim_pattern_fill': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]),
+    'ginsim_pattern_check': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
+    'ginsim_digest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
 }
 _OPTIONAL = {}
 

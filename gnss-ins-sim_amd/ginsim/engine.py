@@ -251,6 +251,26 @@ class Context(object):
     def sync(self):
         check(lib.ginsim_sync(self.handle))
 
+    # ---- memory self-test (ABI 9): kernels on this context's stream; oracle/pattern.py is the NumPy statement of both formulas
+    def pattern_fill(self, buf_or_ptr, nbytes, tag):
+        """Word i (uint64) of the region := (tag << 40) | i."""
+        ptr = getattr(buf_or_ptr, 'ptr', buf_or_ptr)
+        check(lib.ginsim_pattern_fill(self.handle, ptr, int(nbytes), int(tag)))
+
+    def pattern_check(self, buf_or_ptr, nbytes, tag):
+        """(bad words, byte offset of the first bad word or -1, the word found there) against the pattern of `tag`."""
+        ptr = getattr(buf_or_ptr, 'ptr', buf_or_ptr)
+        bad, first, found = C.c_int64(0), C.c_int64(-1), C.c_uint64(0)
+        check(lib.ginsim_pattern_check(self.handle, ptr, int(nbytes), int(tag), C.byref(bad), C.byref(first), C.byref(found)))
+        return int(bad.value), int(first.value), int(found.value)
+
+    def digest(self, buf_or_ptr, nbytes):
+        """Order-independent 64-bit digest of the region (ginsim_digest)."""
+        ptr = getattr(buf_or_ptr, 'ptr', buf_or_ptr)
+        out = C.c_uint64(0)
+        check(lib.ginsim_digest(self.handle, ptr, int(nbytes), C.byref(out)))
+        return int(out.value)
+
     def timer_begin(self):
         check(lib.ginsim_timer_begin(self.handle))
 

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define GINSIM_ABI_VERSION 8
+#define GINSIM_ABI_VERSION 9
 
 /* status codes */
 #define GINSIM_OK          0
@@ -426,6 +426,19 @@ int ginsim_rng_normals(ginsim_ctx* ctx, uint64_t seed, uint64_t run, uint32_t st
  * coefficient table) can be pinned against the oracle. */
 int ginsim_normal_transform(ginsim_ctx* ctx, const uint32_t* host_words /*[count][4]*/, int64_t count, double* host_z0,
                             double* host_z1);
+
+/* ---- ABI 9: memory self-test.  Word i (64-bit, counted from dptr) of a pattern is ((uint64_t)tag << 40) | i: unique per
+ *      (tag, offset), so that a word found in the wrong place names its cause -- another region's tag: an alias; 0: a zero
+ *      fill; a repeated byte: a memset.  Written and read by kernels on the context's stream (oracle/pattern.py spells out
+ *      the same formulas); bytes % 8 == 0, dptr 8-byte aligned, bytes / 8 < 2^40.  Each call synchronises the stream. ---- */
+int ginsim_pattern_fill(ginsim_ctx* ctx, void* dptr, size_t bytes, uint32_t tag);
+/* bad: the number of words that differ from the pattern; first_bad_offset: the byte offset of the lowest (-1: none); found:
+ * the word read there (0 when none). */
+int ginsim_pattern_check(ginsim_ctx* ctx, const void* dptr, size_t bytes, uint32_t tag, int64_t* bad, int64_t* first_bad_offset,
+                         uint64_t* found);
+/* Order-independent 64-bit digest: sum over i of splitmix64(w_i ^ (i * 0x9E3779B97F4A7C15)) mod 2^64, with the standard
+ * splitmix64 finaliser (add 0x9E3779B97F4A7C15, then the two xor-shift-multiplies and a final xor-shift). */
+int ginsim_digest(ginsim_ctx* ctx, const void* dptr, size_t bytes, uint64_t* out);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import pytest
 from conftest import load_golden, REPO, PKG
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_at_abi_9():
     import ctypes
     import ginsim
     hdr = open(os.path.join(REPO, 'include', 'ginsim.h')).read()
@@ -21,14 +21,16 @@ def test_library_exports_every_declared_symbol():
     missing = [s for s in sorted(declared) if not hasattr(raw, s)]
     assert not missing, 'declared in include/ginsim.h but not exported: %s' % missing
     assert set(ginsim.EXPORTS) <= declared
-    assert ginsim.lib.ginsim_abi_version() == 8
+    assert ginsim.lib.ginsim_abi_version() == 9
+    # what ABI 9 added: the memory self-test entry points, declared, exported and bound
+    assert {'ginsim_pattern_fill', 'ginsim_pattern_check', 'ginsim_digest'} <= set(ginsim.EXPORTS)
 
 
 def test_header_is_plain_c(tmp_path):
     """include/ginsim.h is the C ABI: it must compile as C99 on its own (what a cgo / JNI / ctypes-generator user feeds it to)."""
     import subprocess
     src = tmp_path / 'h.c'
-    src.write_text('#include "ginsim.h"\nint main(void) { return GINSIM_ABI_VERSION == 8 ? 0 : 1; }\n')
+    src.write_text('#include "ginsim.h"\nint main(void) { return GINSIM_ABI_VERSION == 9 ? 0 : 1; }\n')
     subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I' + os.path.join(REPO, 'include'), '-fsyntax-only', str(src)],
                    check=True, timeout=120)
 
