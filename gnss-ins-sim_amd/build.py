@@ -33,6 +33,8 @@ SOURCES = [
     # instruction) and paid for the pairing with v_mov: 53 packed + 38 moves of 152 VALU on the common path;
     # scalar, the same step is 169 plain VALU and the launch 15 % faster (nothing kept 0.685 -> 0.584 ms), 132 -> 120 VGPRs
     ('mc_kernel_f32.hip', ['--offload-arch=' + ARCH, '-mllvm', '-disable-machine-licm', '-ffp-contract=off', '-fno-slp-vectorize']),
+    # the sensor synthesis must give mc_kernel.hip's bits (same -ffp-contract=on); the filter code switches contraction off itself
+    ('inclinometer.hip', ['--offload-arch=' + ARCH, '-ffp-contract=on']),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),

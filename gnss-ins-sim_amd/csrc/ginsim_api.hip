@@ -30,6 +30,8 @@ void set_error(const char* fmt, ...) {
 
 hipError_t launch_mc(const ginsim_mc_params& p, hipStream_t stream, char* name, size_t cap, double* proc_about);      // name: report, do not launch
 hipError_t launch_mc_f32(const ginsim_mc_params& p, float* truth32, hipStream_t stream, char* name, size_t cap);
+hipError_t launch_incl(const ginsim_mc_params& p, const ginsim_incl_params& b, hipStream_t stream, char* name, size_t cap);
+int incl_variant(const ginsim_mc_params& p);
 size_t mc_f32_truth_bytes(const ginsim_mc_params& p);
 int mc_variant(const ginsim_mc_params& p);
 bool series_path_applies(const ginsim_mc_params& p);
@@ -397,6 +399,71 @@ int ginsim_mc_run(ginsim_ctx* c, const ginsim_mc_params* p) {
         if (p->out_proc[0] || p->out_proc[1]) HIP_TRY(scratch(c, 3, 9 * sizeof(double), &about));
         HIP_TRY(launch_mc(*p, c->stream, nullptr, 0, reinterpret_cast<double*>(about)));
     }
+    return GINSIM_OK;
+}
+
+static int check_incl_params(const ginsim_mc_params* m, const ginsim_incl_params* p) {
+    REQUIRE(m && p, "incl_run: NULL argument");
+    REQUIRE(m->n >= 1 && m->runs >= 1, "incl_run: n=%lld runs=%lld must be >= 1", (long long)m->n, (long long)m->runs);
+    REQUIRE(m->n <= 0xFFFFFFFFll, "incl_run: n exceeds the 32-bit sample counter of the RNG");
+    REQUIRE(m->runs <= (int64_t)0x7FFFFFFF * 64, "incl_run: too many runs for one launch");
+    REQUIRE(p->algo_mask >= 1 && p->algo_mask <= 3, "incl_run: algo_mask must be a combination of GINSIM_INCL_*");
+    REQUIRE(p->n_list >= 0 && p->n_list <= m->runs, "incl_run: n_list must lie in 0 .. runs");
+    REQUIRE(!(p->algo_mask & GINSIM_INCL_MAHONY) || p->bias_in, "incl_run: the Mahony filter needs bias_in");
+    REQUIRE(std::isfinite(p->dt) && p->dt > 0.0, "incl_run: dt must be positive");
+    REQUIRE(m->block_threads == 0 || m->block_threads == 64 || m->block_threads == 128 || m->block_threads == 256,
+            "incl_run: block_threads must be 0, 64, 128 or 256");
+    REQUIRE(m->precision == 0, "incl_run: the inclinometer kernel is fp64 only");
+    if (m->given_sensors) {
+        REQUIRE(m->in_accel && m->in_gyro, "incl_run: given_sensors needs in_accel and in_gyro");
+    } else {
+        REQUIRE(m->ref_gyro && m->ref_accel, "incl_run: ref_accel/ref_gyro missing");
+        int rc = check_sensor(m->accel, "accel");
+        if (rc) return rc;
+        rc = check_sensor(m->gyro, "gyro");
+        if (rc) return rc;
+    }
+    for (const ginsim_vibration* v : {&m->vib_accel, &m->vib_gyro}) {
+        if (v->type == GINSIM_VIB_NONE) continue;
+        REQUIRE(v->type == GINSIM_VIB_RANDOM || v->type == GINSIM_VIB_SINUSOIDAL,
+                "incl_run: the inclinometer kernel takes the 'random' and 'sinusoidal' vibration only");
+        REQUIRE(!m->given_sensors, "incl_run: a vibration term cannot be added to given sensors");
+        REQUIRE(std::isfinite(v->amp[0]) && std::isfinite(v->amp[1]) && std::isfinite(v->amp[2]) && std::isfinite(v->omega_dt),
+                "incl_run: vibration amplitudes / frequency must be finite");
+    }
+    const bool stats = p->out_end[0] || p->out_end[1] || p->out_proc[0] || p->out_proc[1];
+    REQUIRE(!stats || m->ref_nav, "incl_run: statistics need ref_nav");
+    REQUIRE(!stats || m->proc_first >= 0, "incl_run: proc_first must be >= 0");
+    REQUIRE(!(p->out_quat[0] || p->out_euler[0] || p->out_wb || p->out_ab || p->out_end[0] || p->out_proc[0]) ||
+            (p->algo_mask & GINSIM_INCL_MAHONY), "incl_run: Mahony outputs without the Mahony bit");
+    REQUIRE(!(p->out_quat[1] || p->out_euler[1] || p->out_end[1] || p->out_proc[1]) || (p->algo_mask & GINSIM_INCL_TILT),
+            "incl_run: tilt outputs without the tilt bit");
+    return GINSIM_OK;
+}
+
+int ginsim_incl_variant(const ginsim_mc_params* mc, const ginsim_incl_params* p, int32_t* variant) {
+    REQUIRE(variant, "incl_variant: NULL argument");
+    const int rc = check_incl_params(mc, p);
+    if (rc) return rc;
+    *variant = incl_variant(*mc);
+    return GINSIM_OK;
+}
+
+int ginsim_incl_kernel_name(const ginsim_mc_params* mc, const ginsim_incl_params* p, char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "incl_kernel_name: bad arguments");
+    const int rc = check_incl_params(mc, p);
+    if (rc) return rc;
+    buf[0] = 0;
+    (void)launch_incl(*mc, *p, nullptr, buf, cap);
+    return GINSIM_OK;
+}
+
+int ginsim_incl_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_incl_params* p) {
+    REQUIRE(c, "incl_run: NULL argument");
+    const int rc = check_incl_params(mc, p);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_incl(*mc, *p, c->stream, nullptr, 0));
     return GINSIM_OK;
 }
 

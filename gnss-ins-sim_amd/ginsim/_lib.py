@@ -77,6 +77,19 @@ class McParams(C.Structure):
                 ('vib_accel', Vibration), ('vib_gyro', Vibration)]
 
 
+INCL_MAHONY = 1
+INCL_TILT = 2
+
+
+class InclParams(C.Structure):
+    """ginsim_incl_params: MahonyFilter / TiltAcc over a batch of runs (csrc/inclinometer.hip)."""
+    _fields_ = [('algo_mask', C.c_int32), ('reserved', C.c_int32), ('dt', C.c_double),
+                ('kp_high', C.c_double), ('kp_low', C.c_double), ('ki_high', C.c_double), ('ki_low', C.c_double),
+                ('innovation_limit', C.c_double), ('run_list', C.c_void_p), ('n_list', C.c_int64),
+                ('bias_in', C.c_void_p), ('bias_out', C.c_void_p), ('out_quat', C.c_void_p * 2), ('out_euler', C.c_void_p * 2),
+                ('out_wb', C.c_void_p), ('out_ab', C.c_void_p), ('out_end', C.c_void_p * 2), ('out_proc', C.c_void_p * 2)]
+
+
 class PathgenParams(C.Structure):
     _fields_ = [('ini_pva', C.c_double * 9), ('mobility', C.c_double * 3), ('fs', C.c_double),
                 ('fs_gps', C.c_double), ('ref_frame', C.c_int32), ('enable_gps', C.c_int32),
@@ -132,6 +145,9 @@ _SIGS = {
     'ginsim_mc_run': (C.c_int, [C.c_void_p, C.POINTER(McParams)]),
     'ginsim_mc_variant': (C.c_int, [C.POINTER(McParams), C.POINTER(C.c_int32)]),
     'ginsim_mc_kernel_name': (C.c_int, [C.POINTER(McParams), C.c_char_p, C.c_size_t]),
+    'ginsim_incl_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(InclParams)]),
+    'ginsim_incl_variant': (C.c_int, [C.POINTER(McParams), C.POINTER(InclParams), C.POINTER(C.c_int32)]),
+    'ginsim_incl_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(InclParams), C.c_char_p, C.c_size_t]),
     'ginsim_end_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     'ginsim_end_stats_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     'ginsim_end_stats_finish': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Stats)]),

@@ -161,7 +161,7 @@ class InsDataMgr(object):
         if ned:
             units, out_units = list(_XYZ), list(_XYZ)
         on_device = self._mc is not None and data_name in _END_SLICE
-        names = list(self._mc.algo_names) if on_device else []
+        names = (list(self._mc.names_of(data_name)) if hasattr(self._mc, 'names_of') else list(self._mc.algo_names)) if on_device else []
         host = self._host_part(src.data, names)                 # {key: array} (or {None: array}) computed on the host
         end_point = err_stats_start == -1
         stat = None

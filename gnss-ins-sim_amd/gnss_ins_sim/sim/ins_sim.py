@@ -118,6 +118,14 @@ class _McResults(object):
         self._make_kept_job, self._block_runs = make_kept_job, int(block_runs)
         self.exchange = None                # which exchange merged the records: 'abi', 'torch (...)', None = one process
 
+    fused_names = None      # set by Sim when inclinometer plugins are present: only these produce 'pos' and 'vel'
+
+    def names_of(self, data_name):
+        """The algorithms whose output holds `data_name`: every one for 'att_euler', the fused free integrations for 'pos' / 'vel'."""
+        if self.fused_names is None or data_name == 'att_euler':
+            return list(self.algo_names)
+        return list(self.fused_names)
+
     def job_of(self, name):
         return self.jobs[self.algo_names.index(name)]
 
@@ -187,8 +195,9 @@ class _McResults(object):
         from .sim_data import RunStats
         sl = {'att_euler': slice(0, 3), 'pos': slice(3, 6), 'vel': slice(6, 9)}[data_name]
         parts = {'max': [], 'avg': [], 'std': []}
+        wanted = self.names_of(data_name)
         for idx, name in enumerate(self.algo_names):
-            if self.jobs[idx] is None:
+            if self.jobs[idx] is None or name not in wanted:
                 continue
             arr = self._process_array(idx, start_sample, ned)
             for row, s in enumerate(('max', 'avg', 'std')):
@@ -406,7 +415,12 @@ class Sim(object):
         algos = self.amgr.algo or []
         kinds = [getattr(a, 'mc_algo', None) for a in algos]
         fused = [i for i, k in enumerate(kinds) if k in ('free', 'odo')]
-        hosted = [i for i in range(len(algos)) if i not in fused]
+        # the inclinometer plugins of demo_algorithms.inclinometer_device: their own kernel, same seed and run ids
+        incl = [i for i, k in enumerate(kinds) if k in ('mahony', 'tilt')]
+        hosted = [i for i in range(len(algos)) if i not in fused and i not in incl]
+        if incl and self.precision != 'f64':
+            raise NotImplementedError("the inclinometer plugins (MahonyFilter, TiltAcc of demo_algorithms.inclinometer_device) run "
+                                      "in fp64 only: use precision='f64'")
         for i in fused:
             if kinds[i] == 'odo' and not self.imu.odo:
                 raise ValueError("algorithm %d needs 'odo' but the IMU model has no odometer" % i)
@@ -434,16 +448,24 @@ class Sim(object):
         rank, world, group, xdev = self._dist()
         first, count = distributed.shard(self.sim_count, world, rank)
         seed = self._pick_seed(group, xdev)
-        ctx = self._context(self.sim_count * n, group is not None)     # one GPU (Context) or several (multi.DeviceSet)
+        if incl and group is not None:
+            raise ValueError('the runs of a MahonyFilter are a chain (each starts from the gyro_bias the previous one ended with), '
+                             'which does not cross torch.distributed ranks: run a Sim with inclinometer plugins in one process')
+        # an inclinometer chain runs on one device: never spread it automatically
+        ctx = self._context(0 if incl else self.sim_count * n, group is not None)     # one GPU (Context) or several (multi.DeviceSet)
         from ginsim import multi
         spread = isinstance(ctx, multi.DeviceSet)
+        if incl and spread:
+            raise ValueError('the runs of a MahonyFilter are a chain (each starts from the gyro_bias the previous one ended with), '
+                             'which does not cross devices: give Sim(device=...) one GPU, not devices=... (or $GINSIM_DEVICES)')
         ndev = len(ctx) if spread else 1
         if spread and group is not None:
             raise ValueError('Sim(devices=...) spreads the runs of ONE process over several GPUs; under torch.distributed the '
                              'split is one process per GPU (drop devices=, or do not initialise a process group)')
         new_job = (lambda *a, **kw: multi.JobSet(ctx, *a, **kw)) if spread else (lambda *a, **kw: ginsim.MonteCarloJob(ctx, *a, **kw))
         per_sample = 48 + (8 if self.imu.odo else 0) + 72 * len(fused) + (24 if self.imu.magnetometer else 0) + \
-            (48.0 * raw['gps'].shape[0] / n if self.imu.gps else 0)
+            (48.0 * raw['gps'].shape[0] / n if self.imu.gps else 0) + \
+            sum(104 if kinds[i] == 'mahony' else 56 for i in incl)
         keep = self.keep_trajectories
         if keep == 'auto':
             # decided on the LARGEST share of any rank / device (rank 0's), so that every rank takes the same decision -- the
@@ -554,6 +576,7 @@ class Sim(object):
             self.placement = sensor_job.placement() if sensor_job is not None and hasattr(sensor_job, 'placement') else None
         for i in fused:                         # FreeIntegration.run_times accounting (free_integration.py:69)
             algos[i].run_times += self.sim_count
+        incl_groups = self._run_inclinometers(ctx, algos, kinds, incl, truth, vib, seed, first, count, kcount, keep, sample_of)
 
         # expose device series through the data manager
         runs = range(first, first + kcount)
@@ -581,15 +604,20 @@ class Sim(object):
         if self.amgr.algo is not None:
             d.set_algo_output(self.amgr.output)
         names = [self.amgr.get_algo_name(i) for i in fused]
-        if fused and kcount > 0:
+        if incl:
+            self._inclinometer_views(kept_jobs, fused, kinds, names, incl_groups, first, kcount)
+        elif fused and kcount > 0:
             for out_name, comp in (('att_euler', 0), ('pos', 1), ('vel', 2)):
                 d.add_data(out_name, self._output_view(kept_jobs, fused, kinds, names, comp, first, kcount))
             d.add_data('att_quat', self._output_view(kept_jobs, fused, kinds, names, 0, first, kcount, quat=True))
         elif fused:
             for out_name in ('att_euler', 'pos', 'vel'):       # stats-only: names are known, series are not kept
                 d.add_data(out_name, {})
-        if fused:
+        if fused or incl:
             def make_ps_job(idx, start_sample, ned):
+                if idx >= len(fused):           # an inclinometer: one pass from the converged initial biases
+                    g = incl_groups[idx - len(fused)][1]
+                    return g['make'](count, False, start_bias=g['job'].initial_biases(), proc_first=start_sample)
                 i = fused[idx]
                 return make_job(group_of[i], [kinds[i]], count, False, False, proc_first=start_sample,
                                 proc_ned=ned, end_ned=False)
@@ -602,9 +630,13 @@ class Sim(object):
                                keep_sensors=False, keep_traj=True, precision=self.precision, **vib)
             esize = 4 if self.precision == 'f32' else 8
             block_runs = ndev * max(256, int(self.max_device_bytes // (9 * esize * n)) // 256 * 256)
-            self.mc = _McResults([stats_jobs.get(i) for i in fused], [kept_jobs.get(i) for i in fused], names,
-                                 [kinds[i] for i in fused], first, count, self.sim_count, group, xdev, make_ps_job, ctx=ctx,
-                                 make_kept_job=make_kept_job, block_runs=block_runs, ned_from_traj=not end_ned)
+            inames = [self.amgr.get_algo_name(i) for i, _ in incl_groups]
+            self.mc = _McResults([stats_jobs.get(i) for i in fused] + [g.get('job') for _, g in incl_groups],
+                                 [kept_jobs.get(i) for i in fused] + [g.get('kept') for _, g in incl_groups], names + inames,
+                                 [kinds[i] for i in fused] + [kinds[i] for i, _ in incl_groups], first, count, self.sim_count, group,
+                                 xdev, make_ps_job, ctx=ctx, make_kept_job=make_kept_job, block_runs=block_runs,
+                                 ned_from_traj=not end_ned)
+            self.mc.fused_names = names
             self.mc.devices = list(ctx.devices) if spread else None
             self.mc.kept_block = any(isinstance(j, _BlockAndRest) for j in stats_jobs.values())    # the kept runs rode along
             d.set_mc_results(self.mc)
@@ -632,6 +664,110 @@ class Sim(object):
                         d.add_data(oname, ChainSeries(cur, merged[j]))
                     else:
                         d.add_data(oname, merged[j])
+
+    def _run_inclinometers(self, ctx, algos, kinds, incl, truth, vib, seed, first, count, kcount, keep, sample_of):
+        """The inclinometer plugins (kinds 'mahony' / 'tilt'): one InclinometerJob per pair of one MahonyFilter and one TiltAcc (both
+        bits in one launch), the chain of the MahonyFilter's runs solved by its passes; the first kcount runs kept.  Leaves every
+        plugin object as the reference's loop leaves it: gyro_bias, q, quat, wb, ab (Mahony), results and q (tilt) of the last run.
+        Returns [(algorithm index, group)] in plugin order."""
+        import ginsim
+        fs_imu = self.fs[0]
+        groups = []
+        for i in incl:
+            for g in groups:
+                if kinds[i] not in g['kinds']:
+                    g['kinds'].append(kinds[i])
+                    g['idx'].append(i)
+                    break
+            else:
+                groups.append({'kinds': [kinds[i]], 'idx': [i]})
+        pf = sample_of(self.stats_start) if self.stats_start not in (None, -1) else 0
+        for g in groups:
+            mah = algos[g['idx'][g['kinds'].index('mahony')]] if 'mahony' in g['kinds'] else None
+            g['passes'] = 0
+
+            def make(runs_, keep_, start_bias=None, stats=True, proc_first=pf, off=0, g=g, mah=mah):
+                return ginsim.InclinometerJob(ctx, fs_imu, truth, self.imu.accel_err, self.imu.gyro_err, runs_, algos=tuple(g['kinds']),
+                                              gains=mah.gains() if mah is not None else None, dt=1.0 / fs_imu,
+                                              bias0=mah.gyro_bias if mah is not None else (0.0, 0.0, 0.0), start_bias=start_bias,
+                                              seed=seed, run_offset=first + off, stats=stats, proc_first=proc_first, keep=keep_,
+                                              placed=self.placed, **vib)
+            g['make'] = make
+            if count <= 0:
+                continue
+            job = g['job'] = make(count, bool(keep)).run()
+            g['passes'] = job.passes
+            if keep:
+                g['kept'] = job
+            elif kcount > 0:
+                g['kept'] = make(kcount, True, start_bias=job.initial_biases()[:kcount], stats=False).run()
+            # the last run's series: the plugin objects hold them after the reference's loop
+            last = g.get('kept') if (keep or kcount == count) else None
+            if last is None:
+                last = make(1, True, start_bias=job.initial_biases()[-1:], stats=False, off=count - 1).run()
+                pos = 0
+            else:
+                pos = count - 1
+            if mah is not None:
+                mah.finish(last.series('quat_mahony', [pos])[0], last.series('wb', [pos])[0], last.series('ab', [pos])[0], 1.0 / fs_imu)
+            if 'tilt' in g['kinds']:
+                algos[g['idx'][g['kinds'].index('tilt')]].finish(last.series('quat_tilt', [pos])[0])
+            if last is not g.get('kept'):
+                last.release()
+        self.passes = [g['passes'] for g in groups]
+        out = []
+        for g in groups:
+            for i in g['idx']:
+                out.append((i, g))
+        return sorted(out, key=lambda t: t[0])
+
+    def _inclinometer_views(self, kept_jobs, fused, kinds, names, incl_groups, first, count):
+        """att_euler / att_quat over the fused and the inclinometer plugins, wb / ab over the MahonyFilters: device views keyed
+        '<algo>_<run>' (the first `count` runs), or empty mappings when no run is kept (statistics only)."""
+        d = self.dmgr
+        if count <= 0:
+            for out_name in ('att_euler', 'att_quat') + (('pos', 'vel') if fused else ()):
+                d.add_data(out_name, {})
+            if any(kinds[i] == 'mahony' for i, _ in incl_groups):
+                d.add_data('wb', {})
+                d.add_data('ab', {})
+            return
+        fused_order = [(names[k], kept_jobs[i], kinds[i]) for k, i in enumerate(fused)]
+        inc_order = [(self.amgr.get_algo_name(i), g['kept'], kinds[i]) for i, g in incl_groups]
+
+        def fused_fetch(job, kind, comp, quat):
+            return lambda pos: (lambda x: np.stack([attitude.euler2quat(v) for v in x]) if quat else x)(job.trajectories(kind, pos)[comp])
+
+        def view(entries):
+            def locate(key):
+                if not isinstance(key, str) or '_' not in key:
+                    return None
+                nm, _, r = key.rpartition('_')
+                if not r.isdigit() or not (first <= int(r) < first + count):
+                    return None
+                for a, (name, _) in enumerate(entries):
+                    if name == nm:
+                        return a * count + int(r) - first
+                return None
+
+            def fetch(positions):
+                return np.stack([entries[a][1]([r])[0] for a, r in (divmod(p, count) for p in positions)])
+            return McSeries(count * len(entries), fetch, key_of=lambda p: entries[p // count][0] + '_' + str(first + p % count),
+                            pos_of=locate)
+
+        ser = lambda job, nm: (lambda pos, j=job: j.series(nm, pos))
+        for out_name, comp in (('att_euler', 0), ('pos', 1), ('vel', 2)):
+            ents = [(nm, fused_fetch(j, k, comp, False)) for nm, j, k in fused_order]
+            if out_name == 'att_euler':
+                ents += [(nm, ser(j, 'euler_' + k)) for nm, j, k in inc_order]
+            if ents:
+                d.add_data(out_name, view(ents))
+        d.add_data('att_quat', view([(nm, fused_fetch(j, k, 0, True)) for nm, j, k in fused_order] +
+                                    [(nm, ser(j, 'quat_' + k)) for nm, j, k in inc_order]))
+        mah = [(nm, j) for nm, j, k in inc_order if k == 'mahony']
+        if mah:
+            d.add_data('wb', view([(nm, ser(j, 'wb')) for nm, j in mah]))
+            d.add_data('ab', view([(nm, ser(j, 'ab')) for nm, j in mah]))
 
     def _output_view(self, jobs_by_algo, fused, kinds, names, comp, first, count, quat=False):
         """Mapping '<algo>_<run>' -> (n,3) (or (n,4) quaternion) over the trajectory buffers of all fused plugins."""

@@ -296,6 +296,43 @@ int ginsim_mc_variant(const ginsim_mc_params* p, int32_t* variant);
  * true>"), written by the same dispatch code that launches it -- profiles and bench.py attribute to what really runs. */
 int ginsim_mc_kernel_name(const ginsim_mc_params* p, char* buf, size_t cap);
 
+/* ---- inclinometers: demo_algorithms/inclinometer_mahony.py::MahonyFilter (:50-151) and inclinometer_acc.py::TiltAcc (:37-56)
+ *      over a batch of Monte-Carlo runs, one lane per run (csrc/inclinometer.hip).  Added without a change of
+ *      GINSIM_ABI_VERSION: nothing existing moved.
+ *      The sensors come from the ginsim_mc_params given next to these parameters, read exactly as ginsim_mc_run reads them:
+ *      n, runs, run_offset, seed, accel, gyro, ref_accel, ref_gyro, vib_accel, vib_gyro (types 1 and 2; 'psd' is refused) in
+ *      generate mode -- run r then sees bit for bit the accelerometer and gyroscope samples of run r of a ginsim_mc_run with the
+ *      same seed --, or given_sensors with in_accel / in_gyro ([3][n][runs]).  ref_nav ([n][9], attitude in columns 0-2) and
+ *      proc_first serve the statistics; block_threads the workgroup size (0 = 256).  Every other field is ignored.
+ *      The Mahony filter of a run starts from bias_in (its gyro_bias) with q = (1, 0, 0, 0), err_int = 0 and ini = 0, as the
+ *      reference's MahonyFilter after reset() does when the previous run's final state is that bias; q and err_int are rebuilt at
+ *      the first sample with a non-zero accelerometer.  Chaining runs (run r starts from run r-1's final bias) is the caller's. */
+#define GINSIM_INCL_MAHONY 1
+#define GINSIM_INCL_TILT   2
+typedef struct {
+    int32_t  algo_mask;       /* GINSIM_INCL_* bits; both filters see the same sensor realisation */
+    int32_t  reserved;        /* 0 */
+    double   dt;              /* MahonyFilter.dt (1 / fs of the plugin's input) */
+    double   kp_high, kp_low, ki_high, ki_low, innovation_limit;   /* MahonyFilter.kp_acc_high ... innovationLimit */
+    const int64_t* run_list;  /* device [n_list] or NULL: lane i integrates run run_list[i] (ids < runs); NULL: runs 0 .. n_list-1 */
+    int64_t  n_list;          /* lanes of the launch */
+    const double* bias_in;    /* device [3][runs]: the Mahony filter's gyro_bias at the start of each run (needed with MAHONY) */
+    double*  bias_out;        /* device [3][runs] or NULL: its gyro_bias at the end of each launched run */
+    double*  out_quat[2];     /* per algorithm bit (0 Mahony, 1 tilt): [4][n][runs] att_quat, or NULL */
+    double*  out_euler[2];    /* per algorithm bit: [3][n][runs] att_euler = quat2euler zyx of att_quat, or NULL */
+    double*  out_wb;          /* Mahony: [3][n][runs] gyro_bias after each sample ('wb'), or NULL */
+    double*  out_ab;          /* Mahony: [3][n][runs] the limited innovation acc_err ('ab'), or NULL */
+    double*  out_end[2];      /* per algorithm bit: [3][runs] att_euler error at the last sample, wrapped to [-pi, pi], or NULL */
+    double*  out_proc[2];     /* per algorithm bit: [3][3][runs] max|e|, mean, std (ddof 0) of the att_euler error over samples
+                               * >= proc_first, or NULL */
+} ginsim_incl_params;
+
+int ginsim_incl_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const ginsim_incl_params* p);
+/* 0: generated sensors, 1: given sensors */
+int ginsim_incl_variant(const ginsim_mc_params* mc, const ginsim_incl_params* p, int32_t* variant);
+/* the NAME of the kernel ginsim_incl_run launches, as rocprofv3 reports it (e.g. "ginsim::incl_kernel<3, false, false>") */
+int ginsim_incl_kernel_name(const ginsim_mc_params* mc, const ginsim_incl_params* p, char* buf, size_t cap);
+
 /* ---- auxiliary sensors of a Monte-Carlo batch: pathgen.gps_gen (pathgen.py:596-625) and pathgen.mag_gen (:643-661).
  *      FreeIntegration does not consume them, so they are generated only when they are to be kept. */
 typedef struct {
