@@ -11,6 +11,8 @@ through ONE launch of the fused HIP kernel (noise injection + mechanisation + en
 Sensor series and algorithm outputs stay in HBM; ``dmgr.<series>.data`` are mapping views that pull a run
 to the host only when it is indexed.  With ``torch.distributed`` initialised (one process per GPU) the runs
 are sharded across ranks and the end-point statistics are combined with one all-reduce.
+``run`` is a sequence of steps (Sim._run_monte_carlo): every decision that needs no device is taken by plan_monte_carlo (a
+_Plan), every device job is built by the run's _Jobs factory, and the steps pass both along.
 
 Keyword-only extras (defaults keep the reference behaviour):
     seed               64-bit Philox key.  None: drawn from ``np.random`` (so ``np.random.seed(s)`` before
@@ -51,6 +53,7 @@ import math
 import os
 import sys
 import time
+from collections import namedtuple
 
 import numpy as np
 
@@ -206,6 +209,180 @@ class _McResults(object):
 
     def run_of_key(self, key):
         return int(str(key).rsplit('_', 1)[-1]) if isinstance(key, str) else int(key)
+
+
+# Fused plugins that share one launch: the same initial states, earth_rot and call count (`first`), one plugin per kind
+_FusedGroup = namedtuple('_FusedGroup', 'ini earth_rot first kinds idx')
+
+
+class _InclGroup(object):
+    """One MahonyFilter and / or one TiltAcc (the plugin objects, or None) in one InclinometerJob: `job` over all runs of this rank,
+    `kept` the job whose series are materialised (the same object when everything is kept), `passes` the chain took."""
+    __slots__ = ('kinds', 'idx', 'mahony', 'tilt', 'job', 'kept', 'passes')
+
+    def __init__(self):
+        self.kinds, self.idx, self.mahony, self.tilt, self.job, self.kept, self.passes = [], [], None, None, None, None, 0
+
+
+class _Launched(object):
+    """The fused jobs of one run(): by algorithm index the statistics job over all runs of this rank and the job whose series are
+    materialised; `sensor_job` is the first job launched with keep_sensors (every launch draws the same noise: counter RNG)."""
+
+    def __init__(self):
+        self.stats, self.kept, self.sensor_job = {}, {}, None
+
+    def launch(self, job, sensors=False):
+        job.launch()
+        if sensors:
+            self.sensor_job = self.sensor_job or job
+        return job
+
+
+_Plan = namedtuple('_Plan', 'fused incl hosted groups first count spread ndev per_sample keep kcount online end_ned ride block_runs '
+                            'proc_first')
+
+
+def _sample_of(t_axis, start_s):
+    hit = np.where(t_axis >= max(float(start_s), 0.0))[0]
+    return int(hit[0]) if hit.shape[0] else 0
+
+
+def _plugin_roles(sim, kinds):
+    """(fused, incl, hosted): the indices of the plugins inside the fused kernel, of the inclinometer plugins and of the others."""
+    # which plugins are inside the fused kernel
+    fused = [i for i, k in enumerate(kinds) if k in ('free', 'odo')]
+    # the inclinometer plugins of demo_algorithms.inclinometer_device: their own kernel, same seed and run ids
+    incl = [i for i, k in enumerate(kinds) if k in ('mahony', 'tilt')]
+    hosted = [i for i in range(len(kinds)) if i not in fused and i not in incl]
+    if incl and sim.precision != 'f64':
+        raise NotImplementedError("the inclinometer plugins (MahonyFilter, TiltAcc of demo_algorithms.inclinometer_device) run "
+                                  "in fp64 only: use precision='f64'")
+    for i in fused:
+        if kinds[i] == 'odo' and not sim.imu.odo:
+            raise ValueError("algorithm %d needs 'odo' but the IMU model has no odometer" % i)
+    return fused, incl, hosted
+
+
+def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group, place):
+    """Every decision of one Sim.run() that needs no device, as a _Plan: which runs are this rank's (`first`, `count`), whether
+    all of them are materialised (`keep`) or the first `kcount`, the launch groups of the fused plugins, what the statistics-only
+    launches accumulate (`online`: the process window from sample `proc_first`; `end_ned`), whether the kept runs `ride` along as
+    the first workgroup of the batch, and the runs per block of an fp32 re-integration.  `sim` is read for its configuration only;
+    `roles` is _plugin_roles(); `t_axis` the time of every sample, `gps_rows` the length of the GPS series; `in_group`: a
+    torch.distributed process group exists; `place(work, in_group)` says (spread over several devices?, how many) and is asked
+    between the refusals as Sim._context always was (it may print the auto-spread notice and make a DeviceSet)."""
+    from ginsim import distributed
+    fused, incl, hosted = roles
+    imu, n = sim.imu, t_axis.shape[0]
+    kinds = [getattr(a, 'mc_algo', None) for a in algos]
+    first, count = distributed.shard(sim.sim_count, world, rank)
+    if incl and in_group:
+        raise ValueError('the runs of a MahonyFilter are a chain (each starts from the gyro_bias the previous one ended with), '
+                         'which does not cross torch.distributed ranks: run a Sim with inclinometer plugins in one process')
+    # an inclinometer chain runs on one device: never spread it automatically
+    spread, ndev = place(0 if incl else sim.sim_count * n, in_group)
+    if incl and spread:
+        raise ValueError('the runs of a MahonyFilter are a chain (each starts from the gyro_bias the previous one ended with), '
+                         'which does not cross devices: give Sim(device=...) one GPU, not devices=... (or $GINSIM_DEVICES)')
+    if spread and in_group:
+        raise ValueError('Sim(devices=...) spreads the runs of ONE process over several GPUs; under torch.distributed the '
+                         'split is one process per GPU (drop devices=, or do not initialise a process group)')
+    per_sample = 48 + (8 if imu.odo else 0) + 72 * len(fused) + (24 if imu.magnetometer else 0) + \
+        (48.0 * gps_rows / n if imu.gps else 0) + \
+        sum(104 if kinds[i] == 'mahony' else 56 for i in incl)
+    keep = sim.keep_trajectories
+    if keep == 'auto':
+        # decided on the LARGEST share of any rank / device (rank 0's), so that every rank takes the same decision -- the
+        # ranks enter collectives that depend on it
+        largest = -(-distributed.shard(sim.sim_count, world, 0)[1] // ndev)
+        keep = per_sample * n * max(largest, 1) <= sim.max_device_bytes
+    if hosted and not keep:
+        raise ValueError('plugins outside the fused kernel need the sensor series: use keep_trajectories=True')
+    keep = bool(keep)
+    # one launch per distinct (initial states, earth_rot); identical noise in every launch (counter RNG)
+    groups = []
+    for i in fused:
+        a = algos[i]
+        for g in groups:
+            if np.array_equal(g.ini, a.ini) and g.earth_rot == a.earth_rot and kinds[i] not in g.kinds and g.first == a.run_times:
+                break
+        else:
+            g = _FusedGroup(a.ini, a.earth_rot, a.run_times, [], [])
+            groups.append(g)
+        g.kinds.append(kinds[i])
+        g.idx.append(i)
+    # Which runs have their series materialised: all of this rank's runs (keep), or the first keep_runs of them next to
+    # a stats-only launch over all runs (the counter RNG makes the small launch reproduce exactly those runs).
+    kcount = count if keep else min(sim.keep_runs, count)
+    f64 = sim.precision == 'f64'
+    window = sim.stats_start not in (None, -1)
+    online = (not keep) and f64 and window
+    end_ned = (not keep) and f64 and sim.ref_frame == 0
+    # The kept runs as the FIRST WORKGROUP of the batch (one process, one GPU, fp64): a block of KEPT_BLOCK runs with
+    # everything materialised on a sibling context, at the same time as the statistics-only launch over the other runs
+    # (_BlockAndRest).  Otherwise: one small launch for them in front of the launch over all runs.
+    ride = (0 < kcount <= KEPT_BLOCK < count and f64 and not in_group and not spread and
+            per_sample * n * KEPT_BLOCK <= sim.max_device_bytes)
+    esize = 4 if sim.precision == 'f32' else 8
+    block_runs = ndev * max(256, int(sim.max_device_bytes // (9 * esize * n)) // 256 * 256)
+    proc_first = _sample_of(t_axis, sim.stats_start) if window and (online or incl) else 0
+    return _Plan(fused, incl, hosted, groups, first, count, spread, ndev, per_sample, keep, kcount, online, end_ned, ride,
+                 block_runs, proc_first)
+
+
+class _Jobs(object):
+    """What every device job of one run() shares (sampling rate, frame, truth, the IMU error models, seed, this rank's first run,
+    precision, placement, the two vibration definitions, one context or a DeviceSet), and the one place where a job is built from
+    what differs."""
+
+    def __init__(self, sim, ctx, spread, truth, vib, seed, first):
+        import ginsim
+        from ginsim import multi
+        self.sim, self.ctx, self.truth, self.vib, self.seed, self.first = sim, ctx, truth, vib, seed, first
+        self.fused_class = multi.JobSet if spread else ginsim.MonteCarloJob
+        self.aux_class = multi.AuxJobSet if spread else ginsim.AuxSensorJob
+
+    def fused(self, group, kinds, runs, off=0, ctx=None, keep_sensors=False, keep_traj=False, **kw):
+        """A MonteCarloJob (JobSet) of `runs` runs from run `off` of this rank, for `kinds` of launch group `group`, on `ctx`
+        (default: the run's own).  kw: proc_first / proc_ned / end_ned; and precision / placed / earth_rot / ini_first where a
+        call site does not follow the Sim's and the group's (each such site says so)."""
+        sim = self.sim
+        kw = dict(dict(precision=sim.precision, placed=sim.placed, earth_rot=group.earth_rot,
+                       ini_first=group.first + self.first + off), **kw)
+        return self.fused_class(ctx or self.ctx, sim.fs[0], sim.ref_frame, self.truth, sim.imu.accel_err, sim.imu.gyro_err, group.ini,
+                                runs=runs, algos=tuple(kinds), odo_err=sim.imu.odo_err, seed=self.seed,
+                                run_offset=self.first + off, keep_sensors=keep_sensors, keep_traj=keep_traj, **self.vib, **kw)
+
+    def inclinometer(self, group, runs, keep, start_bias=None, stats=True, proc_first=0, off=0):
+        """An InclinometerJob of `runs` runs from run `off` of this rank for the plugins of `group`; the MahonyFilter's gains and
+        gyro_bias are read now."""
+        import ginsim
+        sim, mah = self.sim, group.mahony
+        return ginsim.InclinometerJob(self.ctx, sim.fs[0], self.truth, sim.imu.accel_err, sim.imu.gyro_err, runs, algos=tuple(group.kinds),
+                                      gains=mah.gains() if mah is not None else None, dt=1.0 / sim.fs[0],
+                                      bias0=mah.gyro_bias if mah is not None else (0.0, 0.0, 0.0), start_bias=start_bias,
+                                      seed=self.seed, run_offset=self.first + off, stats=stats, proc_first=proc_first, keep=keep,
+                                      placed=sim.placed, **self.vib)
+
+
+def _keyed_view(entries, first, count):
+    """Mapping '<algo>_<run>' -> the series of that run over `entries` = [(algorithm name, fetch(positions in the kept job) ->
+    (k, n, c))], for runs first .. first + count - 1."""
+    def locate(key):
+        if not isinstance(key, str) or '_' not in key:
+            return None
+        nm, _, r = key.rpartition('_')
+        if not r.isdigit() or not (first <= int(r) < first + count):
+            return None
+        for a, (name, _) in enumerate(entries):
+            if name == nm:
+                return a * count + int(r) - first
+        return None
+
+    def fetch(positions):
+        return np.stack([entries[a][1]([r])[0] for a, r in (divmod(p, count) for p in positions)])
+    return McSeries(count * len(entries), fetch, key_of=lambda p: entries[p // count][0] + '_' + str(first + p % count),
+                    pos_of=locate)
 
 
 class Sim(object):
@@ -368,10 +545,39 @@ class Sim(object):
         return seed
 
     def _run_monte_carlo(self):
-        import ginsim
-        from ginsim import workloads, distributed
         if self.imu is None:
             raise ValueError('an IMU model is required to generate sensor data from a motion definition')
+        algos = self.amgr.algo or []
+        kinds = [getattr(a, 'mc_algo', None) for a in algos]
+        truth, t_axis, gps_rows = self._truth_to_dmgr()
+        roles = _plugin_roles(self, kinds)
+        vib = self._vibration(t_axis.shape[0])
+        rank, world, group, xdev = self._dist()
+        seed = self._pick_seed(group, xdev)
+        plan = plan_monte_carlo(self, algos, roles, t_axis, gps_rows, rank, world, group is not None, self._place)
+        self.kept = plan.keep
+        jobs = _Jobs(self, self._ctx, plan.spread, truth, vib, seed, plan.first)
+        run = self._launch_fused(plan, jobs)
+        for i in plan.fused:                    # FreeIntegration.run_times accounting (free_integration.py:69)
+            algos[i].run_times += self.sim_count
+        incl_groups = self._run_inclinometers(plan, jobs, kinds)
+        self._sensor_views(plan, run.sensor_job)
+        self._aux_views(plan, jobs)
+        if self.amgr.algo is not None:
+            self.dmgr.set_algo_output(self.amgr.output)
+        name_of = self.amgr.get_algo_name
+        self._output_views(plan, [(name_of(i), run.kept.get(i), kinds[i]) for i in plan.fused],
+                           [(name_of(i), g.kept, kinds[i]) for i, g in incl_groups])
+        if plan.fused or plan.incl:
+            self._publish_results(plan, jobs, run, incl_groups, kinds, group, xdev)
+        if plan.hosted:
+            self._run_hosted(plan, algos, run.sensor_job)
+
+    def _truth_to_dmgr(self):
+        """The motion definition through the native path generator into the data manager (ins_sim.py:467-480).  Returns (the truth
+        dict every job takes, the time of every sample [s], the length of the GPS series)."""
+        import ginsim
+        from ginsim import workloads
         ini_pva, motion_def = workloads.parse_motion(self.data_src)
         mobility = self._parse_mode(self.mode)
         fs_imu = self.fs[0]
@@ -390,7 +596,6 @@ class Sim(object):
                              geo_mag_n=self.geo_mag_n if self.imu.magnetometer else None)
         d = self.dmgr
         nav, imu_t = raw['nav'], raw['imu']
-        n = nav.shape[0]
         d.add_data(d.time.name, nav[:, 0] / fs_imu)                       # ins_sim.py:467-480
         d.add_data(d.ref_pos.name, np.ascontiguousarray(nav[:, 1:4]))
         d.add_data(d.ref_vel.name, np.ascontiguousarray(nav[:, 4:7]))
@@ -410,23 +615,14 @@ class Sim(object):
                  'ref_vel': d.ref_vel.data, 'ref_att': d.ref_att_euler.data}
         if self.imu.odo:
             truth['ref_odo'] = d.ref_odo.data
+        return truth, nav[:, 0] / fs_imu, raw['gps'].shape[0] if self.imu.gps else 0
 
-        # which plugins are inside the fused kernel
-        algos = self.amgr.algo or []
-        kinds = [getattr(a, 'mc_algo', None) for a in algos]
-        fused = [i for i, k in enumerate(kinds) if k in ('free', 'odo')]
-        # the inclinometer plugins of demo_algorithms.inclinometer_device: their own kernel, same seed and run ids
-        incl = [i for i, k in enumerate(kinds) if k in ('mahony', 'tilt')]
-        hosted = [i for i in range(len(algos)) if i not in fused and i not in incl]
-        if incl and self.precision != 'f64':
-            raise NotImplementedError("the inclinometer plugins (MahonyFilter, TiltAcc of demo_algorithms.inclinometer_device) run "
-                                      "in fp64 only: use precision='f64'")
-        for i in fused:
-            if kinds[i] == 'odo' and not self.imu.odo:
-                raise ValueError("algorithm %d needs 'odo' but the IMU model has no odometer" % i)
-
-        # environment --> vibration parameters (ins_sim.py:482-489): 'random' and 'sinusoidal' models are terms of the kernels, a
-        # 'psd' model is a series per run and axis made on the device before the launch (ginsim_vib_psd_series)
+    def _vibration(self, n):
+        """environment --> vibration parameters (ins_sim.py:482-489): 'random' and 'sinusoidal' models are terms of the kernels, a
+        'psd' model is a series per run and axis made on the device before the launch (ginsim_vib_psd_series).  Returns the two
+        definitions as the keyword arguments of a job."""
+        import ginsim
+        fs_imu = self.fs[0]
         vib_acc = vib_gyro = None
         if self.env is not None:
             if 'acc' in self.env.keys():
@@ -438,362 +634,237 @@ class Sim(object):
                     ginsim.vibration(v, fs_imu, False)       # raises for a definition the kernels do not know
                 elif v is not None and self.precision != 'f64':
                     raise NotImplementedError("the 'psd' vibration (an (n, 4) env array) runs on the fp64 kernels only")
-        vib = dict(vib_accel=vib_acc, vib_gyro=vib_gyro)
         # A PSD given on the series' own frequency grid is halved IN PLACE by the reference at every run and axis
         # (time_series_from_psd.py:44-49: no copy is made when no interpolation is needed; the arrays are views of the caller's
         # env).  The device applies run r's factor 0.5^(r + 1); the arrays are left as the reference leaves them, after the run.
         self._psd_on_grid = [v for v in (vib_acc, vib_gyro) if v is not None and v['type'] == 'psd' and
                              (ginsim.psd_amplitudes(v, fs_imu, n) or (0, 0, False))[2]]
+        return dict(vib_accel=vib_acc, vib_gyro=vib_gyro)
 
-        rank, world, group, xdev = self._dist()
-        first, count = distributed.shard(self.sim_count, world, rank)
-        seed = self._pick_seed(group, xdev)
-        if incl and group is not None:
-            raise ValueError('the runs of a MahonyFilter are a chain (each starts from the gyro_bias the previous one ended with), '
-                             'which does not cross torch.distributed ranks: run a Sim with inclinometer plugins in one process')
-        # an inclinometer chain runs on one device: never spread it automatically
-        ctx = self._context(0 if incl else self.sim_count * n, group is not None)     # one GPU (Context) or several (multi.DeviceSet)
+    def _place(self, work, distributed):
+        """plan_monte_carlo's question: (spread over several devices?, how many).  The context is kept in self._ctx."""
         from ginsim import multi
-        spread = isinstance(ctx, multi.DeviceSet)
-        if incl and spread:
-            raise ValueError('the runs of a MahonyFilter are a chain (each starts from the gyro_bias the previous one ended with), '
-                             'which does not cross devices: give Sim(device=...) one GPU, not devices=... (or $GINSIM_DEVICES)')
-        ndev = len(ctx) if spread else 1
-        if spread and group is not None:
-            raise ValueError('Sim(devices=...) spreads the runs of ONE process over several GPUs; under torch.distributed the '
-                             'split is one process per GPU (drop devices=, or do not initialise a process group)')
-        new_job = (lambda *a, **kw: multi.JobSet(ctx, *a, **kw)) if spread else (lambda *a, **kw: ginsim.MonteCarloJob(ctx, *a, **kw))
-        per_sample = 48 + (8 if self.imu.odo else 0) + 72 * len(fused) + (24 if self.imu.magnetometer else 0) + \
-            (48.0 * raw['gps'].shape[0] / n if self.imu.gps else 0) + \
-            sum(104 if kinds[i] == 'mahony' else 56 for i in incl)
-        keep = self.keep_trajectories
-        if keep == 'auto':
-            # decided on the LARGEST share of any rank / device (rank 0's), so that every rank takes the same decision -- the
-            # ranks enter collectives that depend on it
-            largest = -(-distributed.shard(self.sim_count, world, 0)[1] // ndev)
-            keep = per_sample * n * max(largest, 1) <= self.max_device_bytes
-        if hosted and not keep:
-            raise ValueError('plugins outside the fused kernel need the sensor series: use keep_trajectories=True')
-        self.kept = bool(keep)
+        self._ctx = self._context(work, distributed)        # one GPU (Context) or several (multi.DeviceSet)
+        spread = isinstance(self._ctx, multi.DeviceSet)
+        return spread, len(self._ctx) if spread else 1
 
-        # one launch per distinct (initial states, earth_rot); identical noise in every launch (counter RNG)
-        groups = []
-        for i in fused:
-            a = algos[i]
-            for g in groups:
-                if np.array_equal(g['ini'], a.ini) and g['earth_rot'] == a.earth_rot and kinds[i] not in g['kinds'] \
-                        and g['first'] == a.run_times:
-                    g['kinds'].append(kinds[i])
-                    g['idx'].append(i)
-                    break
+    def _launch_fused(self, plan, jobs):
+        """The launches of the fused plugins' groups, each in one of three shapes, or the sensor-only launch of a Sim without
+        algorithm; then the wait for them.  Returns the _Launched record (empty for a rank without runs)."""
+        run = _Launched()
+        if plan.count <= 0:
+            return run
+        for g in plan.groups:
+            if plan.keep:
+                self._launch_all_kept(plan, jobs, g, run)
+            elif plan.ride:
+                self._launch_block_and_rest(plan, jobs, g, run)
             else:
-                groups.append({'ini': a.ini, 'earth_rot': a.earth_rot, 'kinds': [kinds[i]], 'idx': [i], 'first': a.run_times})
-        # Which runs have their series materialised: all of this rank's runs (keep), or the first keep_runs of them next to
-        # a stats-only launch over all runs (the counter RNG makes the small launch reproduce exactly those runs).
-        kcount = count if keep else min(self.keep_runs, count)
-        t_axis = nav[:, 0] / fs_imu
+                self._launch_kept_and_stats(plan, jobs, g, run)
+        if not plan.groups and plan.kcount > 0:      # Sim without algorithm: sensor generation only (demo_no_algo.py)
+            # kept from the parent on purpose and not yet judged: this job is built without the Sim's precision and placed, with
+            # earth_rot and ini_first at the constructor's defaults (there is no table of initial states)
+            run.launch(jobs.fused(_FusedGroup(None, True, 0, (), ()), (), plan.kcount, keep_sensors=True, precision='f64', placed=None,
+                               earth_rot=True, ini_first=0), sensors=True)
+        jobs.ctx.sync()
+        if self._side_ctx is not None:
+            self._side_ctx.sync()
+        sj = run.sensor_job
+        self.placement = sj.placement() if sj is not None and hasattr(sj, 'placement') else None
+        return run
 
-        def sample_of(start_s):
-            hit = np.where(t_axis >= max(float(start_s), 0.0))[0]
-            return int(hit[0]) if hit.shape[0] else 0
+    def _launch_all_kept(self, plan, jobs, g, run):
+        """Everything kept: one launch per group; it is the statistics job and the kept job of its plugins."""
+        job = run.launch(jobs.fused(g, g.kinds, plan.count, keep_sensors=run.sensor_job is None, keep_traj=True), sensors=True)
+        for i in g.idx:
+            run.stats[i] = run.kept[i] = job
 
-        def make_job(g, kinds_, runs_, keep_sens, keep_traj, **kw):
-            return new_job(fs_imu, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err,
-                           g['ini'], runs=runs_, algos=tuple(kinds_), odo_err=self.imu.odo_err,
-                           earth_rot=g['earth_rot'], seed=seed, run_offset=first,
-                           ini_first=g['first'] + first, keep_sensors=keep_sens, keep_traj=keep_traj,
-                           precision=self.precision, placed=self.placed, **vib, **kw)
+    def _launch_block_and_rest(self, plan, jobs, g, run):
+        """Statistics only, the kept runs riding along as the first workgroup of the batch (_BlockAndRest)."""
+        # which of the two contexts takes which launch: by where their launches start (_block_and_rest_contexts)
+        c_block, c_rest = self._block_and_rest_contexts(jobs.ctx, -(-(plan.count - KEPT_BLOCK) // KEPT_BLOCK))
+        kw = dict(proc_first=plan.proc_first) if plan.online else {}
+        for kinds_ in ([[k] for k in g.kinds] if plan.online else [list(g.kinds)]):
+            # placed=None is kept from the parent on purpose and not yet judged: the pair does not follow Sim(placed=)
+            blk = jobs.fused(g, kinds_, KEPT_BLOCK, ctx=c_block, keep_sensors=run.sensor_job is None, keep_traj=True,
+                             end_ned=plan.end_ned, placed=None, **kw)
+            rest = jobs.fused(g, kinds_, plan.count - KEPT_BLOCK, off=KEPT_BLOCK, ctx=c_rest, end_ned=plan.end_ned, placed=None,
+                              **kw)
+            run.launch(blk, sensors=True)
+            run.launch(rest)
+            both = _BlockAndRest(blk, rest)
+            for i, kind in zip(g.idx, g.kinds):
+                if kind in kinds_:
+                    run.stats[i], run.kept[i] = both, blk
 
-        f64 = self.precision == 'f64'
-        online = (not keep) and f64 and self.stats_start is not None and self.stats_start != -1
-        end_ned = (not keep) and f64 and self.ref_frame == 0
-        stats_jobs, kept_jobs, group_of = {}, {}, {}
-        sensor_job = None
-        if count > 0:
-            for g in groups:
-                for i in g['idx']:
-                    group_of[i] = g
-                if keep:
-                    job = make_job(g, g['kinds'], count, sensor_job is None, True)
-                    job.launch()
-                    sensor_job = sensor_job or job
-                    for i in g['idx']:
-                        stats_jobs[i] = kept_jobs[i] = job
-                    continue
-                # The kept runs as the FIRST WORKGROUP of the batch (one process, one GPU, fp64): a block of KEPT_BLOCK runs with
-                # everything materialised on a sibling context, at the same time as the statistics-only launch over the other runs
-                # (_BlockAndRest).  Otherwise: one small launch for them in front of the launch over all runs.
-                ride = (0 < kcount <= KEPT_BLOCK < count and f64 and group is None and not spread and
-                        per_sample * n * KEPT_BLOCK <= self.max_device_bytes)
-                if ride:
-                    # which of the two contexts takes which launch: by where their launches start (_block_and_rest_contexts)
-                    c_block, c_rest = self._block_and_rest_contexts(ctx, -(-(count - KEPT_BLOCK) // KEPT_BLOCK))
-                    per_launch = [[k] for k in g['kinds']] if online else [list(g['kinds'])]
-                    for kinds_ in per_launch:
-                        kw = dict(proc_first=sample_of(self.stats_start)) if online else {}
-                        blk = ginsim.MonteCarloJob(c_block, fs_imu, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, g['ini'],
-                                                   runs=KEPT_BLOCK, algos=tuple(kinds_), odo_err=self.imu.odo_err, earth_rot=g['earth_rot'],
-                                                   seed=seed, run_offset=first, ini_first=g['first'] + first,
-                                                   keep_sensors=sensor_job is None, keep_traj=True, precision=self.precision,
-                                                   end_ned=end_ned, **vib, **kw)
-                        rest = ginsim.MonteCarloJob(c_rest, fs_imu, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, g['ini'],
-                                                    runs=count - KEPT_BLOCK, algos=tuple(kinds_), odo_err=self.imu.odo_err,
-                                                    earth_rot=g['earth_rot'], seed=seed, run_offset=first + KEPT_BLOCK,
-                                                    ini_first=g['first'] + first + KEPT_BLOCK, precision=self.precision,
-                                                    end_ned=end_ned, **vib, **kw)
-                        blk.launch()
-                        rest.launch()
-                        sensor_job = sensor_job or blk
-                        both = _BlockAndRest(blk, rest)
-                        for i, kind in zip(g['idx'], g['kinds']):
-                            if kind in kinds_:
-                                stats_jobs[i], kept_jobs[i] = both, blk
-                    continue
-                if kcount > 0:  # the kept runs: one small launch
-                    kj = make_job(g, g['kinds'], kcount, sensor_job is None, True)
-                    kj.launch()
-                    sensor_job = sensor_job or kj
-                    for i in g['idx']:
-                        kept_jobs[i] = kj
-                if online:      # process-error statistics accumulated inside the kernel: one algorithm per launch
-                    for i, kind in zip(g['idx'], g['kinds']):
-                        stats_jobs[i] = make_job(g, [kind], count, False, False, proc_first=sample_of(self.stats_start),
-                                                 end_ned=end_ned)
-                        stats_jobs[i].launch()
-                else:
-                    job = make_job(g, g['kinds'], count, False, False, end_ned=end_ned)
-                    job.launch()
-                    for i in g['idx']:
-                        stats_jobs[i] = job
-            if not groups and kcount > 0:      # Sim without algorithm: sensor generation only (demo_no_algo.py)
-                sensor_job = new_job(fs_imu, self.ref_frame, truth, self.imu.accel_err,
-                                     self.imu.gyro_err, None, runs=kcount, algos=(), odo_err=self.imu.odo_err,
-                                     seed=seed, run_offset=first, keep_sensors=True, **vib)
-                sensor_job.launch()
-            ctx.sync()
-            if self._side_ctx is not None:
-                self._side_ctx.sync()
-            self.placement = sensor_job.placement() if sensor_job is not None and hasattr(sensor_job, 'placement') else None
-        for i in fused:                         # FreeIntegration.run_times accounting (free_integration.py:69)
-            algos[i].run_times += self.sim_count
-        incl_groups = self._run_inclinometers(ctx, algos, kinds, incl, truth, vib, seed, first, count, kcount, keep, sample_of)
+    def _launch_kept_and_stats(self, plan, jobs, g, run):
+        """Statistics only: one small launch for the kept runs (if any) in front of the launch(es) over all runs."""
+        if plan.kcount > 0:  # the kept runs: one small launch
+            kj = run.launch(jobs.fused(g, g.kinds, plan.kcount, keep_sensors=run.sensor_job is None, keep_traj=True), sensors=True)
+            for i in g.idx:
+                run.kept[i] = kj
+        if plan.online:      # process-error statistics accumulated inside the kernel: one algorithm per launch
+            for i, kind in zip(g.idx, g.kinds):
+                run.stats[i] = run.launch(jobs.fused(g, [kind], plan.count, proc_first=plan.proc_first, end_ned=plan.end_ned))
+        else:
+            job = run.launch(jobs.fused(g, g.kinds, plan.count, end_ned=plan.end_ned))
+            for i in g.idx:
+                run.stats[i] = job
 
-        # expose device series through the data manager
-        runs = range(first, first + kcount)
-        in_kept = lambda k: int(k) - first if isinstance(k, (int, np.integer)) and first <= int(k) < first + kcount else None
-        if sensor_job is not None:
-            def sens(name, squeeze=False, job=sensor_job):
-                return McSeries(kcount, lambda pos, j=job, nm=name: j.sensors(nm, pos)[..., None] if nm == 'odo'
-                                else j.sensors(nm, pos), key_of=lambda i: first + i, pos_of=in_kept, squeeze=squeeze)
-            d.add_data(d.accel.name, sens('accel'))
-            d.add_data(d.gyro.name, sens('gyro'))
-            if self.imu.odo:
-                d.add_data(d.odo.name, sens('odo', squeeze=True))
-        if kcount > 0 and (self.imu.gps or self.imu.magnetometer):      # ins_sim.py:497-503
-            aux = (multi.AuxJobSet if spread else ginsim.AuxSensorJob)(
-                ctx, kcount, seed=seed, run_offset=first,
-                ref_gps=d.ref_gps.data if self.imu.gps else None, gps_err=self.imu.gps_err, ref_frame=self.ref_frame,
-                ref_mag=d.ref_mag.data if self.imu.magnetometer else None, mag_err=self.imu.mag_err).run()
-            self._aux = aux
-            view = lambda nm: McSeries(kcount, lambda pos, a=aux, nm=nm: a.series(nm, pos), key_of=lambda i: first + i,
-                                       pos_of=in_kept)
-            if self.imu.gps:
-                d.add_data(d.gps.name, view('gps'))
-            if self.imu.magnetometer:
-                d.add_data(d.mag.name, view('mag'))
-        if self.amgr.algo is not None:
-            d.set_algo_output(self.amgr.output)
-        names = [self.amgr.get_algo_name(i) for i in fused]
-        if incl:
-            self._inclinometer_views(kept_jobs, fused, kinds, names, incl_groups, first, kcount)
-        elif fused and kcount > 0:
-            for out_name, comp in (('att_euler', 0), ('pos', 1), ('vel', 2)):
-                d.add_data(out_name, self._output_view(kept_jobs, fused, kinds, names, comp, first, kcount))
-            d.add_data('att_quat', self._output_view(kept_jobs, fused, kinds, names, 0, first, kcount, quat=True))
-        elif fused:
-            for out_name in ('att_euler', 'pos', 'vel'):       # stats-only: names are known, series are not kept
-                d.add_data(out_name, {})
-        if fused or incl:
-            def make_ps_job(idx, start_sample, ned):
-                if idx >= len(fused):           # an inclinometer: one pass from the converged initial biases
-                    g = incl_groups[idx - len(fused)][1]
-                    return g['make'](count, False, start_bias=g['job'].initial_biases(), proc_first=start_sample)
-                i = fused[idx]
-                return make_job(group_of[i], [kinds[i]], count, False, False, proc_first=start_sample,
-                                proc_ned=ned, end_ned=False)
-            def make_kept_job(idx, off, runs_):      # a block of this rank's runs, trajectories kept (fp32 statistics)
-                i = fused[idx]
-                g = group_of[i]
-                return new_job(fs_imu, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, g['ini'],
-                               runs=runs_, algos=(kinds[i],), odo_err=self.imu.odo_err, earth_rot=g['earth_rot'],
-                               seed=seed, run_offset=first + off, ini_first=g['first'] + first + off,
-                               keep_sensors=False, keep_traj=True, precision=self.precision, **vib)
-            esize = 4 if self.precision == 'f32' else 8
-            block_runs = ndev * max(256, int(self.max_device_bytes // (9 * esize * n)) // 256 * 256)
-            inames = [self.amgr.get_algo_name(i) for i, _ in incl_groups]
-            self.mc = _McResults([stats_jobs.get(i) for i in fused] + [g.get('job') for _, g in incl_groups],
-                                 [kept_jobs.get(i) for i in fused] + [g.get('kept') for _, g in incl_groups], names + inames,
-                                 [kinds[i] for i in fused] + [kinds[i] for i, _ in incl_groups], first, count, self.sim_count, group,
-                                 xdev, make_ps_job, ctx=ctx, make_kept_job=make_kept_job, block_runs=block_runs,
-                                 ned_from_traj=not end_ned)
-            self.mc.fused_names = names
-            self.mc.devices = list(ctx.devices) if spread else None
-            self.mc.kept_block = any(isinstance(j, _BlockAndRest) for j in stats_jobs.values())    # the kept runs rode along
-            d.set_mc_results(self.mc)
-        # plugins outside the fused kernel: the reference's per-run loop over host copies (user code)
-        if hosted:
-            # plugins that take the device-resident sensor series of all runs at once (demo_algorithms.allan_analysis)
-            on_device = [i for i in hosted if hasattr(algos[i], 'run_device') and sensor_job is not None and count > 0]
-            merged = [{} for _ in self.amgr.output]
-            for i in on_device:
-                name = self.amgr.get_algo_name(i)
-                per_run = algos[i].run_device(sensor_job, fs_imu)
-                for k, res in enumerate(per_run):
-                    for j, slot in enumerate(self.amgr.output_alloc[i]):
-                        merged[slot][name + '_' + str(first + k)] = res[j]
-            rest = [i for i in hosted if i not in on_device]
-            if rest:
-                inputs = d.get_data(self.amgr.input)
-                out = self.amgr.run_algo(inputs, list(runs), only=rest)
-                for j in range(len(merged)):
-                    merged[j].update(out[j])
-            for j, oname in enumerate(self.amgr.output):
-                if merged[j]:
-                    cur = d.get_data_all(oname).data if oname in d.available else None
-                    if isinstance(cur, McSeries):           # a fused plugin produced this output too: keep its device view
-                        d.add_data(oname, ChainSeries(cur, merged[j]))
-                    else:
-                        d.add_data(oname, merged[j])
-
-    def _run_inclinometers(self, ctx, algos, kinds, incl, truth, vib, seed, first, count, kcount, keep, sample_of):
+    def _run_inclinometers(self, plan, jobs, kinds):
         """The inclinometer plugins (kinds 'mahony' / 'tilt'): one InclinometerJob per pair of one MahonyFilter and one TiltAcc (both
         bits in one launch), the chain of the MahonyFilter's runs solved by its passes; the first kcount runs kept.  Leaves every
         plugin object as the reference's loop leaves it: gyro_bias, q, quat, wb, ab (Mahony), results and q (tilt) of the last run.
         Returns [(algorithm index, group)] in plugin order."""
-        import ginsim
-        fs_imu = self.fs[0]
+        algos, count, kcount, pf = self.amgr.algo or [], plan.count, plan.kcount, plan.proc_first
         groups = []
-        for i in incl:
-            for g in groups:
-                if kinds[i] not in g['kinds']:
-                    g['kinds'].append(kinds[i])
-                    g['idx'].append(i)
-                    break
-            else:
-                groups.append({'kinds': [kinds[i]], 'idx': [i]})
-        pf = sample_of(self.stats_start) if self.stats_start not in (None, -1) else 0
+        for i in plan.incl:
+            g = next((g for g in groups if kinds[i] not in g.kinds), None)
+            if g is None:
+                g = _InclGroup()
+                groups.append(g)
+            g.kinds.append(kinds[i])
+            g.idx.append(i)
+            setattr(g, kinds[i], algos[i])
         for g in groups:
-            mah = algos[g['idx'][g['kinds'].index('mahony')]] if 'mahony' in g['kinds'] else None
-            g['passes'] = 0
-
-            def make(runs_, keep_, start_bias=None, stats=True, proc_first=pf, off=0, g=g, mah=mah):
-                return ginsim.InclinometerJob(ctx, fs_imu, truth, self.imu.accel_err, self.imu.gyro_err, runs_, algos=tuple(g['kinds']),
-                                              gains=mah.gains() if mah is not None else None, dt=1.0 / fs_imu,
-                                              bias0=mah.gyro_bias if mah is not None else (0.0, 0.0, 0.0), start_bias=start_bias,
-                                              seed=seed, run_offset=first + off, stats=stats, proc_first=proc_first, keep=keep_,
-                                              placed=self.placed, **vib)
-            g['make'] = make
             if count <= 0:
                 continue
-            job = g['job'] = make(count, bool(keep)).run()
-            g['passes'] = job.passes
-            if keep:
-                g['kept'] = job
+            job = g.job = jobs.inclinometer(g, count, plan.keep, proc_first=pf).run()
+            g.passes = job.passes
+            if plan.keep:
+                g.kept = job
             elif kcount > 0:
-                g['kept'] = make(kcount, True, start_bias=job.initial_biases()[:kcount], stats=False).run()
+                g.kept = jobs.inclinometer(g, kcount, True, start_bias=job.initial_biases()[:kcount], stats=False, proc_first=pf).run()
             # the last run's series: the plugin objects hold them after the reference's loop
-            last = g.get('kept') if (keep or kcount == count) else None
+            last, pos = (g.kept, count - 1) if (plan.keep or kcount == count) else (None, 0)
             if last is None:
-                last = make(1, True, start_bias=job.initial_biases()[-1:], stats=False, off=count - 1).run()
-                pos = 0
-            else:
-                pos = count - 1
-            if mah is not None:
-                mah.finish(last.series('quat_mahony', [pos])[0], last.series('wb', [pos])[0], last.series('ab', [pos])[0], 1.0 / fs_imu)
-            if 'tilt' in g['kinds']:
-                algos[g['idx'][g['kinds'].index('tilt')]].finish(last.series('quat_tilt', [pos])[0])
-            if last is not g.get('kept'):
+                last = jobs.inclinometer(g, 1, True, start_bias=job.initial_biases()[-1:], stats=False, proc_first=pf,
+                                         off=count - 1).run()
+            if g.mahony is not None:
+                g.mahony.finish(last.series('quat_mahony', [pos])[0], last.series('wb', [pos])[0], last.series('ab', [pos])[0],
+                                1.0 / self.fs[0])
+            if g.tilt is not None:
+                g.tilt.finish(last.series('quat_tilt', [pos])[0])
+            if last is not g.kept:
                 last.release()
-        self.passes = [g['passes'] for g in groups]
-        out = []
-        for g in groups:
-            for i in g['idx']:
-                out.append((i, g))
-        return sorted(out, key=lambda t: t[0])
+        self.passes = [g.passes for g in groups]
+        return sorted(((i, g) for g in groups for i in g.idx), key=lambda t: t[0])
 
-    def _inclinometer_views(self, kept_jobs, fused, kinds, names, incl_groups, first, count):
-        """att_euler / att_quat over the fused and the inclinometer plugins, wb / ab over the MahonyFilters: device views keyed
-        '<algo>_<run>' (the first `count` runs), or empty mappings when no run is kept (statistics only)."""
+    def _sensor_views(self, plan, sensor_job):
+        """accel / gyro / odo of the kept runs: views of the sensor job's device series, keyed by run number."""
         d = self.dmgr
-        if count <= 0:
-            for out_name in ('att_euler', 'att_quat') + (('pos', 'vel') if fused else ()):
-                d.add_data(out_name, {})
-            if any(kinds[i] == 'mahony' for i, _ in incl_groups):
-                d.add_data('wb', {})
-                d.add_data('ab', {})
+        if sensor_job is None:
             return
-        fused_order = [(names[k], kept_jobs[i], kinds[i]) for k, i in enumerate(fused)]
-        inc_order = [(self.amgr.get_algo_name(i), g['kept'], kinds[i]) for i, g in incl_groups]
+        def sens(name, squeeze=False, job=sensor_job):
+            return self._run_view(plan, lambda pos, j=job, nm=name: j.sensors(nm, pos)[..., None] if nm == 'odo'
+                                  else j.sensors(nm, pos), squeeze=squeeze)
+        d.add_data(d.accel.name, sens('accel'))
+        d.add_data(d.gyro.name, sens('gyro'))
+        if self.imu.odo:
+            d.add_data(d.odo.name, sens('odo', squeeze=True))
 
-        def fused_fetch(job, kind, comp, quat):
+    @staticmethod
+    def _run_view(plan, fetch, squeeze=False):
+        """Mapping run number -> series of that run over the kept runs of this rank; fetch(positions in the kept job)."""
+        first, kcount = plan.first, plan.kcount
+        in_kept = lambda k: int(k) - first if isinstance(k, (int, np.integer)) and first <= int(k) < first + kcount else None
+        return McSeries(kcount, fetch, key_of=lambda i: first + i, pos_of=in_kept, squeeze=squeeze)
+
+    def _aux_views(self, plan, jobs):
+        """GPS / magnetometer series of the kept runs (ins_sim.py:497-503): their own job, views keyed by run number."""
+        d, kcount = self.dmgr, plan.kcount
+        if not (kcount > 0 and (self.imu.gps or self.imu.magnetometer)):
+            return
+        aux = jobs.aux_class(
+            jobs.ctx, kcount, seed=jobs.seed, run_offset=plan.first,
+            ref_gps=d.ref_gps.data if self.imu.gps else None, gps_err=self.imu.gps_err, ref_frame=self.ref_frame,
+            ref_mag=d.ref_mag.data if self.imu.magnetometer else None, mag_err=self.imu.mag_err).run()
+        self._aux = aux
+        view = lambda nm: self._run_view(plan, lambda pos, a=aux, nm=nm: a.series(nm, pos))
+        if self.imu.gps:
+            d.add_data(d.gps.name, view('gps'))
+        if self.imu.magnetometer:
+            d.add_data(d.mag.name, view('mag'))
+
+    def _output_views(self, plan, fused, incl):
+        """att_euler / pos / vel / att_quat over the fused plugins and att_euler / att_quat over the inclinometer plugins, wb / ab
+        over the MahonyFilters: device views keyed '<algo>_<run>' over the kept runs, or empty mappings when no run is kept
+        (statistics only: names are known, series are not kept).  fused, incl: [(algorithm name, kept job, kind)]."""
+        d, first, count = self.dmgr, plan.first, plan.kcount
+        mahony = [(nm, j) for nm, j, k in incl if k == 'mahony']
+        if not (fused or incl):
+            return
+        if count <= 0:
+            for out_name in ('att_euler',) + (('att_quat',) if incl else ()) + (('pos', 'vel') if fused else ()) + \
+                    (('wb', 'ab') if mahony else ()):
+                d.add_data(out_name, {})
+            return
+
+        def traj(job, kind, comp, quat):
             return lambda pos: (lambda x: np.stack([attitude.euler2quat(v) for v in x]) if quat else x)(job.trajectories(kind, pos)[comp])
-
-        def view(entries):
-            def locate(key):
-                if not isinstance(key, str) or '_' not in key:
-                    return None
-                nm, _, r = key.rpartition('_')
-                if not r.isdigit() or not (first <= int(r) < first + count):
-                    return None
-                for a, (name, _) in enumerate(entries):
-                    if name == nm:
-                        return a * count + int(r) - first
-                return None
-
-            def fetch(positions):
-                return np.stack([entries[a][1]([r])[0] for a, r in (divmod(p, count) for p in positions)])
-            return McSeries(count * len(entries), fetch, key_of=lambda p: entries[p // count][0] + '_' + str(first + p % count),
-                            pos_of=locate)
-
         ser = lambda job, nm: (lambda pos, j=job: j.series(nm, pos))
         for out_name, comp in (('att_euler', 0), ('pos', 1), ('vel', 2)):
-            ents = [(nm, fused_fetch(j, k, comp, False)) for nm, j, k in fused_order]
+            ents = [(nm, traj(j, k, comp, False)) for nm, j, k in fused]
             if out_name == 'att_euler':
-                ents += [(nm, ser(j, 'euler_' + k)) for nm, j, k in inc_order]
+                ents += [(nm, ser(j, 'euler_' + k)) for nm, j, k in incl]
             if ents:
-                d.add_data(out_name, view(ents))
-        d.add_data('att_quat', view([(nm, fused_fetch(j, k, 0, True)) for nm, j, k in fused_order] +
-                                    [(nm, ser(j, 'quat_' + k)) for nm, j, k in inc_order]))
-        mah = [(nm, j) for nm, j, k in inc_order if k == 'mahony']
-        if mah:
-            d.add_data('wb', view([(nm, ser(j, 'wb')) for nm, j in mah]))
-            d.add_data('ab', view([(nm, ser(j, 'ab')) for nm, j in mah]))
+                d.add_data(out_name, _keyed_view(ents, first, count))
+        d.add_data('att_quat', _keyed_view([(nm, traj(j, k, 0, True)) for nm, j, k in fused] +
+                                           [(nm, ser(j, 'quat_' + k)) for nm, j, k in incl], first, count))
+        for out_name in ('wb', 'ab') if mahony else ():
+            d.add_data(out_name, _keyed_view([(nm, ser(j, out_name)) for nm, j in mahony], first, count))
 
-    def _output_view(self, jobs_by_algo, fused, kinds, names, comp, first, count, quat=False):
-        """Mapping '<algo>_<run>' -> (n,3) (or (n,4) quaternion) over the trajectory buffers of all fused plugins."""
-        order = [(names[k], jobs_by_algo[i], kinds[i]) for k, i in enumerate(fused)]
+    def _publish_results(self, plan, jobs, run, incl_groups, kinds, group, xdev):
+        """sim.mc: the statistics and kept jobs of every fused and inclinometer plugin, and how to build the jobs that statistics
+        over another window (make_ps_job) or from trajectories that were not kept (make_kept_job) need."""
+        owners = [next(g for g in plan.groups if i in g.idx) for i in plan.fused] + [g for _, g in incl_groups]
+        order = plan.fused + [i for i, _ in incl_groups]
 
-        def locate(key):
-            if not isinstance(key, str) or '_' not in key:
-                return None
-            nm, _, r = key.rpartition('_')
-            if not r.isdigit() or not (first <= int(r) < first + count):
-                return None
-            for a, (name, _, _) in enumerate(order):
-                if name == nm:
-                    return a * count + int(r) - first
-            return None
+        def make_ps_job(idx, start_sample, ned):
+            g = owners[idx]
+            if isinstance(g, _InclGroup):           # an inclinometer: one pass from the converged initial biases
+                return jobs.inclinometer(g, plan.count, False, start_bias=g.job.initial_biases(), proc_first=start_sample)
+            return jobs.fused(g, [kinds[order[idx]]], plan.count, proc_first=start_sample, proc_ned=ned, end_ned=False)
 
-        def fetch(positions):
-            out = []
-            for p in positions:
-                a, r = divmod(p, count)
-                x = order[a][1].trajectories(order[a][2], [r])[comp][0]
-                out.append(attitude.euler2quat(x) if quat else x)
-            return np.stack(out)
+        def make_kept_job(idx, off, runs_):      # a block of this rank's runs, trajectories kept (fp32 statistics)
+            # placed=None is kept from the parent on purpose and not yet judged: these blocks do not follow Sim(placed=)
+            return jobs.fused(owners[idx], (kinds[order[idx]],), runs_, off=off, keep_traj=True, placed=None)
+        names = [self.amgr.get_algo_name(i) for i in order]
+        self.mc = _McResults([run.stats.get(i) for i in plan.fused] + [g.job for _, g in incl_groups],
+                             [run.kept.get(i) for i in plan.fused] + [g.kept for _, g in incl_groups], names,
+                             [kinds[i] for i in order], plan.first, plan.count, self.sim_count, group,
+                             xdev, make_ps_job, ctx=jobs.ctx, make_kept_job=make_kept_job, block_runs=plan.block_runs,
+                             ned_from_traj=not plan.end_ned)
+        self.mc.fused_names = names[:len(plan.fused)]
+        self.mc.devices = list(jobs.ctx.devices) if plan.spread else None
+        self.mc.kept_block = any(isinstance(j, _BlockAndRest) for j in run.stats.values())    # the kept runs rode along
+        self.dmgr.set_mc_results(self.mc)
 
-        return McSeries(count * len(order), fetch, key_of=lambda p: order[p // count][0] + '_' + str(first + p % count),
-                        pos_of=locate)
+    def _run_hosted(self, plan, algos, sensor_job):
+        """plugins outside the fused kernel: the reference's per-run loop over host copies (user code)"""
+        d, hosted, first = self.dmgr, plan.hosted, plan.first
+        # plugins that take the device-resident sensor series of all runs at once (demo_algorithms.allan_analysis)
+        on_device = [i for i in hosted if hasattr(algos[i], 'run_device') and sensor_job is not None and plan.count > 0]
+        merged = [{} for _ in self.amgr.output]
+        for i in on_device:
+            name = self.amgr.get_algo_name(i)
+            per_run = algos[i].run_device(sensor_job, self.fs[0])
+            for k, res in enumerate(per_run):
+                for j, slot in enumerate(self.amgr.output_alloc[i]):
+                    merged[slot][name + '_' + str(first + k)] = res[j]
+        rest = [i for i in hosted if i not in on_device]
+        if rest:
+            inputs = d.get_data(self.amgr.input)
+            out = self.amgr.run_algo(inputs, list(range(first, first + plan.kcount)), only=rest)
+            for j in range(len(merged)):
+                merged[j].update(out[j])
+        for j, oname in enumerate(self.amgr.output):
+            if merged[j]:
+                cur = d.get_data_all(oname).data if oname in d.available else None
+                if isinstance(cur, McSeries):           # a fused plugin produced this output too: keep its device view
+                    d.add_data(oname, ChainSeries(cur, merged[j]))
+                else:
+                    d.add_data(oname, merged[j])
 
     # ------------------------------------------------------------------------------------ logged data
     def _run_from_files(self):
