@@ -27,6 +27,9 @@ namespace ginsim {
 struct Quat { double q0, q1, q2, q3; };
 
 // attitude.get_cn2b_acc_mag_ned then attitude.dcm2quat (attitude.py:22-45, 294-342); c[i][k] = cn2b[i][k]
+// Both callers (TiltAcc's (1, 0, 0), Mahony's pseudo-magnetometer) give a DCM of zero yaw: c00 = cos(pitch) >= 0, c11 = cos(roll),
+// c22 = c00 c11, so tr <= 0 needs c11 <= 0 and c00 is then the largest diagonal element: only the first and the last branch of
+// dcm2quat are reachable through them (counted by tests/test_inclinometer_oracle.py).  The middle two restate the reference.
 __device__ __forceinline__ Quat acc_mag_quat(double ax, double ay, double az, double mx, double my, double mz) {
 #pragma clang fp contract(off)
     const double an = sqrt(ax * ax + ay * ay + az * az);

@@ -9,6 +9,13 @@ make_golden.py do).  Needs a checkout of the reference (argument or $GNSS_INS_SI
                              [MahonyFilter(), TiltAcc()], ref_frame 1, 6-axis 'mid-accuracy'
   incl_mag9_gps_rf0.npz      (b) the same profile, 9-axis with GPS, ref_frame 0, 2 runs (the demo_multiple_algorithms.py recipe)
   incl_chain_rf1.npz         (c) two Sim(...).run(2) calls with ONE MahonyFilter object: the chain goes on across calls
+  incl_sphere.npz            (d) no Sim, no profile: MahonyFilter / TiltAcc objects driven directly on the hand-built records of
+                             tests/inclinometer_records.py (attitudes over the whole sphere, the neighbourhoods of +-x and of
+                             dcm2quat's tr == 0, rates past cos(theta / 2) = 0, zero accelerometers, other gains and rate),
+                             attitude.quat2euler of their quaternions (a mask where it raises), attitude.angle_range_pi at the wrap
+
+    python tests/golden/make_golden_inclinometer.py --check /path/to/reference   -> regenerates (d) in memory and compares it
+                                                                                    with the committed file, array by array
 """
 import io
 import math
@@ -116,9 +123,64 @@ def case(name, ref):
     print('%-28s %7.1f KB' % (name + '.npz', os.path.getsize(os.path.join(OUT, name + '.npz')) / 1024))
 
 
+def sphere(ref):
+    """(d): every array of incl_sphere.npz, by the unmodified reference objects."""
+    sys.path.insert(0, ref)
+    sys.path.insert(1, os.path.join(REPO, 'tests'))
+    from gnss_ins_sim.attitude import attitude
+    from demo_algorithms import inclinometer_mahony, inclinometer_acc
+    import inclinometer_records as rec
+    names = dict(kp_high='kp_acc_high', kp_low='kp_acc_low', ki_high='ki_acc_high', ki_low='ki_acc_low', innovation_limit='innovationLimit')
+
+    def euler(q):
+        e, bad = np.full(q.shape[:-1] + (3,), np.nan), np.zeros(q.shape[:-1], dtype=bool)
+        for i in np.ndindex(*q.shape[:-1]):
+            try:
+                e[i] = attitude.quat2euler(q[i])
+            except ValueError:                          # math.asin domain error
+                bad[i] = True
+        return e, bad
+    out = dict(seed=rec.SEED, batches=np.array([b['name'] for b in rec.sphere_batches()]))
+    for b in rec.sphere_batches():
+        R, n, _ = b['accel'].shape
+        k = rows(n, 12)
+        p = b['name'] + '_'
+        mq, tq, wb, ab, fin = [], [], [], [], []
+        for r in range(R):
+            m = inclinometer_mahony.MahonyFilter()      # a new object per record: zero gyro_bias
+            for key, attr in names.items():
+                if b['gains'] is not None:
+                    setattr(m, attr, b['gains'][key])
+            m.run([b['fs'], b['gyro'][r], b['accel'][r]])
+            t = inclinometer_acc.TiltAcc()
+            with np.errstate(invalid='ignore', divide='ignore'):
+                t.run([b['accel'][r]])
+            mq.append(m.quat[k]); wb.append(m.wb[k]); ab.append(m.ab[k]); fin.append(m.gyro_bias.copy()); tq.append(t.results[k])
+        out[p + 'rows'], out[p + 'n'], out[p + 'fs'] = k, n, b['fs']
+        out[p + 'accel0'], out[p + 'gyro0'] = b['accel'][:, 0], b['gyro'][:, 0]
+        out[p + 'mahony_quat'], out[p + 'tilt_quat'] = np.stack(mq), np.stack(tq)
+        out[p + 'wb'], out[p + 'ab'], out[p + 'bias_after'] = np.stack(wb), np.stack(ab), np.stack(fin)
+        for a in ('mahony', 'tilt'):
+            out[p + a + '_euler'], out[p + a + '_asin_raises'] = euler(out[p + a + '_quat'])
+        for g, ids in b['groups'].items():
+            out[p + 'group_' + g] = ids
+    out['wrap_x'] = rec.WRAP_VALUES
+    out['wrap_y'] = np.array([attitude.angle_range_pi(float(x)) for x in rec.WRAP_VALUES])
+    return out
+
+
 if __name__ == '__main__':
     if len(sys.argv) >= 3 and sys.argv[1] == '--case':
         case(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) >= 3 and sys.argv[1] == '--sphere':
+        os.makedirs(OUT, exist_ok=True)
+        np.savez_compressed(os.path.join(OUT, 'incl_sphere.npz'), **sphere(sys.argv[2]))
+        print('%-28s %7.1f KB' % ('incl_sphere.npz', os.path.getsize(os.path.join(OUT, 'incl_sphere.npz')) / 1024))
+    elif len(sys.argv) >= 3 and sys.argv[1] == '--check':
+        new, old = sphere(sys.argv[2]), dict(np.load(os.path.join(OUT, 'incl_sphere.npz'), allow_pickle=False))
+        bad = [k for k in sorted(set(new) | set(old)) if k not in new or k not in old or not np.array_equal(np.asarray(new[k]), old[k], equal_nan=np.asarray(new[k]).dtype.kind == 'f')]
+        print('incl_sphere.npz: %d arrays, %s' % (len(old), 'reproduced' if not bad else 'DIFFERENT: %s' % bad))
+        sys.exit(1 if bad else 0)
     else:
         ref = sys.argv[1] if len(sys.argv) > 1 else os.environ['GNSS_INS_SIM_REFERENCE']
         # the reference's motion_def.csv as it is: the workload of examples/demo_inclinometer.py
@@ -128,3 +190,5 @@ if __name__ == '__main__':
         for nm in ('incl_mahony_tilt_rf1', 'incl_mag9_gps_rf0', 'incl_chain_rf1'):
             subprocess.run([sys.executable, os.path.abspath(__file__), '--case', nm, ref], check=True,
                            env=dict(os.environ, PYTHONDONTWRITEBYTECODE='1', MPLBACKEND='Agg'))
+        subprocess.run([sys.executable, os.path.abspath(__file__), '--sphere', ref], check=True,
+                       env=dict(os.environ, PYTHONDONTWRITEBYTECODE='1', MPLBACKEND='Agg'))

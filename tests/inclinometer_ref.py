@@ -26,8 +26,13 @@ def _cross(a, b):
                      a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
 
 
-def acc_mag_quat(acc, mag):
-    """dcm2quat(get_cn2b_acc_mag_ned(acc, mag)) for (R, 3) arrays."""
+def acc_mag_quat(acc, mag, with_branch=False):
+    """dcm2quat(get_cn2b_acc_mag_ned(acc, mag)) for (R, 3) arrays; with_branch: also the dcm2quat branch taken (0-3) per row.
+
+    Both callers (tilt with mag = (1, 0, 0), mahony with its pseudo-magnetometer) build a DCM of zero yaw: c00 = cos(pitch) >= 0
+    (it is a square root), c11 = cos(roll), c22 = cos(pitch) cos(roll), so tr = c00 + c11 (1 + c00) <= 0 needs c11 <= 0 and then
+    c00 is the largest diagonal element: through these callers only the first and the LAST branch are reachable (the census of
+    tests/test_inclinometer_oracle.py counts them).  The two middle branches restate the reference and stay."""
     with np.errstate(invalid='ignore', divide='ignore'):
         z = -acc / _norm3(acc)[:, None]
         c = _cross(z, mag)
@@ -55,7 +60,10 @@ def acc_mag_quat(acc, mag):
         t3 = np.stack([(c12 - c21) * f3, 0.5 * s3, (c01 + c10) * f3, (c20 + c02) * f3], 1)
         for m, v in ((b0, t0), (b1, t1), (b2, t2), (b3, t3)):
             t[m] = v[m]
-    return np.where((t[:, 0] < 0)[:, None], -1.0 * t, t)
+    out = np.where((t[:, 0] < 0)[:, None], -1.0 * t, t)
+    if with_branch:
+        return out, np.select([b0, b1, b2], [0, 1, 2], 3)
+    return out
 
 
 def quat2euler(q):
@@ -66,14 +74,19 @@ def quat2euler(q):
                          np.arctan2(2.0 * (q2 * q3 + q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3)], axis=-1)
 
 
-def tilt(accel):
+def tilt(accel, with_branch=False):
     accel = np.asarray(accel, dtype=np.float64)
     R, n, _ = accel.shape
     mag = np.array([1.0, 0.0, 0.0])
-    return np.stack([acc_mag_quat(accel[:, j], mag) for j in range(n)], axis=1)
+    out = [acc_mag_quat(accel[:, j], mag, True) for j in range(n)]
+    q = np.stack([o[0] for o in out], axis=1)
+    return (q, np.stack([o[1] for o in out], axis=1)) if with_branch else q
 
 
-def mahony(gyro, accel, dt, bias0, gains=None):
+def mahony(gyro, accel, dt, bias0, gains=None, trace=None):
+    """trace: a dict that receives, per run and sample, which way each branch went: 'low' (the low gains), 'limited' (the
+    innovation was limited), 'cneg' (cos(theta / 2) < 0), 'theta0' (theta == 0), 'postponed' (no initialisation yet after this
+    sample: a zero accelerometer so far), and per run 'ini_branch' (the dcm2quat branch of the initialisation, -1: never)."""
     g = dict(GAINS, **(gains or {}))
     gyro, accel = np.asarray(gyro, dtype=np.float64), np.asarray(accel, dtype=np.float64)
     R, n, _ = accel.shape
@@ -83,6 +96,9 @@ def mahony(gyro, accel, dt, bias0, gains=None):
     ini = np.zeros(R, dtype=bool)
     Q, WB, AB = np.empty((R, n, 4)), np.empty((R, n, 3)), np.empty((R, n, 3))
     k, k1 = 0.9, 1 - 0.9
+    if trace is not None:
+        trace.update({nm: np.zeros((R, n), dtype=bool) for nm in ('low', 'limited', 'cneg', 'theta0', 'postponed')})
+        trace['ini_branch'] = np.full(R, -1)
     for j in range(n):
         a, w = accel[:, j].copy(), gyro[:, j]
         valid = np.any(a != 0.0, axis=1)
@@ -102,7 +118,9 @@ def mahony(gyro, accel, dt, bias0, gains=None):
                 pm = np.stack([m0, -s[:, 1] * s[:, 0] / m0, -s[:, 0] * s[:, 2] / m0], 1)
             pm[s[:, 0] >= 1.0] = [0.0, 0.0, 1.0]
             pm[(s[:, 0] < 1.0) & (s[:, 1] <= -1.0)] = [0.0, 0.0, -1.0]
-            q[start] = acc_mag_quat(s, pm)
+            q[start], br = acc_mag_quat(s, pm, True)
+            if trace is not None:
+                trace['ini_branch'][start] = br
         v = np.stack([-2.0 * (q[:, 1] * q[:, 3] - q[:, 0] * q[:, 2]),
                       -2.0 * (q[:, 0] * q[:, 1] + q[:, 2] * q[:, 3]),
                       -q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2] - q[:, 3] * q[:, 3]], 1)
@@ -128,6 +146,9 @@ def mahony(gyro, accel, dt, bias0, gains=None):
         p = np.where((p[:, 0] < 0)[:, None], -p, p)
         q = p / np.sqrt(p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1] + p[:, 2] * p[:, 2] + p[:, 3] * p[:, 3])[:, None]
         Q[:, j], WB[:, j], AB[:, j] = q, b, e
+        if trace is not None:
+            trace['low'][:, j], trace['limited'][:, j], trace['cneg'][:, j] = low, lim, c < 0
+            trace['theta0'][:, j], trace['postponed'][:, j] = th == 0.0, ~ini
     return Q, WB, AB, b.copy()
 
 
@@ -145,9 +166,14 @@ def chain(gyro, accel, dt, bias0=(0.0, 0.0, 0.0), gains=None):
             np.array(starts), b[0].copy())
 
 
+def angle_range_pi(x):
+    """attitude.angle_range_pi (attitude.py:799-812): x % 2 pi, minus 2 pi where that exceeds pi -- -pi, +pi, +-3 pi give +pi."""
+    x = np.mod(x, 2.0 * np.pi)
+    return np.where(x > np.pi, x - 2.0 * np.pi, x)
+
+
 def angle_err(x, ref):
-    e = x - ref
-    return np.mod(e + np.pi, 2.0 * np.pi) - np.pi
+    return angle_range_pi(x - ref)
 
 
 def stats(euler, ref_att, first=0):
