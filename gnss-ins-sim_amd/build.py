@@ -35,6 +35,8 @@ SOURCES = [
     ('mc_kernel_f32.hip', ['--offload-arch=' + ARCH, '-mllvm', '-disable-machine-licm', '-ffp-contract=off', '-fno-slp-vectorize']),
     # the sensor synthesis must give mc_kernel.hip's bits (same -ffp-contract=on); the filter code switches contraction off itself
     ('inclinometer.hip', ['--offload-arch=' + ARCH, '-ffp-contract=on']),
+    # the magnetometer synthesis must give aux_mag_kernel's bits (mag_synth.hpp, same -ffp-contract=on as mc_kernel.hip)
+    ('magcal.hip', ['--offload-arch=' + ARCH, '-ffp-contract=on']),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),

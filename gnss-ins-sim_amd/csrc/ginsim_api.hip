@@ -42,6 +42,7 @@ int mc_variant_f32(const ginsim_mc_params& p);
 hipError_t launch_gather_runs_f32(const float* series, int C, int64_t n, int64_t runs, const int64_t* ids, int nsel,
                                   double* out, hipStream_t s);
 hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s);
+hipError_t launch_magcal(const ginsim_magcal_params& p, hipStream_t s);
 size_t vib_psd_scratch_bytes(int64_t period, int64_t runs);
 int launch_vib_psd(int device, hipStream_t stream, const double* amp, int64_t period, int64_t runs, uint64_t run_offset, uint64_t seed,
                    int sensor, int halve, void* scratch, double* out);
@@ -544,6 +545,23 @@ int ginsim_aux_sensors(ginsim_ctx* c, const ginsim_aux_params* p) {
     REQUIRE((double)p->n * (double)p->runs < 5.0e11 && (double)p->m * (double)p->runs < 5.0e11, "aux_sensors: too many elements");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_aux(*p, c->stream));
+    return GINSIM_OK;
+}
+
+int ginsim_magcal_run(ginsim_ctx* c, const ginsim_magcal_params* p) {
+    REQUIRE(c && p, "magcal_run: NULL argument");
+    REQUIRE(p->runs >= 1, "magcal_run: runs=%lld must be >= 1", (long long)p->runs);
+    REQUIRE(p->n >= 1 && p->n <= 0xFFFFFFFFll, "magcal_run: n must lie in 1 .. the 32-bit sample counter of the RNG");
+    REQUIRE(p->runs <= (int64_t)0x7FFFFFFF * 64, "magcal_run: too many runs for one launch");
+    REQUIRE(p->in_mag || p->ref_mag, "magcal_run: neither ref_mag (generated form) nor in_mag (given form)");
+    REQUIRE(p->out_si && p->out_hi, "magcal_run: out_si / out_hi missing");
+    for (int a = 0; a < 3; ++a) {
+        const long long s0 = (long long)p->seg[2 * a], s1 = (long long)p->seg[2 * a + 1];
+        REQUIRE(s0 >= 0 && s1 <= (long long)p->n, "magcal_run: range %c [%lld, %lld) is outside [0, %lld]", "xyz"[a], s0, s1, (long long)p->n);
+        REQUIRE(s0 < s1, "magcal_run: range %c [%lld, %lld) is empty", "xyz"[a], s0, s1);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_magcal(*p, c->stream));
     return GINSIM_OK;
 }
 

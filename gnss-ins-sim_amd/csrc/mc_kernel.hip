@@ -22,6 +22,7 @@
 #include "philox.hpp"
 #include "device_once.hpp"
 #include "sensor_synth.hpp"
+#include "mag_synth.hpp"
 
 namespace ginsim {
 
@@ -1238,14 +1239,13 @@ __global__ void __launch_bounds__(256) aux_mag_kernel(const ginsim_aux_params a)
     const int64_t r = idx % a.runs, j = idx / a.runs;
     const uint64_t grun = a.run_offset + (uint64_t)r;
     const RngKey key{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)grun, (uint32_t)(grun >> 32)};
-    double z0[2], z1[2];
-    normal_pairs<S_MAG_XY, 2>(key, (uint32_t)j, z0, z1, tab);
-    const double z[3] = {z0[0], z1[0], z0[1]};
+    double z[3];
+    mag_normals(key, (uint32_t)j, tab, z);
     const double v[3] = {a.ref_mag[3 * j] + a.mag_hi[0], a.ref_mag[3 * j + 1] + a.mag_hi[1], a.ref_mag[3 * j + 2] + a.mag_hi[2]};
     const int64_t plane = a.n * a.runs;
 #pragma unroll
-    for (int c = 0; c < 3; ++c)     // (ref + hi) . si^T  + std * N
-        a.out_mag[c * plane + idx] = a.mag_si[3 * c] * v[0] + a.mag_si[3 * c + 1] * v[1] + a.mag_si[3 * c + 2] * v[2] + a.mag_std[c] * z[c];
+    for (int c = 0; c < 3; ++c)     // (ref + hi) . si^T  + std * N  (mag_synth.hpp)
+        a.out_mag[c * plane + idx] = mag_axis(a.mag_si + 3 * c, v, a.mag_std[c], z[c]);
 }
 
 hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s) {

@@ -103,6 +103,14 @@ class AuxParams(C.Structure):
                 ('ref_mag', C.c_void_p), ('out_gps', C.c_void_p), ('out_mag', C.c_void_p)]
 
 
+class MagCalParams(C.Structure):
+    """ginsim_magcal_params: the soft / hard-iron calibration over a batch of runs (csrc/magcal.hip)."""
+    _fields_ = [('n', C.c_int64), ('runs', C.c_int64), ('run_offset', C.c_uint64), ('seed', C.c_uint64),
+                ('mag_si', C.c_double * 9), ('mag_hi', C.c_double * 3), ('mag_std', C.c_double * 3),
+                ('ref_mag', C.c_void_p), ('in_mag', C.c_void_p), ('seg', C.c_int64 * 6),
+                ('out_si', C.c_void_p), ('out_hi', C.c_void_p), ('out_cal', C.c_void_p)]
+
+
 class Stats(C.Structure):
     _fields_ = [('count', C.c_double), ('mean', C.c_double * 9), ('m2', C.c_double * 9),
                 ('maxabs', C.c_double * 9)]
@@ -142,6 +150,7 @@ _SIGS = {
     'ginsim_parse_motion_def': (C.c_int, [_PD, _PD, _PD, _PD, _PD]),
     'ginsim_euler_update_zyx': (C.c_int, [_PD, _PD, C.c_double, _PD]),
     'ginsim_aux_sensors': (C.c_int, [C.c_void_p, C.POINTER(AuxParams)]),
+    'ginsim_magcal_run': (C.c_int, [C.c_void_p, C.POINTER(MagCalParams)]),
     'ginsim_mc_run': (C.c_int, [C.c_void_p, C.POINTER(McParams)]),
     'ginsim_mc_variant': (C.c_int, [C.POINTER(McParams), C.POINTER(C.c_int32)]),
     'ginsim_mc_kernel_name': (C.c_int, [C.POINTER(McParams), C.c_char_p, C.c_size_t]),

@@ -239,7 +239,12 @@ class _Launched(object):
 
 
 _Plan = namedtuple('_Plan', 'fused incl hosted groups first count spread ndev per_sample keep kcount online end_ned ride block_runs '
-                            'proc_first')
+                            'proc_first magcal')
+
+
+class _Roles(tuple):
+    """(fused, incl, hosted) as _plugin_roles always returned them, and `magcal`: the indices of the magnetometer calibrations."""
+    magcal = ()
 
 
 def _sample_of(t_axis, start_s):
@@ -248,19 +253,29 @@ def _sample_of(t_axis, start_s):
 
 
 def _plugin_roles(sim, kinds):
-    """(fused, incl, hosted): the indices of the plugins inside the fused kernel, of the inclinometer plugins and of the others."""
+    """(fused, incl, hosted): the indices of the plugins inside the fused kernel, of the inclinometer plugins and of the others;
+    the indices of the magnetometer calibrations (MagCal of demo_algorithms.mag_calibrate_device: their own kernel) are the
+    result's `magcal`."""
     # which plugins are inside the fused kernel
     fused = [i for i, k in enumerate(kinds) if k in ('free', 'odo')]
     # the inclinometer plugins of demo_algorithms.inclinometer_device: their own kernel, same seed and run ids
     incl = [i for i, k in enumerate(kinds) if k in ('mahony', 'tilt')]
-    hosted = [i for i in range(len(kinds)) if i not in fused and i not in incl]
+    magcal = [i for i, k in enumerate(kinds) if k == 'magcal']
+    hosted = [i for i in range(len(kinds)) if i not in fused and i not in incl and i not in magcal]
     if incl and sim.precision != 'f64':
         raise NotImplementedError("the inclinometer plugins (MahonyFilter, TiltAcc of demo_algorithms.inclinometer_device) run "
                                   "in fp64 only: use precision='f64'")
     for i in fused:
         if kinds[i] == 'odo' and not sim.imu.odo:
             raise ValueError("algorithm %d needs 'odo' but the IMU model has no odometer" % i)
-    return fused, incl, hosted
+    if magcal and not sim.imu.magnetometer:
+        raise ValueError("algorithm %d needs 'mag' but the IMU model has no magnetometer (IMU(axis=9))" % magcal[0])
+    if magcal and sim.precision != 'f64':
+        raise NotImplementedError("the magnetometer calibration (MagCal of demo_algorithms.mag_calibrate_device) runs in fp64 only: "
+                                  "use precision='f64'")
+    roles = _Roles((fused, incl, hosted))
+    roles.magcal = magcal
+    return roles
 
 
 def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group, place):
@@ -273,14 +288,21 @@ def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group,
     between the refusals as Sim._context always was (it may print the auto-spread notice and make a DeviceSet)."""
     from ginsim import distributed
     fused, incl, hosted = roles
+    magcal = list(getattr(roles, 'magcal', ()))
     imu, n = sim.imu, t_axis.shape[0]
     kinds = [getattr(a, 'mc_algo', None) for a in algos]
     first, count = distributed.shard(sim.sim_count, world, rank)
     if incl and in_group:
         raise ValueError('the runs of a MahonyFilter are a chain (each starts from the gyro_bias the previous one ended with), '
                          'which does not cross torch.distributed ranks: run a Sim with inclinometer plugins in one process')
-    # an inclinometer chain runs on one device: never spread it automatically
-    spread, ndev = place(0 if incl else sim.sim_count * n, in_group)
+    if magcal and in_group:
+        raise ValueError('a Sim with a MagCal runs on one device: spreading the magnetometer calibration over the ranks of a '
+                         'torch.distributed process group is not built yet -- run it in one process')
+    # an inclinometer chain runs on one device: never spread it automatically; nor is a magnetometer calibration
+    spread, ndev = place(0 if incl or magcal else sim.sim_count * n, in_group)
+    if magcal and spread:
+        raise ValueError('a Sim with a MagCal runs on one device: spreading the magnetometer calibration over several GPUs is not '
+                         'built yet -- give Sim(device=...) one GPU, not devices=... (or $GINSIM_DEVICES)')
     if incl and spread:
         raise ValueError('the runs of a MahonyFilter are a chain (each starts from the gyro_bias the previous one ended with), '
                          'which does not cross devices: give Sim(device=...) one GPU, not devices=... (or $GINSIM_DEVICES)')
@@ -289,7 +311,7 @@ def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group,
                          'split is one process per GPU (drop devices=, or do not initialise a process group)')
     per_sample = 48 + (8 if imu.odo else 0) + 72 * len(fused) + (24 if imu.magnetometer else 0) + \
         (48.0 * gps_rows / n if imu.gps else 0) + \
-        sum(104 if kinds[i] == 'mahony' else 56 for i in incl)
+        sum(104 if kinds[i] == 'mahony' else 56 for i in incl) + 24 * len(magcal)          # mag_cal: at most n rows of 3
     keep = sim.keep_trajectories
     if keep == 'auto':
         # decided on the LARGEST share of any rank / device (rank 0's), so that every rank takes the same decision -- the
@@ -327,7 +349,7 @@ def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group,
     block_runs = ndev * max(256, int(sim.max_device_bytes // (9 * esize * n)) // 256 * 256)
     proc_first = _sample_of(t_axis, sim.stats_start) if window and (online or incl) else 0
     return _Plan(fused, incl, hosted, groups, first, count, spread, ndev, per_sample, keep, kcount, online, end_ned, ride,
-                 block_runs, proc_first)
+                 block_runs, proc_first, magcal)
 
 
 class _Jobs(object):
@@ -352,6 +374,14 @@ class _Jobs(object):
         return self.fused_class(ctx or self.ctx, sim.fs[0], sim.ref_frame, self.truth, sim.imu.accel_err, sim.imu.gyro_err, group.ini,
                                 runs=runs, algos=tuple(kinds), odo_err=sim.imu.odo_err, seed=self.seed,
                                 run_offset=self.first + off, keep_sensors=keep_sensors, keep_traj=keep_traj, **self.vib, **kw)
+
+    def magcal(self, segments, runs, keep, off=0):
+        """A MagCalJob of `runs` runs from run `off` of this rank: the samples are made inside the kernel, as AuxSensorJob makes
+        them for the same seed and run ids."""
+        import ginsim
+        sim = self.sim
+        return ginsim.MagCalJob(self.ctx, sim.dmgr.ref_mag.data, sim.imu.mag_err, runs, segments, seed=self.seed,
+                                run_offset=self.first + off, keep=keep, placed=sim.placed)
 
     def inclinometer(self, group, runs, keep, start_bias=None, stats=True, proc_first=0, off=0):
         """An InclinometerJob of `runs` runs from run `off` of this rank for the plugins of `group`; the MahonyFilter's gains and
@@ -570,6 +600,8 @@ class Sim(object):
                            [(name_of(i), g.kept, kinds[i]) for i, g in incl_groups])
         if plan.fused or plan.incl:
             self._publish_results(plan, jobs, run, incl_groups, kinds, group, xdev)
+        if plan.magcal:
+            self._run_magcal(plan, jobs)
         if plan.hosted:
             self._run_hosted(plan, algos, run.sensor_job)
 
@@ -749,6 +781,35 @@ class Sim(object):
                 last.release()
         self.passes = [g.passes for g in groups]
         return sorted(((i, g) for g in groups for i in g.idx), key=lambda t: t[0])
+
+    def _run_magcal(self, plan, jobs):
+        """The magnetometer calibrations (kind 'magcal'): one MagCalJob over all runs of this rank per plugin, nothing of `mag`
+        materialised; mag_cal of the first kcount runs kept.  Fills soft_iron / hard_iron / mag_cal keyed '<algo>_<run>' in the
+        reference's shapes ((3, 3), (1, 4), (nx + ny + nz, 3): mag_calibrate.py:77-89), read from the device when first indexed,
+        and leaves every plugin object with the last run's results as the reference's loop does."""
+        from demo_algorithms.mag_calibrate_device import segments_from_truth
+        d, algos, first, count, kcount = self.dmgr, self.amgr.algo or [], plan.first, plan.count, plan.kcount
+        self.magcal_jobs = []
+        ents = {'soft_iron': [], 'hard_iron': [], 'mag_cal': []}
+        for i in plan.magcal:
+            algo, name = algos[i], self.amgr.get_algo_name(i)
+            seg = algo.segments if algo.segments is not None else segments_from_truth(d.ref_gyro.data)
+            if count <= 0:
+                continue
+            job = jobs.magcal(seg, count, plan.keep).run()
+            kept = job if plan.keep else (jobs.magcal(seg, kcount, True).run() if kcount > 0 else None)
+            self.magcal_jobs.append((name, job, kept))
+            ents['soft_iron'].append((name, lambda pos, j=job: j.soft_iron()[list(pos)]))
+            ents['hard_iron'].append((name, lambda pos, j=job: j.hard_iron()[list(pos)][:, None, :]))
+            if kept is not None:
+                ents['mag_cal'].append((name, lambda pos, j=kept: j.mag_cal(pos)))
+            # the last run's results: the plugin object holds them after the reference's loop
+            last, pos = (kept, count - 1) if (plan.keep or kcount == count) else (jobs.magcal(seg, 1, True, off=count - 1).run(), 0)
+            algo.finish(job.soft_iron()[-1], job.hard_iron()[-1], last.mag_cal([pos])[0])
+            if last is not kept:
+                last.release()
+        for out_name, n_runs in (('soft_iron', count), ('hard_iron', count), ('mag_cal', kcount)):
+            d.add_data(out_name, _keyed_view(ents[out_name], first, n_runs) if ents[out_name] and n_runs > 0 else {})
 
     def _sensor_views(self, plan, sensor_job):
         """accel / gyro / odo of the kept runs: views of the sensor job's device series, keyed by run number."""

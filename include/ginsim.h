@@ -353,6 +353,34 @@ typedef struct {
 
 int ginsim_aux_sensors(ginsim_ctx* ctx, const ginsim_aux_params* p);
 
+/* ---- soft / hard-iron magnetometer calibration: demo_algorithms/mag_calibrate.py::MagCal (:63-88) and the library it calls
+ *      (mag_calibrate_src/src/MagCalibration.c) over a batch of Monte-Carlo runs, one lane per run (csrc/magcal.hip).  Added
+ *      without a change of GINSIM_ABI_VERSION: nothing existing moved.
+ *      Per run, from the three row ranges seg = [x0,xf) [y0,yf) [z0,zf) of its (n, 3) magnetometer series (the rotations about
+ *      x, y and z): the normal of each range (3x3 normal equations) -> orthMtx; the relative sensitivities from the (max - min) of
+ *      the rotated columns -> soft_iron = sens . orthMtx; a sphere fit over the scaled rows of all three ranges (4x4 normal
+ *      equations) -> hard_iron = [centre, radius]; mag_cal = the scaled rows minus the centre.
+ *      The series is either GENERATED inside the kernel (ref_mag given: sample j of run r is what ginsim_aux_sensors writes for
+ *      the same seed, run_offset and mag_si / mag_hi / mag_std, bit for bit, and is never stored) or GIVEN (in_mag).
+ *      Arithmetic is IEEE throughout: a degenerate range gives the non-finite values the divisions give, no error. */
+typedef struct {
+    int64_t  n;             /* samples of the magnetometer series */
+    int64_t  runs;
+    uint64_t run_offset;
+    uint64_t seed;
+    double   mag_si[9];     /* generated form: soft-iron matrix, row major; hard iron [uT]; noise sigma [uT] */
+    double   mag_hi[3];
+    double   mag_std[3];
+    const double* ref_mag;  /* device [n][3]: generated form, or NULL */
+    const double* in_mag;   /* device [3][n][runs]: given form (takes precedence), or NULL */
+    int64_t  seg[6];        /* x0, xf, y0, yf, z0, zf: 0 <= start < end <= n */
+    double*  out_si;        /* device [9][runs]: soft_iron, row major */
+    double*  out_hi;        /* device [4][runs]: hard_iron x, y, z, radius */
+    double*  out_cal;       /* device [3][(xf-x0)+(yf-y0)+(zf-z0)][runs]: mag_cal, the three ranges stacked, or NULL */
+} ginsim_magcal_params;
+
+int ginsim_magcal_run(ginsim_ctx* ctx, const ginsim_magcal_params* p);
+
 /* ---- end-point statistics: InsDataMgr.__end_point_error_stats / __array_stats
  *      (gnss_ins_sim/sim/ins_data_manager.py:717-759, 797-808) ------------------------------------ */
 typedef struct {
