@@ -6,6 +6,7 @@ demo_algorithms/mag_calibrate_lib/libmagcal.so called through ctypes exactly as 
 ranges in place of the six prompts.  MagCal.run itself is not executed: it blocks on input() and opens a plot.
 
     cd /some/dir/outside/the/checkout && python /path/to/tests/golden/make_golden_magcal.py /path/to/reference   -> tests/golden/magcal/
+    ... make_golden_magcal.py /path/to/reference signs      -> tests/golden/magcal/signs.npz alone (no Sim run; nothing else is rewritten)
 
 Run it from a working directory outside the checkout (it sets sys.dont_write_bytecode: nothing is left behind in either tree).
 
@@ -15,7 +16,12 @@ Run it from a working directory outside the checkout (it sets sys.dont_write_byt
   arc.npz              600 samples of each: one 360 degree turn at 60 deg/s
   unequal.npz          ranges of 1000, 700 and 693 samples
   norot.npz            the z range over a stretch without rotation: whatever the reference's divisions give (compared by mask)
-Every case holds, for 3 runs: the rows of each range, soft_iron / hard_iron / mag_cal from libmagcal.so, the ranges, and two measured
+  signs.npz            OUTPUTS only (soft_iron, hard_iron, lib_vs_restatement per record, the record names) of libmagcal.so on the
+                       records of tests/magcal_records.signs_records(): hard iron of 500 uT in all eight octants, si with its rows
+                       permuted, mirrored, rotated 45 +- 1 degrees about z -- every sign pattern of the three normals, every
+                       component selected by vecMax.  The inputs are rebuilt by the builder.  Made on its own (argument `signs`):
+                       the five files above are not rewritten by it, and a run without the argument does not write it.
+Every other case holds, for 3 runs: the rows of each range, soft_iron / hard_iron / mag_cal from libmagcal.so, the ranges, and two measured
 spreads, both reference-side only:
   lib_vs_restatement   max |delta| of (si, hi, mag_cal) between libmagcal.so and tests/magcal_ref.py
   reorder_spread       max |delta| of the restatement's (si, hi, mag_cal) over 20 random permutations of the rows inside each range
@@ -66,6 +72,27 @@ def spread(a, b):
     """max |a - b| over the elements finite in both (0 when there is none); the non-finite ones are compared by mask elsewhere."""
     ok = np.isfinite(a) & np.isfinite(b)
     return float(np.max(np.abs(a[ok] - b[ok]))) if ok.any() else 0.0
+
+
+def signs(ref):
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import magcal_ref
+    import magcal_records
+    lib = ctypes.cdll.LoadLibrary(os.path.join(ref, 'demo_algorithms', 'mag_calibrate_lib', 'libmagcal.so'))
+    names, si, hi, lvr, same = [], [], [], [], True
+    for name, mag, seg in magcal_records.signs_records():
+        s, h, cal = lib_calibrate(lib, mag, seg)
+        rs = magcal_ref.calibrate_series(mag, seg)
+        names.append(name)
+        si.append(s)
+        hi.append(h[0])
+        lvr.append([spread(s, rs[0]), spread(h[0], rs[1]), spread(cal, rs[2])])
+        same = same and all(np.array_equal(np.isfinite(a), np.isfinite(b)) for a, b in ((s, rs[0]), (h[0], rs[1]), (cal, rs[2])))
+    path = os.path.join(OUT, 'signs.npz')
+    np.savez_compressed(path, names=np.array(names), soft_iron=np.stack(si), hard_iron=np.stack(hi), lib_vs_restatement=np.array(lvr),
+                        mask_same=same)
+    print('%-12s %7.1f KB  %d records  masks equal %-5s lib_vs_restatement (worst) %s' % (
+        'signs.npz', os.path.getsize(path) / 1024, len(names), same, np.max(np.array(lvr), axis=0)))
 
 
 def main(ref):
@@ -124,4 +151,10 @@ def main(ref):
 
 
 if __name__ == '__main__':
-    main(os.path.abspath(sys.argv[1] if len(sys.argv) > 1 else os.environ['GNSS_INS_SIM_REFERENCE']))
+    reference = os.path.abspath(sys.argv[1] if len(sys.argv) > 1 else os.environ['GNSS_INS_SIM_REFERENCE'])
+    if sys.argv[2:] == ['signs']:
+        signs(reference)
+    elif sys.argv[2:]:
+        sys.exit('usage: make_golden_magcal.py REFERENCE [signs]')
+    else:
+        main(reference)
