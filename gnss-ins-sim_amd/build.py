@@ -38,6 +38,7 @@ SOURCES = [
     # the magnetometer synthesis must give aux_mag_kernel's bits (mag_synth.hpp, same -ffp-contract=on as mc_kernel.hip)
     ('magcal.hip', ['--offload-arch=' + ARCH, '-ffp-contract=on']),
     ('stats.hip', ['--offload-arch=' + ARCH]),
+    ('error_curve.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),
     ('vib_psd.hip', ['--offload-arch=' + ARCH]),

@@ -66,6 +66,12 @@ hipError_t launch_process_stats(const double* traj, const double* ref, int64_t n
                                 int run_major, double* out, hipStream_t s);
 hipError_t launch_process_stats_f32(const float* traj, const double* ref, int64_t n, int64_t runs, int64_t j0, int pos_ned,
                                     int run_major, double* out, const double* origin, int64_t n_ini, uint64_t ini_first, hipStream_t s);
+size_t error_curve_scratch_bytes(const void* traj, int64_t runs, int64_t m);
+hipError_t launch_error_curve(const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
+                              int pos_ned, void* scratch, hipStream_t s);
+hipError_t launch_error_curve_f32(const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
+                                  int pos_ned, void* scratch, const double* origin, int64_t n_ini, uint64_t ini_first, hipStream_t s);
+void curve_merge_host(const double* parts, int nparts, int64_t m, double* out);
 
 
 }  // namespace ginsim
@@ -782,6 +788,64 @@ int ginsim_end_stats_from_traj_f32(ginsim_ctx* c, const float* traj, const doubl
     HIP_TRY(launch_process_stats_f32(traj, ref, n, runs, n - 1, pos_ned, 0, reinterpret_cast<double*>(ws), origin, n_ini, ini_first,
                                      c->stream));
     return ginsim_end_stats(c, reinterpret_cast<double*>(ws) + (size_t)9 * runs, runs, host_out);
+}
+
+// ---- error-growth curves (csrc/error_curve.hip): the across-run record of every requested sample
+static int check_curve_args(const char* who, const void* c, const void* traj, const void* ref, int64_t n, int64_t runs,
+                            const int64_t* samples, int64_t m, const void* host_out) {
+    REQUIRE(c && traj && ref && host_out, "%s: NULL argument", who);
+    REQUIRE(n >= 1 && runs >= 1, "%s: n=%lld runs=%lld must be >= 1", who, (long long)n, (long long)runs);
+    REQUIRE(m >= 1, "%s: m=%lld samples (at least one is needed)", who, (long long)m);
+    REQUIRE(samples || m == n, "%s: samples == NULL means every sample, so m must be n (m=%lld, n=%lld)", who, (long long)m, (long long)n);
+    REQUIRE(m <= 0x7FFFFFFFll, "%s: too many samples for one call", who);
+    if (samples)
+        for (int64_t i = 0; i < m; ++i)
+            REQUIRE(samples[i] >= 0 && samples[i] < n, "%s: sample %lld (entry %lld) is outside [0, %lld)", who, (long long)samples[i],
+                    (long long)i, (long long)n);
+    return GINSIM_OK;
+}
+
+// the scratch region of a curve: [records and slice records of error_curve.hip][m sample indices]
+static int curve_run(ginsim_ctx* c, const void* traj, int f32, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                     int64_t m, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* host_out) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t body = error_curve_scratch_bytes(traj, runs, m);
+    void* ws = nullptr;
+    HIP_TRY(scratch(c, 2, body + sizeof(int64_t) * (size_t)m, &ws));
+    int64_t* d_samples = nullptr;
+    if (samples) {
+        d_samples = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ws) + body);
+        HIP_TRY(hipMemcpyAsync(d_samples, samples, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+    }
+    if (f32)
+        HIP_TRY(launch_error_curve_f32(reinterpret_cast<const float*>(traj), ref, n, runs, d_samples, m, pos_ned, ws, origin, n_ini,
+                                       ini_first, c->stream));
+    else
+        HIP_TRY(launch_error_curve(reinterpret_cast<const double*>(traj), ref, n, runs, d_samples, m, pos_ned, ws, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, ws, sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
+int ginsim_error_curve(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
+                       int32_t pos_ned, double* host_out) {
+    const int rc = check_curve_args("error_curve", c, traj, ref, n, runs, samples, m, host_out);
+    if (rc) return rc;
+    return curve_run(c, traj, 0, ref, n, runs, samples, m, pos_ned, nullptr, 0, 0, host_out);
+}
+
+int ginsim_error_curve_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                           int64_t m, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* host_out) {
+    const int rc = check_curve_args("error_curve_f32", c, traj, ref, n, runs, samples, m, host_out);
+    if (rc) return rc;
+    REQUIRE(origin && n_ini >= 1, "error_curve_f32: the origin table of the displacement series is missing");
+    return curve_run(c, traj, 1, ref, n, runs, samples, m, pos_ned, origin, n_ini, ini_first, host_out);
+}
+
+int ginsim_curve_merge(const double* parts, int32_t nparts, int64_t m, double* out) {
+    REQUIRE(parts && out && nparts >= 1 && m >= 1, "curve_merge: bad arguments");
+    curve_merge_host(parts, nparts, m, out);
+    return GINSIM_OK;
 }
 
 int ginsim_stats_merge(const ginsim_stats* parts, int32_t nparts, ginsim_stats* out) {

@@ -177,6 +177,11 @@ _SIGS = {
     'ginsim_end_stats_from_traj_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                                  C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(Stats)]),
     'ginsim_stats_merge': (C.c_int, [C.POINTER(Stats), C.c_int32, C.POINTER(Stats)]),
+    'ginsim_error_curve': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                     C.c_int32, _PD]),
+    'ginsim_error_curve_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                         C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, _PD]),
+    'ginsim_curve_merge': (C.c_int, [_PD, C.c_int32, C.c_int64, _PD]),
     'ginsim_gather_runs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                      C.POINTER(C.c_int64), C.c_int32, _PD]),
     'ginsim_gather_series': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,

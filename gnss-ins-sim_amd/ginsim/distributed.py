@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .engine import StatsResult
+from .engine import StatsResult, CurveResult
 
 RECORD = 28
 
@@ -57,6 +57,21 @@ def allreduce_stats_end(handle):
     work, table = handle
     work.wait()
     return StatsResult.merge(table.cpu().numpy())
+
+
+def allgather_curve(part, group=None, device=None):
+    """Merge per-rank CurveResult objects (the same samples on every rank) across `group`: every rank's packed records are
+    gathered (one all-gather, whatever the backend) and folded in rank order with the library's Chan merge -- the same curve on
+    every rank.  A rank without runs contributes CurveResult.zero(m).  Identity when not distributed."""
+    if group is None:
+        return part
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    mine = torch.from_numpy(np.ascontiguousarray(part.pack()).reshape(-1)).to(device)
+    rows = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(rows, mine, group=group)
+    return CurveResult.merge([r.cpu().numpy() for r in rows])
 
 
 def _all_agree(ok, group, device):

@@ -535,6 +535,50 @@ class StatsResult(object):
         return StatsResult(out)
 
 
+class CurveResult(object):
+    """count / mean / M2 / max|e| of the 9 error components (att3, pos3, vel3) ACROSS the runs at each of m samples: the
+    error-growth curve of a batch (ginsim_error_curve).  count (m,); mean, m2, maxabs (m, 9).  Curves of disjoint sets of runs
+    over the same samples merge exactly like StatsResult records."""
+
+    def __init__(self, records):
+        r = np.asarray(records, dtype=np.float64).reshape(-1, 9, 4)
+        self.count = r[:, 0, 0].copy()
+        self.mean, self.m2, self.maxabs = r[:, :, 1].copy(), r[:, :, 2].copy(), r[:, :, 3].copy()
+
+    @property
+    def m(self):
+        return self.count.shape[0]
+
+    @staticmethod
+    def zero(m):
+        """The curve of a rank that holds no runs (neutral element of the merge)."""
+        return CurveResult(np.zeros((int(m), 9, 4)))
+
+    @property
+    def std(self):      # np.std(ddof=0), ins_data_manager.py:808
+        return np.sqrt(self.m2 / self.count[:, None])
+
+    def pack(self):
+        """(m, 9, 4) records as the library lays them out."""
+        out = np.empty((self.m, 9, 4))
+        out[:, :, 0] = self.count[:, None]
+        out[:, :, 1], out[:, :, 2], out[:, :, 3] = self.mean, self.m2, self.maxabs
+        return out
+
+    @staticmethod
+    def unpack(v):
+        return CurveResult(v)
+
+    @staticmethod
+    def merge(packed):
+        """Merge packed curves (one (m, 9, 4) array per block of runs, device or rank, in that order) with the library's Chan
+        merge (ginsim_curve_merge); curves without runs are the neutral element."""
+        parts = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.float64).reshape(-1, 9, 4) for p in packed]))
+        out = np.empty(parts.shape[1:])
+        check(lib.ginsim_curve_merge(dptr(parts), parts.shape[0], parts.shape[1], dptr(out)))
+        return CurveResult(out)
+
+
 def starts_on_truth(table, nav0, ref_frame=0):
     """Do all the initial states of `table` ([n_ini][10]: pos3 LLA, body velocity3, yaw / pitch / roll, g) lie ON the truth's first
     sample `nav0` (att3, pos3, vel3)?  Then the error at sample 0 is zero for every run, the launch-wide shift of the online process
@@ -845,6 +889,30 @@ class MonteCarloJob(object):
         check(lib.ginsim_process_stats(self.ctx.handle, self._bufs['traj_' + algo].ptr, self._bufs['ref_nav'].ptr,
                                        self.n, self.runs, int(first_sample), int(bool(pos_ned)), dptr(out)))
         return out
+
+    def error_curve(self, algo, samples=None, pos_ned=False):
+        """The error-growth curve of this batch: the across-run record (CurveResult) of the error at each of `samples` (sample
+        indices in any order, repeats allowed; None: every sample).  Needs the trajectories (keep_traj=True)."""
+        if not self.keep_traj:
+            raise ValueError('process-error statistics need the trajectories (keep_traj=True)')
+        if 'ref_nav' not in self._bufs:
+            self._bufs['ref_nav'] = self.ctx.upload(self._ref_nav)
+        if samples is None:
+            idx, m = None, self.n
+        else:
+            ids = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
+            idx, m = ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size
+        out = np.empty((max(m, 1), 9, 4))
+        traj, ref = self._bufs['traj_' + algo].ptr, self._bufs['ref_nav'].ptr
+        if self.precision == 'f32':     # float series, positions as displacement from the run's initial position
+            org = self._origin().ptr
+            check(self.ctx.retry_oom(lambda: lib.ginsim_error_curve_f32(self.ctx.handle, traj, ref, self.n, self.runs, idx, m,
+                                                                        int(bool(pos_ned)), org, self._ini_table.shape[0],
+                                                                        self._ini_first, dptr(out))))
+        else:
+            check(self.ctx.retry_oom(lambda: lib.ginsim_error_curve(self.ctx.handle, traj, ref, self.n, self.runs, idx, m,
+                                                                    int(bool(pos_ned)), dptr(out))))
+        return CurveResult(out)
 
     def _origin(self):
         """Device table of the initial positions the fp32 displacement series are relative to ([n_ini][3]: ECEF for ref_frame 1,

@@ -21,7 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from .engine import Context, MonteCarloJob, AuxSensorJob, StatsResult, device_count
+from .engine import Context, MonteCarloJob, AuxSensorJob, StatsResult, CurveResult, device_count
 from .distributed import shard
 
 
@@ -181,6 +181,13 @@ class JobSet(_Parts):
 
     def stats_from_traj(self, algo, pos_ned=False):
         return self._merged(lambda j: j.stats_from_traj(algo, pos_ned=pos_ned))
+
+    def error_curve(self, algo, samples=None, pos_ned=False):
+        """MonteCarloJob.error_curve on every device at the same time; the per-device curves folded in device order."""
+        got = [c for c in self._each_part(lambda j: j.error_curve(algo, samples, pos_ned=pos_ned)) if c is not None]
+        if not got:                     # no device holds runs: the empty curve
+            return CurveResult.zero(self.n if samples is None else np.asarray(samples).size)
+        return CurveResult.merge([c.pack() for c in got])
 
     def part_stats(self, algo, ned=False):
         """The unmerged per-device records (device order; None where a device holds no runs)."""

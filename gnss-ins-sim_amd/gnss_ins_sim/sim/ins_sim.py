@@ -207,6 +207,26 @@ class _McResults(object):
                 parts[s].append((name, self.first_run, arr[:, row, sl]))
         return {s: RunStats(parts[s]) for s in parts}
 
+    def error_curve(self, name, samples, n, ned=False):
+        """ginsim.CurveResult of fused algorithm `name` over ALL runs of the Sim: the across-run record of the error at each of
+        `samples` (int64 sample indices; None: every one of the n samples).  Kept trajectories are reduced in one call;
+        statistics-only runs (either precision) are integrated again through _blocks and folded block by block, so the device
+        never holds more than the budget.  Merged over devices (JobSet) and ranks; every rank takes the same branches."""
+        key = ('curve', name, None if samples is None else samples.tobytes(), bool(ned))
+        if key not in self._stats:
+            import ginsim
+            from ginsim import distributed
+            idx = self.algo_names.index(name)
+            job, kind = self.jobs[idx], self.kinds[idx]
+            if job is None:                 # a rank without runs: the empty curve, into the same collective
+                part = ginsim.CurveResult.zero(n if samples is None else samples.size)
+            elif job.keep_traj:
+                part = job.error_curve(kind, samples, pos_ned=ned)
+            else:
+                part = ginsim.CurveResult.merge([b.error_curve(kind, samples, pos_ned=ned).pack() for b in self._blocks(idx)])
+            self._stats[key] = distributed.allgather_curve(part, self._group, self._device)
+        return self._stats[key]
+
     def run_of_key(self, key):
         return int(str(key).rsplit('_', 1)[-1]) if isinstance(key, str) else int(key)
 
@@ -1048,6 +1068,61 @@ class Sim(object):
                         f.write(self.sum + '\n')
                 except Exception:
                     raise IOError('Unable to save summary to %s.' % data_dir)
+
+    def error_curve(self, data_names=('att_euler', 'pos', 'vel'), *, every=None, samples=None, extra_opt=''):
+        """How the error grows with time: the across-run max |e|, mean and std (ddof 0) of the attitude, position and velocity
+        error at each instant -- at sample j what ``results(err_stats_start=-1)`` reports for the series cut after j
+        (ins_data_manager.py:717-759, 797-808).  The reference draws one error line per run (``plot(..., opt={'pos': 'error'})``);
+        this is the same information for any number of runs, reduced on the device.
+          every     seconds between the instants (from the first sample); None and samples=None: every sample
+          samples   or the sample indices themselves (any order, repeats allowed)
+          extra_opt 'ned': position error in local NED metres (ref_frame 0), as in ``results``
+        Returns {name: {'time': (m,), 'units': [...], 'max' | 'avg' | 'std': {algorithm name: (m, 3)}}} in the output units of
+        ``get_error_stats(use_output_units=True)`` (attitude in degrees).  Only the fused free-integration plugins carry these
+        curves.  Statistics-only Sims integrate their runs again in blocks that fit ``max_device_bytes``."""
+        if not self.sim_complete:
+            print("Call Sim.run() to run the simulaltion first.")
+            return None
+        d, mc = self.dmgr, self.mc
+        names = list(getattr(mc, 'fused_names', None) or []) if mc is not None and not self.data_from_files else []
+        if isinstance(data_names, str):
+            data_names = (data_names,)
+        slices = {'att_euler': slice(0, 3), 'pos': slice(3, 6), 'vel': slice(6, 9)}
+        for nm in data_names:
+            if nm not in slices:
+                raise ValueError("error_curve: %r has no error curve (one of 'att_euler', 'pos', 'vel')" % (nm,))
+        if not names:
+            raise ValueError('error_curve: the curves of %s come from the fused free-integration plugins (FreeIntegration, '
+                             'FreeIntegrationOdo), and this Sim has none -- inclinometer, MagCal and host plugins are not covered'
+                             % (', '.join(data_names),))
+        t = np.asarray(d.time.data)
+        n = t.shape[0]
+        if every is not None and samples is not None:
+            raise ValueError('error_curve: give every (seconds) or samples (indices), not both')
+        if every is not None:
+            step = int(round(float(every) * float(self.fs[0])))
+            if step < 1:
+                raise ValueError('error_curve: every=%r s is shorter than one sample at %g Hz' % (every, self.fs[0]))
+            samples = np.arange(0, n, step, dtype=np.int64)
+        if samples is not None:
+            samples = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
+            if samples.size == 0 or samples.min() < 0 or samples.max() >= n:
+                raise ValueError('error_curve: samples must be indices in [0, %d), at least one' % n)
+        # one reduction serves every name: the NED form changes the position components only
+        use_ned = self.ref_frame == 0 and extra_opt == 'ned' and 'pos' in data_names
+        out = {}
+        for nm in data_names:
+            src = d.get_data_all(nm)
+            units, out_units = list(src.units), list(src.output_units)
+            if use_ned and nm == 'pos':
+                units, out_units = ['m', 'm', 'm'], ['m', 'm', 'm']
+            res = {'time': t.copy() if samples is None else t[samples], 'units': out_units, 'max': {}, 'avg': {}, 'std': {}}
+            for a in names:
+                c = mc.error_curve(a, samples, n, ned=use_ned)
+                for stat, arr in (('max', c.maxabs), ('avg', c.mean), ('std', c.std)):
+                    res[stat][a] = sim_data.convert_unit(np.ascontiguousarray(arr[:, slices[nm]]), units, out_units)
+            out[nm] = res
+        return out
 
     def plot(self, what_to_plot, sim_idx=None, opt=None, extra_opt=''):
         """Plotting is outside the accelerated path; the call is accepted (the reference's demo scripts end with it) and

@@ -446,6 +446,26 @@ int ginsim_end_stats_from_traj_f32(ginsim_ctx* ctx, const float* traj, const dou
                                    const double* origin, int32_t n_ini, uint64_t ini_first, ginsim_stats* host_out);
 int ginsim_stats_merge(const ginsim_stats* parts, int32_t nparts, ginsim_stats* out);
 
+/* ---- error-growth curves: the ACROSS-RUN statistics of the error at every requested sample (csrc/error_curve.hip).  At sample
+ *      j this is __end_point_error_stats + __array_stats (ins_data_manager.py:717-759, 797-808) applied to the series cut after j,
+ *      with the error expression of ginsim_process_stats (attitude wrapped, pos_ned as there).  Added without a change of
+ *      GINSIM_ABI_VERSION: nothing existing moved.
+ *      traj: device [9][n][runs]; ref: device [n][9]; samples: HOST int64[m] sample indices in [0, n), in any order, repeats
+ *      allowed, or NULL = every sample (m must then be n).  host_out: [m][9] records of GINSIM_CURVE_RECORD doubles
+ *      (count, mean, M2, max|e|): std(ddof=0) = sqrt(M2 / count).  The order of the sums depends on n, runs, m and on whether
+ *      traj is 16-byte aligned (hipMalloc'ed and placed regions are; an aligned traj with an even run count of at least 128 is
+ *      read two runs per lane, anything else one): the same (n, runs, m, alignment of traj) gives the same bits at every call,
+ *      another alignment the same numbers to rounding. */
+#define GINSIM_CURVE_RECORD 4
+int ginsim_error_curve(ginsim_ctx* ctx, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                       int64_t m, int32_t pos_ned, double* host_out);
+/* the same over the FLOAT trajectories of the fp32 kernel; origin, n_ini, ini_first as ginsim_process_stats_f32 takes them */
+int ginsim_error_curve_f32(ginsim_ctx* ctx, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                           int64_t m, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* host_out);
+/* Host only: the curves of nparts sets of runs (parts: [nparts][m][9] records; a set without runs is all zeros) folded record by
+ * record with the Chan merge of ginsim_stats_merge, in the order given. */
+int ginsim_curve_merge(const double* parts, int32_t nparts, int64_t m, double* out);
+
 /* ---- data access: pull selected runs out of a [ncomp][n][runs] device series into host [nsel][n][ncomp] */
 int ginsim_gather_runs(ginsim_ctx* ctx, const double* series, int32_t ncomp, int64_t n, int64_t runs,
                        const int64_t* run_ids /*host*/, int32_t nsel, double* host_out);
