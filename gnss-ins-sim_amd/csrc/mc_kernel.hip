@@ -463,6 +463,27 @@ constexpr int kSplitStep = 12 * 4;                      // bytes per step and ru
 constexpr size_t kSplitRing = (size_t)2 * kSplitTile * kSplitStep * kSplitRuns;
 constexpr size_t kSplitLds = kSplitRing > 100 * 1024 ? kSplitRing : 100 * 1024;
 
+// The inputs of a step of the consumer besides the normals (DESIGN_EXPERIMENTS "The consumer's four scalar waits").
+// The truth rows of a tile are fetched by the producers, which idle most of a tile, into `truth` while they fill the tile's normals
+// (one lane per number, NOT gated on the lane's run: the last workgroup may have no active lane in a producer wavefront; no row at
+// or beyond n_noise <= n is read); the consumer reads its step's row with uniform-address LDS loads next to its ring reads.  The
+// tile barrier orders these writes and reads exactly as it orders the normals.
+struct SplitInputs {
+    double truth[2][ginsim::kSplitTile][8];     // [stage][step of the tile][accel x y z, gyro x y z, forward speed, -]
+};
+typedef const SplitInputs __attribute__((address_space(3))) * split_inputs_ptr;
+
+// -DGINSIM_STEP_TIMING (experiment builds only, build.py tag=): consumer wave 0 of every workgroup sums s_memtime deltas from the top
+// of a step to the finished sensor sums (every memory wait of the step's inputs lies before that point) and over the whole step, and
+// writes {input cycles, step cycles} once at its end; ginsim_step_timing copies the table out.
+#ifdef GINSIM_STEP_TIMING
+constexpr int kTimingGroups = 1024;
+__device__ unsigned long long g_step_timing[kTimingGroups][2];
+#define GINSIM_TIMING(...) __VA_ARGS__
+#else
+#define GINSIM_TIMING(...)
+#endif
+
 // PROD producer wavefronts per consumer wavefront: with two (768 threads, three wavefronts per SIMD, <= 168 registers) the
 // steps of a tile alternate between the two producer groups.
 // KEEP = false: a statistics-only launch (no series pointer set): the store code and its address registers are compiled out,
@@ -500,11 +521,29 @@ __global__ void __launch_bounds__(256 * (1 + PROD)) mc_kernel_split(const ginsim
     mk.init<(ALGOS != (GINSIM_ALGO_FREE | GINSIM_ALGO_ODO))>();     // the two-algorithm consumer would spill
     __shared__ uint32_t ntab[kNormalLdsWords];
     const NormalTables tab = fill_normal_tables(ntab, threadIdx.x, blockDim.x);
+    static_assert(kSplitTile <= ginsim::kSplitTile, "SplitInputs::truth is sized by the longer tile");
+    // the two-producer instantiations only (the headline's, C4's): in the one-producer ones the same source costs the compiler
+    // 36 bytes of scratch per lane that nothing uses, and they keep the step as it was
+    constexpr bool STAGED = PROD == 2;
+    __shared__ SplitInputs in;
+    const bool need_odo = ODO || a.out_odo;
     __syncthreads();
 
 
     if (producer) {
+        const int sl = (int)threadIdx.x - kSplitRuns;       // the first 8 T lanes of the first producer group stage the truth
         for (int64_t i = 0; i <= ntiles; ++i) {
+            if (STAGED && i < ntiles && sl < 8 * kSplitTile) {
+                const int t = sl >> 3, c = sl & 7;
+                const int64_t j = i * kSplitTile + t;
+                if (j < n_noise) {
+                    double v = 0.0;
+                    if (c < 3) v = a.ref_accel[3 * j + c];
+                    else if (c < 6) v = a.ref_gyro[3 * j + (c - 3)];
+                    else if (c == 6 && need_odo) v = a.ref_odo[j];
+                    in.truth[i & 1][t][c] = v;
+                }
+            }
             if (i < ntiles && active) {
                 float* stage = zring + (i & 1) * (kSplitTile * kStepFloats);
 #pragma unroll
@@ -556,6 +595,7 @@ __global__ void __launch_bounds__(256 * (1 + PROD)) mc_kernel_split(const ginsim
         if (FREE && a.out_traj[0]) store9(a.out_traj[0], plane, r, fi);
         if (ODO && a.out_traj[1]) store9(a.out_traj[1], plane, r, od);
     }
+    GINSIM_TIMING(uint64_t tm_in = 0, tm_step = 0;)
     for (int64_t i = 0; i <= ntiles; ++i) {
         if (i >= 1 && active) {
             const float* stage = zring + ((i - 1) & 1) * (kSplitTile * kStepFloats);
@@ -565,7 +605,29 @@ __global__ void __launch_bounds__(256 * (1 + PROD)) mc_kernel_split(const ginsim
                 if (j >= n_noise) break;
                 const int64_t off = j * runs + r;
                 const bool last = (j == n - 1);
-                const Vec3 cur_a = load3(as_uniform(a.ref_accel), j), cur_g = load3(as_uniform(a.ref_gyro), j);
+                GINSIM_TIMING(const uint64_t tm0 = __builtin_amdgcn_s_memtime();)
+                Vec3 cur_a, cur_g;
+                ModelBatch ma{}, mg{};
+                const double __attribute__((address_space(3))) * tr = nullptr;
+                if constexpr (STAGED) {
+                    // this step's truth row: the same LDS address in every lane (a broadcast); opaque per step so that the loads stay here
+                    split_inputs_ptr q = (split_inputs_ptr)&in;
+                    asm volatile("" : "+v"(q));
+                    tr = q->truth[(i - 1) & 1][t];
+                    cur_a = Vec3{tr[0], tr[1], tr[2]};
+                    cur_g = Vec3{tr[3], tr[4], tr[5]};
+                    // the eighteen coefficients of the simple model in ONE batch of scalar loads, asked for here and all due at the asm:
+                    // taken where sense3 uses them they came in three batches, each behind a wait of its own
+                    const params_ptr kp = kernarg_params();
+                    ma = load_model(&kp->accel);
+                    mg = load_model(&kp->gyro);
+                    asm volatile("" :: "s"(ma.gm_a[0]), "s"(ma.gm_a[1]), "s"(ma.gm_a[2]), "s"(ma.gm_b[0]), "s"(ma.gm_b[1]), "s"(ma.gm_b[2]),
+                                 "s"(ma.white[0]), "s"(ma.white[1]), "s"(ma.white[2]), "s"(mg.gm_a[0]), "s"(mg.gm_a[1]), "s"(mg.gm_a[2]),
+                                 "s"(mg.gm_b[0]), "s"(mg.gm_b[1]), "s"(mg.gm_b[2]), "s"(mg.white[0]), "s"(mg.white[1]), "s"(mg.white[2]));
+                } else {
+                    cur_a = load3(as_uniform(a.ref_accel), j);
+                    cur_g = load3(as_uniform(a.ref_gyro), j);
+                }
                 const float* zb = stage + t * kStepFloats + lane;
                 double p0[6], p1[6];                  // z0 / z1 of streams 0..5
 #pragma unroll
@@ -573,9 +635,21 @@ __global__ void __launch_bounds__(256 * (1 + PROD)) mc_kernel_split(const ginsim
                     p0[k] = (double)zb[(2 * k) * kSplitRuns];
                     p1[k] = (double)zb[(2 * k + 1) * kSplitRuns];
                 }
-                const params_ptr kp = kernarg_params();
-                Vec3 acc = sense3<WD>(cur_a, &kp->accel, da, Vec3{p0[0], p1[0], p0[1]}, Vec3{p1[1], p0[2], p1[2]});
-                Vec3 gyr = sense3<WD>(cur_g, &kp->gyro, dg, Vec3{p0[3], p1[3], p0[4]}, Vec3{p1[4], p0[5], p1[5]});
+                Vec3 acc, gyr;
+                if constexpr (STAGED) {
+                    acc = sense3<WD>(cur_a, &ma, da, Vec3{p0[0], p1[0], p0[1]}, Vec3{p1[1], p0[2], p1[2]});
+                    gyr = sense3<WD>(cur_g, &mg, dg, Vec3{p0[3], p1[3], p0[4]}, Vec3{p1[4], p0[5], p1[5]});
+                    // the drift update is due HERE: left alone it sinks to the bottom of the step, and the twelve coefficients and six
+                    // normals it needs stay in registers through the whole mechanisation
+                    asm volatile("" : "+v"(da.x), "+v"(da.y), "+v"(da.z), "+v"(dg.x), "+v"(dg.y), "+v"(dg.z));
+                } else {
+                    const params_ptr kp = kernarg_params();
+                    acc = sense3<WD>(cur_a, &kp->accel, da, Vec3{p0[0], p1[0], p0[1]}, Vec3{p1[1], p0[2], p1[2]});
+                    gyr = sense3<WD>(cur_g, &kp->gyro, dg, Vec3{p0[3], p1[3], p0[4]}, Vec3{p1[4], p0[5], p1[5]});
+                }
+                GINSIM_TIMING(
+                    asm volatile("" : "+v"(acc.x), "+v"(acc.y), "+v"(acc.z), "+v"(gyr.x), "+v"(gyr.y), "+v"(gyr.z));
+                    tm_in += __builtin_amdgcn_s_memtime() - tm0;)
                 if (VIB) {              // added last, as pathgen.py:500, 562 do
                     const params_ptr kv = kernarg_params();
                     double va[3] = {0.0, 0.0, 0.0}, vg[3] = {0.0, 0.0, 0.0};
@@ -591,11 +665,11 @@ __global__ void __launch_bounds__(256 * (1 + PROD)) mc_kernel_split(const ginsim
                 if (a.out_accel) store3(a.out_accel, plane, off, acc);
                 if (a.out_gyro) store3(a.out_gyro, plane, off, gyr);
                 double odo = 0.0;
-                if (ODO || a.out_odo) {
+                if (need_odo) {
                     double z0, z1;
                     normal_pair(key, S_ODO, (uint32_t)j, z0, z1, tab);
                     const params_ptr kq = kernarg_params();
-                    odo = kq->odo_scale * as_uniform(a.ref_odo)[j] + kq->odo_stdv * z0;
+                    odo = kq->odo_scale * (STAGED ? tr[6] : as_uniform(a.ref_odo)[j]) + kq->odo_stdv * z0;
                     if (a.out_odo) a.out_odo[off] = odo;
                 }
                 if (last) break;
@@ -608,10 +682,16 @@ __global__ void __launch_bounds__(256 * (1 + PROD)) mc_kernel_split(const ginsim
                     nav_step<RF, true>(od, gyr, acc, odo, dt, a.earth_rot, resync, mk);
                     if (a.out_traj[1]) store9(a.out_traj[1], plane, off + runs, od);
                 }
+                GINSIM_TIMING(tm_step += __builtin_amdgcn_s_memtime() - tm0;)
             }
         }
         __syncthreads();
     }
+    GINSIM_TIMING(
+        if (threadIdx.x == 0 && blockIdx.x < kTimingGroups) {
+            unsigned long long* q = g_step_timing[blockIdx.x];
+            q[0] = tm_in; q[1] = tm_step;
+        })
     if (active) {
         if (FREE && a.out_end[0]) store_end(a.out_end[0], runs, r, fi);
         if (ODO && a.out_end[1]) store_end(a.out_end[1], runs, r, od);
@@ -1394,4 +1474,14 @@ hipError_t launch_gather_runs(const double* series, int C, int64_t n, int64_t ru
 }
 
 }  // namespace ginsim
+
+#ifdef GINSIM_STEP_TIMING
+// experiment builds only: the timing table of the last wave-specialised launch, [groups][2]; returns the number of rows copied
+extern "C" int ginsim_step_timing(unsigned long long* out, int groups) {
+    if (groups > ginsim::kTimingGroups) groups = ginsim::kTimingGroups;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ginsim::g_step_timing), sizeof(unsigned long long) * 2 * groups) != hipSuccess) return -1;
+    return groups;
+}
+#endif
 

@@ -43,6 +43,24 @@ __device__ __forceinline__ uniform_ptr as_uniform(const double* p) {
     return (uniform_ptr)(uintptr_t)p;
 }
 
+// The nine coefficients of the simple sensor model as values, all asked for at once (one batch of scalar loads), for a caller that
+// wants them due at one point instead of where sense3 uses them.  The bias and the white-drift flags of the general model (WD) stay
+// behind the pointer and are read where they are used, as through model_ptr.
+struct ModelBatch {
+    double gm_a[3], gm_b[3], white[3];
+    struct Bias {
+        model_ptr m;
+        __device__ __forceinline__ double operator[](int k) const { return m->bias[k]; }
+    } bias;
+    struct WhiteDrift {
+        model_ptr m;
+        __device__ __forceinline__ int32_t operator[](int k) const { return m->white_drift[k]; }
+    } white_drift;
+};
+__device__ __forceinline__ ModelBatch load_model(model_ptr m) {
+    return ModelBatch{{m->gm_a[0], m->gm_a[1], m->gm_a[2]}, {m->gm_b[0], m->gm_b[1], m->gm_b[2]}, {m->white[0], m->white[1], m->white[2]}, {m}, {m}};
+}
+
 // Sensor sample j of one 3-axis sensor: truth + bias + drift + white  (pathgen.py:500, 562), and the
 // Gauss-Markov update d[j+1] = a d[j] + b N[j] (pathgen.py:589-590).
 __device__ __forceinline__ Vec3 load3(uniform_ptr ref, int64_t j) { return Vec3{ref[3 * j], ref[3 * j + 1], ref[3 * j + 2]}; }
@@ -50,8 +68,10 @@ __device__ __forceinline__ Vec3 load3(uniform_ptr ref, int64_t j) { return Vec3{
 // WD = false: the launcher saw no axis with an infinite correlation time (white_drift) and no constant bias in either
 // sensor -- every standard IMU grade of imu_model.py -- so the six wave-uniform selects and the three bias additions
 // per sensor are compiled out (x + 0.0 == x: the values are the same).
-template <bool WD = true>
-__device__ __forceinline__ Vec3 sense3(const Vec3& truth, model_ptr m, Vec3& drift, const Vec3& zd,
+// M: where the model is read from -- model_ptr (the kernarg segment, scalar loads at each use) or a pointer to a ModelBatch the caller
+// loaded itself (the consumer of mc_kernel_split); the same expressions on the same values either way.
+template <bool WD = true, class M = model_ptr>
+__device__ __forceinline__ Vec3 sense3(const Vec3& truth, M m, Vec3& drift, const Vec3& zd,
                                        const Vec3& zw) {
     const double bx = m->gm_b[0] * zd.x, by = m->gm_b[1] * zd.y, bz = m->gm_b[2] * zd.z;
     const double dx = (WD && m->white_drift[0]) ? bx : drift.x;

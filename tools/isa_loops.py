@@ -7,10 +7,38 @@
 Finds backward branches (a loop = the lines between a label and a later branch to it) and prints, per loop, the
 count of VALU / SALU / VMEM / LDS / SMEM instructions and the most frequent opcodes.  A static count: it says what one
 trip through the straight-line body issues, which is what matters for a VALU-issue-bound kernel.
+
+SMEMWAIT: the s_waitcnt on lgkmcnt of the loop that are issued while a scalar load may be outstanding.  A scalar load shares
+lgkmcnt with LDS and returns out of order, so only lgkmcnt(0) retires it, and every such wait costs the wavefront a scalar-cache
+(or L2) round trip however short the LDS queue is.  Counted along the listing, branches inside the body not followed, a load
+issued at the bottom of the loop carried to its top.
 """
 import collections
 import re
 import sys
+
+
+def smem_waits(body):
+    """waits on lgkmcnt met while a scalar load is outstanding, along the listing; the second trip is the one counted, so that
+    a load the bottom of the loop leaves in flight is seen by the top"""
+    pending, count = False, 0
+    for trip in range(2):
+        count = 0
+        for l in body:
+            m = re.match(r'^\s+([a-z_0-9]+)\s*(.*)', l)
+            if not m:
+                continue
+            op, args = m.group(1), m.group(2)
+            if op.startswith(('s_load', 's_buffer_load', 's_memtime', 's_memrealtime')):
+                pending = True
+            elif op == 's_waitcnt':
+                w = re.search(r'lgkmcnt\((\d+)\)', args)
+                if w:
+                    if pending:
+                        count += 1
+                    if int(w.group(1)) == 0:
+                        pending = False
+    return count
 
 
 def main():
@@ -54,6 +82,7 @@ def main():
                 cls['VMEM'] += 1
             elif op.startswith('ds_'):
                 cls['LDS'] += 1
+        cls['SMEMWAIT'] = smem_waits(body[a:b + 1])
         print('\nloop %s: lines %d..%d (%d)  %s' % (t, a, b, b - a, dict(cls)))
         print('   ' + ', '.join('%s %d' % kv for kv in ops.most_common(28)))
 
