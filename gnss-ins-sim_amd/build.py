@@ -20,13 +20,20 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 
 COMMON = ['-O3', '-std=c++17', '-fPIC', '-I' + os.path.join(REPO, 'include'), '-I' + CSRC, '-Wall',
           '-Wno-unused-function']
+# The fp64 kernel flags: mc_kernel.hip's, shared by the four files split off from it (series, aux_sensors, rng_probe, layout) so
+# that their kernels compile to the ISA they had inside it.
+# machine-LICM hoists ~35 fp64 polynomial constants (SGPR pairs) out of the time loop and then spills them
+# to VGPR lanes; without it they are re-materialised with s_mov next to their use (SGPR spills 192 -> 71)
+# -ffp-contract=on: fused multiply-adds only where one source expression spells a*b+c, decided in the front
+# end, so the plain and the wave-specialised kernels (same inlined functions) give identical bits
+MC_FLAGS = ['--offload-arch=' + ARCH, '-mllvm', '-disable-machine-licm', '-ffp-contract=on']
 # (source, extra flags)
 SOURCES = [
-    # machine-LICM hoists ~35 fp64 polynomial constants (SGPR pairs) out of the time loop and then spills them
-    # to VGPR lanes; without it they are re-materialised with s_mov next to their use (SGPR spills 192 -> 71)
-    # -ffp-contract=on: fused multiply-adds only where one source expression spells a*b+c, decided in the front
-    # end, so the plain and the wave-specialised kernels (same inlined functions) give identical bits
-    ('mc_kernel.hip', ['--offload-arch=' + ARCH, '-mllvm', '-disable-machine-licm', '-ffp-contract=on']),
+    ('mc_kernel.hip', MC_FLAGS),
+    ('series.hip', MC_FLAGS),
+    ('aux_sensors.hip', MC_FLAGS),
+    ('rng_probe.hip', MC_FLAGS),
+    ('layout.hip', MC_FLAGS),
     # the fp32 kernel is DEFINED operation by operation (the float oracle repeats it to the bit): no contraction at all,
     # fused multiply-adds only where the source spells __builtin_fmaf
     # no SLP vectorisation either: it packed the consumer's float arithmetic into v_pk_*_f32 pairs (a 4-cycle-class
@@ -35,7 +42,7 @@ SOURCES = [
     ('mc_kernel_f32.hip', ['--offload-arch=' + ARCH, '-mllvm', '-disable-machine-licm', '-ffp-contract=off', '-fno-slp-vectorize']),
     # the sensor synthesis must give mc_kernel.hip's bits (same -ffp-contract=on); the filter code switches contraction off itself
     ('inclinometer.hip', ['--offload-arch=' + ARCH, '-ffp-contract=on']),
-    # the magnetometer synthesis must give aux_mag_kernel's bits (mag_synth.hpp, same -ffp-contract=on as mc_kernel.hip)
+    # the magnetometer synthesis must give aux_mag_kernel's bits (mag_synth.hpp, same -ffp-contract=on as aux_sensors.hip)
     ('magcal.hip', ['--offload-arch=' + ARCH, '-ffp-contract=on']),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
@@ -100,7 +107,8 @@ def build(force=False, verbose=False, tag=None, defines=(), xflags=()):
             if p.returncode != 0:
                 raise subprocess.CalledProcessError(p.returncode, cmd)
     if force or any(newer(o, LIB) for o in objs):
-        cmd = [HIPCC, '-shared', '-fPIC', '--offload-arch=' + ARCH, '-o', LIB] + objs + ['-ldl']
+        # no undefined symbols: a launcher that launch.hpp declares and nothing defines fails here, not when the library is loaded
+        cmd = [HIPCC, '-shared', '-fPIC', '-Wl,-z,defs', '--offload-arch=' + ARCH, '-o', LIB] + objs + ['-ldl']
         if verbose:
             print(' '.join(cmd))
         subprocess.check_call(cmd)

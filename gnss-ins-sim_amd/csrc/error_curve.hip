@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
 #include "moments.hpp"
+#include "launch.hpp"
 
 namespace ginsim {
 

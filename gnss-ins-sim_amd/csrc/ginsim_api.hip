@@ -13,6 +13,7 @@
 #include "ginsim.h"
 #include "allan.hpp"
 #include "comm.hpp"
+#include "launch.hpp"
 #include "placed.hpp"
 
 namespace ginsim {
@@ -27,52 +28,6 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
     g_err = buf;
 }
-
-hipError_t launch_mc(const ginsim_mc_params& p, hipStream_t stream, char* name, size_t cap, double* proc_about);      // name: report, do not launch
-hipError_t launch_mc_f32(const ginsim_mc_params& p, float* truth32, hipStream_t stream, char* name, size_t cap);
-hipError_t launch_incl(const ginsim_mc_params& p, const ginsim_incl_params& b, hipStream_t stream, char* name, size_t cap);
-int incl_variant(const ginsim_mc_params& p);
-size_t mc_f32_truth_bytes(const ginsim_mc_params& p);
-int mc_variant(const ginsim_mc_params& p);
-bool series_path_applies(const ginsim_mc_params& p);
-int series_pass_b(const ginsim_mc_params& p);
-int64_t series_chunks(const ginsim_mc_params& p, int32_t* L_out);
-hipError_t launch_series(const ginsim_mc_params& p, double* carry, hipStream_t stream);
-int mc_variant_f32(const ginsim_mc_params& p);
-hipError_t launch_gather_runs_f32(const float* series, int C, int64_t n, int64_t runs, const int64_t* ids, int nsel,
-                                  double* out, hipStream_t s);
-hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s);
-hipError_t launch_magcal(const ginsim_magcal_params& p, hipStream_t s);
-size_t vib_psd_scratch_bytes(int64_t period, int64_t runs);
-int launch_vib_psd(int device, hipStream_t stream, const double* amp, int64_t period, int64_t runs, uint64_t run_offset, uint64_t seed,
-                   int sensor, int halve, void* scratch, double* out);
-void vib_psd_drop_plans(hipStream_t stream);
-hipError_t launch_rng_probe(uint64_t seed, uint64_t run, uint32_t stream, int64_t count, double* z0, double* z1,
-                            uint32_t* words, hipStream_t stream_h);
-hipError_t launch_aos_to_soa(const double* src, double* dst, int64_t R, int64_t n, int C, hipStream_t s);
-hipError_t launch_runs_to_series(const double* in, double* out, int C, int64_t n, int64_t R, hipStream_t s);
-hipError_t launch_normal_transform(const uint32_t* words, int64_t count, double* z0, double* z1, hipStream_t s);
-hipError_t launch_pattern_fill(void* p, uint64_t words, uint32_t tag, hipStream_t s);
-hipError_t launch_pattern_check(const void* p, uint64_t words, uint32_t tag, unsigned long long* out, hipStream_t s);
-hipError_t launch_digest(const void* p, uint64_t words, unsigned long long* out, hipStream_t s);
-hipError_t launch_gather_runs(const double* series, int C, int64_t n, int64_t runs, const int64_t* ids, int nsel,
-                              double* out, hipStream_t s);
-hipError_t launch_gather_series(const double* series, int C, int64_t n, const int64_t* ids, int nsel, double* out, hipStream_t s);
-size_t stats_scratch_bytes(int64_t runs);
-int stats_blocks(int64_t runs);
-hipError_t launch_end_stats(const double* end_err, int64_t runs, void* scratch, hipStream_t s);
-void stats_merge_host(const ginsim_stats* parts, int nparts, ginsim_stats* out);
-hipError_t launch_process_stats(const double* traj, const double* ref, int64_t n, int64_t runs, int64_t j0, int pos_ned,
-                                int run_major, double* out, hipStream_t s);
-hipError_t launch_process_stats_f32(const float* traj, const double* ref, int64_t n, int64_t runs, int64_t j0, int pos_ned,
-                                    int run_major, double* out, const double* origin, int64_t n_ini, uint64_t ini_first, hipStream_t s);
-size_t error_curve_scratch_bytes(const void* traj, int64_t runs, int64_t m);
-hipError_t launch_error_curve(const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                              int pos_ned, void* scratch, hipStream_t s);
-hipError_t launch_error_curve_f32(const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                                  int pos_ned, void* scratch, const double* origin, int64_t n_ini, uint64_t ini_first, hipStream_t s);
-void curve_merge_host(const double* parts, int nparts, int64_t m, double* out);
-
 
 }  // namespace ginsim
 

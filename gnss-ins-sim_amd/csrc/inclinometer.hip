@@ -21,6 +21,7 @@
 #include "ins_math.hpp"
 #include "philox.hpp"
 #include "sensor_synth.hpp"
+#include "launch.hpp"
 
 namespace ginsim {
 

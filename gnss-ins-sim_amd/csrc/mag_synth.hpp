@@ -1,7 +1,7 @@
-// Magnetometer synthesis shared by the kernels that make a run's magnetometer samples (aux_mag_kernel of mc_kernel.hip, which
+// Magnetometer synthesis shared by the kernels that make a run's magnetometer samples (aux_mag_kernel of aux_sensors.hip, which
 // writes them, and magcal.hip, which consumes them in registers): pathgen.mag_gen (pathgen.py:658-661),
 //     mag = si . (ref_mag + hi) + std * N,    N = the three normals of (seed, run) at counter j, stream S_MAG_XY.
-// Moved here verbatim from aux_mag_kernel: the ISA of mc_kernel.hip's kernels is unchanged.  Both files are compiled with
+// Moved here verbatim from aux_mag_kernel: the ISA of that kernel is unchanged.  Both files are compiled with
 // -ffp-contract=on, and mag_axis is ONE source expression, so the front end fuses the same multiply-adds in both: the same bits.
 #pragma once
 #include <hip/hip_runtime.h>

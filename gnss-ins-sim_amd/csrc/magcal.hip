@@ -23,6 +23,7 @@
 #include "philox.hpp"
 #include "sensor_synth.hpp"
 #include "mag_synth.hpp"
+#include "launch.hpp"
 
 namespace ginsim {
 

@@ -28,6 +28,7 @@
 #include "ins_math.hpp"
 #include "philox.hpp"
 #include "device_once.hpp"
+#include "launch.hpp"
 
 namespace ginsim {
 
@@ -691,11 +692,6 @@ __global__ void __launch_bounds__(256 * (1 + PROD)) mc_kernel_f32_split(const gi
 
 }  // namespace f32
 
-static int split_policy_f32() {
-    static const int v = [] { const char* e = getenv("GINSIM_SPLIT"); return e ? atoi(e) : -1; }();
-    return v;
-}
-
 // producer groups of the wave-specialised fp32 kernel asked for by GINSIM_SPLIT_PROD (1..3), 0: the default of the variant
 static int split_prod_f32() {
     static const int v = [] { const char* e = getenv("GINSIM_SPLIT_PROD"); const int k = e ? atoi(e) : 0; return k >= 1 && k <= 3 ? k : 0; }();
@@ -710,25 +706,16 @@ static int keep_mode_f32(const ginsim_mc_params& p) {
     return all ? 1 : (none ? 0 : -1);
 }
 
-static bool any_vibration_f32(const ginsim_mc_params& p) { return p.vib_accel.type != GINSIM_VIB_NONE || p.vib_gyro.type != GINSIM_VIB_NONE; }
-
 int mc_variant_f32(const ginsim_mc_params& p) {
-    if (any_vibration_f32(p)) return 0;         // the vibration term lives in the plain kernel (general sensor model)
+    if (any_vibration(p)) return 0;         // the vibration term lives in the plain kernel (general sensor model)
     if (!(p.algo_mask & GINSIM_ALGO_FREE) || p.given_sensors || p.block_threads != 0 || p.n < 2) return 0;      // block_threads: the plain kernel (tests)
     const int keep = keep_mode_f32(p);
     if (keep < 0) return 0;
     // the wave-specialised kernel addresses a group of three planes with 32-bit byte offsets
     if (keep == 1 && (double)p.n * (double)p.runs * 12.0 >= 4294967296.0) return 0;
-    const int pol = split_policy_f32();
+    const int pol = split_policy();
     if (pol >= 0) return pol != 0;
     return 1;       // three wavefronts per SIMD beat the plain kernel at every size (as for the fp64 kernel)
-}
-
-static bool any_white_drift_f32(const ginsim_mc_params& p) {
-    bool f = false;
-    for (int k = 0; k < 3; ++k)
-        f = f || p.accel.white_drift[k] || p.gyro.white_drift[k] || p.accel.bias[k] != 0.0 || p.gyro.bias[k] != 0.0;
-    return f;
 }
 
 template <int RF, int ALGOS, bool WD, int PROD, bool KEEP>
@@ -774,7 +761,7 @@ static hipError_t launch3_f32(const ginsim_mc_params& p, const float* truth32, h
             return keep ? launch_split_f32<RF, ALGOS, WD, 1, true>(p, truth32, stream) : launch_split_f32<RF, ALGOS, WD, 1, false>(p, truth32, stream);
         }
     }
-    const bool vib = WD && any_vibration_f32(p);
+    const bool vib = WD && any_vibration(p);
     if (name) {
         snprintf(name, cap, "ginsim::f32::mc_kernel_f32<%d, %d, false, %s, %s>", RF, ALGOS, WD ? "true" : "false", vib ? "true" : "false");
         return hipSuccess;
@@ -805,7 +792,7 @@ static hipError_t launch2_f32(const ginsim_mc_params& p, const float* truth32, h
         hipLaunchKernelGGL((f32::mc_kernel_f32<RF, ALGOS, true, false>), dim3((unsigned)((p.runs + 255) / 256)), dim3(256), lds, stream, p);
         return hipGetLastError();
     }
-    return any_white_drift_f32(p) || any_vibration_f32(p) ? launch3_f32<RF, ALGOS, true>(p, truth32, stream, name, cap)
+    return any_white_drift(p) || any_vibration(p) ? launch3_f32<RF, ALGOS, true>(p, truth32, stream, name, cap)
                                                           : launch3_f32<RF, ALGOS, false>(p, truth32, stream, name, cap);
 }
 
@@ -828,27 +815,6 @@ hipError_t launch_mc_f32(const ginsim_mc_params& p_in, float* truth32, hipStream
     p.accel.reserved = exp;
 #endif
     return p.ref_frame == 1 ? launch1_f32<1>(p, truth32, stream, name, cap) : launch1_f32<0>(p, truth32, stream, name, cap);
-}
-
-// gather selected runs of a float series: [C][n][runs] (float) -> out [nsel][n][C] (double), optional per-component origin
-__global__ void gather_runs_f32_kernel(const float* __restrict__ series, int C, int64_t n, int64_t runs,
-                                       const int64_t* __restrict__ ids, int nsel, double* __restrict__ out) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t total = (int64_t)nsel * n * C;
-    if (idx >= total) return;
-    const int c = (int)(idx % C);
-    const int64_t j = (idx / C) % n;
-    const int64_t k = idx / (C * n);
-    out[idx] = (double)series[((int64_t)c * n + j) * runs + ids[k]];
-}
-
-hipError_t launch_gather_runs_f32(const float* series, int C, int64_t n, int64_t runs, const int64_t* ids, int nsel,
-                                  double* out, hipStream_t s) {
-    const int tb = 256;
-    const int64_t total = (int64_t)nsel * n * C;
-    hipLaunchKernelGGL(gather_runs_f32_kernel, dim3((unsigned)((total + tb - 1) / tb)), dim3(tb), 0, s, series, C, n, runs,
-                       ids, nsel, out);
-    return hipGetLastError();
 }
 
 }  // namespace ginsim

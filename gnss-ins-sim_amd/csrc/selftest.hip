@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include "launch.hpp"
 
 namespace ginsim {
 

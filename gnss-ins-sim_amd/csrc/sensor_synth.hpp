@@ -1,4 +1,4 @@
-// Sensor synthesis shared by the lane-per-run kernels of the fp64 path (mc_kernel.hip, inclinometer.hip): one run's
+// Sensor synthesis shared by the kernels of the fp64 path (mc_kernel.hip, series.hip, inclinometer.hip): one run's
 // accelerometer and gyroscope samples from the truth, the Gauss-Markov drift, the white noise and the vibration term, and
 // the helpers they read their inputs through.  Kernels that include it take a ginsim_mc_params BY VALUE as their FIRST
 // argument (kernarg_params).  Moved here verbatim from mc_kernel.hip: the ISA of its kernels is unchanged.
@@ -172,5 +172,8 @@ __device__ __forceinline__ Vec3 add_vibration(const Vec3& o, vib_ptr v, const Rn
     }
     return r;
 }
+
+// Series are written once and not read back by the kernel: non-temporal stores keep them from displacing the L2.
+__device__ __forceinline__ void st(double* p, double v) { __builtin_nontemporal_store(v, p); }
 
 }  // namespace ginsim

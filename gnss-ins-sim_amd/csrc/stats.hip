@@ -9,6 +9,7 @@
 #include "fastmath.hpp"
 #include "ins_math.hpp"
 #include "moments.hpp"
+#include "launch.hpp"
 
 namespace ginsim {
 

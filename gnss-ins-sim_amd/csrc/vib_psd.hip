@@ -22,10 +22,9 @@
 
 #include "ginsim.h"
 #include "philox.hpp"
+#include "launch.hpp"
 
 namespace ginsim {
-
-void set_error(const char* fmt, ...);
 
 namespace {
 

@@ -327,7 +327,7 @@ def test_hot_kernels_keep_two_wavefronts_per_simd():
     to 256 VGPRs + 4 AGPRs once ran 30 % slower at 262 144 runs without any functional symptom.)"""
     build = os.path.join(PKG, 'build')
     kernels = {}
-    for fn in ('mc_kernel', 'mc_kernel_f32', 'allan', 'stats'):
+    for fn in ('mc_kernel', 'mc_kernel_f32', 'series', 'allan', 'stats'):
         path = os.path.join(build, fn + '.resources.txt')
         assert os.path.exists(path), 'run gnss-ins-sim_amd/build.py (it writes %s)' % path
         cur = None
@@ -337,7 +337,7 @@ def test_hot_kernels_keep_two_wavefronts_per_simd():
                 cur = kernels.setdefault(v.strip(), {})
             elif cur is not None and v.strip():
                 cur[k.split('[')[0].strip()] = v.strip()
-    checked = 0
+    checked = series_seen = 0
     split_seen = {}
     for name, r in kernels.items():         # Itanium-mangled: ...9mc_kernelILi<rf>ELi<algos>ELb<given>ELb<general>EEEv...
         occ, agpr, scratch = int(r['Occupancy']), int(r['AGPRs']), int(r['ScratchSize'])
@@ -346,6 +346,7 @@ def test_hot_kernels_keep_two_wavefronts_per_simd():
         if not hot:
             continue
         checked += 1
+        series_seen += '13series_kernelI' in name
         two_algos = 'ILi0ELi3E' in name or 'ILi1ELi3E' in name
         assert occ >= 2, '%s: %d wavefront(s) per SIMD' % (name, occ)
         if '15mc_kernel_splitI' in name or '19mc_kernel_f32_splitI' in name:
@@ -362,6 +363,7 @@ def test_hot_kernels_keep_two_wavefronts_per_simd():
         vib = re.search(r'9mc_kernelILi\dELi\dELb0ELb1ELi\dELb1EEE', name) is not None
         assert scratch <= (192 if vib else 128 if two_algos else 32), '%s: %d bytes of scratch per lane' % (name, scratch)
     assert checked >= 40, checked
+    assert series_seen == 4, series_seen         # series_kernel<0..3> (csrc/series.hip): none may fall out of the check
     assert split_seen.get(2, 0) >= 8 and split_seen.get(3, 0) >= 4, split_seen
 
 
@@ -711,7 +713,7 @@ def test_reported_kernel_names_are_the_compiled_kernels():
     if not shutil.which('c++filt'):
         pytest.skip('no c++filt to demangle the build\'s kernel list')
     mangled = []
-    for fn in ('mc_kernel', 'mc_kernel_f32'):
+    for fn in ('mc_kernel', 'mc_kernel_f32', 'series'):
         for line in open(os.path.join(PKG, 'build', fn + '.resources.txt')):
             if line.startswith('Function Name:'):
                 mangled.append(line.split(':', 1)[1].strip())

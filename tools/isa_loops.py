@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction mix of the loops of one kernel in a hipcc -S listing.
 
-    hipcc ... --cuda-device-only -S -o mc.s csrc/mc_kernel.hip
+    hipcc ... --cuda-device-only -S -o mc.s csrc/mc_kernel.hip      (or series.hip, ...: the file that defines the kernel)
     python tools/isa_loops.py mc.s <mangled kernel name substring> [min_len]
 
 Finds backward branches (a loop = the lines between a label and a later branch to it) and prints, per loop, the
