@@ -44,6 +44,10 @@ SOURCES = [
     ('inclinometer.hip', ['--offload-arch=' + ARCH, '-ffp-contract=on']),
     # the magnetometer synthesis must give aux_mag_kernel's bits (mag_synth.hpp, same -ffp-contract=on as aux_sensors.hip)
     ('magcal.hip', ['--offload-arch=' + ARCH, '-ffp-contract=on']),
+    # sensors as mc_kernel.hip's, fixes as aux_sensors.hip's (gps_synth.hpp): the same -ffp-contract=on; machine-LICM off as for
+    # mc_kernel.hip: 0 bytes of scratch in every instantiation (the file's header has the whole account; tests/test_ins_loose_oracle.py
+    # reads the report)
+    ('ins_loose.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),

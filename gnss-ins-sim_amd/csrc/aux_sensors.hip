@@ -4,6 +4,7 @@
 #include "ins_math.hpp"
 #include "philox.hpp"
 #include "mag_synth.hpp"
+#include "gps_synth.hpp"
 #include "launch.hpp"
 
 namespace ginsim {
@@ -22,12 +23,11 @@ __global__ void __launch_bounds__(256) aux_gps_kernel(const ginsim_aux_params a)
     const int64_t r = idx % a.runs, k = idx / a.runs;
     const uint64_t grun = a.run_offset + (uint64_t)r;
     const RngKey key{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)grun, (uint32_t)(grun >> 32)};
-    double z0[3], z1[3];
-    normal_pairs<S_GPS_P_XY, 3>(key, (uint32_t)k, z0, z1, tab);
-    const double z[6] = {z0[0], z1[0], z0[1], z1[1], z0[2], z1[2]};     // pos x,y,z  vel x,y,z
+    double fix[6];
+    gps_fix(a.ref_gps + 6 * k, a.gps_sigma, key, (uint32_t)k, tab, fix);     // ref + sigma * N  (gps_synth.hpp)
     const int64_t plane = a.m * a.runs;
 #pragma unroll
-    for (int c = 0; c < 6; ++c) a.out_gps[c * plane + idx] = a.ref_gps[6 * k + c] + a.gps_sigma[c] * z[c];
+    for (int c = 0; c < 6; ++c) a.out_gps[c * plane + idx] = fix[c];
 }
 
 __global__ void __launch_bounds__(256) aux_mag_kernel(const ginsim_aux_params a) {

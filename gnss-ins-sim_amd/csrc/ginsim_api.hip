@@ -429,6 +429,99 @@ int ginsim_incl_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_incl
     return GINSIM_OK;
 }
 
+static int check_loose_params(const ginsim_mc_params* m, const ginsim_loose_params* p) {
+    REQUIRE(m && p, "loose_run: NULL argument");
+    REQUIRE(m->n >= 1 && m->runs >= 1, "loose_run: n=%lld runs=%lld must be >= 1", (long long)m->n, (long long)m->runs);
+    REQUIRE(m->n <= 0xFFFFFFFFll, "loose_run: n exceeds the 32-bit sample counter of the RNG");
+    REQUIRE(m->runs <= (int64_t)0x7FFFFFFF * 64, "loose_run: too many runs for one launch");
+    REQUIRE(std::isfinite(m->fs) && m->fs > 0.0, "loose_run: fs must be positive");
+    REQUIRE(m->ref_frame == 0 || m->ref_frame == 1, "loose_run: ref_frame must be 0 or 1");
+    REQUIRE(m->precision == 0, "loose_run: the filter kernel is fp64 only");
+    REQUIRE(m->n_ini >= 1 && m->ini, "loose_run: initial-state table missing");
+    REQUIRE(m->block_threads == 0 || m->block_threads == 64, "loose_run: block_threads must be 0 or 64 (one wavefront per workgroup)");
+    REQUIRE(p->n_list >= 0 && p->n_list <= m->runs, "loose_run: n_list must lie in 0 .. runs");
+    REQUIRE(p->m >= 0 && p->m <= m->n, "loose_run: m=%lld fixes for n=%lld samples", (long long)p->m, (long long)m->n);
+    REQUIRE(p->m == 0 || p->gps_stamp, "loose_run: gps_stamp missing");
+    for (int64_t k = 0; k < p->m; ++k) {
+        const long long s = (long long)p->gps_stamp[k];
+        REQUIRE(s >= 0 && s < (long long)m->n, "loose_run: the stamp of fix %lld (%lld) is outside [0, %lld)", (long long)k, s, (long long)m->n);
+        REQUIRE(k == 0 || s > (long long)p->gps_stamp[k - 1], "loose_run: the stamps are not strictly increasing at fix %lld", (long long)k);
+    }
+    if (m->given_sensors) {
+        REQUIRE(m->in_accel && m->in_gyro, "loose_run: given_sensors needs in_accel and in_gyro");
+        REQUIRE(p->m == 0 || p->in_gps, "loose_run: given_sensors needs in_gps");
+    } else {
+        REQUIRE(m->ref_gyro && m->ref_accel, "loose_run: ref_accel/ref_gyro missing");
+        REQUIRE(p->m == 0 || p->ref_gps, "loose_run: ref_gps missing");
+        int rc = check_sensor(m->accel, "accel");
+        if (rc) return rc;
+        rc = check_sensor(m->gyro, "gyro");
+        if (rc) return rc;
+        for (int k = 0; k < 6; ++k) REQUIRE(std::isfinite(p->gps_sigma[k]), "loose_run: gps_sigma must be finite");
+    }
+    for (const ginsim_vibration* v : {&m->vib_accel, &m->vib_gyro}) {
+        if (v->type == GINSIM_VIB_NONE) continue;
+        REQUIRE(v->type == GINSIM_VIB_RANDOM || v->type == GINSIM_VIB_SINUSOIDAL,
+                "loose_run: the filter kernel takes the 'random' and 'sinusoidal' vibration only");
+        REQUIRE(!m->given_sensors, "loose_run: a vibration term cannot be added to given sensors");
+        REQUIRE(std::isfinite(v->amp[0]) && std::isfinite(v->amp[1]) && std::isfinite(v->amp[2]) && std::isfinite(v->omega_dt),
+                "loose_run: vibration amplitudes / frequency must be finite");
+    }
+    for (int k = 0; k < 6; ++k) REQUIRE(std::isfinite(p->r_diag[k]) && p->r_diag[k] > 0.0, "loose_run: r_diag must be positive");
+    for (int k = 0; k < 5; ++k) REQUIRE(std::isfinite(p->p0[k]) && p->p0[k] > 0.0, "loose_run: p0 must be positive");
+    for (int k = 0; k < 3; ++k) {
+        REQUIRE(std::isfinite(p->q_v[k]) && p->q_v[k] >= 0.0 && std::isfinite(p->q_psi[k]) && p->q_psi[k] >= 0.0 &&
+                std::isfinite(p->q_bg[k]) && p->q_bg[k] >= 0.0 && std::isfinite(p->q_ba[k]) && p->q_ba[k] >= 0.0,
+                "loose_run: the process noise must be finite and not negative");
+        REQUIRE(std::isfinite(p->decay_g[k]) && std::isfinite(p->decay_a[k]), "loose_run: decay_g / decay_a must be finite");
+    }
+    REQUIRE(!p->out_proc || m->ref_nav, "loose_run: out_proc needs ref_nav");
+    REQUIRE(!p->out_proc || (m->proc_first >= 0 && m->proc_first < m->n), "loose_run: proc_first out of range");
+    REQUIRE(!m->proc_pos_ned || m->ref_frame == 0, "loose_run: NED position errors exist in ref_frame 0 only");
+    REQUIRE(!p->out_end_ned || m->ref_frame == 0, "loose_run: out_end_ned needs ref_frame 0");
+    return GINSIM_OK;
+}
+
+int ginsim_loose_variant(const ginsim_mc_params* mc, const ginsim_loose_params* p, int32_t* variant) {
+    REQUIRE(variant, "loose_variant: NULL argument");
+    const int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    *variant = loose_variant(*mc);
+    return GINSIM_OK;
+}
+
+int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_kernel_name: bad arguments");
+    const int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    buf[0] = 0;
+    (void)launch_loose(*mc, *p, nullptr, nullptr, nullptr, buf, cap);
+    return GINSIM_OK;
+}
+
+int ginsim_loose_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p) {
+    REQUIRE(c, "loose_run: NULL argument");
+    const int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the stamps and the visibility flags of the fixes, copied next to each other into the context's scratch
+    int64_t* d_stamp = nullptr;
+    int32_t* d_vis = nullptr;
+    if (p->m > 0) {
+        void* ws = nullptr;
+        const size_t sb = sizeof(int64_t) * (size_t)p->m;
+        HIP_TRY(scratch(c, 3, sb + sizeof(int32_t) * (size_t)p->m, &ws));
+        d_stamp = reinterpret_cast<int64_t*>(ws);
+        HIP_TRY(hipMemcpyAsync(d_stamp, p->gps_stamp, sb, hipMemcpyHostToDevice, c->stream));
+        if (p->gps_visible) {
+            d_vis = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + sb);
+            HIP_TRY(hipMemcpyAsync(d_vis, p->gps_visible, sizeof(int32_t) * (size_t)p->m, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    HIP_TRY(launch_loose(*mc, *p, d_stamp, d_vis, c->stream, nullptr, 0));
+    return GINSIM_OK;
+}
+
 }  // extern "C"
 
 static int check_mc_params(const ginsim_mc_params* p) {

@@ -32,6 +32,11 @@ hipError_t launch_series(const ginsim_mc_params& p, double* carry, hipStream_t s
 hipError_t launch_incl(const ginsim_mc_params& p, const ginsim_incl_params& b, hipStream_t stream, char* name, size_t cap);
 int incl_variant(const ginsim_mc_params& p);
 
+// ins_loose.hip
+hipError_t launch_loose(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
+                        hipStream_t stream, char* name, size_t cap);      // stamp / visible: device copies of b.gps_stamp / b.gps_visible
+int loose_variant(const ginsim_mc_params& p);
+
 // aux_sensors.hip
 hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s);
 

@@ -1,0 +1,93 @@
+"""The reference's loosely coupled GPS/INS plugin on the GPU: ``InsLoose`` (demo_algorithms/ins_loose.py) with the same
+``input`` / ``output`` / ``batch`` and ``run`` / ``get_results`` / ``reset``.
+
+The reference declares the interface and leaves ``prediction`` and ``correction`` as ``pass``; this class fills them in with a
+15-state closed-loop error-state Kalman filter (csrc/ins_loose.hip, ginsim.InsLooseJob; the equations are in DESIGN 4.11 and,
+as NumPy, in tests/ins_loose_ref.py).  ``Sim`` runs an instance (``mc_algo`` 'loose') over all Monte-Carlo runs in one launch,
+every lane making its own IMU samples and GPS fixes; ``run(set_of_input)`` on one logged series runs the same kernel on that series.
+The checkout's own stub (demo_algorithms.ins_loose) stays hosted.  fp64 only.
+
+    InsLoose(ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None)
+
+ini_pos_vel_att: the initial states FreeIntegration takes ((9|10,) or (9|10, k)); None under a Sim: the motion definition's.
+imu: the IMU model the filter is tuned to (its accel_err, gyro_err, gps_err); None under a Sim: the Sim's own.  ref_frame is the
+Sim's under a Sim and needed by ``run`` on a logged series.
+q_scale multiplies the process noise; p0 = (sigma_r [m], sigma_v [m/s], sigma_psi [rad], sigma_bg [rad/s], sigma_ba [m/s^2]), the
+initial 1 sigma; default (1e-3, 1e-3, 1e-5, 1e-7, 1e-5), the two bias terms raised to the sensor's largest constant bias.
+"""
+import numpy as np
+
+VERSION = '1.0'
+
+
+class InsLoose(object):
+    '''
+    Loosely coupled INS algorithm (ins_loose.py:20-36), run on the GPU.
+    '''
+    mc_algo = 'loose'
+
+    def __init__(self, ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None):
+        self.input = ['fs', 'gyro', 'accel', 'time', 'gps_time', 'gps']
+        self.output = ['pos', 'vel', 'att_euler', 'wb', 'ab']
+        self.batch = True
+        self.results = None
+        self.ini = None if ini_pos_vel_att is None else np.array(ini_pos_vel_att, dtype=np.float64)
+        self.earth_rot, self.ref_frame, self.imu = bool(earth_rot), ref_frame, imu
+        self.q_scale = float(q_scale)
+        if p0 is not None:
+            p0 = tuple(float(x) for x in np.asarray(p0, dtype=np.float64).reshape(-1))
+            if len(p0) != 5 or not all(x > 0.0 and np.isfinite(x) for x in p0):
+                raise ValueError('p0 = (sigma_r, sigma_v, sigma_psi, sigma_bg, sigma_ba), five positive numbers')
+        if not (self.q_scale > 0.0 and np.isfinite(self.q_scale)):
+            raise ValueError('q_scale must be positive')
+        self.p0 = p0
+        self.run_times = 0
+
+    def finish(self, pos, vel, att, wb, ab):
+        """State the plugin holds after a run: the last run's series, each (n, 3), in the order of `output`."""
+        self.results = [pos, vel, att, wb, ab]
+
+    def run(self, set_of_input):
+        '''
+        set_of_input: [fs, gyro (n, 3), accel (n, 3), time (n,), gps_time (m,), gps (m, 6 | 7)], as the reference's run; a seventh
+        gps column is the visibility.  Needs InsLoose(ini_pos_vel_att=..., ref_frame=..., imu=...).
+        '''
+        import ginsim
+        from ginsim.ins_loose import InsLooseJob
+        if self.ini is None or self.ref_frame not in (0, 1) or self.imu is None:
+            raise ValueError('InsLoose.run on a logged series needs InsLoose(ini_pos_vel_att=..., ref_frame=0 | 1, imu=...): '
+                             'there is no Sim to take them from')
+        fs = float(np.asarray(set_of_input[0]).reshape(-1)[0])
+        gyro = np.ascontiguousarray(np.asarray(set_of_input[1], dtype=np.float64))
+        accel = np.ascontiguousarray(np.asarray(set_of_input[2], dtype=np.float64))
+        time = np.asarray(set_of_input[3], dtype=np.float64).reshape(-1)
+        gps_time = np.asarray(set_of_input[4], dtype=np.float64).reshape(-1)
+        gps = np.asarray(set_of_input[5], dtype=np.float64).reshape(gps_time.shape[0], -1)
+        n = gyro.shape[0]
+        if gyro.shape != (n, 3) or accel.shape != (n, 3) or gps.shape[1] < 6:
+            raise ValueError('gyro and accel must be (n, 3) arrays, gps (m, 6)')
+        t0 = time[0] if time.size else 0.0
+        truth = {'ref_accel': accel, 'ref_gyro': gyro, 'ref_att': np.zeros((n, 3)), 'ref_pos': np.zeros((n, 3)), 'ref_vel': np.zeros((n, 3)),
+                 'ref_gps': np.ascontiguousarray(gps[:, 0:6]), 'gps_time': gps_time - t0,
+                 'gps_visibility': gps[:, 6] if gps.shape[1] > 6 else np.ones(gps.shape[0])}
+        ctx = ginsim.default_context()
+        bufs = {'accel': ctx.upload(np.ascontiguousarray(accel.T)), 'gyro': ctx.upload(np.ascontiguousarray(gyro.T)),       # [3][n][1]
+                'gps': ctx.upload(np.ascontiguousarray(gps[:, 0:6].T))}
+        job = None
+        try:
+            job = InsLooseJob(ctx, fs, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, self.imu.gps_err, self.ini, 1,
+                              ini_first=self.run_times, earth_rot=self.earth_rot, given=bufs, q_scale=self.q_scale, p0=self.p0,
+                              keep_traj=True).run()
+            self.finish(*[job.series(k, [0])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab')])
+        finally:
+            if job is not None:
+                job.release()
+            for b in bufs.values():
+                b.free()
+        self.run_times += 1
+
+    def get_results(self):
+        return self.results
+
+    def reset(self):
+        pass

@@ -90,6 +90,16 @@ class InclParams(C.Structure):
                 ('out_wb', C.c_void_p), ('out_ab', C.c_void_p), ('out_end', C.c_void_p * 2), ('out_proc', C.c_void_p * 2)]
 
 
+class LooseParams(C.Structure):
+    """ginsim_loose_params: the loosely coupled GPS/INS filter over a batch of runs (csrc/ins_loose.hip)."""
+    _fields_ = [('m', C.c_int64), ('gps_stamp', C.c_void_p), ('gps_visible', C.c_void_p), ('ref_gps', C.c_void_p),
+                ('gps_sigma', C.c_double * 6), ('in_gps', C.c_void_p), ('r_diag', C.c_double * 6), ('p0', C.c_double * 5),
+                ('q_v', C.c_double * 3), ('q_psi', C.c_double * 3), ('q_bg', C.c_double * 3), ('q_ba', C.c_double * 3),
+                ('decay_g', C.c_double * 3), ('decay_a', C.c_double * 3), ('run_list', C.c_void_p), ('n_list', C.c_int64),
+                ('out_traj', C.c_void_p), ('out_wb', C.c_void_p), ('out_ab', C.c_void_p), ('out_end', C.c_void_p),
+                ('out_proc', C.c_void_p), ('out_bias_end', C.c_void_p), ('out_pdiag_end', C.c_void_p), ('out_end_ned', C.c_void_p)]
+
+
 class PathgenParams(C.Structure):
     _fields_ = [('ini_pva', C.c_double * 9), ('mobility', C.c_double * 3), ('fs', C.c_double),
                 ('fs_gps', C.c_double), ('ref_frame', C.c_int32), ('enable_gps', C.c_int32),
@@ -157,6 +167,9 @@ _SIGS = {
     'ginsim_incl_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(InclParams)]),
     'ginsim_incl_variant': (C.c_int, [C.POINTER(McParams), C.POINTER(InclParams), C.POINTER(C.c_int32)]),
     'ginsim_incl_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(InclParams), C.c_char_p, C.c_size_t]),
+    'ginsim_loose_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams)]),
+    'ginsim_loose_variant': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(C.c_int32)]),
+    'ginsim_loose_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.c_char_p, C.c_size_t]),
     'ginsim_end_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     'ginsim_end_stats_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     'ginsim_end_stats_finish': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Stats)]),

@@ -1,0 +1,303 @@
+"""InsLooseJob: the loosely coupled GPS/INS Kalman filter (the interface demo_algorithms/ins_loose.py::InsLoose declares, whose
+prediction and correction are `pass` in the reference) over a batch of Monte-Carlo runs on one device (csrc/ins_loose.hip,
+ginsim_loose_run).  One launch: every lane makes its own IMU samples and GPS fixes again from the run's Philox streams (the bits
+MonteCarloJob and AuxSensorJob would store), mechanises them with the free-integration step on bias-corrected samples and runs a
+15-state closed-loop error-state filter next to it.  tests/ins_loose_ref.py restates the arithmetic in NumPy.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import lib, check, dptr
+from .engine import DeviceView, StatsResult, CurveResult, ini_table, sensor_model, vibration
+
+P0_FLOOR = (1e-3, 1e-3, 1e-5, 1e-7, 1e-5)      # m, m/s, rad, rad/s, m/s^2
+
+
+def filter_model(fs, accel_err, gyro_err, gps_err, q_scale=1.0, p0=None):
+    """The numbers of ginsim_loose_params that describe the filter, from the error dicts the run is generated with.
+
+      r_diag    gps_err['stdp']^2, gps_err['stdv']^2 (stdp in metres in both frames)
+      q_v/q_psi (vrw^2 | arw^2) dt per body axis; an axis whose drift is white (b_corr = inf: pathgen.bias_drift draws an
+                independent drift every sample) adds that sample noise, b_drift^2 dt^2, and its bias state is a constant
+      q_bg/q_ba the driving noise of the Gauss-Markov drift as pathgen.bias_drift generates it, 2 sigma^2 / tau dt
+      decay_*   1 - dt / tau (1 for a random walk)
+      p0        initial 1 sigma of (dr, dv, psi, dbg, dba).  Default: the runs start ON the truth with zero drift, so the floor
+                P0_FLOOR = (1e-3 m, 1e-3 m/s, 1e-5 rad, 1e-7 rad/s, 1e-5 m/s^2), and for the two bias states the largest constant
+                bias |b| of the sensor where that is larger
+    q_scale multiplies every Qd."""
+    dt = 1.0 / float(fs)
+    m = {'r_diag': np.concatenate([(np.asarray(gps_err['stdp'], dtype=np.float64) * np.ones(3)) ** 2,
+                                   (np.asarray(gps_err['stdv'], dtype=np.float64) * np.ones(3)) ** 2])}
+    for err, rw, qn, qb, dec in ((accel_err, 'vrw', 'q_v', 'q_ba', 'decay_a'), (gyro_err, 'arw', 'q_psi', 'q_bg', 'decay_g')):
+        w = np.asarray(err[rw], dtype=np.float64) * np.ones(3)
+        sig = np.asarray(err['b_drift'], dtype=np.float64) * np.ones(3)
+        tau = np.asarray(err['b_corr'], dtype=np.float64) * np.ones(3)
+        inf = np.isinf(tau)
+        tau_f = np.where(inf, 1.0, tau)
+        m[qn] = (w * w * dt + np.where(inf, sig * sig * dt * dt, 0.0)) * float(q_scale)
+        m[qb] = np.where(inf, 0.0, 2.0 * sig * sig / tau_f * dt) * float(q_scale)
+        m[dec] = np.where(inf, 1.0, 1.0 - dt / tau_f)
+    if p0 is None:
+        p0 = list(P0_FLOOR)
+        p0[3] = max(p0[3], float(np.max(np.abs(np.asarray(gyro_err['b'], dtype=np.float64)))))
+        p0[4] = max(p0[4], float(np.max(np.abs(np.asarray(accel_err['b'], dtype=np.float64)))))
+    m['p0'] = np.asarray(p0, dtype=np.float64).reshape(5)
+    return m
+
+
+def gps_sigma(gps_err, ref_gps, ref_frame):
+    """ginsim_aux_params.gps_sigma as AuxSensorJob makes it (pathgen.py:616-619: metres -> rad at the FIRST fix in ref_frame 0)."""
+    from gnss_ins_sim.geoparams import geoparams
+    sig = np.concatenate([np.asarray(gps_err['stdp'], dtype=np.float64) * np.ones(3),
+                          np.asarray(gps_err['stdv'], dtype=np.float64) * np.ones(3)])
+    if ref_frame == 0:
+        rm, rn, _, _, cl, _ = geoparams.geo_param(ref_gps[0, 0:3])
+        sig[0] = sig[0] / rm
+        sig[1] = sig[1] / rn / cl
+    return sig
+
+
+class InsLooseJob(object):
+    """One batch of runs of the loosely coupled filter on one device.
+
+    truth: dict with 'ref_accel', 'ref_gyro', 'ref_att', 'ref_pos', 'ref_vel' (n, 3) and 'ref_gps' (m, 6), 'gps_time' (m,)
+    [seconds: fix k is applied at IMU sample round(gps_time[k] fs)], 'gps_visibility' (m,) as workloads.truth_from_profile(gps=True)
+    makes them.  ini: the initial states FreeIntegration takes.  gps_err: {'stdp', 'stdv'}.
+    given: None (samples and fixes are regenerated per lane: same seed and run ids as MonteCarloJob / AuxSensorJob, same bits) or a
+    dict of device buffers {'accel', 'gyro'} [3][n][runs] and 'gps' [6][m][runs].
+    model: filter_model(...) or None (made from the error dicts, q_scale and p0).
+    keep_traj: materialise att / pos / vel ([9][n][runs]) and wb, ab ([3][n][runs] each).
+    proc_first: None, or the first sample of the online process-error window.  end_pos_ned / proc_ned (ref_frame 0): position
+    errors of the end-point record / of the process statistics in local NED metres; end_ned: a second end-point record in NED metres.
+    placed: as MonteCarloJob (kept planes of Context.PLACED_MIN_JOB bytes or more come from the placed arena).
+    """
+
+    precision = 'f64'
+    algos = ('loose',)
+
+    def __init__(self, ctx, fs, ref_frame, truth, accel_err, gyro_err, gps_err, ini, runs, seed=0, run_offset=0, ini_first=0,
+                 earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
+                 end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None):
+        self.ctx = ctx
+        self.n, self.runs = int(truth['ref_accel'].shape[0]), int(runs)
+        if self.runs < 1:
+            raise ValueError('runs must be >= 1')
+        self.keep_traj = bool(keep_traj)
+        self.proc_first, self.proc_ned, self.end_ned = proc_first, bool(proc_ned), bool(end_ned)
+        if end_ned and int(ref_frame) != 0:
+            raise ValueError('end_ned: ref_frame 0 only')
+        self._bufs = {}
+        self._ref_frame = int(ref_frame)
+        m = self.mc = _lib.McParams()
+        m.n, m.runs, m.run_offset, m.seed = self.n, self.runs, int(run_offset), int(seed) & (2 ** 64 - 1)
+        m.fs, m.ref_frame, m.earth_rot, m.end_pos_ned = float(fs), int(ref_frame), int(bool(earth_rot)), int(bool(end_pos_ned))
+        table, has_g = ini_table(ini)
+        m.n_ini, m.ini_first, m.ini_has_g = table.shape[0], int(ini_first), int(has_g)
+        ref_gps = np.ascontiguousarray(truth['ref_gps'], dtype=np.float64).reshape(-1, 6) if 'ref_gps' in truth else np.zeros((0, 6))
+        self.m = int(ref_gps.shape[0])
+        if gps_stamps is None:
+            gps_stamps = np.rint(np.asarray(truth['gps_time'], dtype=np.float64) * float(fs)) if self.m else np.zeros(0)
+        self._stamps = np.ascontiguousarray(gps_stamps, dtype=np.int64).reshape(-1)
+        vis = truth['gps_visibility'] if 'gps_visibility' in truth else np.ones(self.m)
+        self._visible = np.ascontiguousarray(np.asarray(vis) != 0, dtype=np.int32).reshape(-1)
+        if self._stamps.size != self.m or self._visible.size != self.m:
+            raise ValueError('gps_time / gps_visibility do not match ref_gps')
+        self.model = model if model is not None else filter_model(fs, accel_err, gyro_err, gps_err, q_scale, p0)
+        p = self.params = _lib.LooseParams()
+        p.m = self.m
+        p.gps_stamp, p.gps_visible = self._stamps.ctypes.data, self._visible.ctypes.data
+        for k in ('r_diag', 'p0', 'q_v', 'q_psi', 'q_bg', 'q_ba', 'decay_g', 'decay_a'):
+            getattr(p, k)[:] = [float(x) for x in np.asarray(self.model[k], dtype=np.float64).reshape(-1)]
+        self._ref_nav = np.ascontiguousarray(np.concatenate([truth['ref_att'], truth['ref_pos'], truth['ref_vel']], axis=1))
+        m.ref_end[:] = [float(x) for x in self._ref_nav[-1]]
+        parts = [table.reshape(-1)]
+        if given is None:
+            m.accel = sensor_model(accel_err, 'vrw', fs)
+            m.gyro = sensor_model(gyro_err, 'arw', fs)
+            for v in (vib_accel, vib_gyro):
+                if v is not None and str(v['type']).lower() == 'psd':
+                    raise NotImplementedError("the 'psd' vibration is not a term of the filter kernel (random and sinusoidal are)")
+            m.vib_accel = vibration(vib_accel, float(fs), False)
+            m.vib_gyro = vibration(vib_gyro, float(fs), True)
+            parts += [np.asarray(truth['ref_accel'], dtype=np.float64).reshape(-1), np.asarray(truth['ref_gyro'], dtype=np.float64).reshape(-1),
+                      ref_gps.reshape(-1)]
+            if self.m:
+                p.gps_sigma[:] = [float(x) for x in gps_sigma(gps_err, ref_gps, int(ref_frame))]
+        else:
+            if vib_accel is not None or vib_gyro is not None:
+                raise ValueError('given sensors: a vibration model cannot be added to sensor series that already exist')
+            for k, c, length in (('accel', 3, self.n), ('gyro', 3, self.n), ('gps', 6, self.m)):
+                if length and (k not in given or given[k].nbytes < c * length * self.runs * 8 or getattr(given[k], 'layout', 'runs') != 'runs'):
+                    raise ValueError('given sensors: %r missing, too small or not [component][sample][run]' % (k,))
+            m.given_sensors, m.in_accel, m.in_gyro = 1, given['accel'].ptr, given['gyro'].ptr
+            p.in_gps = given['gps'].ptr if self.m else None
+            self._given = given
+        offs = np.cumsum([0] + [q.size for q in parts]) * 8
+        self._bufs['inputs'] = ctx.upload(np.concatenate(parts))
+        m.ini = self._bufs['inputs'].at(offs[0])
+        if given is None:
+            m.ref_accel, m.ref_gyro = self._bufs['inputs'].at(offs[1]), self._bufs['inputs'].at(offs[2])
+            p.ref_gps = self._bufs['inputs'].at(offs[3]) if self.m else None
+        R = self.runs
+        # end [9][R], bias_end [6][R], pdiag_end [15][R], run list [R], the NED end record [9][R]
+        self._bufs['small'] = ctx.malloc((9 + 6 + 15 + 1 + 9) * R * 8)
+        small = self._bufs['small']
+        if end_ned:
+            p.out_end_ned = small.at(31 * R * 8)
+        p.out_end, p.out_bias_end, p.out_pdiag_end, self._list = small.ptr, small.at(9 * R * 8), small.at(15 * R * 8), small.at(30 * R * 8)
+        if proc_first is not None:
+            if not 0 <= int(proc_first) < self.n:
+                raise ValueError('proc_first must be a sample index of the run')
+            if proc_ned and int(ref_frame) != 0:
+                raise ValueError('NED position errors exist in ref_frame 0 only')
+            self._bufs['ref_nav'] = ctx.upload(self._ref_nav)
+            self._bufs['proc'] = ctx.malloc(27 * R * 8)
+            m.ref_nav, m.proc_first, m.proc_pos_ned = self._bufs['ref_nav'].ptr, int(proc_first), int(bool(proc_ned))
+            p.out_proc = self._bufs['proc'].ptr
+        if self.keep_traj:
+            plane = self.n * R * 8
+            total = 15 * plane
+            use_placed = (total >= ctx.PLACED_MIN_JOB) if placed is None else bool(placed)
+            use_placed = bool(use_placed and ctx.placed_reserve(total))
+            self._bufs['series'] = ctx.malloc(total, placed=use_placed)
+            self._bufs['traj_loose'] = DeviceView(self._bufs['series'], 0, 9 * plane)
+            self._bufs['wb'] = DeviceView(self._bufs['series'], 9 * plane, 3 * plane)
+            self._bufs['ab'] = DeviceView(self._bufs['series'], 12 * plane, 3 * plane)
+            p.out_traj, p.out_wb, p.out_ab = self._bufs['traj_loose'].ptr, self._bufs['wb'].ptr, self._bufs['ab'].ptr
+        p.n_list = R
+
+    # ------------------------------------------------------------------ launches
+    def kernel_name(self):
+        buf = C.create_string_buffer(256)
+        check(lib.ginsim_loose_kernel_name(C.byref(self.mc), C.byref(self.params), buf, 256))
+        return buf.value.decode()
+
+    def variant(self):
+        v = C.c_int32(0)
+        check(lib.ginsim_loose_variant(C.byref(self.mc), C.byref(self.params), C.byref(v)))
+        return v.value
+
+    def launch(self, ids=None):
+        """Enqueue the kernel (asynchronous).  ids: launch these runs only (lane i filters run ids[i]); the others keep what they hold."""
+        p = self.params
+        if ids is None:
+            p.run_list, p.n_list = None, self.runs
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            check(lib.ginsim_memcpy_h2d(self.ctx.handle, self._list, ids.ctypes.data, ids.nbytes))
+            p.run_list, p.n_list = self._list, ids.size
+        check(self.ctx.retry_oom(lambda: lib.ginsim_loose_run(self.ctx.handle, C.byref(self.mc), C.byref(p))))
+
+    def run(self, ids=None):
+        self.launch(ids)
+        self.ctx.sync()
+        return self
+
+    def placement(self):
+        b = self._bufs.get('series')
+        return {'placed': ['series'] if b is not None and b.placed else [], 'unplaced': ['series'] if b is not None and not b.placed else []}
+
+    # ------------------------------------------------------------------ results
+    def stats(self, algo='loose', ned=False):
+        """End-point statistics (att3 wrapped, pos3, vel3) of the last launch.  ned: the job must have end_pos_ned=True."""
+        s = _lib.Stats()
+        check(lib.ginsim_end_stats(self.ctx.handle, self._end_ptr(ned), self.runs, C.byref(s)))
+        return StatsResult(s)
+
+    def _end_ptr(self, ned):
+        if ned and not (self.end_ned or self.mc.end_pos_ned):
+            raise ValueError('the NED end-point record was not requested (end_ned=True)')
+        return self.params.out_end_ned if (ned and self.end_ned) else self.params.out_end
+
+    def end_errors(self, algo='loose', ned=False):
+        """(runs, 9) end-point errors [att3 wrapped, pos3, vel3]; ned=True: the NED record (end_ned=True)."""
+        return self.ctx.download(self._end_ptr(ned), (9, self.runs)).T.copy()
+
+    def stats_from_traj(self, algo='loose', pos_ned=False):
+        """End-point statistics recomputed on the device from the kept trajectories (extra_opt='ned')."""
+        if not self.keep_traj:
+            raise ValueError('needs the trajectories (keep_traj=True)')
+        s = _lib.Stats()
+        check(lib.ginsim_end_stats_from_traj(self.ctx.handle, self._bufs['traj_loose'].ptr, self._nav(), self.n, self.runs,
+                                             int(bool(pos_ned)), C.byref(s)))
+        return StatsResult(s)
+
+    def process_stats_online(self, algo='loose'):
+        """(runs, 3, 9) = max|e|, mean, std of the error over samples >= proc_first."""
+        if self.proc_first is None:
+            raise ValueError('online process statistics were not requested (proc_first=...)')
+        return self.ctx.download(self._bufs['proc'], (3, 9, self.runs)).transpose(2, 0, 1)
+
+    def final_biases(self):
+        """(wb, ab), each (runs, 3): the bias estimates at the last sample."""
+        a = self.ctx.download(self.params.out_bias_end, (6, self.runs))
+        return a[0:3].T.copy(), a[3:6].T.copy()
+
+    def final_pdiag(self):
+        """(runs, 15): the diagonal of P at the last sample."""
+        return self.ctx.download(self.params.out_pdiag_end, (15, self.runs)).T.copy()
+
+    def final_sigmas(self):
+        """(runs, 15): the 1 sigma of every state at the last sample, sqrt(final_pdiag())."""
+        return np.sqrt(self.final_pdiag())
+
+    def _gather(self, ptr, ncomp, run_ids):
+        ids = np.ascontiguousarray(np.asarray(run_ids, dtype=np.int64).reshape(-1))
+        out = np.empty((ids.size, self.n, ncomp))
+        check(self.ctx.retry_oom(lambda: lib.ginsim_gather_runs(self.ctx.handle, ptr, ncomp, self.n, self.runs,
+                                                                ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size, dptr(out))))
+        return out
+
+    def series(self, name, run_ids):
+        """Kept series of selected runs, each (k, n, 3): 'att', 'pos', 'vel', 'wb', 'ab'."""
+        if not self.keep_traj:
+            raise ValueError('the series were not kept (keep_traj=True)')
+        plane = self.n * self.runs * 8
+        if name in ('wb', 'ab'):
+            return self._gather(self._bufs[name].ptr, 3, run_ids)
+        k = ('att', 'pos', 'vel').index(name)
+        return self._gather(self._bufs['traj_loose'].ptr + 3 * k * plane, 3, run_ids)
+
+    def trajectories(self, algo='loose', run_ids=(0,), displacement=False):
+        return tuple(self.series(k, run_ids) for k in ('att', 'pos', 'vel'))
+
+    def _nav(self):
+        if 'ref_nav' not in self._bufs:
+            self._bufs['ref_nav'] = self.ctx.upload(self._ref_nav)
+        return self._bufs['ref_nav'].ptr
+
+    def process_stats(self, algo='loose', first_sample=0, pos_ned=False):
+        """(runs, 3, 9) from the kept trajectories (ginsim_process_stats)."""
+        if not self.keep_traj:
+            raise ValueError('process-error statistics need the trajectories (keep_traj=True)')
+        out = np.empty((self.runs, 3, 9))
+        check(lib.ginsim_process_stats(self.ctx.handle, self._bufs['traj_loose'].ptr, self._nav(), self.n, self.runs, int(first_sample),
+                                       int(bool(pos_ned)), dptr(out)))
+        return out
+
+    def error_curve(self, algo='loose', samples=None, pos_ned=False):
+        """The across-run record (CurveResult) of the error at each of `samples` (None: every sample), from the kept planes."""
+        if not self.keep_traj:
+            raise ValueError('an error-growth curve needs the trajectories (keep_traj=True): this job kept statistics only')
+        if samples is None:
+            idx, m = None, self.n
+        else:
+            ids = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
+            idx, m = ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size
+        out = np.empty((max(m, 1), 9, 4))
+        traj, ref = self._bufs['traj_loose'].ptr, self._nav()
+        check(self.ctx.retry_oom(lambda: lib.ginsim_error_curve(self.ctx.handle, traj, ref, self.n, self.runs, idx, m,
+                                                                int(bool(pos_ned)), dptr(out))))
+        return CurveResult(out)
+
+    def buffer(self, name):
+        if name not in self._bufs:
+            raise ValueError('%r was not kept by this job' % (name,))
+        return self._bufs[name]
+
+    def release(self):
+        for b in self._bufs.values():
+            b.free()
+        self._bufs = {}

@@ -122,12 +122,15 @@ class _McResults(object):
         self.exchange = None                # which exchange merged the records: 'abi', 'torch (...)', None = one process
 
     fused_names = None      # set by Sim when inclinometer plugins are present: only these produce 'pos' and 'vel'
+    loose_names = ()        # the loosely coupled GPS/INS filters (InsLoose): their output holds 'pos' and 'vel' too
+    nav_names = None        # fused_names + loose_names: every plugin whose output is a navigation solution
 
     def names_of(self, data_name):
         """The algorithms whose output holds `data_name`: every one for 'att_euler', the fused free integrations for 'pos' / 'vel'."""
-        if self.fused_names is None or data_name == 'att_euler':
+        nav = self.nav_names if self.nav_names is not None else self.fused_names
+        if nav is None or data_name == 'att_euler':
             return list(self.algo_names)
-        return list(self.fused_names)
+        return list(nav)
 
     def job_of(self, name):
         return self.jobs[self.algo_names.index(name)]
@@ -259,12 +262,13 @@ class _Launched(object):
 
 
 _Plan = namedtuple('_Plan', 'fused incl hosted groups first count spread ndev per_sample keep kcount online end_ned ride block_runs '
-                            'proc_first magcal')
+                            'proc_first magcal loose')
 
 
 class _Roles(tuple):
     """(fused, incl, hosted) as _plugin_roles always returned them, and `magcal`: the indices of the magnetometer calibrations."""
     magcal = ()
+    loose = ()          # the indices of the loosely coupled GPS/INS filters (InsLoose of demo_algorithms.ins_loose_device)
 
 
 def _sample_of(t_axis, start_s):
@@ -281,7 +285,9 @@ def _plugin_roles(sim, kinds):
     # the inclinometer plugins of demo_algorithms.inclinometer_device: their own kernel, same seed and run ids
     incl = [i for i, k in enumerate(kinds) if k in ('mahony', 'tilt')]
     magcal = [i for i, k in enumerate(kinds) if k == 'magcal']
-    hosted = [i for i in range(len(kinds)) if i not in fused and i not in incl and i not in magcal]
+    # the loosely coupled GPS/INS filters of demo_algorithms.ins_loose_device: their own kernel, same seed and run ids
+    loose = [i for i, k in enumerate(kinds) if k == 'loose']
+    hosted = [i for i in range(len(kinds)) if i not in fused and i not in incl and i not in magcal and i not in loose]
     if incl and sim.precision != 'f64':
         raise NotImplementedError("the inclinometer plugins (MahonyFilter, TiltAcc of demo_algorithms.inclinometer_device) run "
                                   "in fp64 only: use precision='f64'")
@@ -293,8 +299,17 @@ def _plugin_roles(sim, kinds):
     if magcal and sim.precision != 'f64':
         raise NotImplementedError("the magnetometer calibration (MagCal of demo_algorithms.mag_calibrate_device) runs in fp64 only: "
                                   "use precision='f64'")
+    if loose and not sim.imu.gps:
+        raise ValueError("algorithm %d needs 'gps' but the IMU model has no GPS (IMU(gps=True))" % loose[0])
+    if loose and sim.precision != 'f64':
+        raise NotImplementedError("the loosely coupled filter (InsLoose of demo_algorithms.ins_loose_device) runs in fp64 only: "
+                                  "use precision='f64'")
+    if loose and sim.env is not None and any(isinstance(sim.env.get(k), np.ndarray) for k in ('acc', 'gyro')):
+        raise NotImplementedError("the 'psd' vibration (an (n, 4) env array) is not a term of the loosely coupled filter's kernel "
+                                  "(InsLoose of demo_algorithms.ins_loose_device): 'random' and 'sinusoidal' are")
     roles = _Roles((fused, incl, hosted))
     roles.magcal = magcal
+    roles.loose = loose
     return roles
 
 
@@ -309,6 +324,7 @@ def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group,
     from ginsim import distributed
     fused, incl, hosted = roles
     magcal = list(getattr(roles, 'magcal', ()))
+    loose = list(getattr(roles, 'loose', ()))
     imu, n = sim.imu, t_axis.shape[0]
     kinds = [getattr(a, 'mc_algo', None) for a in algos]
     first, count = distributed.shard(sim.sim_count, world, rank)
@@ -318,8 +334,14 @@ def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group,
     if magcal and in_group:
         raise ValueError('a Sim with a MagCal runs on one device: spreading the magnetometer calibration over the ranks of a '
                          'torch.distributed process group is not built yet -- run it in one process')
-    # an inclinometer chain runs on one device: never spread it automatically; nor is a magnetometer calibration
-    spread, ndev = place(0 if incl or magcal else sim.sim_count * n, in_group)
+    if loose and in_group:
+        raise ValueError('a Sim with an InsLoose runs on one device: spreading the filter over the ranks of a torch.distributed '
+                         'process group is not built yet (the runs are independent) -- run it in one process')
+    # an inclinometer chain runs on one device: never spread it automatically; nor is a magnetometer calibration or a GPS/INS filter
+    spread, ndev = place(0 if incl or magcal or loose else sim.sim_count * n, in_group)
+    if loose and spread:
+        raise ValueError('a Sim with an InsLoose runs on one device: spreading the filter over several GPUs is not built yet (the '
+                         'runs are independent) -- give Sim(device=...) one GPU, not devices=... (or $GINSIM_DEVICES)')
     if magcal and spread:
         raise ValueError('a Sim with a MagCal runs on one device: spreading the magnetometer calibration over several GPUs is not '
                          'built yet -- give Sim(device=...) one GPU, not devices=... (or $GINSIM_DEVICES)')
@@ -331,7 +353,8 @@ def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group,
                          'split is one process per GPU (drop devices=, or do not initialise a process group)')
     per_sample = 48 + (8 if imu.odo else 0) + 72 * len(fused) + (24 if imu.magnetometer else 0) + \
         (48.0 * gps_rows / n if imu.gps else 0) + \
-        sum(104 if kinds[i] == 'mahony' else 56 for i in incl) + 24 * len(magcal)          # mag_cal: at most n rows of 3
+        sum(104 if kinds[i] == 'mahony' else 56 for i in incl) + 24 * len(magcal) + \
+        120 * len(loose)                                                                  # mag_cal: at most n rows of 3
     keep = sim.keep_trajectories
     if keep == 'auto':
         # decided on the LARGEST share of any rank / device (rank 0's), so that every rank takes the same decision -- the
@@ -369,7 +392,7 @@ def plan_monte_carlo(sim, algos, roles, t_axis, gps_rows, rank, world, in_group,
     block_runs = ndev * max(256, int(sim.max_device_bytes // (9 * esize * n)) // 256 * 256)
     proc_first = _sample_of(t_axis, sim.stats_start) if window and (online or incl) else 0
     return _Plan(fused, incl, hosted, groups, first, count, spread, ndev, per_sample, keep, kcount, online, end_ned, ride,
-                 block_runs, proc_first, magcal)
+                 block_runs, proc_first, magcal, loose)
 
 
 class _Jobs(object):
@@ -402,6 +425,22 @@ class _Jobs(object):
         sim = self.sim
         return ginsim.MagCalJob(self.ctx, sim.dmgr.ref_mag.data, sim.imu.mag_err, runs, segments, seed=self.seed,
                                 run_offset=self.first + off, keep=keep, placed=sim.placed)
+
+    def loose(self, algo, runs, keep, off=0, **kw):
+        """An InsLooseJob of `runs` runs from run `off` of this rank for the plugin `algo`: the IMU samples and the fixes are made
+        inside the kernel, as the fused job and AuxSensorJob make them for the same seed and run ids.  The SENSORS are the Sim's;
+        the filter is tuned to the plugin's IMU model where it has one (else the Sim's).  kw: proc_first / proc_ned / end_ned."""
+        from ginsim import workloads
+        from ginsim.ins_loose import InsLooseJob, filter_model
+        sim, d = self.sim, self.sim.dmgr
+        tuned = algo.imu if algo.imu is not None else sim.imu
+        truth = dict(self.truth, ref_gps=d.ref_gps.data, gps_time=d.gps_time.data, gps_visibility=d.gps_visibility.data)
+        ini = algo.ini if algo.ini is not None else workloads.parse_motion(sim.data_src)[0]
+        return InsLooseJob(self.ctx, sim.fs[0], sim.ref_frame, truth, sim.imu.accel_err, sim.imu.gyro_err, sim.imu.gps_err, ini, runs,
+                           seed=self.seed, run_offset=self.first + off, ini_first=algo.run_times + self.first + off,
+                           earth_rot=algo.earth_rot, keep_traj=keep, placed=sim.placed,
+                           model=filter_model(sim.fs[0], tuned.accel_err, tuned.gyro_err, tuned.gps_err, algo.q_scale, algo.p0),
+                           **self.vib, **kw)
 
     def inclinometer(self, group, runs, keep, start_bias=None, stats=True, proc_first=0, off=0):
         """An InclinometerJob of `runs` runs from run `off` of this rank for the plugins of `group`; the MahonyFilter's gains and
@@ -610,6 +649,7 @@ class Sim(object):
         run = self._launch_fused(plan, jobs)
         for i in plan.fused:                    # FreeIntegration.run_times accounting (free_integration.py:69)
             algos[i].run_times += self.sim_count
+        loose_jobs = self._run_loose(plan, jobs)
         incl_groups = self._run_inclinometers(plan, jobs, kinds)
         self._sensor_views(plan, run.sensor_job)
         self._aux_views(plan, jobs)
@@ -617,9 +657,10 @@ class Sim(object):
             self.dmgr.set_algo_output(self.amgr.output)
         name_of = self.amgr.get_algo_name
         self._output_views(plan, [(name_of(i), run.kept.get(i), kinds[i]) for i in plan.fused],
-                           [(name_of(i), g.kept, kinds[i]) for i, g in incl_groups])
-        if plan.fused or plan.incl:
-            self._publish_results(plan, jobs, run, incl_groups, kinds, group, xdev)
+                           [(name_of(i), g.kept, kinds[i]) for i, g in incl_groups],
+                           [(name_of(i), kept) for i, _, kept in loose_jobs])
+        if plan.fused or plan.incl or plan.loose:
+            self._publish_results(plan, jobs, run, incl_groups, kinds, group, xdev, loose_jobs)
         if plan.magcal:
             self._run_magcal(plan, jobs)
         if plan.hosted:
@@ -802,6 +843,34 @@ class Sim(object):
         self.passes = [g.passes for g in groups]
         return sorted(((i, g) for g in groups for i in g.idx), key=lambda t: t[0])
 
+    def _run_loose(self, plan, jobs):
+        """The loosely coupled GPS/INS filters (kind 'loose'): one InsLooseJob over all runs of this rank per plugin -- with
+        everything kept, or statistics only (the online process window, the NED end record) next to a job over the first kcount
+        runs whose series are kept.  Leaves every plugin object with the last run's series as the reference's loop does.
+        Returns [(algorithm index, statistics job, kept job or None)]."""
+        algos, count, kcount = self.amgr.algo or [], plan.count, plan.kcount
+        out = []
+        for i in plan.loose:
+            algo = algos[i]
+            if count <= 0:
+                out.append((i, None, None))
+                continue
+            if plan.keep:
+                job = kept = jobs.loose(algo, count, True).run()
+            else:
+                kw = dict(proc_first=plan.proc_first) if plan.online else {}
+                job = jobs.loose(algo, count, False, end_ned=plan.end_ned, **kw).run()
+                kept = jobs.loose(algo, kcount, True).run() if kcount > 0 else None
+            last, pos = (kept, count - 1) if (plan.keep or kcount == count) else (jobs.loose(algo, 1, True, off=count - 1).run(), 0)
+            algo.finish(*[last.series(k, [pos])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab')])
+            if last is not kept:
+                last.release()
+            out.append((i, job, kept))
+        for i in plan.loose:
+            algos[i].run_times += self.sim_count
+        self.loose_jobs = out
+        return out
+
     def _run_magcal(self, plan, jobs):
         """The magnetometer calibrations (kind 'magcal'): one MagCalJob over all runs of this rank per plugin, nothing of `mag`
         materialised; mag_cal of the first kcount runs kept.  Fills soft_iron / hard_iron / mag_cal keyed '<algo>_<run>' in the
@@ -867,17 +936,19 @@ class Sim(object):
         if self.imu.magnetometer:
             d.add_data(d.mag.name, view('mag'))
 
-    def _output_views(self, plan, fused, incl):
-        """att_euler / pos / vel / att_quat over the fused plugins and att_euler / att_quat over the inclinometer plugins, wb / ab
-        over the MahonyFilters: device views keyed '<algo>_<run>' over the kept runs, or empty mappings when no run is kept
-        (statistics only: names are known, series are not kept).  fused, incl: [(algorithm name, kept job, kind)]."""
+    def _output_views(self, plan, fused, incl, loose=()):
+        """att_euler / pos / vel / att_quat over the fused plugins and the GPS/INS filters, att_euler / att_quat over the
+        inclinometer plugins, wb / ab over the MahonyFilters and the GPS/INS filters: device views keyed '<algo>_<run>' over the
+        kept runs, or empty mappings when no run is kept (statistics only: names are known, series are not kept).
+        fused, incl: [(algorithm name, kept job, kind)]; loose: [(algorithm name, kept job)]."""
         d, first, count = self.dmgr, plan.first, plan.kcount
-        mahony = [(nm, j) for nm, j, k in incl if k == 'mahony']
-        if not (fused or incl):
+        nav = list(fused) + [(nm, j, 'loose') for nm, j in loose]           # the navigation solutions: att, pos, vel
+        with_bias = [(nm, j) for nm, j, k in incl if k == 'mahony'] + list(loose)
+        if not (nav or incl):
             return
         if count <= 0:
-            for out_name in ('att_euler',) + (('att_quat',) if incl else ()) + (('pos', 'vel') if fused else ()) + \
-                    (('wb', 'ab') if mahony else ()):
+            for out_name in ('att_euler',) + (('att_quat',) if incl else ()) + (('pos', 'vel') if nav else ()) + \
+                    (('wb', 'ab') if with_bias else ()):
                 d.add_data(out_name, {})
             return
 
@@ -885,38 +956,47 @@ class Sim(object):
             return lambda pos: (lambda x: np.stack([attitude.euler2quat(v) for v in x]) if quat else x)(job.trajectories(kind, pos)[comp])
         ser = lambda job, nm: (lambda pos, j=job: j.series(nm, pos))
         for out_name, comp in (('att_euler', 0), ('pos', 1), ('vel', 2)):
-            ents = [(nm, traj(j, k, comp, False)) for nm, j, k in fused]
+            ents = [(nm, traj(j, k, comp, False)) for nm, j, k in nav]
             if out_name == 'att_euler':
                 ents += [(nm, ser(j, 'euler_' + k)) for nm, j, k in incl]
             if ents:
                 d.add_data(out_name, _keyed_view(ents, first, count))
-        d.add_data('att_quat', _keyed_view([(nm, traj(j, k, 0, True)) for nm, j, k in fused] +
+        d.add_data('att_quat', _keyed_view([(nm, traj(j, k, 0, True)) for nm, j, k in nav] +
                                            [(nm, ser(j, 'quat_' + k)) for nm, j, k in incl], first, count))
-        for out_name in ('wb', 'ab') if mahony else ():
-            d.add_data(out_name, _keyed_view([(nm, ser(j, out_name)) for nm, j in mahony], first, count))
+        for out_name in ('wb', 'ab') if with_bias else ():
+            d.add_data(out_name, _keyed_view([(nm, ser(j, out_name)) for nm, j in with_bias], first, count))
 
-    def _publish_results(self, plan, jobs, run, incl_groups, kinds, group, xdev):
+    def _publish_results(self, plan, jobs, run, incl_groups, kinds, group, xdev, loose_jobs=()):
         """sim.mc: the statistics and kept jobs of every fused and inclinometer plugin, and how to build the jobs that statistics
         over another window (make_ps_job) or from trajectories that were not kept (make_kept_job) need."""
-        owners = [next(g for g in plan.groups if i in g.idx) for i in plan.fused] + [g for _, g in incl_groups]
-        order = plan.fused + [i for i, _ in incl_groups]
+        algos = self.amgr.algo or []
+        owners = [next(g for g in plan.groups if i in g.idx) for i in plan.fused] + [algos[i] for i, _, _ in loose_jobs] + \
+            [g for _, g in incl_groups]
+        order = plan.fused + [i for i, _, _ in loose_jobs] + [i for i, _ in incl_groups]
+        n_loose = len(loose_jobs)
 
         def make_ps_job(idx, start_sample, ned):
             g = owners[idx]
             if isinstance(g, _InclGroup):           # an inclinometer: one pass from the converged initial biases
                 return jobs.inclinometer(g, plan.count, False, start_bias=g.job.initial_biases(), proc_first=start_sample)
+            if kinds[order[idx]] == 'loose':
+                return jobs.loose(g, plan.count, False, proc_first=start_sample, proc_ned=ned)
             return jobs.fused(g, [kinds[order[idx]]], plan.count, proc_first=start_sample, proc_ned=ned, end_ned=False)
 
         def make_kept_job(idx, off, runs_):      # a block of this rank's runs, trajectories kept (fp32 statistics)
+            if kinds[order[idx]] == 'loose':
+                return jobs.loose(owners[idx], runs_, True, off=off)
             # placed=None is kept from the parent on purpose and not yet judged: these blocks do not follow Sim(placed=)
             return jobs.fused(owners[idx], (kinds[order[idx]],), runs_, off=off, keep_traj=True, placed=None)
         names = [self.amgr.get_algo_name(i) for i in order]
-        self.mc = _McResults([run.stats.get(i) for i in plan.fused] + [g.job for _, g in incl_groups],
-                             [run.kept.get(i) for i in plan.fused] + [g.kept for _, g in incl_groups], names,
+        self.mc = _McResults([run.stats.get(i) for i in plan.fused] + [j for _, j, _ in loose_jobs] + [g.job for _, g in incl_groups],
+                             [run.kept.get(i) for i in plan.fused] + [k for _, _, k in loose_jobs] + [g.kept for _, g in incl_groups], names,
                              [kinds[i] for i in order], plan.first, plan.count, self.sim_count, group,
                              xdev, make_ps_job, ctx=jobs.ctx, make_kept_job=make_kept_job, block_runs=plan.block_runs,
                              ned_from_traj=not plan.end_ned)
         self.mc.fused_names = names[:len(plan.fused)]
+        self.mc.loose_names = names[len(plan.fused):len(plan.fused) + n_loose]
+        self.mc.nav_names = names[:len(plan.fused) + n_loose]       # the plugins whose output holds 'pos' and 'vel'
         self.mc.devices = list(jobs.ctx.devices) if plan.spread else None
         self.mc.kept_block = any(isinstance(j, _BlockAndRest) for j in run.stats.values())    # the kept runs rode along
         self.dmgr.set_mc_results(self.mc)
@@ -1084,7 +1164,8 @@ class Sim(object):
             print("Call Sim.run() to run the simulaltion first.")
             return None
         d, mc = self.dmgr, self.mc
-        names = list(getattr(mc, 'fused_names', None) or []) if mc is not None and not self.data_from_files else []
+        names = list(getattr(mc, 'nav_names', None) or getattr(mc, 'fused_names', None) or []) \
+            if mc is not None and not self.data_from_files else []
         if isinstance(data_names, str):
             data_names = (data_names,)
         slices = {'att_euler': slice(0, 3), 'pos': slice(3, 6), 'vel': slice(6, 9)}
@@ -1095,6 +1176,10 @@ class Sim(object):
             raise ValueError('error_curve: the curves of %s come from the fused free-integration plugins (FreeIntegration, '
                              'FreeIntegrationOdo), and this Sim has none -- inclinometer, MagCal and host plugins are not covered'
                              % (', '.join(data_names),))
+        for a in getattr(mc, 'loose_names', ()):
+            if not mc.job_of(a).keep_traj:
+                raise ValueError('error_curve: %s (InsLoose) kept statistics only: its curve is read from the kept trajectory '
+                                 'planes -- run the Sim with keep_trajectories=True' % a)
         t = np.asarray(d.time.data)
         n = t.shape[0]
         if every is not None and samples is not None:

@@ -333,6 +333,54 @@ int ginsim_incl_variant(const ginsim_mc_params* mc, const ginsim_incl_params* p,
 /* the NAME of the kernel ginsim_incl_run launches, as rocprofv3 reports it (e.g. "ginsim::incl_kernel<3, false, false>") */
 int ginsim_incl_kernel_name(const ginsim_mc_params* mc, const ginsim_incl_params* p, char* buf, size_t cap);
 
+/* ---- loosely coupled GPS/INS Kalman filter: the interface demo_algorithms/ins_loose.py::InsLoose declares (input fs, gyro,
+ *      accel, time, gps_time, gps; output pos, vel, att_euler, wb, ab; its prediction and correction are `pass`) filled in as a
+ *      15-state closed-loop error-state filter over a batch of Monte-Carlo runs, one lane per run (csrc/ins_loose.hip).  Added
+ *      without a change of GINSIM_ABI_VERSION: nothing existing moved.
+ *      The IMU samples come from the ginsim_mc_params given next to these parameters, read exactly as ginsim_incl_run reads them
+ *      (generate mode with vibration types 1 and 2, 'psd' refused; or given_sensors with in_accel / in_gyro); the initial states
+ *      (ini, n_ini, ini_first, ini_has_g), ref_frame, earth_rot, fs, ref_end, end_pos_ned, ref_nav, proc_first and block_threads
+ *      as ginsim_mc_run reads them.  The mechanisation is ginsim_mc_run's free integration on accel - ab and gyro - wb: a
+ *      launch without a usable fix IS free integration.
+ *      GPS fix k of run r is regenerated in the lane (ref_gps given: what ginsim_aux_sensors writes for the same seed, run_offset
+ *      and gps_sigma, bit for bit, never stored) or read from in_gps (given_sensors).  It is applied at IMU sample gps_stamp[k]
+ *      to the state that sample's row reports, before the row is stored, when gps_visible[k] != 0.
+ *      Error state x = estimate - truth: dr (NED metres in ref_frame 0, the virtual-inertial axes in ref_frame 1), dv, psi (a
+ *      small rotation in the navigation frame: C_est = (I - [psi x]) C, C = body -> navigation), dbg, dba.  Per IMU sample
+ *      P <- Phi P Phi^T + Qd with Phi = I + F dt; the blocks of F are (r,v) = I, (v,psi) = [f^n x], (v,ba) = -C, (psi,bg) = C,
+ *      (bg,bg) = -1/tau_g, (ba,ba) = -1/tau_a (Earth and transport rate neglected in F only).  A fix is six sequential scalar
+ *      updates with z = ins - gps, H = [I6 0]; the state is fed back at once and zeroed. */
+typedef struct {
+    int64_t  m;               /* GPS fixes (0: none) */
+    const int64_t* gps_stamp; /* HOST [m]: the IMU sample index of each fix (gps_time fs), strictly increasing, in [0, n) */
+    const int32_t* gps_visible; /* HOST [m]: gps_visibility; a fix with 0 is skipped.  NULL: all visible */
+    const double* ref_gps;    /* device [m][6]: generated form (truth pos3, vel3 of every fix), or NULL */
+    double   gps_sigma[6];    /* generated form: as ginsim_aux_params.gps_sigma (position sigma in rad, rad, m for ref_frame 0) */
+    const double* in_gps;     /* device [6][m][runs]: given form (with given_sensors) */
+    double   r_diag[6];       /* measurement variances: position (m^2, NED metres in ref_frame 0) and velocity */
+    double   p0[5];           /* initial 1 sigma of dr, dv, psi, dbg, dba (P0 is diagonal); all > 0 */
+    double   q_v[3], q_psi[3];/* Qd of one IMU sample on dv and psi per BODY axis (rotated by C in the kernel): (vrw^2 | arw^2) dt */
+    double   q_bg[3], q_ba[3];/* Qd of one IMU sample on the bias states: 2 sigma^2 / tau dt (0: a constant) */
+    double   decay_g[3], decay_a[3]; /* 1 - dt / tau of the bias states (1: a random walk) */
+    const int64_t* run_list;  /* device [n_list] or NULL: lane i filters run run_list[i] (ids < runs); NULL: runs 0 .. n_list-1 */
+    int64_t  n_list;          /* lanes of the launch */
+    double*  out_traj;        /* [9][n][runs] = att3, pos3, vel3 (the layout ginsim_process_stats / ginsim_error_curve read), or NULL */
+    double*  out_wb;          /* [3][n][runs] estimated gyro bias at every sample, or NULL */
+    double*  out_ab;          /* [3][n][runs] estimated accelerometer bias at every sample, or NULL */
+    double*  out_end;         /* [9][runs] end-point error as ginsim_mc_params.out_end (attitude wrapped, end_pos_ned honoured), or NULL */
+    double*  out_proc;        /* [3][9][runs] max|e|, mean, std (ddof 0) of the error over samples >= proc_first (needs ref_nav), or NULL */
+    double*  out_bias_end;    /* [6][runs] wb3, ab3 at the last sample, or NULL */
+    double*  out_pdiag_end;   /* [15][runs] diagonal of P at the last sample, or NULL */
+    double*  out_end_ned;     /* [9][runs] a second end-point record with the position error in local NED metres, as
+                               * ginsim_mc_params.out_end_ned (ref_frame 0 only), or NULL */
+} ginsim_loose_params;
+
+int ginsim_loose_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const ginsim_loose_params* p);
+/* 0: generated sensors and fixes, 1: given */
+int ginsim_loose_variant(const ginsim_mc_params* mc, const ginsim_loose_params* p, int32_t* variant);
+/* the NAME of the kernel ginsim_loose_run launches, as rocprofv3 reports it (e.g. "ginsim::loose_kernel<1, false, false, false>") */
+int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, char* buf, size_t cap);
+
 /* ---- auxiliary sensors of a Monte-Carlo batch: pathgen.gps_gen (pathgen.py:596-625) and pathgen.mag_gen (:643-661).
  *      FreeIntegration does not consume them, so they are generated only when they are to be kept. */
 typedef struct {

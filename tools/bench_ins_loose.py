@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Kernel time of the loosely coupled GPS/INS filter (csrc/ins_loose.hip) against its arithmetic floor.
+
+    python tools/bench_ins_loose.py --isa                 # no GPU: fp64 instructions of the kernels' time loops, counted in the ISA
+    python tools/bench_ins_loose.py [--runs 65536] [--reps 5] [--out profiles/ins_loose_timing.json]
+
+Workload: 65 536 runs x the 1000 samples of the 90-degree turn at 100 Hz (BASELINE config C2's shape) with GPS at 10 Hz, ref_frame 1,
+'mid-accuracy' IMU; statistics only (nothing but the per-run end records is written) and with everything kept (trajectory, wb, ab).
+Times are HIP-event times of the launch alone (the job's buffers exist before the timer starts), the median of --reps launches
+after one warm-up.
+
+The arithmetic: the file is compiled to assembly with the build's flags and, for the instantiation each job launches
+(InsLooseJob.kernel_name), the fp64 VALU instructions (v_fma_f64, v_mul_f64, v_add_f64, ...; a fused multiply-add is one
+instruction) of the TIME LOOP are counted: the span of the kernel's longest backward branch, which leaves out the initialisation
+of P and the epilogue.  The loop's text also holds the correction (six scalar updates), which one step in ten executes here, so
+the count is an UPPER bound of a step's arithmetic and the time over the floor printed from it a LOWER bound.
+Floor = instructions x runs x steps / (256 CUs x 4 SIMDs x 16 fp64 lanes per clock x 2.4 GHz).  --ops N overrides the count.
+No threshold is set here."""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+PKG = os.path.join(REPO, 'gnss-ins-sim_amd')
+sys.path.insert(0, PKG)
+CLOCK_HZ = 2.4e9
+FP64_LANES_PER_CLOCK = 256 * 4 * 16
+
+
+def isa_counts():
+    """{kernel name: (fp64 VALU instructions, of them fused multiply-adds)} from the assembly of csrc/ins_loose.hip."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('ginsim_build', os.path.join(PKG, 'build.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    flags = dict(b.SOURCES)['ins_loose.hip']
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, 'ins_loose.s')
+        subprocess.check_call([b.HIPCC] + b.COMMON + list(flags) + ['-S', '--cuda-device-only', os.path.join(b.CSRC, 'ins_loose.hip'), '-o', out],
+                              stderr=subprocess.DEVNULL)
+        text = open(out).read()
+    return {k: count_loop(body) for k, body in kernel_bodies(text).items()}
+
+
+def kernel_bodies(text):
+    """{mangled kernel name: its instruction lines} of an AMDGPU assembly file."""
+    res, cur = {}, None
+    for line in text.splitlines():
+        m = re.match(r'^(_ZN6ginsim12loose_kernel\w+):', line)
+        if m:
+            cur = m.group(1)
+            res[cur] = []
+        elif cur and '.end_amdhsa_kernel' in line:
+            cur = None
+        elif cur:
+            res[cur].append(line)
+    return res
+
+
+def count_loop(lines):
+    """(fp64 VALU instructions, of them fused multiply-adds, lines of the span) of the longest backward branch of a kernel."""
+    labels = {}
+    for i, line in enumerate(lines):
+        m = re.match(r'^(\.?[A-Za-z_][\w.$]*):', line.strip())
+        if m:
+            labels[m.group(1)] = i
+    lo, hi = 0, len(lines)
+    best = 0
+    for i, line in enumerate(lines):
+        t = line.split()
+        if len(t) >= 2 and (t[0].startswith('s_cbranch') or t[0] == 's_branch') and labels.get(t[1], i) < i and i - labels[t[1]] > best:
+            best, lo, hi = i - labels[t[1]], labels[t[1]], i
+    n = f = 0
+    for line in lines[lo:hi]:
+        op = line.split()[0] if line.split() else ''
+        if re.match(r'^v_\w+_f64', op) and not op.startswith('v_cvt') and not op.startswith('v_cmp'):
+            n += 1
+            f += op.startswith('v_fma_f64')
+    return n, f, hi - lo
+
+
+def mangled_prefix(kernel_name):
+    """'ginsim::loose_kernel<1, false, false, false>' -> '_ZN6ginsim12loose_kernelILi1ELb0ELb0ELb0EEE'."""
+    args = [a.strip() for a in kernel_name[kernel_name.index('<') + 1:kernel_name.rindex('>')].split(',')]
+    return '_ZN6ginsim12loose_kernelILi%sE' % args[0] + ''.join('Lb%dE' % (a == 'true') for a in args[1:]) + 'EE'
+
+
+def time_launches(runs, reps):
+    import numpy as np
+    import ginsim
+    from ginsim import workloads
+    fs, rf = 100.0, 1
+    ini, truth, _ = workloads.truth_from_profile('turn_90deg', fs, rf, fs_gps=10.0, gps=True)
+    acc, gyr = workloads.imu_grade('mid-accuracy')
+    gps_err = {'stdp': np.array([5.0, 5.0, 7.0]), 'stdv': np.array([0.05, 0.05, 0.05])}
+    ctx = ginsim.Context(0)
+    out = {'device': ctx.name(), 'runs': runs, 'samples': int(truth['ref_accel'].shape[0]), 'fixes': int(truth['ref_gps'].shape[0])}
+    for label, keep in (('statistics_only', False), ('everything_kept', True)):
+        job = ginsim.InsLooseJob(ctx, fs, rf, truth, acc, gyr, gps_err, ini, runs, seed=1, keep_traj=keep)
+        job.run()                                   # warm-up: code object, LDS attribute
+        ms = []
+        for _ in range(reps):
+            ctx.timer_begin()
+            job.launch()
+            ms.append(ctx.timer_end())
+        out[label] = {'kernel': job.kernel_name(), 'ms_median': float(np.median(ms)), 'ms_all': [float(x) for x in ms],
+                      'bytes_written': (15 * out['samples'] * 8 if keep else 0) * runs + 30 * 8 * runs}
+        job.release()
+    ctx.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--isa', action='store_true')
+    ap.add_argument('--runs', type=int, default=65536)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--ops', type=int, default=0, help='fp64 instructions per step, instead of the count from the ISA')
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    if a.isa:
+        for k, (n, f, span) in sorted(isa_counts().items()):
+            print('%s: %d fp64 VALU instructions (%d fused multiply-adds) in a time loop of %d lines' % (k, n, f, span))
+        return
+    res = time_launches(a.runs, a.reps)
+    counts = {} if a.ops else isa_counts()
+    for label in ('statistics_only', 'everything_kept'):
+        r = res[label]
+        ops = a.ops or next(v[0] for k, v in counts.items() if k.startswith(mangled_prefix(r['kernel'])))
+        r['fp64_instructions_per_step'] = int(ops)
+        r['floor_ms'] = ops * res['runs'] * (res['samples'] - 1) / (FP64_LANES_PER_CLOCK * CLOCK_HZ) * 1e3
+        r['time_over_floor'] = r['ms_median'] / r['floor_ms']
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+
+
+if __name__ == '__main__':
+    main()
