@@ -48,6 +48,9 @@ SOURCES = [
     # mc_kernel.hip: 0 bytes of scratch in every instantiation (the file's header has the whole account; tests/test_ins_loose_oracle.py
     # reads the report)
     ('ins_loose.hip', MC_FLAGS),
+    # the same lane with the odometer / non-holonomic aiding block (ins_loose.hpp): the same flags, its own resource report
+    # (tests/test_ins_loose_aided_oracle.py reads it)
+    ('ins_loose_aided.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),

@@ -479,6 +479,21 @@ static int check_loose_params(const ginsim_mc_params* m, const ginsim_loose_para
     REQUIRE(!p->out_proc || (m->proc_first >= 0 && m->proc_first < m->n), "loose_run: proc_first out of range");
     REQUIRE(!m->proc_pos_ned || m->ref_frame == 0, "loose_run: NED position errors exist in ref_frame 0 only");
     REQUIRE(!p->out_end_ned || m->ref_frame == 0, "loose_run: out_end_ned needs ref_frame 0");
+    REQUIRE(p->aid_mask >= 0 && p->aid_mask <= 7, "loose_run: aid_mask=%d must lie in 0 .. 7", (int)p->aid_mask);
+    if (p->aid_mask != 0) {
+        REQUIRE(p->aid_every >= 1, "loose_run: aid_every must be >= 1");
+        REQUIRE((p->aid_mask & 6) == 0 || (std::isfinite(p->r_nhc) && p->r_nhc > 0.0), "loose_run: r_nhc must be positive");
+        if (p->aid_mask & 1) {
+            REQUIRE(std::isfinite(p->r_odo) && p->r_odo > 0.0, "loose_run: r_odo must be positive");
+            REQUIRE(std::isfinite(p->odo_scale_f) && p->odo_scale_f > 0.0, "loose_run: odo_scale_f must be positive");
+            if (m->given_sensors) {
+                REQUIRE(m->in_odo, "loose_run: odometer aiding with given_sensors needs in_odo");
+            } else {
+                REQUIRE(m->ref_odo, "loose_run: odometer aiding needs ref_odo");
+                REQUIRE(std::isfinite(m->odo_scale) && std::isfinite(m->odo_stdv), "loose_run: odo_scale / odo_stdv must be finite");
+            }
+        }
+    }
     return GINSIM_OK;
 }
 

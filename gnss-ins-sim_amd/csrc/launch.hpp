@@ -37,6 +37,10 @@ hipError_t launch_loose(const ginsim_mc_params& p, const ginsim_loose_params& b,
                         hipStream_t stream, char* name, size_t cap);      // stamp / visible: device copies of b.gps_stamp / b.gps_visible
 int loose_variant(const ginsim_mc_params& p);
 
+// ins_loose_aided.hip: what launch_loose calls when b.aid_mask != 0
+hipError_t launch_loose_aided(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
+                              hipStream_t stream, char* name, size_t cap);
+
 // aux_sensors.hip
 hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s);
 

@@ -7,13 +7,20 @@ as NumPy, in tests/ins_loose_ref.py).  ``Sim`` runs an instance (``mc_algo`` 'lo
 every lane making its own IMU samples and GPS fixes; ``run(set_of_input)`` on one logged series runs the same kernel on that series.
 The checkout's own stub (demo_algorithms.ins_loose) stays hosted.  fp64 only.
 
-    InsLoose(ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None)
+    InsLoose(ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None,
+             odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None)
 
 ini_pos_vel_att: the initial states FreeIntegration takes ((9|10,) or (9|10, k)); None under a Sim: the motion definition's.
 imu: the IMU model the filter is tuned to (its accel_err, gyro_err, gps_err); None under a Sim: the Sim's own.  ref_frame is the
 Sim's under a Sim and needed by ``run`` on a logged series.
 q_scale multiplies the process noise; p0 = (sigma_r [m], sigma_v [m/s], sigma_psi [rad], sigma_bg [rad/s], sigma_ba [m/s^2]), the
 initial 1 sigma; default (1e-3, 1e-3, 1e-5, 1e-7, 1e-5), the two bias terms raised to the sensor's largest constant bias.
+
+The two aids of a land vehicle (csrc/ins_loose_aided.hip; as NumPy in tests/ins_loose_aided_ref.py):
+odo=True uses the odometer (``input`` gains a trailing 'odo'; the IMU model needs odo=True), nhc=True the non-holonomic constraints
+(no sideways and no vertical body velocity), both every odo_every IMU samples.  odo_std [m/s]: 1 sigma of the scaled odometer
+sample (default: the IMU model's odo_err['stdv'] / scale); nhc_std [m/s]: the constraints' pseudo-noise; odo_scale: the scale
+factor the filter assumes (default: the IMU model's odo_err['scale']).
 """
 import numpy as np
 
@@ -26,8 +33,10 @@ class InsLoose(object):
     '''
     mc_algo = 'loose'
 
-    def __init__(self, ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None):
-        self.input = ['fs', 'gyro', 'accel', 'time', 'gps_time', 'gps']
+    def __init__(self, ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None,
+                 odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None):
+        self.odo, self.nhc = bool(odo), bool(nhc)
+        self.input = ['fs', 'gyro', 'accel', 'time', 'gps_time', 'gps'] + (['odo'] if self.odo else [])
         self.output = ['pos', 'vel', 'att_euler', 'wb', 'ab']
         self.batch = True
         self.results = None
@@ -41,7 +50,22 @@ class InsLoose(object):
         if not (self.q_scale > 0.0 and np.isfinite(self.q_scale)):
             raise ValueError('q_scale must be positive')
         self.p0 = p0
+        if int(odo_every) != odo_every or int(odo_every) < 1:
+            raise ValueError('odo_every must be an integer >= 1')
+        for name, v, optional in (('odo_std', odo_std, True), ('nhc_std', nhc_std, False), ('odo_scale', odo_scale, True)):
+            if not (optional and v is None) and not (float(v) > 0.0 and np.isfinite(float(v))):
+                raise ValueError('%s must be positive' % name)
+        self.odo_every, self.nhc_std = int(odo_every), float(nhc_std)
+        self.odo_std = None if odo_std is None else float(odo_std)
+        self.odo_scale = None if odo_scale is None else float(odo_scale)
         self.run_times = 0
+
+    def aid(self):
+        """The aiding options ginsim.InsLooseJob takes (ginsim.ins_loose.aiding_model), or None without aiding."""
+        if not (self.odo or self.nhc):
+            return None
+        return {'odo': self.odo, 'nhc': self.nhc, 'every': self.odo_every, 'odo_std': self.odo_std, 'nhc_std': self.nhc_std,
+                'scale': self.odo_scale}
 
     def finish(self, pos, vel, att, wb, ab):
         """State the plugin holds after a run: the last run's series, each (n, 3), in the order of `output`."""
@@ -50,7 +74,8 @@ class InsLoose(object):
     def run(self, set_of_input):
         '''
         set_of_input: [fs, gyro (n, 3), accel (n, 3), time (n,), gps_time (m,), gps (m, 6 | 7)], as the reference's run; a seventh
-        gps column is the visibility.  Needs InsLoose(ini_pos_vel_att=..., ref_frame=..., imu=...).
+        gps column is the visibility; with InsLoose(odo=True) a seventh element, odo (n,).  Needs InsLoose(ini_pos_vel_att=...,
+        ref_frame=..., imu=...).
         '''
         import ginsim
         from ginsim.ins_loose import InsLooseJob
@@ -66,6 +91,13 @@ class InsLoose(object):
         n = gyro.shape[0]
         if gyro.shape != (n, 3) or accel.shape != (n, 3) or gps.shape[1] < 6:
             raise ValueError('gyro and accel must be (n, 3) arrays, gps (m, 6)')
+        odo = None
+        if self.odo:
+            if len(set_of_input) < 7:
+                raise ValueError("InsLoose(odo=True).run needs the odometer series as the seventh element ('odo')")
+            odo = np.ascontiguousarray(np.asarray(set_of_input[6], dtype=np.float64).reshape(-1))
+            if odo.shape[0] != n:
+                raise ValueError('odo must be an (n,) array')
         t0 = time[0] if time.size else 0.0
         truth = {'ref_accel': accel, 'ref_gyro': gyro, 'ref_att': np.zeros((n, 3)), 'ref_pos': np.zeros((n, 3)), 'ref_vel': np.zeros((n, 3)),
                  'ref_gps': np.ascontiguousarray(gps[:, 0:6]), 'gps_time': gps_time - t0,
@@ -73,11 +105,13 @@ class InsLoose(object):
         ctx = ginsim.default_context()
         bufs = {'accel': ctx.upload(np.ascontiguousarray(accel.T)), 'gyro': ctx.upload(np.ascontiguousarray(gyro.T)),       # [3][n][1]
                 'gps': ctx.upload(np.ascontiguousarray(gps[:, 0:6].T))}
+        if odo is not None:
+            bufs['odo'] = ctx.upload(odo)                                                                                   # [n][1]
         job = None
         try:
             job = InsLooseJob(ctx, fs, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, self.imu.gps_err, self.ini, 1,
                               ini_first=self.run_times, earth_rot=self.earth_rot, given=bufs, q_scale=self.q_scale, p0=self.p0,
-                              keep_traj=True).run()
+                              keep_traj=True, odo_err=getattr(self.imu, 'odo_err', None), aid=self.aid()).run()
             self.finish(*[job.series(k, [0])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab')])
         finally:
             if job is not None:

@@ -97,7 +97,9 @@ class LooseParams(C.Structure):
                 ('q_v', C.c_double * 3), ('q_psi', C.c_double * 3), ('q_bg', C.c_double * 3), ('q_ba', C.c_double * 3),
                 ('decay_g', C.c_double * 3), ('decay_a', C.c_double * 3), ('run_list', C.c_void_p), ('n_list', C.c_int64),
                 ('out_traj', C.c_void_p), ('out_wb', C.c_void_p), ('out_ab', C.c_void_p), ('out_end', C.c_void_p),
-                ('out_proc', C.c_void_p), ('out_bias_end', C.c_void_p), ('out_pdiag_end', C.c_void_p), ('out_end_ned', C.c_void_p)]
+                ('out_proc', C.c_void_p), ('out_bias_end', C.c_void_p), ('out_pdiag_end', C.c_void_p), ('out_end_ned', C.c_void_p),
+                ('aid_mask', C.c_int32), ('aid_every', C.c_int64), ('odo_scale_f', C.c_double), ('r_odo', C.c_double),
+                ('r_nhc', C.c_double)]
 
 
 class PathgenParams(C.Structure):

@@ -3,6 +3,8 @@ prediction and correction are `pass` in the reference) over a batch of Monte-Car
 ginsim_loose_run).  One launch: every lane makes its own IMU samples and GPS fixes again from the run's Philox streams (the bits
 MonteCarloJob and AuxSensorJob would store), mechanises them with the free-integration step on bias-corrected samples and runs a
 15-state closed-loop error-state filter next to it.  tests/ins_loose_ref.py restates the arithmetic in NumPy.
+With aid=... the filter also uses the odometer and the non-holonomic constraints of a land vehicle (csrc/ins_loose_aided.hip,
+aiding_model; restated by tests/ins_loose_aided_ref.py).
 """
 import ctypes as C
 
@@ -59,6 +61,48 @@ def gps_sigma(gps_err, ref_gps, ref_frame):
     return sig
 
 
+def aiding_model(odo_err, aid):
+    """The five aiding numbers of ginsim_loose_params, {'aid_mask', 'aid_every', 'odo_scale_f', 'r_odo', 'r_nhc'}, from the
+    odometer's error dict {'scale', 'stdv'} (None without an odometer) and the options
+    aid = {'odo': bool, 'nhc': bool, 'every': int, 'odo_std': float | None, 'nhc_std': float, 'scale': float | None}:
+
+      aid_mask     bit 0 'odo' (z = v_b[0] - odo / scale), bits 1 and 2 'nhc' (z = v_b[1], v_b[2])
+      odo_scale_f  'scale': the scale factor the FILTER assumes; default odo_err['scale'].  It is a parameter, not a state: a
+                   filter that assumes 1.0 of an odometer that reads 0.99 is inconsistent by a factor of tens
+      r_odo        'odo_std'^2 [m/s]: of the SCALED sample; default odo_err['stdv'] / scale
+      r_nhc        'nhc_std'^2 [m/s]; default 0.05: a pseudo-noise, how far the vehicle may slide
+      aid_every    'every': a block every so many IMU samples; default 1
+    aid None or without 'odo' and 'nhc': no aiding (aid_mask 0)."""
+    aid = dict(aid or {})
+    unknown = set(aid) - {'odo', 'nhc', 'every', 'odo_std', 'nhc_std', 'scale'}
+    if unknown:
+        raise ValueError('aid: unknown keys %s' % sorted(unknown))
+    odo, nhc = bool(aid.get('odo', False)), bool(aid.get('nhc', False))
+    out = {'aid_mask': (1 if odo else 0) | (6 if nhc else 0), 'aid_every': 0, 'odo_scale_f': 0.0, 'r_odo': 0.0, 'r_nhc': 0.0}
+    if not out['aid_mask']:
+        return out
+    every = aid.get('every', 1)
+    if int(every) != every or int(every) < 1:
+        raise ValueError("aid['every'] must be an integer >= 1")
+    out['aid_every'] = int(every)
+
+    def positive(name, v):
+        v = float(v)
+        if not (v > 0.0 and np.isfinite(v)):
+            raise ValueError('aid[%r] must be positive and finite' % (name,))
+        return v
+    if nhc:
+        out['r_nhc'] = positive('nhc_std', aid.get('nhc_std', 0.05)) ** 2
+    if odo:
+        scale, std = aid.get('scale'), aid.get('odo_std')
+        if (scale is None or std is None) and odo_err is None:
+            raise ValueError("aid['odo'] needs odo_err={'scale', 'stdv'} or both aid['scale'] and aid['odo_std']")
+        scale = positive('scale', odo_err['scale'] if scale is None else scale)
+        out['odo_scale_f'] = scale
+        out['r_odo'] = positive('odo_std', float(odo_err['stdv']) / scale if std is None else std) ** 2
+    return out
+
+
 class InsLooseJob(object):
     """One batch of runs of the loosely coupled filter on one device.
 
@@ -66,7 +110,10 @@ class InsLooseJob(object):
     [seconds: fix k is applied at IMU sample round(gps_time[k] fs)], 'gps_visibility' (m,) as workloads.truth_from_profile(gps=True)
     makes them.  ini: the initial states FreeIntegration takes.  gps_err: {'stdp', 'stdv'}.
     given: None (samples and fixes are regenerated per lane: same seed and run ids as MonteCarloJob / AuxSensorJob, same bits) or a
-    dict of device buffers {'accel', 'gyro'} [3][n][runs] and 'gps' [6][m][runs].
+    dict of device buffers {'accel', 'gyro'} [3][n][runs] and 'gps' [6][m][runs] (and 'odo' [n][runs] for aid['odo']).
+    odo_err, aid: the odometer's error dict {'scale', 'stdv'} and the aiding options of aiding_model() (csrc/ins_loose_aided.hip;
+    None: the filter without aiding).  aid['odo'] needs truth['ref_odo'] (n,) and odo_err in the generated form: the lane makes the
+    odometer sample MonteCarloJob(keep_sensors) would store for the same seed and run ids.
     model: filter_model(...) or None (made from the error dicts, q_scale and p0).
     keep_traj: materialise att / pos / vel ([9][n][runs]) and wb, ab ([3][n][runs] each).
     proc_first: None, or the first sample of the online process-error window.  end_pos_ned / proc_ned (ref_frame 0): position
@@ -79,7 +126,7 @@ class InsLooseJob(object):
 
     def __init__(self, ctx, fs, ref_frame, truth, accel_err, gyro_err, gps_err, ini, runs, seed=0, run_offset=0, ini_first=0,
                  earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
-                 end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None):
+                 end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None):
         self.ctx = ctx
         self.n, self.runs = int(truth['ref_accel'].shape[0]), int(runs)
         if self.runs < 1:
@@ -110,6 +157,10 @@ class InsLooseJob(object):
         p.gps_stamp, p.gps_visible = self._stamps.ctypes.data, self._visible.ctypes.data
         for k in ('r_diag', 'p0', 'q_v', 'q_psi', 'q_bg', 'q_ba', 'decay_g', 'decay_a'):
             getattr(p, k)[:] = [float(x) for x in np.asarray(self.model[k], dtype=np.float64).reshape(-1)]
+        self.aid = aiding_model(odo_err, aid)
+        for k, v in self.aid.items():
+            setattr(p, k, v)
+        use_odo = bool(self.aid['aid_mask'] & 1)
         self._ref_nav = np.ascontiguousarray(np.concatenate([truth['ref_att'], truth['ref_pos'], truth['ref_vel']], axis=1))
         m.ref_end[:] = [float(x) for x in self._ref_nav[-1]]
         parts = [table.reshape(-1)]
@@ -125,14 +176,24 @@ class InsLooseJob(object):
                       ref_gps.reshape(-1)]
             if self.m:
                 p.gps_sigma[:] = [float(x) for x in gps_sigma(gps_err, ref_gps, int(ref_frame))]
+            if use_odo:
+                if 'ref_odo' not in truth or odo_err is None:
+                    raise ValueError("aid['odo'] in the generated form needs truth['ref_odo'] and odo_err")
+                ref_odo = np.asarray(truth['ref_odo'], dtype=np.float64).reshape(-1)
+                if ref_odo.size != self.n:
+                    raise ValueError("truth['ref_odo'] must have one value per IMU sample")
+                m.odo_scale, m.odo_stdv = float(odo_err['scale']), float(odo_err['stdv'])
+                parts.append(ref_odo)
         else:
             if vib_accel is not None or vib_gyro is not None:
                 raise ValueError('given sensors: a vibration model cannot be added to sensor series that already exist')
-            for k, c, length in (('accel', 3, self.n), ('gyro', 3, self.n), ('gps', 6, self.m)):
+            for k, c, length in (('accel', 3, self.n), ('gyro', 3, self.n), ('gps', 6, self.m)) + ((('odo', 1, self.n),) if use_odo else ()):
                 if length and (k not in given or given[k].nbytes < c * length * self.runs * 8 or getattr(given[k], 'layout', 'runs') != 'runs'):
                     raise ValueError('given sensors: %r missing, too small or not [component][sample][run]' % (k,))
             m.given_sensors, m.in_accel, m.in_gyro = 1, given['accel'].ptr, given['gyro'].ptr
             p.in_gps = given['gps'].ptr if self.m else None
+            if use_odo:
+                m.in_odo = given['odo'].ptr
             self._given = given
         offs = np.cumsum([0] + [q.size for q in parts]) * 8
         self._bufs['inputs'] = ctx.upload(np.concatenate(parts))
@@ -140,6 +201,8 @@ class InsLooseJob(object):
         if given is None:
             m.ref_accel, m.ref_gyro = self._bufs['inputs'].at(offs[1]), self._bufs['inputs'].at(offs[2])
             p.ref_gps = self._bufs['inputs'].at(offs[3]) if self.m else None
+            if use_odo:
+                m.ref_odo = self._bufs['inputs'].at(offs[4])
         R = self.runs
         # end [9][R], bias_end [6][R], pdiag_end [15][R], run list [R], the NED end record [9][R]
         self._bufs['small'] = ctx.malloc((9 + 6 + 15 + 1 + 9) * R * 8)

@@ -301,6 +301,9 @@ def _plugin_roles(sim, kinds):
                                   "use precision='f64'")
     if loose and not sim.imu.gps:
         raise ValueError("algorithm %d needs 'gps' but the IMU model has no GPS (IMU(gps=True))" % loose[0])
+    for i in loose:
+        if getattr(sim.amgr.algo[i], 'odo', False) and not sim.imu.odo:
+            raise ValueError("algorithm %d needs 'odo' but the IMU model has no odometer" % i)
     if loose and sim.precision != 'f64':
         raise NotImplementedError("the loosely coupled filter (InsLoose of demo_algorithms.ins_loose_device) runs in fp64 only: "
                                   "use precision='f64'")
@@ -440,7 +443,13 @@ class _Jobs(object):
                            seed=self.seed, run_offset=self.first + off, ini_first=algo.run_times + self.first + off,
                            earth_rot=algo.earth_rot, keep_traj=keep, placed=sim.placed,
                            model=filter_model(sim.fs[0], tuned.accel_err, tuned.gyro_err, tuned.gps_err, algo.q_scale, algo.p0),
-                           **self.vib, **kw)
+                           **self._aiding(algo), **self.vib, **kw)
+
+    def _aiding(self, algo):
+        """The aiding arguments of an InsLooseJob: none for a plugin without aiding.  The odometer SAMPLES are the Sim's
+        (truth['ref_odo'] and the IMU's odo_err, as the fused job makes them); what the filter assumes of them is the plugin's."""
+        aid = algo.aid() if hasattr(algo, 'aid') else None
+        return {} if aid is None else {'odo_err': self.sim.imu.odo_err if self.sim.imu.odo else None, 'aid': aid}
 
     def inclinometer(self, group, runs, keep, start_bias=None, stats=True, proc_first=0, off=0):
         """An InclinometerJob of `runs` runs from run `off` of this rank for the plugins of `group`; the MahonyFilter's gains and

@@ -373,6 +373,21 @@ typedef struct {
     double*  out_pdiag_end;   /* [15][runs] diagonal of P at the last sample, or NULL */
     double*  out_end_ned;     /* [9][runs] a second end-point record with the position error in local NED metres, as
                                * ginsim_mc_params.out_end_ned (ref_frame 0 only), or NULL */
+    /* Odometer and non-holonomic aiding (csrc/ins_loose_aided.hip), appended without a change of
+     * GINSIM_ABI_VERSION: a zeroed tail is the filter as it was.  With D = C_est^T (navigation -> body) of the reported attitude, v
+     * the reported navigation-frame velocity and v_b = D v, bit i of aid_mask selects the scalar measurement
+     *   i = 0       z = v_b[0] - odo_j / odo_scale_f, variance r_odo      (the odometer)
+     *   i = 1, 2    z = v_b[i] - 0,                   variance r_nhc      (no sideways, no vertical body velocity)
+     * with the row h_i = [0, D[i,:], -(D [v x])[i,:], 0, 0].  One block runs the selected rows in ascending order from x = 0
+     * (D, v and the rows from the state before the first one) and ends with the feedback of a GPS fix.  It runs at every IMU
+     * sample j > 0 with j % aid_every == 0 on the state that sample's row reports, after a fix of the same sample, before the row
+     * is stored.  odo_j is what ginsim_mc_run writes to out_odo for the same seed and run (the mc block's ref_odo, odo_scale,
+     * odo_stdv; never stored), or in_odo[j runs + r] with given_sensors.  aid_mask != 0 launches loose_aided_kernel. */
+    int32_t  aid_mask;        /* 0 .. 7; 0: no aiding (aid_every, odo_scale_f, r_odo, r_nhc are not read) */
+    int64_t  aid_every;       /* >= 1: a block every aid_every IMU samples (n or more: never) */
+    double   odo_scale_f;     /* the odometer scale factor the FILTER assumes (bit 0); finite, > 0 */
+    double   r_odo;           /* variance of the scaled odometer sample, (m/s)^2 (bit 0); finite, > 0 */
+    double   r_nhc;           /* variance of the two constraint rows, (m/s)^2 (bits 1, 2); finite, > 0 */
 } ginsim_loose_params;
 
 int ginsim_loose_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const ginsim_loose_params* p);

@@ -1,0 +1,280 @@
+"""CPU: InsLoose's odometer / non-holonomic aiding: the C ABI's appended fields and refusals, the build's resource
+report of loose_aided_kernel, the restatement (tests/ins_loose_aided_ref.py) against the statistics of its own covariance and the
+benefit it measures through the GPS outage, the plugin's surface and the Sim's refusal.
+
+Recorded in ins_loose_aided_cases (measured by test_restatement_consistency and test_outage_benefit; 1024 runs drawn from the filter's
+own model, outage profile at 20 Hz with 2 Hz GPS, 'mid-accuracy' IMU, odometer scale 0.99 / stdv 0.1, NHC sigma 0.05 m/s, a block
+at every sample, ref_frame 1): CONSISTENCY_RATIOS for masks 1 and 7 and OUTAGE_TABLE, the horizontal position 1 sigma at the
+outage's start / its end / 5 s later / the profile's end for masks 0, 1 and 7."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import ins_loose_aided_cases as ac
+import ins_loose_aided_ref as aref
+import ins_loose_cases as cs
+import ins_loose_ref as ref
+from conftest import REPO
+
+
+# ------------------------------------------------------------------------------------------------- C ABI
+def test_the_ctypes_mirror_has_the_appended_fields():
+    from ginsim import _lib
+    names = [f[0] for f in _lib.LooseParams._fields_]
+    assert names[-5:] == ['aid_mask', 'aid_every', 'odo_scale_f', 'r_odo', 'r_nhc']
+    assert names[-6] == 'out_end_ned'                                          # appended: nothing existing moved
+    types = dict(_lib.LooseParams._fields_)
+    assert types['aid_mask'] is ctypes.c_int32 and types['aid_every'] is ctypes.c_int64
+    assert all(types[k] is ctypes.c_double for k in ('odo_scale_f', 'r_odo', 'r_nhc'))
+    hdr = open(os.path.join(REPO, 'include', 'ginsim.h')).read()
+    body = re.search(r'typedef struct \{((?:(?!typedef struct).)*?)\}\s*ginsim_loose_params\s*;', hdr, re.S).group(1)
+    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
+    assert re.search(r'int32_t\s+aid_mask;\s*int64_t\s+aid_every;\s*double\s+odo_scale_f;\s*double\s+r_odo;\s*double\s+r_nhc;\s*$', body)
+    import ginsim
+    assert ginsim.lib.ginsim_abi_version() == 9
+    assert hasattr(ginsim, 'aiding_model')
+
+
+def test_aiding_arguments_are_refused_without_a_device():
+    from ginsim import _lib as L
+    m, p = L.McParams(), L.LooseParams()
+    buf = ctypes.create_string_buffer(256)
+    ini, dummy = np.zeros(10), np.zeros(64)
+    stamps = np.array([0, 10, 20], dtype=np.int64)
+    m.n, m.runs, m.fs, m.ref_frame, m.n_ini, m.ini = 30, 4, 100.0, 1, 1, ini.ctypes.data
+    m.given_sensors, m.in_accel, m.in_gyro, m.in_odo = 1, dummy.ctypes.data, dummy.ctypes.data, dummy.ctypes.data
+    p.m, p.gps_stamp, p.in_gps, p.n_list = 3, stamps.ctypes.data, dummy.ctypes.data, 4
+    p.r_diag[:], p.p0[:] = [1.0] * 6, [1.0] * 5
+    p.decay_g[:], p.decay_a[:] = [1.0] * 3, [1.0] * 3
+
+    def name():
+        rc = L.lib.ginsim_loose_kernel_name(ctypes.byref(m), ctypes.byref(p), buf, 256)
+        v = ctypes.c_int32(-1)
+        assert L.lib.ginsim_loose_variant(ctypes.byref(m), ctypes.byref(p), ctypes.byref(v)) == rc      # the same check
+        return rc
+
+    # a zeroed tail is the filter as it was, whatever the other aiding numbers say
+    assert name() == L.OK and buf.value == b'ginsim::loose_kernel<1, true, false, false>'
+    p.aid_every, p.r_odo, p.r_nhc, p.odo_scale_f = -5, -1.0, float('nan'), 0.0
+    assert name() == L.OK and buf.value == b'ginsim::loose_kernel<1, true, false, false>'
+    p.aid_mask, p.aid_every, p.odo_scale_f, p.r_odo, p.r_nhc = 7, 1, 0.99, 0.01, 0.0025
+    assert name() == L.OK and buf.value == b'ginsim::loose_aided_kernel<1, true, false, false>'
+    for mask in (-1, 8, 1 << 20):
+        p.aid_mask = mask
+        assert name() == L.ERR_ARG, mask
+    p.aid_mask = 7
+    for every in (0, -1):
+        p.aid_every = every
+        assert name() == L.ERR_ARG, every
+    p.aid_every = 2 ** 40                                                      # never fires: legal
+    assert name() == L.OK
+    p.aid_every = 1
+    for field, masks_bad, masks_ok in (('r_nhc', (2, 4, 6, 7), (1,)), ('r_odo', (1, 7), (6,)), ('odo_scale_f', (1, 7), (6,))):
+        good = getattr(p, field)
+        for bad in (0.0, -1.0, float('nan'), float('inf')):
+            setattr(p, field, bad)
+            for mask in masks_bad:
+                p.aid_mask = mask
+                assert name() == L.ERR_ARG, (field, bad, mask)
+            for mask in masks_ok:                                              # not read by these rows
+                p.aid_mask = mask
+                assert name() == L.OK, (field, bad, mask)
+        setattr(p, field, good)
+    # bit 0 without the odometer's source
+    p.aid_mask, m.in_odo = 1, None
+    assert name() == L.ERR_ARG
+    p.aid_mask = 6
+    assert name() == L.OK and buf.value == b'ginsim::loose_aided_kernel<1, true, false, false>'
+    # generated form: ref_odo
+    m.given_sensors, m.in_odo = 0, dummy.ctypes.data
+    m.ref_accel, m.ref_gyro, p.ref_gps = dummy.ctypes.data, dummy.ctypes.data, dummy.ctypes.data
+    m.odo_scale = 0.99
+    p.aid_mask = 1
+    assert name() == L.ERR_ARG
+    m.ref_odo = dummy.ctypes.data
+    m.ref_frame = 0
+    assert name() == L.OK and buf.value == b'ginsim::loose_aided_kernel<0, false, false, false>'
+    m.vib_accel.type = 1
+    assert name() == L.OK and buf.value == b'ginsim::loose_aided_kernel<0, false, true, false>'
+
+
+def test_build_reports_no_scratch_for_any_instantiation_of_the_aided_kernel():
+    """build/ins_loose_aided.resources.txt (written by build.py): the 12 instantiations <RF, GIVEN, VIB, PS> of loose_aided_kernel,
+    each with 0 bytes of scratch, at most 256 VGPRs and the static LDS bound tests/test_ins_loose_oracle.py holds loose_kernel to."""
+    from conftest import PKG
+    path = os.path.join(PKG, 'build', 'ins_loose_aided.resources.txt')
+    assert os.path.exists(path), 'run gnss-ins-sim_amd/build.py (it writes %s)' % path
+    kernels, cur = {}, None
+    for line in open(path):
+        k, _, v = line.strip().partition(':')
+        if k == 'Function Name':
+            cur = kernels.setdefault(v.strip(), {})
+        elif cur is not None and v.strip():
+            cur[k.split('[')[0].strip()] = v.strip()
+    aided = {n: r for n, r in kernels.items() if '18loose_aided_kernelI' in n}
+    seen = set(re.search(r'loose_aided_kernelILi(\d)ELb(\d)ELb(\d)ELb(\d)E', n).groups() for n in aided)
+    want = set((rf, g, v, ps) for rf in '01' for g in '01' for v in '01' for ps in '01' if not (g == '1' and v == '1'))
+    assert seen == want, seen ^ want
+    for n, r in aided.items():
+        print(n, {k: r[k] for k in ('VGPRs', 'AGPRs', 'ScratchSize', 'Occupancy', 'LDS Size') if k in r})
+        assert int(r['ScratchSize']) == 0, '%s: %s bytes of scratch per lane' % (n, r['ScratchSize'])
+        assert int(r['Occupancy']) >= 1 and int(r['VGPRs']) <= 256, (n, r)
+        assert int(r['LDS Size']) <= 8192 + 4 * 4, (n, r['LDS Size'])
+
+
+# ------------------------------------------------------------------------------------------------- the restatement
+def test_mask_zero_is_the_unaided_restatement_and_a_block_shrinks_p():
+    ini, truth, stamps = ac.outage_truth(100.0, 1, 10.0, 400)
+    acc_e, gyr_e = cs.imu_errors()
+    rng = np.random.default_rng(3)
+    accel, gyro, _, _ = ref.sample_sensors(rng, 100.0, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, 5)
+    gps = cs.sample_gps(rng, truth, 1, 5)
+    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, 5)
+    from ginsim.ins_loose import filter_model
+    model = filter_model(100.0, acc_e, gyr_e, cs.GPS_ERR)
+    args = (1, 100.0, gyro, accel, ini, model, gps, stamps, truth['gps_visibility'])
+    a, b = ref.run(*args), aref.run(*args, odo=odo, aid=None)
+    for k in cs.PARITY_KEYS:
+        assert np.array_equal(a[k], b[k]), k
+    never = aref.run(*args, odo=odo, aid=ac.aid(7, every=400))
+    for k in cs.PARITY_KEYS:
+        assert np.array_equal(a[k], never[k]), k
+    c = aref.run(*args, odo=odo, aid=ac.aid(7))
+    assert not np.array_equal(a['vel'], c['vel'])
+    assert np.all(c['pdiag_end'][:, 3:9] < a['pdiag_end'][:, 3:9])              # dv and psi are what the rows see
+    d = c['P_end']
+    dd = np.sqrt(c['pdiag_end'])
+    assert np.max(np.abs(d - np.swapaxes(d, 1, 2)) / (dd[:, :, None] * dd[:, None, :])) < 1e-12
+    assert np.all(np.linalg.eigvalsh(d / (dd[:, :, None] * dd[:, None, :])) > -1e-9)
+
+
+def test_rows_follow_the_first_order_model():
+    """h_i is the derivative of v_b,est with respect to the error state: a filter whose velocity and attitude are perturbed by a
+    small (dv, psi) sees v_b change by h.(dv, psi) to first order."""
+    ini, truth, _ = ac.outage_truth(100.0, 1, 10.0, 1500)
+    from ginsim.ins_loose import filter_model
+    acc_e, gyr_e = cs.imu_errors()
+    model = filter_model(100.0, acc_e, gyr_e, cs.GPS_ERR)
+    f = aref.AidedFilter(1, 100.0, ini, 1, model)
+    for j in range(1400):                                                       # into the first turn: a general attitude
+        f.propagate(truth['ref_gyro'][None, j], truth['ref_accel'][None, j])
+    D, v = f.D[0], f.vel[0]
+    vb = D @ v
+    dv, psi = np.array([2e-4, -1e-4, 3e-4]), np.array([1e-5, 2e-5, -3e-5])
+    skew = lambda a: np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0.0]])
+    C_est = (np.eye(3) - skew(psi)) @ D.T
+    vb_est = C_est.T @ (v + dv)
+    H = np.concatenate([D, -D @ skew(v)], axis=1)
+    assert np.linalg.norm(v) > 1.0
+    np.testing.assert_allclose(vb_est - vb, H @ np.concatenate([dv, psi]), rtol=0, atol=1e-8)
+
+
+@pytest.fixture(scope='module')
+def consistency():
+    """The 1024-run case once: accel, gyro and GPS as tests/test_ins_loose_oracle.py::test_restatement_consistency draws them (so
+    mask 0 IS that test's filter), then the odometer; the restatement for masks 0, 1 and 7."""
+    from ginsim.ins_loose import filter_model
+    fs, fs_gps, R = cs.CONSISTENCY_FS, cs.CONSISTENCY_FS_GPS, cs.CONSISTENCY_RUNS
+    ini, truth, stamps = ac.outage_truth(fs, 1, fs_gps)
+    acc_e, gyr_e = cs.imu_errors()
+    rng = np.random.default_rng(cs.CONSISTENCY_SEED)
+    accel, gyro, tba, tbg = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, R)
+    gps = cs.sample_gps(rng, truth, 1, R)
+    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
+    model = filter_model(fs, acc_e, gyr_e, cs.GPS_ERR)
+    samples = ac.outage_samples(truth, stamps, fs, fs_gps)
+    out = {}
+    for mask in (0, 1, 7):
+        o = aref.run(1, fs, gyro, accel, ini, model, gps, stamps, truth['gps_visibility'], odo=odo, aid=ac.aid(mask) if mask else None)
+        e = ref.error_state(1, o['att'][:, -1], o['pos'][:, -1], o['vel'][:, -1], o['wb'][:, -1], o['ab'][:, -1], truth['ref_att'][-1],
+                            truth['ref_pos'][-1], truth['ref_vel'][-1], tbg[:, -1], tba[:, -1])
+        ratio = np.sqrt(np.mean(e * e, axis=0)) / np.sqrt(np.mean(o['pdiag_end'], axis=0))
+        h = [float(np.linalg.norm(np.std(o['pos'][:, j, 0:2] - truth['ref_pos'][j, 0:2], axis=0))) for j in samples]
+        out[mask] = (ratio, np.array(h))
+    return out
+
+
+def test_restatement_consistency(consistency):
+    """RMS end error over sqrt(mean pdiag_end) per state.  Mask 1 (the odometer alone): inside the band the project uses for the
+    unaided filter, [0.7, 1.4].  Mask 7: every ratio <= 1.4 -- overconfidence is the failure.  Its pessimistic side is recorded, not
+    bounded: the profile's truth obeys the constraints exactly (vby = vbz = 0 to 2e-15 m/s), so the 0.05 m/s pseudo-noise of the
+    two constraint rows overstates their error and the filter reports more uncertainty than it has."""
+    for mask in (0, 1, 7):
+        print('mask %d consistency ratios:' % mask, np.array2string(consistency[mask][0], precision=3, separator=', '))
+    np.testing.assert_allclose(consistency[0][0], cs.CONSISTENCY_RATIOS, rtol=0, atol=2e-3)       # mask 0 is the unaided case
+    r1, r7 = consistency[1][0], consistency[7][0]
+    assert np.all(r1 >= 0.7) and np.all(r1 <= 1.4), r1
+    assert np.all(r7 <= 1.4), r7
+    np.testing.assert_allclose(r1, ac.CONSISTENCY_RATIOS[1], rtol=0, atol=2e-3)
+    np.testing.assert_allclose(r7, ac.CONSISTENCY_RATIOS[7], rtol=0, atol=2e-3)
+
+
+def test_outage_benefit(consistency):
+    """On the same draws, the horizontal position 1 sigma at the last sample of the outage with the odometer and the constraints is
+    below half the unaided filter's; the four-instant table of masks 0, 1 and 7 is the one recorded."""
+    for mask in (0, 1, 7):
+        print('mask %d horizontal 1 sigma [m] at outage start / end / +5 s / profile end:' % mask,
+              np.array2string(consistency[mask][1], precision=3, separator=', '))
+    h0, h1, h7 = (consistency[k][1] for k in (0, 1, 7))
+    assert h7[1] < 0.5 * h0[1], (h7[1], h0[1])
+    assert h1[1] < h0[1]
+    for mask in (0, 1, 7):
+        np.testing.assert_allclose(consistency[mask][1], ac.OUTAGE_TABLE[mask], rtol=0, atol=2e-3)
+
+
+# ------------------------------------------------------------------------------------------------- Python surface
+def test_aiding_model_defaults_and_refusals():
+    from ginsim.ins_loose import aiding_model
+    off = aiding_model(None, None)
+    assert off == {'aid_mask': 0, 'aid_every': 0, 'odo_scale_f': 0.0, 'r_odo': 0.0, 'r_nhc': 0.0}
+    assert aiding_model(ac.ODO_ERR, {'odo': False, 'nhc': False, 'every': 3}) == off
+    a = aiding_model(ac.ODO_ERR, {'odo': True, 'nhc': True})
+    assert (a['aid_mask'], a['aid_every'], a['odo_scale_f']) == (7, 1, 0.99)
+    assert a['r_odo'] == (0.1 / 0.99) ** 2 and a['r_nhc'] == 0.05 ** 2
+    b = aiding_model(ac.ODO_ERR, {'odo': True, 'every': 4, 'odo_std': 0.2, 'scale': 1.0})
+    assert (b['aid_mask'], b['aid_every'], b['odo_scale_f'], b['r_odo'], b['r_nhc']) == (1, 4, 1.0, 0.2 ** 2, 0.0)
+    assert aiding_model(None, {'nhc': True, 'nhc_std': 0.1}) == {'aid_mask': 6, 'aid_every': 1, 'odo_scale_f': 0.0, 'r_odo': 0.0, 'r_nhc': 0.1 ** 2}
+    for bad in ({'odo': True, 'every': 0}, {'odo': True, 'every': 1.5}, {'nhc': True, 'nhc_std': 0.0}, {'odo': True, 'odo_std': -1.0},
+                {'odo': True, 'scale': float('nan')}, {'odo': True, 'oddo': 1}):
+        with pytest.raises(ValueError):
+            aiding_model(ac.ODO_ERR, bad)
+    with pytest.raises(ValueError, match='odo_err'):
+        aiding_model(None, {'odo': True})
+
+
+def test_plugin_surface():
+    from demo_algorithms.ins_loose_device import InsLoose
+    plain = InsLoose()
+    assert plain.input == ['fs', 'gyro', 'accel', 'time', 'gps_time', 'gps'] and plain.aid() is None
+    nhc = InsLoose(nhc=True)
+    assert nhc.input == plain.input and nhc.aid()['nhc'] and not nhc.aid()['odo']
+    a = InsLoose(odo=True, nhc=True, odo_every=4, odo_std=0.2, nhc_std=0.1, odo_scale=1.01)
+    assert a.input == plain.input + ['odo']
+    assert a.output == ['pos', 'vel', 'att_euler', 'wb', 'ab'] and (a.batch, a.mc_algo) == (True, 'loose')
+    assert a.aid() == {'odo': True, 'nhc': True, 'every': 4, 'odo_std': 0.2, 'nhc_std': 0.1, 'scale': 1.01}
+    assert InsLoose(odo=True).aid() == {'odo': True, 'nhc': False, 'every': 1, 'odo_std': None, 'nhc_std': 0.05, 'scale': None}
+    for bad in (dict(odo_every=0), dict(odo_every=2.5), dict(odo_std=0.0), dict(odo_std=float('inf')), dict(nhc_std=-0.05),
+                dict(nhc_std=None), dict(odo_scale=0.0), dict(odo_scale=float('nan'))):
+        with pytest.raises((ValueError, TypeError)):
+            InsLoose(odo=True, nhc=True, **bad)
+    with pytest.raises(ValueError, match='logged series'):
+        a.run([100.0, np.zeros((10, 3)), np.zeros((10, 3)), np.arange(10) / 100.0, np.zeros(1), np.zeros((1, 6)), np.zeros(10)])
+
+
+def test_sim_refuses_an_odometer_aided_insloose_without_an_odometer():
+    from gnss_ins_sim.sim import imu_model, ins_sim
+    from demo_algorithms.ins_loose_device import InsLoose
+
+    def roles(algo, odo):
+        sim = ins_sim.Sim([100.0, 10.0, 0.0], cs.OUTAGE_CSV, ref_frame=1,
+                          imu=imu_model.IMU(accuracy='mid-accuracy', axis=6, gps=True, odo=odo), algorithm=algo)
+        return ins_sim._plugin_roles(sim, [getattr(a, 'mc_algo', None) for a in sim.amgr.algo])
+    with pytest.raises(ValueError, match="algorithm 0 needs 'odo' but the IMU model has no odometer"):
+        roles(InsLoose(odo=True, nhc=True), False)
+    with pytest.raises(ValueError, match="algorithm 1 needs 'odo' but the IMU model has no odometer"):
+        roles([InsLoose(), InsLoose(odo=True)], False)
+    assert roles(InsLoose(nhc=True), False).loose == [0]                       # the constraints need no sensor
+    assert roles([InsLoose(), InsLoose(odo=True, nhc=True)], True).loose == [0, 1]

@@ -3,6 +3,7 @@
 
     python tools/bench_ins_loose.py --isa                 # no GPU: fp64 instructions of the kernels' time loops, counted in the ISA
     python tools/bench_ins_loose.py [--runs 65536] [--reps 5] [--out profiles/ins_loose_timing.json]
+    python tools/bench_ins_loose.py --aided [--reps 20] [--out profiles/ins_loose_aided_timing.json]
 
 Workload: 65 536 runs x the 1000 samples of the 90-degree turn at 100 Hz (BASELINE config C2's shape) with GPS at 10 Hz, ref_frame 1,
 'mid-accuracy' IMU; statistics only (nothing but the per-run end records is written) and with everything kept (trajectory, wb, ab).
@@ -15,7 +16,12 @@ instruction) of the TIME LOOP are counted: the span of the kernel's longest back
 of P and the epilogue.  The loop's text also holds the correction (six scalar updates), which one step in ten executes here, so
 the count is an UPPER bound of a step's arithmetic and the time over the floor printed from it a LOWER bound.
 Floor = instructions x runs x steps / (256 CUs x 4 SIMDs x 16 fp64 lanes per clock x 2.4 GHz).  --ops N overrides the count.
-No threshold is set here."""
+No threshold is set here.
+
+--aided: the odometer / non-holonomic aiding of csrc/ins_loose_aided.hip on the same case, statistics only: the
+unaided launch and aid_mask 7 at aid_every 1 and 10 (odometer scale 0.99, stdv 0.1, NHC sigma 0.05 m/s), launched in turn --reps
+times after one warm-up each, so that a drift of the clocks falls on all three alike.  --unaided-only times the first leg alone
+(a library without the aiding fields, named by $GINSIM_LIB, can run it: the comparison against an earlier build)."""
 import argparse
 import json
 import os
@@ -115,9 +121,48 @@ def time_launches(runs, reps):
     return out
 
 
+def time_aided(runs, reps, unaided_only=False):
+    """{leg: {'kernel', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the unaided launch and the two aided ones, interleaved."""
+    import numpy as np
+    import ginsim
+    from ginsim import workloads
+    fs, rf = 100.0, 1
+    ini, truth, _ = workloads.truth_from_profile('turn_90deg', fs, rf, fs_gps=10.0, gps=True)
+    acc, gyr = workloads.imu_grade('mid-accuracy')
+    gps_err = {'stdp': np.array([5.0, 5.0, 7.0]), 'stdv': np.array([0.05, 0.05, 0.05])}
+    odo_err = {'scale': 0.99, 'stdv': 0.1}
+    ctx = ginsim.Context(0)
+    out = {'device': ctx.name(), 'runs': runs, 'samples': int(truth['ref_accel'].shape[0]), 'fixes': int(truth['ref_gps'].shape[0]),
+           'library': os.path.basename(ginsim.LIB_PATH)}
+    legs = [('unaided', {})]
+    if not unaided_only:
+        legs += [('aided_mask7_every1', {'odo_err': odo_err, 'aid': {'odo': True, 'nhc': True, 'every': 1}}),
+                 ('aided_mask7_every10', {'odo_err': odo_err, 'aid': {'odo': True, 'nhc': True, 'every': 10}})]
+    jobs = [(label, ginsim.InsLooseJob(ctx, fs, rf, truth, acc, gyr, gps_err, ini, runs, seed=1, keep_traj=False, **kw)) for label, kw in legs]
+    ms = {label: [] for label, _ in jobs}
+    for _, job in jobs:
+        job.run()                                       # warm-up: code object, LDS attribute
+    for _ in range(reps):
+        for label, job in jobs:
+            ctx.timer_begin()
+            job.launch()
+            ms[label].append(ctx.timer_end())
+    for label, job in jobs:
+        t = ms[label]
+        out[label] = {'kernel': job.kernel_name(), 'ms_median': float(np.median(t)), 'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)),
+                      'ms_all': [float(x) for x in t]}
+        job.release()
+    for label, _ in jobs[1:]:
+        out[label]['over_unaided'] = out[label]['ms_median'] / out['unaided']['ms_median']
+    ctx.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--isa', action='store_true')
+    ap.add_argument('--aided', action='store_true', help='the aided leg: unaided, aid_mask 7 at aid_every 1 and 10')
+    ap.add_argument('--unaided-only', action='store_true', help='with --aided: the unaided launch alone')
     ap.add_argument('--runs', type=int, default=65536)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ops', type=int, default=0, help='fp64 instructions per step, instead of the count from the ISA')
@@ -126,6 +171,14 @@ def main():
     if a.isa:
         for k, (n, f, span) in sorted(isa_counts().items()):
             print('%s: %d fp64 VALU instructions (%d fused multiply-adds) in a time loop of %d lines' % (k, n, f, span))
+        return
+    if a.aided:
+        res = time_aided(a.runs, a.reps, a.unaided_only)
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, 'w') as f:
+                json.dump(res, f, indent=1)
+                f.write('\n')
         return
     res = time_launches(a.runs, a.reps)
     counts = {} if a.ops else isa_counts()
