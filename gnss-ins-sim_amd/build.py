@@ -51,6 +51,9 @@ SOURCES = [
     # the same lane with the odometer / non-holonomic aiding block (ins_loose.hpp): the same flags, its own resource report
     # (tests/test_ins_loose_aided_oracle.py reads it)
     ('ins_loose_aided.hip', MC_FLAGS),
+    # the same lane once more with consistency checkpoints (ins_loose.hpp, CONS): the same flags, its own resource report
+    # (tests/test_ins_loose_cons_oracle.py reads it)
+    ('ins_loose_cons.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),

@@ -514,27 +514,80 @@ int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_para
     return GINSIM_OK;
 }
 
+// The launch of the filter, with checkpoints when cons is not NULL (checked by the caller).  The stamps and the visibility flags of
+// the fixes and the checkpoint samples are copied next to each other into the context's scratch.
+static int loose_launch(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons) {
+    HIP_TRY(hipSetDevice(c->device));
+    int64_t* d_stamp = nullptr;
+    int32_t* d_vis = nullptr;
+    int64_t* d_cons = nullptr;
+    const size_t sb = sizeof(int64_t) * (size_t)p->m, vb = (sizeof(int32_t) * (size_t)p->m + 7) / 8 * 8;
+    const size_t cb = cons ? sizeof(int64_t) * (size_t)cons->cons_m : 0;
+    if (sb + cb > 0) {
+        void* ws = nullptr;
+        HIP_TRY(scratch(c, 3, sb + vb + cb, &ws));
+        if (p->m > 0) {
+            d_stamp = reinterpret_cast<int64_t*>(ws);
+            HIP_TRY(hipMemcpyAsync(d_stamp, p->gps_stamp, sb, hipMemcpyHostToDevice, c->stream));
+            if (p->gps_visible) {
+                d_vis = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + sb);
+                HIP_TRY(hipMemcpyAsync(d_vis, p->gps_visible, sizeof(int32_t) * (size_t)p->m, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        if (cb > 0) {
+            d_cons = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ws) + sb + vb);
+            HIP_TRY(hipMemcpyAsync(d_cons, cons->cons_sample, cb, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    if (cons) HIP_TRY(launch_loose_cons(*mc, *p, *cons, d_stamp, d_vis, d_cons, c->stream, nullptr, 0));
+    else HIP_TRY(launch_loose(*mc, *p, d_stamp, d_vis, c->stream, nullptr, 0));
+    return GINSIM_OK;
+}
+
 int ginsim_loose_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p) {
     REQUIRE(c, "loose_run: NULL argument");
     const int rc = check_loose_params(mc, p);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    // the stamps and the visibility flags of the fixes, copied next to each other into the context's scratch
-    int64_t* d_stamp = nullptr;
-    int32_t* d_vis = nullptr;
-    if (p->m > 0) {
-        void* ws = nullptr;
-        const size_t sb = sizeof(int64_t) * (size_t)p->m;
-        HIP_TRY(scratch(c, 3, sb + sizeof(int32_t) * (size_t)p->m, &ws));
-        d_stamp = reinterpret_cast<int64_t*>(ws);
-        HIP_TRY(hipMemcpyAsync(d_stamp, p->gps_stamp, sb, hipMemcpyHostToDevice, c->stream));
-        if (p->gps_visible) {
-            d_vis = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + sb);
-            HIP_TRY(hipMemcpyAsync(d_vis, p->gps_visible, sizeof(int32_t) * (size_t)p->m, hipMemcpyHostToDevice, c->stream));
-        }
+    return loose_launch(c, mc, p, nullptr);
+}
+
+// the checkpoint block of a launch whose other two blocks passed check_loose_params
+static int check_loose_cons(const ginsim_mc_params* m, const ginsim_loose_params* p, const ginsim_loose_cons_params* q) {
+    REQUIRE(q, "loose_cons_run: NULL argument");
+    REQUIRE(q->cons_m >= 0, "loose_cons_run: cons_m=%lld must be >= 0", (long long)q->cons_m);
+    if (q->cons_m == 0) return GINSIM_OK;
+    REQUIRE(q->cons_m <= m->n, "loose_cons_run: cons_m=%lld checkpoints for n=%lld samples", (long long)q->cons_m, (long long)m->n);
+    REQUIRE(q->cons_sample && q->out_cons && q->cons_work, "loose_cons_run: cons_sample, out_cons or cons_work missing");
+    REQUIRE(m->ref_nav, "loose_cons_run: checkpoints need ref_nav");
+    REQUIRE(!p->out_proc, "loose_cons_run: online process statistics (out_proc) and checkpoints in one launch are refused");
+    for (int64_t k = 0; k < q->cons_m; ++k) {
+        const long long s = (long long)q->cons_sample[k];
+        REQUIRE(s >= 0 && s < (long long)m->n, "loose_cons_run: checkpoint %lld (%lld) is outside [0, %lld)", (long long)k, s, (long long)m->n);
+        REQUIRE(k == 0 || s > (long long)q->cons_sample[k - 1], "loose_cons_run: the checkpoints are not strictly increasing at %lld", (long long)k);
     }
-    HIP_TRY(launch_loose(*mc, *p, d_stamp, d_vis, c->stream, nullptr, 0));
     return GINSIM_OK;
+}
+
+int ginsim_loose_cons_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
+                                  char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_cons_kernel_name: bad arguments");
+    int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    rc = check_loose_cons(mc, p, cons);
+    if (rc) return rc;
+    buf[0] = 0;
+    if (cons->cons_m > 0) (void)launch_loose_cons(*mc, *p, *cons, nullptr, nullptr, nullptr, nullptr, buf, cap);
+    else (void)launch_loose(*mc, *p, nullptr, nullptr, nullptr, buf, cap);
+    return GINSIM_OK;
+}
+
+int ginsim_loose_cons_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons) {
+    REQUIRE(c, "loose_cons_run: NULL argument");
+    int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    rc = check_loose_cons(mc, p, cons);
+    if (rc) return rc;
+    return loose_launch(c, mc, p, cons->cons_m > 0 ? cons : nullptr);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // What the kernels of the loosely coupled GPS/INS filter share (ins_loose.hip: loose_kernel; ins_loose_aided.hip:
 // loose_aided_kernel): the covariance in LDS (Cov), its propagation, the GPS correction, the odometer / non-holonomic aiding block,
-// the feedback both end with, and the time loop (loose_body), whose AID = false form is loose_kernel as it was.  The account of
+// the feedback both end with, and the time loop (loose_body), whose AID = false form is loose_kernel as it was; and, for
+// ins_loose_cons.hip's loose_cons_kernel, the consistency checkpoint (loose_checkpoint) behind the flag CONS.  The account of
 // the register budget that put P into LDS is in ins_loose.hip's header; the aiding block's equations are in ins_loose_aided.hip's.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -287,6 +288,109 @@ __device__ __forceinline__ void loose_aid(Cov& P, Nav& s, Vec3& bg, Vec3& ba, do
     loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
 }
 
+// ---- consistency checkpoints (ins_loose_cons.hip)
+// What loose_cons_kernel passes to the lane next to the two parameter blocks: the DEVICE copy of the checkpoint samples, their
+// number and the wavefronts' partial records [wave][checkpoint][GINSIM_CONS_RECORD].  Not read unless CONS.
+struct ConsArgs {
+    const int64_t* sample = nullptr;
+    int64_t m = 0;
+    double* work = nullptr;
+};
+
+// the sum of v over the 64 lanes, in every lane: a 6-level butterfly whose order does not depend on the data
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int d = 1; d < kLooseBlock; d <<= 1) v += __shfl_xor(v, d, kLooseBlock);
+    return v;
+}
+
+// e^T B^-1 e of the symmetric 3x3 block I of P by its adjugate and determinant; NaN unless the block is positive definite
+// (Sylvester: the three leading minors)
+template <int I>
+__device__ __forceinline__ double block_nees(const Cov& P, const double* e) {
+    const double a = P.get(I, I), b = P.get(I, I + 1), c = P.get(I, I + 2), d = P.get(I + 1, I + 1), f = P.get(I + 1, I + 2), g = P.get(I + 2, I + 2);
+    const double a00 = d * g - f * f, a01 = c * f - b * g, a02 = b * f - c * d;
+    const double a11 = a * g - c * c, a12 = b * c - a * f, a22 = a * d - b * b;
+    const double det = a * a00 + b * a01 + c * a02;
+    const double q = (e[0] * e[0] * a00 + e[1] * e[1] * a11 + e[2] * e[2] * a22) + 2.0 * (e[0] * e[1] * a01 + e[0] * e[2] * a02 + e[1] * e[2] * a12);
+    return (a > 0.0 && a22 > 0.0 && det > 0.0) ? q / det : __builtin_nan("");
+}
+
+// One checkpoint: the lane's error state against the truth row t (att3, pos3, vel3) in the filter's own coordinates
+// (tests/ins_loose_ref.py, error_state), the record's values of this lane, their sums over the wavefront, and lane 0's store of
+// the partial record.  live: the lane carries a run of its own (a tail lane repeats the last run with weight 0).  Every lane of
+// the wavefront arrives here together (the checkpoints are wave-uniform).
+template <int RF>
+__device__ __forceinline__ void loose_checkpoint(const Cov& P, const Nav& s, uniform_ptr t, bool live, double* __restrict__ rec) {
+    double e[9];
+    if (RF == 0) {
+        const Geo g = geo_param(t[3], t[5]);
+        e[0] = (s.pos.x - t[3]) * (g.rm + t[5]);
+        e[1] = (s.pos.y - t[4]) * (g.rn + t[5]) * g.cl;
+        e[2] = -(s.pos.z - t[5]);
+    } else {
+        e[0] = s.pos.x - t[3]; e[1] = s.pos.y - t[4]; e[2] = s.pos.z - t[5];
+    }
+    e[3] = s.vel.x - t[6]; e[4] = s.vel.y - t[7]; e[5] = s.vel.z - t[8];
+    {   // [psi x] = I - C_est C^T, both body -> navigation; psi from its antisymmetric part
+        Att ta;
+        ta.set(t[0], t[1], t[2]);
+        double Ce[3][3], Ct[3][3];
+        body_to_nav(s.att, Ce);
+        body_to_nav(ta, Ct);
+        const double m12 = Ce[1][0] * Ct[2][0] + Ce[1][1] * Ct[2][1] + Ce[1][2] * Ct[2][2];
+        const double m21 = Ce[2][0] * Ct[1][0] + Ce[2][1] * Ct[1][1] + Ce[2][2] * Ct[1][2];
+        const double m20 = Ce[2][0] * Ct[0][0] + Ce[2][1] * Ct[0][1] + Ce[2][2] * Ct[0][2];
+        const double m02 = Ce[0][0] * Ct[2][0] + Ce[0][1] * Ct[2][1] + Ce[0][2] * Ct[2][2];
+        const double m01 = Ce[0][0] * Ct[1][0] + Ce[0][1] * Ct[1][1] + Ce[0][2] * Ct[1][2];
+        const double m10 = Ce[1][0] * Ct[0][0] + Ce[1][1] * Ct[0][1] + Ce[1][2] * Ct[0][2];
+        e[6] = 0.5 * (m12 - m21);
+        e[7] = 0.5 * (m20 - m02);
+        e[8] = 0.5 * (m01 - m10);
+    }
+    phase_fence();
+    const double nees[3] = {block_nees<0>(P, e), block_nees<3>(P, e + 3), block_nees<6>(P, e + 6)};
+    // is the lane included?  every value finite, every P_kk > 0, every block positive definite (block_nees)
+    bool ok = live;
+#pragma unroll
+    for (int k = 0; k < kLooseStates; ++k) {
+        const double pk = P.get(k, k);
+        ok = ok && pk > 0.0 && isfinite(pk);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const double e2 = e[k] * e[k], q = e2 / P.get(k, k);
+        ok = ok && isfinite(e2) && isfinite(q);
+    }
+#pragma unroll
+    for (int b = 0; b < 3; ++b) ok = ok && isfinite(nees[b]);
+    phase_fence();
+    // one value at a time: made again from e and the lane's column of P, summed, stored -- nothing of the record stays in registers
+    const bool first = threadIdx.x == 0;
+    const double cnt = wave_sum(ok ? 1.0 : 0.0);
+    if (first) rec[0] = cnt;
+#pragma unroll
+    for (int k = 0; k < kLooseStates; ++k) {
+        const double v = wave_sum(ok ? P.get(k, k) : 0.0);
+        if (first) rec[1 + k] = v;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const double e2 = e[k] * e[k];
+        const double v = wave_sum(ok ? e2 : 0.0), w = wave_sum(ok ? e2 / P.get(k, k) : 0.0);
+        if (first) { rec[16 + k] = v; rec[25 + k] = w; }
+    }
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        const double v = wave_sum(ok ? nees[b] : 0.0);
+        if (first) rec[34 + b] = v;
+    }
+    if (first) {
+#pragma unroll
+        for (int k = 37; k < GINSIM_CONS_RECORD; ++k) rec[k] = 0.0;
+    }
+}
+
 __device__ __forceinline__ void put3(double* base, int64_t plane, int64_t off, const Vec3& v) {
     if (base) store3(base, plane, off, v);
 }
@@ -294,17 +398,25 @@ __device__ __forceinline__ void put3(double* base, int64_t plane, int64_t off, c
 // The whole lane: RF: ref_frame.  GIVEN: samples from in_accel / in_gyro (/ in_odo), fixes from in_gps.  VIB: the generated sensors
 // carry a vibration term.  PS: online process-error statistics (out_proc).  AID: the aiding block (aid_mask != 0) at every sample
 // j > 0 with j % aid_every == 0, after a fix of the same sample and before the row is stored.  ntab: the kernel's static LDS for
-// the normal tables.
-template <int RF, bool GIVEN, bool VIB, bool PS, bool AID>
+// the normal tables.  CONS: consistency checkpoints (loose_checkpoint) at the samples cq.sample[0 .. cq.m), on the state that row j reports:
+// after a fix and an aiding block of the same sample, before the row is stored.  CONS = false is the lane as it was.
+template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false>
 __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const ginsim_loose_params& b, const int64_t* __restrict__ stamp,
-                                           const int32_t* __restrict__ visible, uint32_t* ntab) {
+                                           const int32_t* __restrict__ visible, uint32_t* ntab, const ConsArgs& cq = ConsArgs{}) {
     NormalTables tab{};
     if (!GIVEN) {
         tab = fill_normal_tables(ntab, threadIdx.x, blockDim.x);
         __syncthreads();
     }
-    const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (lane >= b.n_list) return;
+    int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = lane < b.n_list;
+    if (CONS) {
+        // the cross-lane sums of a checkpoint need all 64 lanes in the loop: a tail lane filters the last run of the list again
+        // (it stores that run's own bits a second time) and enters every sum with weight 0
+        if (!live) lane = b.n_list - 1;
+    } else if (!live) {
+        return;
+    }
     const int64_t r = b.run_list ? b.run_list[lane] : lane;
     const int64_t n = a.n, runs = a.runs, plane = n * runs, m = b.m;
     const double dt = 1.0 / a.fs;
@@ -338,6 +450,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
     // the next aiding block (wave-uniform); a period of n or more never fires
     const int64_t every = AID ? (b.aid_every < n ? b.aid_every : n) : 0;
     int64_t ja = every;
+    int64_t kc = 0;         // the next checkpoint (wave-uniform)
 
     for (int64_t j = 0; j < n; ++j) {
         const int64_t off = j * runs + r;
@@ -376,6 +489,14 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
                 phase_fence();
                 loose_aid<RF>(P, s, bg, ba, odo, mask);
                 phase_fence();
+            }
+        }
+        if (CONS) {
+            if (kc < cq.m && cq.sample[kc] == j) {
+                phase_fence();
+                loose_checkpoint<RF>(P, s, nav_truth + 9 * j, live, cq.work + ((int64_t)blockIdx.x * cq.m + kc) * GINSIM_CONS_RECORD);
+                phase_fence();
+                ++kc;
             }
         }
         if (lb->out_traj) store9(lb->out_traj, plane, off, s);

@@ -41,6 +41,10 @@ int loose_variant(const ginsim_mc_params& p);
 hipError_t launch_loose_aided(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
                               hipStream_t stream, char* name, size_t cap);
 
+// ins_loose_cons.hip: the filter with consistency checkpoints (c.cons_m > 0); samples: the device copy of c.cons_sample
+hipError_t launch_loose_cons(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_cons_params& c, const int64_t* stamp,
+                             const int32_t* visible, const int64_t* samples, hipStream_t stream, char* name, size_t cap);
+
 // aux_sensors.hip
 hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s);
 

@@ -102,6 +102,14 @@ class LooseParams(C.Structure):
                 ('r_nhc', C.c_double)]
 
 
+CONS_RECORD = 43       # GINSIM_CONS_RECORD
+
+
+class LooseConsParams(C.Structure):
+    """ginsim_loose_cons_params: the consistency checkpoints of a filter launch (csrc/ins_loose_cons.hip)."""
+    _fields_ = [('cons_sample', C.c_void_p), ('cons_m', C.c_int64), ('out_cons', C.c_void_p), ('cons_work', C.c_void_p)]
+
+
 class PathgenParams(C.Structure):
     _fields_ = [('ini_pva', C.c_double * 9), ('mobility', C.c_double * 3), ('fs', C.c_double),
                 ('fs_gps', C.c_double), ('ref_frame', C.c_int32), ('enable_gps', C.c_int32),
@@ -172,6 +180,9 @@ _SIGS = {
     'ginsim_loose_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams)]),
     'ginsim_loose_variant': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(C.c_int32)]),
     'ginsim_loose_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.c_char_p, C.c_size_t]),
+    'ginsim_loose_cons_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseConsParams)]),
+    'ginsim_loose_cons_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseConsParams), C.c_char_p,
+                                                C.c_size_t]),
     'ginsim_end_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     'ginsim_end_stats_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     'ginsim_end_stats_finish': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Stats)]),

@@ -579,6 +579,61 @@ class CurveResult(object):
         return CurveResult(out)
 
 
+class ConsistencyResult(object):
+    """The consistency record of a filter launch at each of m checkpoints (ginsim_loose_cons_run, GINSIM_CONS_RECORD doubles each):
+    across the runs included, count (m,) and the MEANS pbar (m, 15) of P_kk, e2 (m, 9) of the squared navigation-state errors,
+    nes (m, 9) of e_k^2 / P_kk and nees (m, 3) of the position / velocity / attitude block's e^T P_bb^-1 e (3 when consistent).
+    States in the filter's order and units: dr [m], dv [m/s], psi [rad], dbg [rad/s], dba [m/s^2].  The records themselves are
+    sums, so the records of disjoint sets of runs over the same checkpoints merge by addition."""
+
+    WIDTH = 43          # GINSIM_CONS_RECORD: count, 15, 9, 9, 3 and six reserved zeros
+
+    def __init__(self, records):
+        self.records = np.array(records, dtype=np.float64).reshape(-1, self.WIDTH)
+        self.count = self.records[:, 0].copy()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            mean = self.records / self.count[:, None]
+        self.pbar, self.e2, self.nes, self.nees = mean[:, 1:16], mean[:, 16:25], mean[:, 25:34], mean[:, 34:37]
+
+    @property
+    def m(self):
+        return self.count.shape[0]
+
+    @staticmethod
+    def zero(m):
+        """The record of a rank that holds no runs (neutral element of the merge)."""
+        return ConsistencyResult(np.zeros((int(m), ConsistencyResult.WIDTH)))
+
+    @property
+    def sigma(self):    # the filter's predicted 1 sigma of the 15 states
+        return np.sqrt(self.pbar)
+
+    @property
+    def rms(self):      # the across-run RMS error of the 9 navigation states
+        return np.sqrt(self.e2)
+
+    @property
+    def ratio(self):    # 1 for a consistent filter; above 1: overconfident
+        return self.rms / self.sigma[:, :9]
+
+    def pack(self):
+        """(m, 43) sums as the library lays them out."""
+        return self.records.copy()
+
+    @staticmethod
+    def unpack(v):
+        return ConsistencyResult(v)
+
+    @staticmethod
+    def merge(packed):
+        """Merge packed records (one (m, 43) array per block of runs, device or rank): their sum, taken in that order."""
+        parts = [np.asarray(p, dtype=np.float64).reshape(-1, ConsistencyResult.WIDTH) for p in packed]
+        out = np.zeros_like(parts[0])
+        for p in parts:
+            out = out + p
+        return ConsistencyResult(out)
+
+
 def starts_on_truth(table, nav0, ref_frame=0):
     """Do all the initial states of `table` ([n_ini][10]: pos3 LLA, body velocity3, yaw / pitch / roll, g) lie ON the truth's first
     sample `nav0` (att3, pos3, vel3)?  Then the error at sample 0 is zero for every run, the launch-wide shift of the online process

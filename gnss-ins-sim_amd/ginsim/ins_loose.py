@@ -4,7 +4,9 @@ ginsim_loose_run).  One launch: every lane makes its own IMU samples and GPS fix
 MonteCarloJob and AuxSensorJob would store), mechanises them with the free-integration step on bias-corrected samples and runs a
 15-state closed-loop error-state filter next to it.  tests/ins_loose_ref.py restates the arithmetic in NumPy.
 With aid=... the filter also uses the odometer and the non-holonomic constraints of a land vehicle (csrc/ins_loose_aided.hip,
-aiding_model; restated by tests/ins_loose_aided_ref.py).
+aiding_model; restated by tests/ins_loose_aided_ref.py).  With cons_samples=... the launch also reduces, across its runs, the
+filter's covariance and its actual error at those samples (csrc/ins_loose_cons.hip, consistency(); restated by
+tests/ins_loose_cons_ref.py).
 """
 import ctypes as C
 
@@ -12,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check, dptr
-from .engine import DeviceView, StatsResult, CurveResult, ini_table, sensor_model, vibration
+from .engine import DeviceView, StatsResult, CurveResult, ConsistencyResult, ini_table, sensor_model, vibration
 
 P0_FLOOR = (1e-3, 1e-3, 1e-5, 1e-7, 1e-5)      # m, m/s, rad, rad/s, m/s^2
 
@@ -119,6 +121,8 @@ class InsLooseJob(object):
     proc_first: None, or the first sample of the online process-error window.  end_pos_ned / proc_ned (ref_frame 0): position
     errors of the end-point record / of the process statistics in local NED metres; end_ned: a second end-point record in NED metres.
     placed: as MonteCarloJob (kept planes of Context.PLACED_MIN_JOB bytes or more come from the placed arena).
+    cons_samples: None, or the IMU sample indices (any order, repeats allowed) at which the launch reduces the consistency record
+    across its runs (consistency()): the filter's P against its error in its own coordinates.  Not together with proc_first.
     """
 
     precision = 'f64'
@@ -126,7 +130,8 @@ class InsLooseJob(object):
 
     def __init__(self, ctx, fs, ref_frame, truth, accel_err, gyro_err, gps_err, ini, runs, seed=0, run_offset=0, ini_first=0,
                  earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
-                 end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None):
+                 end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None,
+                 cons_samples=None):
         self.ctx = ctx
         self.n, self.runs = int(truth['ref_accel'].shape[0]), int(runs)
         if self.runs < 1:
@@ -230,11 +235,30 @@ class InsLooseJob(object):
             self._bufs['ab'] = DeviceView(self._bufs['series'], 12 * plane, 3 * plane)
             p.out_traj, p.out_wb, p.out_ab = self._bufs['traj_loose'].ptr, self._bufs['wb'].ptr, self._bufs['ab'].ptr
         p.n_list = R
+        self.cons = None
+        if cons_samples is not None:
+            if proc_first is not None:
+                raise ValueError('cons_samples: online process statistics (proc_first) and checkpoints in one launch are refused')
+            asked = np.asarray(cons_samples, dtype=np.int64).reshape(-1)
+            if asked.size == 0 or asked.min() < 0 or asked.max() >= self.n:
+                raise ValueError('cons_samples must be sample indices in [0, %d), at least one' % self.n)
+            # the kernel walks a strictly increasing list; _cons_back maps its records to the caller's order
+            self._cons_samples, self._cons_back = np.unique(asked, return_inverse=True)
+            self._cons_samples = np.ascontiguousarray(self._cons_samples, dtype=np.int64)
+            mu, waves = self._cons_samples.size, (R + 63) // 64
+            self._bufs['cons'] = ctx.malloc((1 + waves) * mu * _lib.CONS_RECORD * 8)
+            m.ref_nav = self._nav()
+            c = self.cons = _lib.LooseConsParams()
+            c.cons_sample, c.cons_m = self._cons_samples.ctypes.data, mu
+            c.out_cons, c.cons_work = self._bufs['cons'].ptr, self._bufs['cons'].at(mu * _lib.CONS_RECORD * 8)
 
     # ------------------------------------------------------------------ launches
     def kernel_name(self):
         buf = C.create_string_buffer(256)
-        check(lib.ginsim_loose_kernel_name(C.byref(self.mc), C.byref(self.params), buf, 256))
+        if self.cons is not None:
+            check(lib.ginsim_loose_cons_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.cons), buf, 256))
+        else:
+            check(lib.ginsim_loose_kernel_name(C.byref(self.mc), C.byref(self.params), buf, 256))
         return buf.value.decode()
 
     def variant(self):
@@ -243,7 +267,8 @@ class InsLooseJob(object):
         return v.value
 
     def launch(self, ids=None):
-        """Enqueue the kernel (asynchronous).  ids: launch these runs only (lane i filters run ids[i]); the others keep what they hold."""
+        """Enqueue the kernel (asynchronous).  ids: launch these runs only (lane i filters run ids[i]); the others keep what they hold,
+        and the consistency record is over the listed runs."""
         p = self.params
         if ids is None:
             p.run_list, p.n_list = None, self.runs
@@ -251,7 +276,10 @@ class InsLooseJob(object):
             ids = np.ascontiguousarray(ids, dtype=np.int64)
             check(lib.ginsim_memcpy_h2d(self.ctx.handle, self._list, ids.ctypes.data, ids.nbytes))
             p.run_list, p.n_list = self._list, ids.size
-        check(self.ctx.retry_oom(lambda: lib.ginsim_loose_run(self.ctx.handle, C.byref(self.mc), C.byref(p))))
+        if self.cons is not None:
+            check(self.ctx.retry_oom(lambda: lib.ginsim_loose_cons_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.cons))))
+        else:
+            check(self.ctx.retry_oom(lambda: lib.ginsim_loose_run(self.ctx.handle, C.byref(self.mc), C.byref(p))))
 
     def run(self, ids=None):
         self.launch(ids)
@@ -305,6 +333,15 @@ class InsLooseJob(object):
     def final_sigmas(self):
         """(runs, 15): the 1 sigma of every state at the last sample, sqrt(final_pdiag())."""
         return np.sqrt(self.final_pdiag())
+
+    def consistency(self):
+        """ConsistencyResult of the last launch at cons_samples, in the caller's order: across the runs launched, the filter's
+        mean P_kk next to the mean squared error of the navigation states in the filter's own coordinates, and the normalised
+        errors (per state and per 3x3 block)."""
+        if self.cons is None:
+            raise ValueError('the consistency record was not requested (cons_samples=...)')
+        rec = self.ctx.download(self._bufs['cons'], (self._cons_samples.size, _lib.CONS_RECORD))
+        return ConsistencyResult(rec[self._cons_back])
 
     def _gather(self, ptr, ncomp, run_ids):
         ids = np.ascontiguousarray(np.asarray(run_ids, dtype=np.int64).reshape(-1))

@@ -109,7 +109,7 @@ class _McResults(object):
     """
 
     def __init__(self, jobs, kept, names, kinds, first_run, runs_local, total_runs, group, device, make_ps_job=None, ctx=None,
-                 make_kept_job=None, block_runs=0, ned_from_traj=False):
+                 make_kept_job=None, block_runs=0, ned_from_traj=False, make_cons_job=None):
         self.jobs, self.kept, self.algo_names, self.kinds = jobs, kept, names, kinds
         # does the NED end-point record have to be recomputed from trajectories?  Decided by Sim from the CONFIGURATION
         # (identical on every rank), never from a rank's own jobs: a rank without runs has none, and the ranks must enter the
@@ -119,6 +119,7 @@ class _McResults(object):
         self._group, self._device, self._stats = group, device, {}
         self._make_ps_job, self._ctx = make_ps_job, ctx
         self._make_kept_job, self._block_runs = make_kept_job, int(block_runs)
+        self._make_cons_job = make_cons_job
         self.exchange = None                # which exchange merged the records: 'abi', 'torch (...)', None = one process
 
     fused_names = None      # set by Sim when inclinometer plugins are present: only these produce 'pos' and 'vel'
@@ -228,6 +229,25 @@ class _McResults(object):
             else:
                 part = ginsim.CurveResult.merge([b.error_curve(kind, samples, pos_ned=ned).pack() for b in self._blocks(idx)])
             self._stats[key] = distributed.allgather_curve(part, self._group, self._device)
+        return self._stats[key]
+
+    def consistency(self, name, samples):
+        """ginsim.ConsistencyResult of the InsLoose `name` over ALL runs of the Sim at `samples` (int64 sample indices): one more
+        statistics-only launch of the filter with checkpoints (the counter RNG reproduces the same runs; nothing kept is needed),
+        merged over ranks; every rank takes the same branches."""
+        key = ('cons', name, samples.tobytes())
+        if key not in self._stats:
+            import ginsim
+            from ginsim import distributed
+            idx = self.algo_names.index(name)
+            if self.jobs[idx] is None:      # a rank without runs: the empty record, into the same collective
+                part = ginsim.ConsistencyResult.zero(samples.size)
+            else:
+                job = self._make_cons_job(idx, samples)
+                job.run()
+                part = job.consistency()
+                job.release()
+            self._stats[key] = distributed.allgather_consistency(part, self._group, self._device)
         return self._stats[key]
 
     def run_of_key(self, key):
@@ -432,7 +452,8 @@ class _Jobs(object):
     def loose(self, algo, runs, keep, off=0, **kw):
         """An InsLooseJob of `runs` runs from run `off` of this rank for the plugin `algo`: the IMU samples and the fixes are made
         inside the kernel, as the fused job and AuxSensorJob make them for the same seed and run ids.  The SENSORS are the Sim's;
-        the filter is tuned to the plugin's IMU model where it has one (else the Sim's).  kw: proc_first / proc_ned / end_ned."""
+        the filter is tuned to the plugin's IMU model where it has one (else the Sim's).  kw: proc_first / proc_ned / end_ned /
+        cons_samples, and ini_first where a launch of run() is made again."""
         from ginsim import workloads
         from ginsim.ins_loose import InsLooseJob, filter_model
         sim, d = self.sim, self.sim.dmgr
@@ -440,7 +461,7 @@ class _Jobs(object):
         truth = dict(self.truth, ref_gps=d.ref_gps.data, gps_time=d.gps_time.data, gps_visibility=d.gps_visibility.data)
         ini = algo.ini if algo.ini is not None else workloads.parse_motion(sim.data_src)[0]
         return InsLooseJob(self.ctx, sim.fs[0], sim.ref_frame, truth, sim.imu.accel_err, sim.imu.gyro_err, sim.imu.gps_err, ini, runs,
-                           seed=self.seed, run_offset=self.first + off, ini_first=algo.run_times + self.first + off,
+                           seed=self.seed, run_offset=self.first + off, ini_first=kw.pop('ini_first', algo.run_times + self.first + off),
                            earth_rot=algo.earth_rot, keep_traj=keep, placed=sim.placed,
                            model=filter_model(sim.fs[0], tuned.accel_err, tuned.gyro_err, tuned.gps_err, algo.q_scale, algo.p0),
                            **self._aiding(algo), **self.vib, **kw)
@@ -997,12 +1018,17 @@ class Sim(object):
                 return jobs.loose(owners[idx], runs_, True, off=off)
             # placed=None is kept from the parent on purpose and not yet judged: these blocks do not follow Sim(placed=)
             return jobs.fused(owners[idx], (kinds[order[idx]],), runs_, off=off, keep_traj=True, placed=None)
+
+        def make_cons_job(idx, samples):        # the filter over this rank's runs again, nothing kept, checkpoints at `samples`;
+            # the initial states of the launch run() made (the plugin's call count has moved on since)
+            first = next(j for i, j, _ in loose_jobs if i == order[idx]).mc.ini_first
+            return jobs.loose(owners[idx], plan.count, False, cons_samples=samples, ini_first=first)
         names = [self.amgr.get_algo_name(i) for i in order]
         self.mc = _McResults([run.stats.get(i) for i in plan.fused] + [j for _, j, _ in loose_jobs] + [g.job for _, g in incl_groups],
                              [run.kept.get(i) for i in plan.fused] + [k for _, _, k in loose_jobs] + [g.kept for _, g in incl_groups], names,
                              [kinds[i] for i in order], plan.first, plan.count, self.sim_count, group,
                              xdev, make_ps_job, ctx=jobs.ctx, make_kept_job=make_kept_job, block_runs=plan.block_runs,
-                             ned_from_traj=not plan.end_ned)
+                             ned_from_traj=not plan.end_ned, make_cons_job=make_cons_job)
         self.mc.fused_names = names[:len(plan.fused)]
         self.mc.loose_names = names[len(plan.fused):len(plan.fused) + n_loose]
         self.mc.nav_names = names[:len(plan.fused) + n_loose]       # the plugins whose output holds 'pos' and 'vel'
@@ -1216,6 +1242,48 @@ class Sim(object):
                 for stat, arr in (('max', c.maxabs), ('avg', c.mean), ('std', c.std)):
                     res[stat][a] = sim_data.convert_unit(np.ascontiguousarray(arr[:, slices[nm]]), units, out_units)
             out[nm] = res
+        return out
+
+    def consistency_curve(self, *, every=None, samples=None):
+        """Is the covariance of the Sim's InsLoose filters honest along the run?  At each instant, across all runs: the filter's
+        predicted 1 sigma next to the RMS of its actual error, state by state, and the normalised error of the position, velocity
+        and attitude block -- before, during and after a GPS outage.  For every InsLoose of the Sim (aided ones included) the
+        filter is launched once more over the Sim's runs, statistics only, with the same seed and run ids; the sums are taken
+        inside the launch, so statistics-only Sims are served and no kept plane is read.
+          every     seconds between the instants (from the first sample); None and samples=None: every sample
+          samples   or the sample indices themselves (any order, repeats allowed)
+        Returns {'time': (m,), 'states': ['dr_x', ..., 'dba_z'], algorithm name: {'count': (m,) runs included, 'sigma': (m, 15)
+        sqrt(mean P_kk), 'rms': (m, 9) RMS error of dr, dv, psi, 'ratio': (m, 9) rms / sigma (1: consistent; above: overconfident),
+        'nees': (m, 3) mean e^T P_bb^-1 e of the three blocks (3: consistent)}}.
+        Units are the FILTER's, not the output units of ``results``: dr in m (NED metres in ref_frame 0), dv in m/s, psi in rad
+        (a small rotation in the navigation frame, not Euler angles), dbg in rad/s, dba in m/s^2.  A run whose state or covariance
+        is not finite, or whose P is not positive definite on a block, is left out and missing from 'count'."""
+        if not self.sim_complete:
+            print("Call Sim.run() to run the simulaltion first.")
+            return None
+        mc = self.mc
+        names = list(getattr(mc, 'loose_names', ())) if mc is not None and not self.data_from_files else []
+        if not names:
+            raise ValueError('consistency_curve: the curves come from the loosely coupled GPS/INS filter plugins (InsLoose), and '
+                             'this Sim has none -- free integration, inclinometer, MagCal and host plugins carry no covariance')
+        t = np.asarray(self.dmgr.time.data)
+        n = t.shape[0]
+        if every is not None and samples is not None:
+            raise ValueError('consistency_curve: give every (seconds) or samples (indices), not both')
+        if every is not None:
+            step = int(round(float(every) * float(self.fs[0])))
+            if step < 1:
+                raise ValueError('consistency_curve: every=%r s is shorter than one sample at %g Hz' % (every, self.fs[0]))
+            samples = np.arange(0, n, step, dtype=np.int64)
+        if samples is None:
+            samples = np.arange(n, dtype=np.int64)
+        samples = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
+        if samples.size == 0 or samples.min() < 0 or samples.max() >= n:
+            raise ValueError('consistency_curve: samples must be indices in [0, %d), at least one' % n)
+        out = {'time': t[samples], 'states': ['%s_%s' % (b, a) for b in ('dr', 'dv', 'psi', 'dbg', 'dba') for a in 'xyz']}
+        for a in names:
+            c = mc.consistency(a, samples)
+            out[a] = {'count': c.count, 'sigma': c.sigma, 'rms': c.rms, 'ratio': c.ratio, 'nees': c.nees}
         return out
 
     def plot(self, what_to_plot, sim_idx=None, opt=None, extra_opt=''):

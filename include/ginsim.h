@@ -396,6 +396,39 @@ int ginsim_loose_variant(const ginsim_mc_params* mc, const ginsim_loose_params* 
 /* the NAME of the kernel ginsim_loose_run launches, as rocprofv3 reports it (e.g. "ginsim::loose_kernel<1, false, false, false>") */
 int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, char* buf, size_t cap);
 
+/* ---- consistency checkpoints of the filter (csrc/ins_loose_cons.hip): its predicted covariance and its actual
+ *      error, reduced ACROSS the runs of a launch at chosen samples, inside the launch, where P lives.  Added without a change of
+ *      GINSIM_ABI_VERSION and as a block of its own: ginsim_loose_params and ginsim_loose_run are exactly what they were.
+ *      At IMU sample cons_sample[c], on the state that sample's row reports (after a fix and an aiding block of the same sample,
+ *      before the row is stored), every lane forms the error state e = estimate - truth in the filter's own coordinates against
+ *      row cons_sample[c] of the mc block's ref_nav (dr: NED metres through the truth's Rm + h and (Rn + h) cos(lat) in
+ *      ref_frame 0, the plain difference in ref_frame 1; dv; psi: the antisymmetric part of I - C_est C^T), and the launch sums
+ *      over its runs into out_cons[c][GINSIM_CONS_RECORD]:
+ *        [0]       the number of runs included
+ *        [1..15]   P_kk of the 15 states
+ *        [16..24]  e_k^2 of the 9 navigation states (dr, dv, psi)
+ *        [25..33]  e_k^2 / P_kk of the same
+ *        [34..36]  e_b^T P_bb^-1 e_b of the position, velocity and attitude block (3 each for a consistent filter)
+ *        [37..42]  reserved, written as 0
+ *      A run with a non-finite value among these, a P_kk <= 0 or a 3x3 block that is not positive definite is left out of every
+ *      sum and of the count.  The sums are taken in a fixed order (the lanes of a wavefront by a butterfly, the wavefronts
+ *      ascending, no atomics): the record is a function of the inputs and the run list, bit for bit from launch to launch. */
+#define GINSIM_CONS_RECORD 43
+typedef struct {
+    const int64_t* cons_sample; /* HOST [cons_m]: IMU sample indices, strictly increasing, in [0, n) */
+    int64_t  cons_m;          /* checkpoints; 0: none -- the call is ginsim_loose_run (the pointers are not read) */
+    double*  out_cons;        /* device [cons_m][GINSIM_CONS_RECORD] */
+    double*  cons_work;       /* device [(n_list + 63) / 64][cons_m][GINSIM_CONS_RECORD]: the wavefronts' partial sums */
+} ginsim_loose_cons_params;
+
+/* ginsim_loose_run with checkpoints: launches loose_cons_kernel, then the kernel that adds the wavefronts' partial sums.  Refused:
+ * cons_m < 0; cons_m > 0 with cons_sample, out_cons, cons_work or the mc block's ref_nav NULL, with samples outside [0, n) or
+ * not strictly increasing, or together with p->out_proc (online process statistics and checkpoints in one launch). */
+int ginsim_loose_cons_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons);
+/* the NAME of the kernel it launches (e.g. "ginsim::loose_cons_kernel<1, false, false, false>" = RF, GIVEN, VIB, AID) */
+int ginsim_loose_cons_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
+                                  char* buf, size_t cap);
+
 /* ---- auxiliary sensors of a Monte-Carlo batch: pathgen.gps_gen (pathgen.py:596-625) and pathgen.mag_gen (:643-661).
  *      FreeIntegration does not consume them, so they are generated only when they are to be kept. */
 typedef struct {

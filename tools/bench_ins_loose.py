@@ -4,6 +4,7 @@
     python tools/bench_ins_loose.py --isa                 # no GPU: fp64 instructions of the kernels' time loops, counted in the ISA
     python tools/bench_ins_loose.py [--runs 65536] [--reps 5] [--out profiles/ins_loose_timing.json]
     python tools/bench_ins_loose.py --aided [--reps 20] [--out profiles/ins_loose_aided_timing.json]
+    python tools/bench_ins_loose.py --cons [--reps 20] [--out profiles/ins_loose_cons_timing.json]
 
 Workload: 65 536 runs x the 1000 samples of the 90-degree turn at 100 Hz (BASELINE config C2's shape) with GPS at 10 Hz, ref_frame 1,
 'mid-accuracy' IMU; statistics only (nothing but the per-run end records is written) and with everything kept (trajectory, wb, ab).
@@ -21,7 +22,12 @@ No threshold is set here.
 --aided: the odometer / non-holonomic aiding of csrc/ins_loose_aided.hip on the same case, statistics only: the
 unaided launch and aid_mask 7 at aid_every 1 and 10 (odometer scale 0.99, stdv 0.1, NHC sigma 0.05 m/s), launched in turn --reps
 times after one warm-up each, so that a drift of the clocks falls on all three alike.  --unaided-only times the first leg alone
-(a library without the aiding fields, named by $GINSIM_LIB, can run it: the comparison against an earlier build)."""
+(a library without the aiding fields, named by $GINSIM_LIB, can run it: the comparison against an earlier build).
+
+--cons: the consistency checkpoints of csrc/ins_loose_cons.hip on the same case, statistics only: the unaided launch
+without checkpoints, with one every 100 samples and with one at every sample, launched in turn --reps times after one warm-up each.
+The times with checkpoints include the kernel that adds the wavefronts' partial records.  A checkpoint's cost is printed in steps:
+(time with m checkpoints - time without) / m over the time of one step of the launch without."""
 import argparse
 import json
 import os
@@ -158,11 +164,49 @@ def time_aided(runs, reps, unaided_only=False):
     return out
 
 
+def time_cons(runs, reps):
+    """{leg: {'kernel', 'checkpoints', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the unaided launch without checkpoints, with one
+    every 100 samples and with one at every sample, interleaved; and what one checkpoint costs, in steps."""
+    import numpy as np
+    import ginsim
+    from ginsim import workloads
+    fs, rf = 100.0, 1
+    ini, truth, _ = workloads.truth_from_profile('turn_90deg', fs, rf, fs_gps=10.0, gps=True)
+    acc, gyr = workloads.imu_grade('mid-accuracy')
+    gps_err = {'stdp': np.array([5.0, 5.0, 7.0]), 'stdv': np.array([0.05, 0.05, 0.05])}
+    n = int(truth['ref_accel'].shape[0])
+    ctx = ginsim.Context(0)
+    out = {'device': ctx.name(), 'runs': runs, 'samples': n, 'fixes': int(truth['ref_gps'].shape[0]), 'library': os.path.basename(ginsim.LIB_PATH)}
+    legs = [('no_checkpoints', None), ('every_100_samples', np.arange(0, n, 100)), ('every_sample', np.arange(n))]
+    jobs = [(label, ginsim.InsLooseJob(ctx, fs, rf, truth, acc, gyr, gps_err, ini, runs, seed=1, keep_traj=False, cons_samples=c)) for label, c in legs]
+    ms = {label: [] for label, _ in jobs}
+    for _, job in jobs:
+        job.run()                                       # warm-up: code object, LDS attribute
+    for _ in range(reps):
+        for label, job in jobs:
+            ctx.timer_begin()
+            job.launch()
+            ms[label].append(ctx.timer_end())
+    for (label, job), (_, c) in zip(jobs, legs):
+        t = ms[label]
+        out[label] = {'kernel': job.kernel_name(), 'checkpoints': 0 if c is None else int(c.size), 'ms_median': float(np.median(t)),
+                      'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)), 'ms_all': [float(x) for x in t]}
+        job.release()
+    step_ms = out['no_checkpoints']['ms_median'] / (n - 1)
+    for label, _ in jobs[1:]:
+        r = out[label]
+        r['over_no_checkpoints'] = r['ms_median'] / out['no_checkpoints']['ms_median']
+        r['checkpoint_cost_in_steps'] = (r['ms_median'] - out['no_checkpoints']['ms_median']) / r['checkpoints'] / step_ms
+    ctx.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--isa', action='store_true')
     ap.add_argument('--aided', action='store_true', help='the aided leg: unaided, aid_mask 7 at aid_every 1 and 10')
     ap.add_argument('--unaided-only', action='store_true', help='with --aided: the unaided launch alone')
+    ap.add_argument('--cons', action='store_true', help='the checkpoint leg: none, one every 100 samples, one at every sample')
     ap.add_argument('--runs', type=int, default=65536)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ops', type=int, default=0, help='fp64 instructions per step, instead of the count from the ISA')
@@ -172,8 +216,8 @@ def main():
         for k, (n, f, span) in sorted(isa_counts().items()):
             print('%s: %d fp64 VALU instructions (%d fused multiply-adds) in a time loop of %d lines' % (k, n, f, span))
         return
-    if a.aided:
-        res = time_aided(a.runs, a.reps, a.unaided_only)
+    if a.aided or a.cons:
+        res = time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
         print(json.dumps(res))
         if a.out:
             with open(a.out, 'w') as f:
