@@ -100,6 +100,27 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// The selected runs of a device-resident series as [nsel][n][ncomp] doubles on the host: the body of the three ginsim_gather_*
+// entry points.  launch(ids, out): the gather kernel of the series' layout and precision, on device copies.
+template <class Launch>
+static int gather_run(const char* who, ginsim_ctx* c, const void* series, int32_t ncomp, int64_t n, int64_t runs, const int64_t* run_ids,
+                      int32_t nsel, double* host_out, Launch launch) {
+    REQUIRE(c && series && run_ids && host_out, "%s: NULL argument", who);
+    REQUIRE(ncomp >= 1 && n >= 1 && runs >= 1 && nsel >= 1, "%s: bad sizes", who);
+    for (int i = 0; i < nsel; ++i)
+        REQUIRE(run_ids[i] >= 0 && run_ids[i] < runs, "%s: run id %lld out of range", who, (long long)run_ids[i]);
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf ids, out;
+    const size_t out_bytes = sizeof(double) * (size_t)nsel * n * ncomp;
+    HIP_TRY(ids.alloc(sizeof(int64_t) * nsel));
+    HIP_TRY(out.alloc(out_bytes));
+    HIP_TRY(hipMemcpyAsync(ids.p, run_ids, sizeof(int64_t) * nsel, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch(ids.as<int64_t>(), out.as<double>()));
+    HIP_TRY(hipMemcpyAsync(host_out, out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
 extern "C" {
 
 int ginsim_abi_version(void) { return GINSIM_ABI_VERSION; }
@@ -319,13 +340,109 @@ static int check_sensor(const ginsim_sensor_model& m, const char* what) {
     return GINSIM_OK;
 }
 
+// The checks that the parameter blocks of several entry points share.  who: the prefix of the messages.
+static int check_sizes(const char* who, const ginsim_mc_params* m) {
+    REQUIRE(m->n >= 1 && m->runs >= 1, "%s: n=%lld runs=%lld must be >= 1", who, (long long)m->n, (long long)m->runs);
+    REQUIRE(m->n <= 0xFFFFFFFFll, "%s: n exceeds the 32-bit sample counter of the RNG", who);
+    REQUIRE(m->runs <= (int64_t)0x7FFFFFFF * 64, "%s: too many runs for one launch", who);
+    return GINSIM_OK;
+}
+
+// Where the samples of the inclinometer and the filter kernel come from: the given series, or the truth and the two sensor models.
+// gps_in / gps_ref: the fixes of that source are there (true where the kernel takes none).
+static int check_sensor_source(const char* who, const ginsim_mc_params* m, bool gps_in, bool gps_ref) {
+    if (m->given_sensors) {
+        REQUIRE(m->in_accel && m->in_gyro, "%s: given_sensors needs in_accel and in_gyro", who);
+        REQUIRE(gps_in, "%s: given_sensors needs in_gps", who);
+        return GINSIM_OK;
+    }
+    REQUIRE(m->ref_gyro && m->ref_accel, "%s: ref_accel/ref_gyro missing", who);
+    REQUIRE(gps_ref, "%s: ref_gps missing", who);
+    const int rc = check_sensor(m->accel, "accel");
+    return rc ? rc : check_sensor(m->gyro, "gyro");
+}
+
+// the vibration terms of the kernels without the 'psd' form; noun: "inclinometer" / "filter"
+static int check_vibration_no_psd(const char* who, const ginsim_mc_params* m, const char* noun) {
+    for (const ginsim_vibration* v : {&m->vib_accel, &m->vib_gyro}) {
+        if (v->type == GINSIM_VIB_NONE) continue;
+        REQUIRE(v->type == GINSIM_VIB_RANDOM || v->type == GINSIM_VIB_SINUSOIDAL,
+                "%s: the %s kernel takes the 'random' and 'sinusoidal' vibration only", who, noun);
+        REQUIRE(!m->given_sensors, "%s: a vibration term cannot be added to given sensors", who);
+        REQUIRE(std::isfinite(v->amp[0]) && std::isfinite(v->amp[1]) && std::isfinite(v->amp[2]) && std::isfinite(v->omega_dt),
+                "%s: vibration amplitudes / frequency must be finite", who);
+    }
+    return GINSIM_OK;
+}
+
+static int check_mc_params(const ginsim_mc_params* p) {
+    REQUIRE(p, "mc_run: NULL argument");
+    int rc = check_sizes("mc_run", p);
+    if (rc) return rc;
+    REQUIRE(p->fs > 0.0, "mc_run: fs must be positive");
+    REQUIRE(p->ref_frame == 0 || p->ref_frame == 1, "mc_run: ref_frame must be 0 or 1");
+    REQUIRE(p->proc_plain_sums == 0 || p->proc_plain_sums == 1, "mc_run: proc_plain_sums must be 0 or 1");
+    REQUIRE(p->algo_mask >= 0 && p->algo_mask <= 3, "mc_run: algo_mask must be a combination of GINSIM_ALGO_*");
+    REQUIRE(p->algo_mask != 0 || (!p->given_sensors && (p->out_accel || p->out_gyro || p->out_odo)),
+            "mc_run: algo_mask 0 (sensors only) needs sensor outputs");
+    REQUIRE(p->algo_mask == 0 || (p->n_ini >= 1 && p->ini), "mc_run: initial-state table missing");
+    REQUIRE(p->block_threads == 0 || p->block_threads == 64 || p->block_threads == 128 || p->block_threads == 256,
+            "mc_run: block_threads must be 0, 64, 128 or 256");
+    const bool odo = (p->algo_mask & GINSIM_ALGO_ODO) != 0, fre = (p->algo_mask & GINSIM_ALGO_FREE) != 0;
+    if (p->given_sensors) {
+        REQUIRE(p->in_gyro, "mc_run: given_sensors needs in_gyro");
+        REQUIRE(!fre || p->in_accel, "mc_run: given_sensors free integration needs in_accel");
+        REQUIRE(!odo || p->in_odo, "mc_run: given_sensors odometer integration needs in_odo");
+    } else {
+        REQUIRE(p->ref_gyro && p->ref_accel, "mc_run: ref_accel/ref_gyro missing");
+        REQUIRE((!odo && !p->out_odo) || p->ref_odo, "mc_run: ref_odo missing");
+        rc = check_sensor(p->accel, "accel");
+        if (rc) return rc;
+        rc = check_sensor(p->gyro, "gyro");
+        if (rc) return rc;
+    }
+    for (const ginsim_vibration* v : {&p->vib_accel, &p->vib_gyro}) {
+        REQUIRE(v->type == GINSIM_VIB_NONE || v->type == GINSIM_VIB_RANDOM || v->type == GINSIM_VIB_SINUSOIDAL || v->type == GINSIM_VIB_PSD,
+                "mc_run: vibration type must be 0 (none), 1 (random), 2 (sinusoidal) or 3 (psd)");
+        if (v->type == GINSIM_VIB_NONE) continue;
+        REQUIRE(!p->given_sensors, "mc_run: a vibration term cannot be added to given sensors");
+        if (v->type == GINSIM_VIB_PSD) {
+            REQUIRE(v->series && v->period >= 2 && v->period <= 16384, "mc_run: a psd vibration needs its series (ginsim_vib_psd_series) and their period (2 .. 16384)");
+            REQUIRE(p->precision == 0, "mc_run: the psd vibration runs on the fp64 kernels only");
+            REQUIRE(p->sensor_layout == 0, "mc_run: the psd vibration runs on the lane-per-run kernels only (sensor_layout 0)");
+        }
+        REQUIRE(std::isfinite(v->amp[0]) && std::isfinite(v->amp[1]) && std::isfinite(v->amp[2]) && std::isfinite(v->omega_dt),
+                "mc_run: vibration amplitudes / frequency must be finite");
+    }
+    REQUIRE(p->precision == 0 || p->precision == 1, "mc_run: precision must be 0 (fp64) or 1 (fp32)");
+    REQUIRE(p->sensor_layout == 0 || p->sensor_layout == 1, "mc_run: sensor_layout must be 0 ([axis][sample][run]) or 1 ([run][axis][sample])");
+    REQUIRE(p->sensor_layout == 0 || series_path_applies(*p),
+            "mc_run: sensor_layout 1 is written by the time-parallel series kernels only (sensors only, fp64, <= 1024 runs, >= 2048 samples)");
+    if (p->out_proc[0] || p->out_proc[1]) {
+        REQUIRE(!p->given_sensors && p->precision == 0, "mc_run: online process statistics need generate mode and fp64");
+        REQUIRE((p->algo_mask == GINSIM_ALGO_FREE && p->out_proc[0] && !p->out_proc[1]) ||
+                (p->algo_mask == GINSIM_ALGO_ODO && p->out_proc[1] && !p->out_proc[0]),
+                "mc_run: online process statistics take ONE algorithm per launch (out_proc of that algorithm only)");
+        REQUIRE(p->ref_nav, "mc_run: online process statistics need ref_nav");
+        REQUIRE(p->proc_first >= 0 && p->proc_first < p->n, "mc_run: proc_first out of range");
+        REQUIRE(!p->proc_pos_ned || p->ref_frame == 0, "mc_run: NED position errors exist in ref_frame 0 only");
+    }
+    REQUIRE(!(p->out_end_ned[0] || p->out_end_ned[1]) || (p->ref_frame == 0 && p->precision == 0 && !p->given_sensors),
+            "mc_run: out_end_ned needs ref_frame 0, fp64, generate mode");
+    if (p->precision == 1) {
+        REQUIRE(p->algo_mask != 0, "mc_run: the fp32 kernel needs an algorithm");
+        REQUIRE(!(p->out_proc[0] || p->out_proc[1] || p->out_end_ned[0] || p->out_end_ned[1] || p->wave_trace),
+                "mc_run: the fp32 kernel has no online process statistics, NED record or wave trace");
+        REQUIRE(p->block_threads == 0 || p->block_threads == 256, "mc_run: the fp32 kernel takes block_threads 0 or 256 (256 = the plain kernel)");
+    }
+    return GINSIM_OK;
+}
+
 int ginsim_mc_variant(const ginsim_mc_params* p, int32_t* variant) {
     REQUIRE(p && variant, "mc_variant: NULL argument");
     *variant = p->precision == 1 ? mc_variant_f32(*p) : (series_path_applies(*p) ? 2 : mc_variant(*p));
     return GINSIM_OK;
 }
-
-static int check_mc_params(const ginsim_mc_params* p);
 
 int ginsim_mc_kernel_name(const ginsim_mc_params* p, char* buf, size_t cap) {
     REQUIRE(p && buf && cap > 0, "mc_kernel_name: bad arguments");
@@ -366,9 +483,8 @@ int ginsim_mc_run(ginsim_ctx* c, const ginsim_mc_params* p) {
 
 static int check_incl_params(const ginsim_mc_params* m, const ginsim_incl_params* p) {
     REQUIRE(m && p, "incl_run: NULL argument");
-    REQUIRE(m->n >= 1 && m->runs >= 1, "incl_run: n=%lld runs=%lld must be >= 1", (long long)m->n, (long long)m->runs);
-    REQUIRE(m->n <= 0xFFFFFFFFll, "incl_run: n exceeds the 32-bit sample counter of the RNG");
-    REQUIRE(m->runs <= (int64_t)0x7FFFFFFF * 64, "incl_run: too many runs for one launch");
+    int rc = check_sizes("incl_run", m);
+    if (rc) return rc;
     REQUIRE(p->algo_mask >= 1 && p->algo_mask <= 3, "incl_run: algo_mask must be a combination of GINSIM_INCL_*");
     REQUIRE(p->n_list >= 0 && p->n_list <= m->runs, "incl_run: n_list must lie in 0 .. runs");
     REQUIRE(!(p->algo_mask & GINSIM_INCL_MAHONY) || p->bias_in, "incl_run: the Mahony filter needs bias_in");
@@ -376,23 +492,10 @@ static int check_incl_params(const ginsim_mc_params* m, const ginsim_incl_params
     REQUIRE(m->block_threads == 0 || m->block_threads == 64 || m->block_threads == 128 || m->block_threads == 256,
             "incl_run: block_threads must be 0, 64, 128 or 256");
     REQUIRE(m->precision == 0, "incl_run: the inclinometer kernel is fp64 only");
-    if (m->given_sensors) {
-        REQUIRE(m->in_accel && m->in_gyro, "incl_run: given_sensors needs in_accel and in_gyro");
-    } else {
-        REQUIRE(m->ref_gyro && m->ref_accel, "incl_run: ref_accel/ref_gyro missing");
-        int rc = check_sensor(m->accel, "accel");
-        if (rc) return rc;
-        rc = check_sensor(m->gyro, "gyro");
-        if (rc) return rc;
-    }
-    for (const ginsim_vibration* v : {&m->vib_accel, &m->vib_gyro}) {
-        if (v->type == GINSIM_VIB_NONE) continue;
-        REQUIRE(v->type == GINSIM_VIB_RANDOM || v->type == GINSIM_VIB_SINUSOIDAL,
-                "incl_run: the inclinometer kernel takes the 'random' and 'sinusoidal' vibration only");
-        REQUIRE(!m->given_sensors, "incl_run: a vibration term cannot be added to given sensors");
-        REQUIRE(std::isfinite(v->amp[0]) && std::isfinite(v->amp[1]) && std::isfinite(v->amp[2]) && std::isfinite(v->omega_dt),
-                "incl_run: vibration amplitudes / frequency must be finite");
-    }
+    rc = check_sensor_source("incl_run", m, true, true);
+    if (rc) return rc;
+    rc = check_vibration_no_psd("incl_run", m, "inclinometer");
+    if (rc) return rc;
     const bool stats = p->out_end[0] || p->out_end[1] || p->out_proc[0] || p->out_proc[1];
     REQUIRE(!stats || m->ref_nav, "incl_run: statistics need ref_nav");
     REQUIRE(!stats || m->proc_first >= 0, "incl_run: proc_first must be >= 0");
@@ -431,9 +534,8 @@ int ginsim_incl_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_incl
 
 static int check_loose_params(const ginsim_mc_params* m, const ginsim_loose_params* p) {
     REQUIRE(m && p, "loose_run: NULL argument");
-    REQUIRE(m->n >= 1 && m->runs >= 1, "loose_run: n=%lld runs=%lld must be >= 1", (long long)m->n, (long long)m->runs);
-    REQUIRE(m->n <= 0xFFFFFFFFll, "loose_run: n exceeds the 32-bit sample counter of the RNG");
-    REQUIRE(m->runs <= (int64_t)0x7FFFFFFF * 64, "loose_run: too many runs for one launch");
+    int rc = check_sizes("loose_run", m);
+    if (rc) return rc;
     REQUIRE(std::isfinite(m->fs) && m->fs > 0.0, "loose_run: fs must be positive");
     REQUIRE(m->ref_frame == 0 || m->ref_frame == 1, "loose_run: ref_frame must be 0 or 1");
     REQUIRE(m->precision == 0, "loose_run: the filter kernel is fp64 only");
@@ -447,26 +549,12 @@ static int check_loose_params(const ginsim_mc_params* m, const ginsim_loose_para
         REQUIRE(s >= 0 && s < (long long)m->n, "loose_run: the stamp of fix %lld (%lld) is outside [0, %lld)", (long long)k, s, (long long)m->n);
         REQUIRE(k == 0 || s > (long long)p->gps_stamp[k - 1], "loose_run: the stamps are not strictly increasing at fix %lld", (long long)k);
     }
-    if (m->given_sensors) {
-        REQUIRE(m->in_accel && m->in_gyro, "loose_run: given_sensors needs in_accel and in_gyro");
-        REQUIRE(p->m == 0 || p->in_gps, "loose_run: given_sensors needs in_gps");
-    } else {
-        REQUIRE(m->ref_gyro && m->ref_accel, "loose_run: ref_accel/ref_gyro missing");
-        REQUIRE(p->m == 0 || p->ref_gps, "loose_run: ref_gps missing");
-        int rc = check_sensor(m->accel, "accel");
-        if (rc) return rc;
-        rc = check_sensor(m->gyro, "gyro");
-        if (rc) return rc;
+    rc = check_sensor_source("loose_run", m, p->m == 0 || p->in_gps, p->m == 0 || p->ref_gps);
+    if (rc) return rc;
+    if (!m->given_sensors)
         for (int k = 0; k < 6; ++k) REQUIRE(std::isfinite(p->gps_sigma[k]), "loose_run: gps_sigma must be finite");
-    }
-    for (const ginsim_vibration* v : {&m->vib_accel, &m->vib_gyro}) {
-        if (v->type == GINSIM_VIB_NONE) continue;
-        REQUIRE(v->type == GINSIM_VIB_RANDOM || v->type == GINSIM_VIB_SINUSOIDAL,
-                "loose_run: the filter kernel takes the 'random' and 'sinusoidal' vibration only");
-        REQUIRE(!m->given_sensors, "loose_run: a vibration term cannot be added to given sensors");
-        REQUIRE(std::isfinite(v->amp[0]) && std::isfinite(v->amp[1]) && std::isfinite(v->amp[2]) && std::isfinite(v->omega_dt),
-                "loose_run: vibration amplitudes / frequency must be finite");
-    }
+    rc = check_vibration_no_psd("loose_run", m, "filter");
+    if (rc) return rc;
     for (int k = 0; k < 6; ++k) REQUIRE(std::isfinite(p->r_diag[k]) && p->r_diag[k] > 0.0, "loose_run: r_diag must be positive");
     for (int k = 0; k < 5; ++k) REQUIRE(std::isfinite(p->p0[k]) && p->p0[k] > 0.0, "loose_run: p0 must be positive");
     for (int k = 0; k < 3; ++k) {
@@ -589,74 +677,6 @@ int ginsim_loose_cons_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsi
     if (rc) return rc;
     return loose_launch(c, mc, p, cons->cons_m > 0 ? cons : nullptr);
 }
-
-}  // extern "C"
-
-static int check_mc_params(const ginsim_mc_params* p) {
-    REQUIRE(p, "mc_run: NULL argument");
-    REQUIRE(p->n >= 1 && p->runs >= 1, "mc_run: n=%lld runs=%lld must be >= 1", (long long)p->n, (long long)p->runs);
-    REQUIRE(p->n <= 0xFFFFFFFFll, "mc_run: n exceeds the 32-bit sample counter of the RNG");
-    REQUIRE(p->runs <= (int64_t)0x7FFFFFFF * 64, "mc_run: too many runs for one launch");
-    REQUIRE(p->fs > 0.0, "mc_run: fs must be positive");
-    REQUIRE(p->ref_frame == 0 || p->ref_frame == 1, "mc_run: ref_frame must be 0 or 1");
-    REQUIRE(p->proc_plain_sums == 0 || p->proc_plain_sums == 1, "mc_run: proc_plain_sums must be 0 or 1");
-    REQUIRE(p->algo_mask >= 0 && p->algo_mask <= 3, "mc_run: algo_mask must be a combination of GINSIM_ALGO_*");
-    REQUIRE(p->algo_mask != 0 || (!p->given_sensors && (p->out_accel || p->out_gyro || p->out_odo)),
-            "mc_run: algo_mask 0 (sensors only) needs sensor outputs");
-    REQUIRE(p->algo_mask == 0 || (p->n_ini >= 1 && p->ini), "mc_run: initial-state table missing");
-    REQUIRE(p->block_threads == 0 || p->block_threads == 64 || p->block_threads == 128 || p->block_threads == 256,
-            "mc_run: block_threads must be 0, 64, 128 or 256");
-    const bool odo = (p->algo_mask & GINSIM_ALGO_ODO) != 0, fre = (p->algo_mask & GINSIM_ALGO_FREE) != 0;
-    if (p->given_sensors) {
-        REQUIRE(p->in_gyro, "mc_run: given_sensors needs in_gyro");
-        REQUIRE(!fre || p->in_accel, "mc_run: given_sensors free integration needs in_accel");
-        REQUIRE(!odo || p->in_odo, "mc_run: given_sensors odometer integration needs in_odo");
-    } else {
-        REQUIRE(p->ref_gyro && p->ref_accel, "mc_run: ref_accel/ref_gyro missing");
-        REQUIRE((!odo && !p->out_odo) || p->ref_odo, "mc_run: ref_odo missing");
-        int rc = check_sensor(p->accel, "accel");
-        if (rc) return rc;
-        rc = check_sensor(p->gyro, "gyro");
-        if (rc) return rc;
-    }
-    for (const ginsim_vibration* v : {&p->vib_accel, &p->vib_gyro}) {
-        REQUIRE(v->type == GINSIM_VIB_NONE || v->type == GINSIM_VIB_RANDOM || v->type == GINSIM_VIB_SINUSOIDAL || v->type == GINSIM_VIB_PSD,
-                "mc_run: vibration type must be 0 (none), 1 (random), 2 (sinusoidal) or 3 (psd)");
-        if (v->type == GINSIM_VIB_NONE) continue;
-        REQUIRE(!p->given_sensors, "mc_run: a vibration term cannot be added to given sensors");
-        if (v->type == GINSIM_VIB_PSD) {
-            REQUIRE(v->series && v->period >= 2 && v->period <= 16384, "mc_run: a psd vibration needs its series (ginsim_vib_psd_series) and their period (2 .. 16384)");
-            REQUIRE(p->precision == 0, "mc_run: the psd vibration runs on the fp64 kernels only");
-            REQUIRE(p->sensor_layout == 0, "mc_run: the psd vibration runs on the lane-per-run kernels only (sensor_layout 0)");
-        }
-        REQUIRE(std::isfinite(v->amp[0]) && std::isfinite(v->amp[1]) && std::isfinite(v->amp[2]) && std::isfinite(v->omega_dt),
-                "mc_run: vibration amplitudes / frequency must be finite");
-    }
-    REQUIRE(p->precision == 0 || p->precision == 1, "mc_run: precision must be 0 (fp64) or 1 (fp32)");
-    REQUIRE(p->sensor_layout == 0 || p->sensor_layout == 1, "mc_run: sensor_layout must be 0 ([axis][sample][run]) or 1 ([run][axis][sample])");
-    REQUIRE(p->sensor_layout == 0 || series_path_applies(*p),
-            "mc_run: sensor_layout 1 is written by the time-parallel series kernels only (sensors only, fp64, <= 1024 runs, >= 2048 samples)");
-    if (p->out_proc[0] || p->out_proc[1]) {
-        REQUIRE(!p->given_sensors && p->precision == 0, "mc_run: online process statistics need generate mode and fp64");
-        REQUIRE((p->algo_mask == GINSIM_ALGO_FREE && p->out_proc[0] && !p->out_proc[1]) ||
-                (p->algo_mask == GINSIM_ALGO_ODO && p->out_proc[1] && !p->out_proc[0]),
-                "mc_run: online process statistics take ONE algorithm per launch (out_proc of that algorithm only)");
-        REQUIRE(p->ref_nav, "mc_run: online process statistics need ref_nav");
-        REQUIRE(p->proc_first >= 0 && p->proc_first < p->n, "mc_run: proc_first out of range");
-        REQUIRE(!p->proc_pos_ned || p->ref_frame == 0, "mc_run: NED position errors exist in ref_frame 0 only");
-    }
-    REQUIRE(!(p->out_end_ned[0] || p->out_end_ned[1]) || (p->ref_frame == 0 && p->precision == 0 && !p->given_sensors),
-            "mc_run: out_end_ned needs ref_frame 0, fp64, generate mode");
-    if (p->precision == 1) {
-        REQUIRE(p->algo_mask != 0, "mc_run: the fp32 kernel needs an algorithm");
-        REQUIRE(!(p->out_proc[0] || p->out_proc[1] || p->out_end_ned[0] || p->out_end_ned[1] || p->wave_trace),
-                "mc_run: the fp32 kernel has no online process statistics, NED record or wave trace");
-        REQUIRE(p->block_threads == 0 || p->block_threads == 256, "mc_run: the fp32 kernel takes block_threads 0 or 256 (256 = the plain kernel)");
-    }
-    return GINSIM_OK;
-}
-
-extern "C" {
 
 int ginsim_aux_sensors(ginsim_ctx* c, const ginsim_aux_params* p) {
     REQUIRE(c && p, "aux_sensors: NULL argument");
@@ -855,55 +875,53 @@ int ginsim_end_stats_all_finish(ginsim_ctx* c, int32_t slot, ginsim_stats* merge
     return GINSIM_OK;
 }
 
-int ginsim_process_stats(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, int64_t first_sample,
-                         int32_t pos_ned, double* host_out) {
-    REQUIRE(c && traj && ref && host_out, "process_stats: NULL argument");
-    REQUIRE(n >= 1 && runs >= 1 && first_sample >= 0 && first_sample < n, "process_stats: bad sizes");
+// The per-run statistics of kept trajectories (stats.hip's process kernel) in the context's scratch.  proc_out: the records of the
+// samples >= first_sample, [runs][3][9], to the host.  end_out (proc_out NULL): a one-sample window at n - 1, whose "mean" plane
+// [9][runs] IS the end-point error, reduced by ginsim_end_stats.  f32: traj is float, positions as displacement from origin.
+static int traj_stats_run(ginsim_ctx* c, const void* traj, int f32, const double* ref, int64_t n, int64_t runs, int64_t first_sample,
+                          int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* proc_out, ginsim_stats* end_out) {
     HIP_TRY(hipSetDevice(c->device));
     void* ws = nullptr;
     const size_t bytes = sizeof(double) * 27 * (size_t)runs;
     HIP_TRY(scratch(c, 2, bytes, &ws));
-    HIP_TRY(launch_process_stats(traj, ref, n, runs, first_sample, pos_ned, 1, reinterpret_cast<double*>(ws), c->stream));
-    HIP_TRY(hipMemcpyAsync(host_out, ws, bytes, hipMemcpyDeviceToHost, c->stream));      // already [runs][3][9]
+    double* rec = reinterpret_cast<double*>(ws);
+    const int64_t j0 = proc_out ? first_sample : n - 1;
+    const int run_major = proc_out ? 1 : 0;
+    if (f32)
+        HIP_TRY(launch_process_stats_f32(reinterpret_cast<const float*>(traj), ref, n, runs, j0, pos_ned, run_major, rec, origin, n_ini,
+                                         ini_first, c->stream));
+    else
+        HIP_TRY(launch_process_stats(reinterpret_cast<const double*>(traj), ref, n, runs, j0, pos_ned, run_major, rec, c->stream));
+    if (!proc_out) return ginsim_end_stats(c, rec + (size_t)9 * runs, runs, end_out);
+    HIP_TRY(hipMemcpyAsync(proc_out, ws, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GINSIM_OK;
+}
+
+int ginsim_process_stats(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, int64_t first_sample,
+                         int32_t pos_ned, double* host_out) {
+    REQUIRE(c && traj && ref && host_out, "process_stats: NULL argument");
+    REQUIRE(n >= 1 && runs >= 1 && first_sample >= 0 && first_sample < n, "process_stats: bad sizes");
+    return traj_stats_run(c, traj, 0, ref, n, runs, first_sample, pos_ned, nullptr, 0, 0, host_out, nullptr);
 }
 
 int ginsim_end_stats_from_traj(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, int32_t pos_ned,
                                ginsim_stats* host_out) {
     REQUIRE(c && traj && ref && host_out && n >= 1 && runs >= 1, "end_stats_from_traj: bad arguments");
-    HIP_TRY(hipSetDevice(c->device));
-    void* ws = nullptr;
-    HIP_TRY(scratch(c, 2, sizeof(double) * 27 * (size_t)runs, &ws));
-    // a one-sample window: the "mean" plane [9][runs] of the process kernel IS the end-point error
-    HIP_TRY(launch_process_stats(traj, ref, n, runs, n - 1, pos_ned, 0, reinterpret_cast<double*>(ws), c->stream));
-    return ginsim_end_stats(c, reinterpret_cast<double*>(ws) + (size_t)9 * runs, runs, host_out);
+    return traj_stats_run(c, traj, 0, ref, n, runs, 0, pos_ned, nullptr, 0, 0, nullptr, host_out);
 }
 
 int ginsim_process_stats_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, int64_t first_sample,
                              int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* host_out) {
     REQUIRE(c && traj && ref && origin && host_out, "process_stats_f32: NULL argument");
     REQUIRE(n >= 1 && runs >= 1 && first_sample >= 0 && first_sample < n && n_ini >= 1, "process_stats_f32: bad sizes");
-    HIP_TRY(hipSetDevice(c->device));
-    void* ws = nullptr;
-    const size_t bytes = sizeof(double) * 27 * (size_t)runs;
-    HIP_TRY(scratch(c, 2, bytes, &ws));
-    HIP_TRY(launch_process_stats_f32(traj, ref, n, runs, first_sample, pos_ned, 1, reinterpret_cast<double*>(ws), origin, n_ini,
-                                     ini_first, c->stream));
-    HIP_TRY(hipMemcpyAsync(host_out, ws, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GINSIM_OK;
+    return traj_stats_run(c, traj, 1, ref, n, runs, first_sample, pos_ned, origin, n_ini, ini_first, host_out, nullptr);
 }
 
 int ginsim_end_stats_from_traj_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, int32_t pos_ned,
                                    const double* origin, int32_t n_ini, uint64_t ini_first, ginsim_stats* host_out) {
     REQUIRE(c && traj && ref && origin && host_out && n >= 1 && runs >= 1 && n_ini >= 1, "end_stats_from_traj_f32: bad arguments");
-    HIP_TRY(hipSetDevice(c->device));
-    void* ws = nullptr;
-    HIP_TRY(scratch(c, 2, sizeof(double) * 27 * (size_t)runs, &ws));
-    HIP_TRY(launch_process_stats_f32(traj, ref, n, runs, n - 1, pos_ned, 0, reinterpret_cast<double*>(ws), origin, n_ini, ini_first,
-                                     c->stream));
-    return ginsim_end_stats(c, reinterpret_cast<double*>(ws) + (size_t)9 * runs, runs, host_out);
+    return traj_stats_run(c, traj, 1, ref, n, runs, 0, pos_ned, origin, n_ini, ini_first, nullptr, host_out);
 }
 
 // ---- error-growth curves (csrc/error_curve.hip): the across-run record of every requested sample
@@ -972,56 +990,23 @@ int ginsim_stats_merge(const ginsim_stats* parts, int32_t nparts, ginsim_stats* 
 
 int ginsim_gather_runs(ginsim_ctx* c, const double* series, int32_t ncomp, int64_t n, int64_t runs,
                        const int64_t* run_ids, int32_t nsel, double* host_out) {
-    REQUIRE(c && series && run_ids && host_out, "gather_runs: NULL argument");
-    REQUIRE(ncomp >= 1 && n >= 1 && runs >= 1 && nsel >= 1, "gather_runs: bad sizes");
-    for (int i = 0; i < nsel; ++i)
-        REQUIRE(run_ids[i] >= 0 && run_ids[i] < runs, "gather_runs: run id %lld out of range", (long long)run_ids[i]);
-    HIP_TRY(hipSetDevice(c->device));
-    DevBuf ids, out;
-    const size_t out_bytes = sizeof(double) * (size_t)nsel * n * ncomp;
-    HIP_TRY(ids.alloc(sizeof(int64_t) * nsel));
-    HIP_TRY(out.alloc(out_bytes));
-    HIP_TRY(hipMemcpyAsync(ids.p, run_ids, sizeof(int64_t) * nsel, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch_gather_runs(series, ncomp, n, runs, ids.as<int64_t>(), nsel, out.as<double>(), c->stream));
-    HIP_TRY(hipMemcpyAsync(host_out, out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GINSIM_OK;
+    return gather_run("gather_runs", c, series, ncomp, n, runs, run_ids, nsel, host_out, [&](const int64_t* ids, double* out) {
+        return launch_gather_runs(series, ncomp, n, runs, ids, nsel, out, c->stream);
+    });
 }
 
 int ginsim_gather_series(ginsim_ctx* c, const double* series, int32_t ncomp, int64_t n, int64_t runs, const int64_t* run_ids,
                          int32_t nsel, double* host_out) {
-    REQUIRE(c && series && run_ids && host_out, "gather_series: NULL argument");
-    REQUIRE(ncomp >= 1 && n >= 1 && runs >= 1 && nsel >= 1, "gather_series: bad sizes");
-    for (int i = 0; i < nsel; ++i)
-        REQUIRE(run_ids[i] >= 0 && run_ids[i] < runs, "gather_series: run id %lld out of range", (long long)run_ids[i]);
-    HIP_TRY(hipSetDevice(c->device));
-    DevBuf ids, out;
-    const size_t out_bytes = sizeof(double) * (size_t)nsel * n * ncomp;
-    HIP_TRY(ids.alloc(sizeof(int64_t) * nsel));
-    HIP_TRY(out.alloc(out_bytes));
-    HIP_TRY(hipMemcpyAsync(ids.p, run_ids, sizeof(int64_t) * nsel, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch_gather_series(series, ncomp, n, ids.as<int64_t>(), nsel, out.as<double>(), c->stream));
-    HIP_TRY(hipMemcpyAsync(host_out, out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GINSIM_OK;
+    return gather_run("gather_series", c, series, ncomp, n, runs, run_ids, nsel, host_out, [&](const int64_t* ids, double* out) {
+        return launch_gather_series(series, ncomp, n, ids, nsel, out, c->stream);
+    });
 }
 
 int ginsim_gather_runs_f32(ginsim_ctx* c, const float* series, int32_t ncomp, int64_t n, int64_t runs,
                            const int64_t* run_ids, int32_t nsel, double* host_out) {
-    REQUIRE(c && series && run_ids && host_out, "gather_runs_f32: NULL argument");
-    REQUIRE(ncomp >= 1 && n >= 1 && runs >= 1 && nsel >= 1, "gather_runs_f32: bad sizes");
-    for (int i = 0; i < nsel; ++i)
-        REQUIRE(run_ids[i] >= 0 && run_ids[i] < runs, "gather_runs_f32: run id %lld out of range", (long long)run_ids[i]);
-    HIP_TRY(hipSetDevice(c->device));
-    DevBuf ids, out;
-    const size_t out_bytes = sizeof(double) * (size_t)nsel * n * ncomp;
-    HIP_TRY(ids.alloc(sizeof(int64_t) * nsel));
-    HIP_TRY(out.alloc(out_bytes));
-    HIP_TRY(hipMemcpyAsync(ids.p, run_ids, sizeof(int64_t) * nsel, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch_gather_runs_f32(series, ncomp, n, runs, ids.as<int64_t>(), nsel, out.as<double>(), c->stream));
-    HIP_TRY(hipMemcpyAsync(host_out, out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GINSIM_OK;
+    return gather_run("gather_runs_f32", c, series, ncomp, n, runs, run_ids, nsel, host_out, [&](const int64_t* ids, double* out) {
+        return launch_gather_runs_f32(series, ncomp, n, runs, ids, nsel, out, c->stream);
+    });
 }
 
 int ginsim_free_integration(ginsim_ctx* c, int32_t algo, int32_t ref_frame, double fs, int32_t earth_rot,

@@ -24,13 +24,13 @@
 // gps_synth.hpp (same bits as ginsim_aux_sensors).  The generated and the given form share every line after the samples are in
 // registers.
 // What loose_aided_kernel (ins_loose_aided.hip) shares with this file -- Cov, the propagation, the correction, the time loop -- is
-// in ins_loose.hpp.
+// in ins_loose.hpp; the host side that launches an instantiation of either, or of loose_cons_kernel (ins_loose_cons.hip), is
+// launch_loose_trio (loose_launch.hpp): this file keeps the choice of <RF, PS> and hands over to the aided kernel.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include "ginsim.h"
-#include "device_once.hpp"
 #include "ins_loose.hpp"
 #include "launch.hpp"
+#include "loose_launch.hpp"
 
 namespace ginsim {
 
@@ -49,27 +49,12 @@ int loose_variant(const ginsim_mc_params& p) { return p.given_sensors ? 1 : 0; }
 template <int RF, bool PS>
 static hipError_t launch_loose_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
                                  hipStream_t stream, char* name, size_t cap) {
-    const int tb = kLooseBlock;
-    const dim3 grid((unsigned)((b.n_list + tb - 1) / tb)), block((unsigned)tb);
-    const bool given = p.given_sensors != 0, vib = any_vibration(p);
-    if (name) {
-        snprintf(name, cap, "ginsim::loose_kernel<%d, %s, %s, %s>", RF, given ? "true" : "false", vib ? "true" : "false", PS ? "true" : "false");
-        return hipSuccess;
-    }
-    constexpr size_t kLooseLds = kLooseCovLds;
-    static PerDeviceOnce once;          // more than 64 KB of dynamic LDS: the attribute, on every device that launches
-    once.run([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_kernel<RF, true, false, PS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_kernel<RF, false, true, PS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_kernel<RF, false, false, PS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-    });
-    if (given) hipLaunchKernelGGL((loose_kernel<RF, true, false, PS>), grid, block, kLooseLds, stream, p, b, stamp, visible);
-    else if (vib) hipLaunchKernelGGL((loose_kernel<RF, false, true, PS>), grid, block, kLooseLds, stream, p, b, stamp, visible);
-    else hipLaunchKernelGGL((loose_kernel<RF, false, false, PS>), grid, block, kLooseLds, stream, p, b, stamp, visible);
-    return hipGetLastError();
+    return launch_loose_trio<&loose_kernel<RF, true, false, PS>, &loose_kernel<RF, false, true, PS>, &loose_kernel<RF, false, false, PS>>(
+        "loose_kernel", RF, PS, p, b, stamp, visible, stream, name, cap);
 }
 
-// name != NULL: report the kernel's name, do not launch.  stamp / visible: DEVICE copies of b.gps_stamp / b.gps_visible
+// name != NULL: report the kernel's name, do not launch.  stamp / visible: DEVICE copies of b.gps_stamp / b.gps_visible.
+// aid_mask != 0: loose_aided_kernel
 hipError_t launch_loose(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
                         hipStream_t stream, char* name, size_t cap) {
     if (b.n_list <= 0 && !name) return hipSuccess;

@@ -14,14 +14,14 @@
 // counter j (the bits ginsim_mc_run writes to out_odo) or read from in_odo[j runs + r] (given_sensors).
 // aid_mask and aid_every are wave-uniform kernel arguments, not template parameters: 12 instantiations as loose_kernel's.
 //
+// The launch is launch_loose_trio (loose_launch.hpp); launch_loose_aided chooses <RF, PS>.
 // Built with ins_loose.hip's flags; P stays in LDS as [120][64], one wavefront per workgroup.  The build's resource report
 // (build/ins_loose_aided.resources.txt, read by tests/test_ins_loose_aided_oracle.py): 0 bytes of scratch in all 12.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include "ginsim.h"
-#include "device_once.hpp"
 #include "ins_loose.hpp"
 #include "launch.hpp"
+#include "loose_launch.hpp"
 
 namespace ginsim {
 
@@ -36,24 +36,8 @@ loose_aided_kernel(const ginsim_mc_params a, const ginsim_loose_params b, const 
 template <int RF, bool PS>
 static hipError_t launch_aided_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
                                  hipStream_t stream, char* name, size_t cap) {
-    const int tb = kLooseBlock;
-    const dim3 grid((unsigned)((b.n_list + tb - 1) / tb)), block((unsigned)tb);
-    const bool given = p.given_sensors != 0, vib = any_vibration(p);
-    if (name) {
-        snprintf(name, cap, "ginsim::loose_aided_kernel<%d, %s, %s, %s>", RF, given ? "true" : "false", vib ? "true" : "false", PS ? "true" : "false");
-        return hipSuccess;
-    }
-    constexpr size_t kLooseLds = kLooseCovLds;
-    static PerDeviceOnce once;          // more than 64 KB of dynamic LDS: the attribute, on every device that launches
-    once.run([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_aided_kernel<RF, true, false, PS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_aided_kernel<RF, false, true, PS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_aided_kernel<RF, false, false, PS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-    });
-    if (given) hipLaunchKernelGGL((loose_aided_kernel<RF, true, false, PS>), grid, block, kLooseLds, stream, p, b, stamp, visible);
-    else if (vib) hipLaunchKernelGGL((loose_aided_kernel<RF, false, true, PS>), grid, block, kLooseLds, stream, p, b, stamp, visible);
-    else hipLaunchKernelGGL((loose_aided_kernel<RF, false, false, PS>), grid, block, kLooseLds, stream, p, b, stamp, visible);
-    return hipGetLastError();
+    return launch_loose_trio<&loose_aided_kernel<RF, true, false, PS>, &loose_aided_kernel<RF, false, true, PS>,
+                             &loose_aided_kernel<RF, false, false, PS>>("loose_aided_kernel", RF, PS, p, b, stamp, visible, stream, name, cap);
 }
 
 // name != NULL: report the kernel's name, do not launch.  stamp / visible: DEVICE copies of b.gps_stamp / b.gps_visible

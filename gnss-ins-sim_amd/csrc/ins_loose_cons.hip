@@ -18,14 +18,15 @@
 // list again and weigh 0.
 // The errors of the six bias states are left out (they carry P_kk only): the given form has no bias truth.
 // PS is false here: online process statistics and checkpoints in one launch are refused.  12 instantiations, <RF, GIVEN, VIB, AID>.
+// The filter's launch is launch_loose_trio (loose_launch.hpp) with the checkpoint arguments behind the filter's own;
+// launch_loose_cons chooses <RF, AID> and launches cons_final_kernel after it.
 // Built with ins_loose.hip's flags; the build's resource report is build/ins_loose_cons.resources.txt
 // (tests/test_ins_loose_cons_oracle.py reads it).
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include "ginsim.h"
-#include "device_once.hpp"
 #include "ins_loose.hpp"
 #include "launch.hpp"
+#include "loose_launch.hpp"
 
 namespace ginsim {
 
@@ -50,31 +51,15 @@ __global__ void __launch_bounds__(256) cons_final_kernel(const double* __restric
 template <int RF, bool AID>
 static hipError_t launch_cons_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_cons_params& c,
                                 const int64_t* stamp, const int32_t* visible, const int64_t* samples, hipStream_t stream, char* name, size_t cap) {
-    const int tb = kLooseBlock;
-    const int64_t waves = (b.n_list + tb - 1) / tb;
-    const dim3 grid((unsigned)waves), block((unsigned)tb);
-    const bool given = p.given_sensors != 0, vib = any_vibration(p);
-    if (name) {
-        snprintf(name, cap, "ginsim::loose_cons_kernel<%d, %s, %s, %s>", RF, given ? "true" : "false", vib ? "true" : "false", AID ? "true" : "false");
-        return hipSuccess;
-    }
     ConsArgs cq;
     cq.sample = samples;
     cq.m = c.cons_m;
     cq.work = c.cons_work;
-    constexpr size_t kLooseLds = kLooseCovLds;
-    static PerDeviceOnce once;          // more than 64 KB of dynamic LDS: the attribute, on every device that launches
-    once.run([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_cons_kernel<RF, true, false, AID>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_cons_kernel<RF, false, true, AID>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&loose_cons_kernel<RF, false, false, AID>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseLds);
-    });
-    if (given) hipLaunchKernelGGL((loose_cons_kernel<RF, true, false, AID>), grid, block, kLooseLds, stream, p, b, stamp, visible, cq);
-    else if (vib) hipLaunchKernelGGL((loose_cons_kernel<RF, false, true, AID>), grid, block, kLooseLds, stream, p, b, stamp, visible, cq);
-    else hipLaunchKernelGGL((loose_cons_kernel<RF, false, false, AID>), grid, block, kLooseLds, stream, p, b, stamp, visible, cq);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int64_t len = c.cons_m * GINSIM_CONS_RECORD;
+    const hipError_t e = launch_loose_trio<&loose_cons_kernel<RF, true, false, AID>, &loose_cons_kernel<RF, false, true, AID>,
+                                           &loose_cons_kernel<RF, false, false, AID>>("loose_cons_kernel", RF, AID, p, b, stamp, visible, stream,
+                                                                                      name, cap, cq);
+    if (name || e != hipSuccess) return e;
+    const int64_t waves = (b.n_list + kLooseBlock - 1) / kLooseBlock, len = c.cons_m * GINSIM_CONS_RECORD;
     hipLaunchKernelGGL(cons_final_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, stream, c.cons_work, waves, len, c.out_cons);
     return hipGetLastError();
 }

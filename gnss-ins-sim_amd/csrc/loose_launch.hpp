@@ -1,0 +1,35 @@
+// The host-side launch of the loose family (ins_loose.hip, ins_loose_aided.hip, ins_loose_cons.hip): each file defines its own
+// __global__ wrapper of loose_body and hands its instantiations to launch_loose_trio in threes.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include "ginsim.h"
+#include "device_once.hpp"
+#include "ins_loose.hpp"
+#include "launch.hpp"
+
+namespace ginsim {
+
+// GIVEN / VIB / PLAIN: the instantiations <RF, true, false, F>, <RF, false, true, F> and <RF, false, false, F> of one kernel template
+// (samples from in_accel / in_gyro; generated with a vibration term; generated without).  kernel, rf, flag: the template's name and
+// the values of RF and F, for the printed name.  tail: the kernel's arguments after (p, b, stamp, visible).
+// name != NULL: report the kernel's name, do not launch.
+template <auto GIVEN, auto VIB, auto PLAIN, class... Tail>
+hipError_t launch_loose_trio(const char* kernel, int rf, bool flag, const ginsim_mc_params& p, const ginsim_loose_params& b,
+                             const int64_t* stamp, const int32_t* visible, hipStream_t stream, char* name, size_t cap, Tail... tail) {
+    const dim3 grid((unsigned)((b.n_list + kLooseBlock - 1) / kLooseBlock)), block((unsigned)kLooseBlock);
+    const bool given = p.given_sensors != 0, vib = any_vibration(p);
+    if (name) {
+        snprintf(name, cap, "ginsim::%s<%d, %s, %s, %s>", kernel, rf, given ? "true" : "false", vib ? "true" : "false", flag ? "true" : "false");
+        return hipSuccess;
+    }
+    static PerDeviceOnce once;          // one per trio.  More than 64 KB of dynamic LDS: the attribute, on every device that launches
+    once.run([] {
+        for (auto k : {GIVEN, VIB, PLAIN})
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseCovLds);
+    });
+    hipLaunchKernelGGL(given ? GIVEN : (vib ? VIB : PLAIN), grid, block, kLooseCovLds, stream, p, b, stamp, visible, tail...);
+    return hipGetLastError();
+}
+
+}  // namespace ginsim

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check, dptr, ALGO_FREE, ALGO_ODO
+from .job import BatchJob
 
 ALGO_BITS = {'free': ALGO_FREE, 'odo': ALGO_ODO}
 ALGO_SLOT = {'free': 0, 'odo': 1}
@@ -657,7 +658,7 @@ def starts_on_truth(table, nav0, ref_frame=0):
     return True
 
 
-class MonteCarloJob(object):
+class MonteCarloJob(BatchJob):
     """One batch of MC runs on one device: fused noise injection + mechanisation + end-point error.
 
     truth: dict with 'ref_accel' (n,3), 'ref_gyro' (n,3), 'ref_att'/'ref_pos'/'ref_vel' (n,3) and, for
@@ -711,8 +712,8 @@ class MonteCarloJob(object):
                                      '[axis][sample][run]' % (k,))
             self.want_odo = False
         p = self.params = _lib.McParams()
-        p.n, p.runs, p.run_offset, p.seed = self.n, self.runs, int(run_offset), int(seed) & (2 ** 64 - 1)
-        p.fs, p.ref_frame = float(fs), int(ref_frame)
+        self._fill_batch(p, fs, run_offset, seed)
+        p.ref_frame = int(ref_frame)
         p.algo_mask = sum(ALGO_BITS[a] for a in self.algos)
         p.earth_rot = int(bool(earth_rot))
         p.end_pos_ned = int(bool(end_pos_ned))
@@ -771,8 +772,7 @@ class MonteCarloJob(object):
         # the regions a launch streams at once (sensor series, every algorithm's trajectories): carved from the device's placed
         # arena when they are large -- ONE reservation for all of them, so that the arena grows (searches) once
         big = (6 * plane + (plane if self.want_odo else 0) if self.keep_sensors else 0) + (9 * plane * len(self.algos) if self.keep_traj else 0)
-        use_placed = (big >= ctx.PLACED_MIN_JOB) if placed is None else bool(placed)
-        use_placed = bool(use_placed and big > 0 and ctx.placed_reserve(big))
+        use_placed = self._use_placed(placed, big)
         if self.keep_sensors:
             if not self.algos and given is None and precision == 'f64' and _lib.VIB_PSD not in (p.vib_accel.type, p.vib_gyro.type):
                 # few runs, long series: the time-parallel series kernels, series-major output (the library decides)
@@ -801,8 +801,7 @@ class MonteCarloJob(object):
                 raise ValueError('proc_first must be a sample index of the run')
             if proc_ned and int(ref_frame) != 0:
                 raise ValueError('NED position errors exist in ref_frame 0 only')
-            self._bufs['ref_nav'] = ctx.upload(self._ref_nav)
-            p.ref_nav, p.proc_first, p.proc_pos_ned = self._bufs['ref_nav'].ptr, int(proc_first), int(bool(proc_ned))
+            p.ref_nav, p.proc_first, p.proc_pos_ned = self._nav(), int(proc_first), int(bool(proc_ned))
             p.proc_plain_sums = int(starts_on_truth(table, self._ref_nav[0], ref_frame))
         if end_ned and (int(ref_frame) != 0 or precision != 'f64' or given is not None):
             raise ValueError('end_ned: ref_frame 0, fp64, generated sensors')
@@ -852,12 +851,6 @@ class MonteCarloJob(object):
         avar, tau = allan_var(self.ctx, ptr, self.n, 3 * self.runs * len(names), self.n, fs)
         ad = np.sqrt(avar).reshape(len(names), self.runs, 3, -1)
         return tau, {nm: ad[i].transpose(0, 2, 1).copy() for i, nm in enumerate(names)}
-
-    def buffer(self, name):
-        """Device buffer of a materialised series ('accel', 'gyro', 'odo', 'traj_free', ...), e.g. to feed given=."""
-        if name not in self._bufs:
-            raise ValueError('%r was not kept by this job' % (name,))
-        return self._bufs[name]
 
     def bytes_written(self):
         per_sample = 0
@@ -928,83 +921,13 @@ class MonteCarloJob(object):
         check(lib.ginsim_end_stats_all_finish(self.ctx.handle, int(slot), C.byref(s)))
         return StatsResult(s)
 
-    def process_stats(self, algo, first_sample=0, pos_ned=False):
-        """Per-run statistics of the error over time (samples >= first_sample): (runs, 3, 9) = max|e|, mean, std.
-        Needs the trajectories (keep_traj=True) and truth['ref_att'/'ref_pos'/'ref_vel']."""
-        if not self.keep_traj:
-            raise ValueError('process-error statistics need the trajectories (keep_traj=True)')
-        if 'ref_nav' not in self._bufs:
-            self._bufs['ref_nav'] = self.ctx.upload(self._ref_nav)
-        out = np.empty((self.runs, 3, 9))
-        if self.precision == 'f32':     # float series, positions as displacement from the run's initial position
-            check(lib.ginsim_process_stats_f32(self.ctx.handle, self._bufs['traj_' + algo].ptr, self._bufs['ref_nav'].ptr, self.n,
-                                               self.runs, int(first_sample), int(bool(pos_ned)), self._origin().ptr,
-                                               self._ini_table.shape[0], self._ini_first, dptr(out)))
-            return out
-        check(lib.ginsim_process_stats(self.ctx.handle, self._bufs['traj_' + algo].ptr, self._bufs['ref_nav'].ptr,
-                                       self.n, self.runs, int(first_sample), int(bool(pos_ned)), dptr(out)))
-        return out
-
-    def error_curve(self, algo, samples=None, pos_ned=False):
-        """The error-growth curve of this batch: the across-run record (CurveResult) of the error at each of `samples` (sample
-        indices in any order, repeats allowed; None: every sample).  Needs the trajectories (keep_traj=True)."""
-        if not self.keep_traj:
-            raise ValueError('process-error statistics need the trajectories (keep_traj=True)')
-        if 'ref_nav' not in self._bufs:
-            self._bufs['ref_nav'] = self.ctx.upload(self._ref_nav)
-        if samples is None:
-            idx, m = None, self.n
-        else:
-            ids = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
-            idx, m = ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size
-        out = np.empty((max(m, 1), 9, 4))
-        traj, ref = self._bufs['traj_' + algo].ptr, self._bufs['ref_nav'].ptr
-        if self.precision == 'f32':     # float series, positions as displacement from the run's initial position
-            org = self._origin().ptr
-            check(self.ctx.retry_oom(lambda: lib.ginsim_error_curve_f32(self.ctx.handle, traj, ref, self.n, self.runs, idx, m,
-                                                                        int(bool(pos_ned)), org, self._ini_table.shape[0],
-                                                                        self._ini_first, dptr(out))))
-        else:
-            check(self.ctx.retry_oom(lambda: lib.ginsim_error_curve(self.ctx.handle, traj, ref, self.n, self.runs, idx, m,
-                                                                    int(bool(pos_ned)), dptr(out))))
-        return CurveResult(out)
-
-    def _origin(self):
-        """Device table of the initial positions the fp32 displacement series are relative to ([n_ini][3]: ECEF for ref_frame 1,
-        LLA for ref_frame 0; free_integration.py:96-98 / :127-128)."""
-        if '_origin' not in self._bufs:
-            from gnss_ins_sim.geoparams import geoparams
-            lla = self._ini_table[:, 0:3]
-            self._bufs['_origin'] = self.ctx.upload(np.ascontiguousarray(geoparams.lla2ecef(lla) if self._ref_frame == 1 else lla))
-        return self._bufs['_origin']
-
-    def stats_from_traj(self, algo, pos_ned=False):
-        """End-point statistics recomputed on the device from the kept trajectories (used for extra_opt='ned')."""
-        if not self.keep_traj:
-            raise ValueError('needs the trajectories (keep_traj=True)')
-        if 'ref_nav' not in self._bufs:
-            self._bufs['ref_nav'] = self.ctx.upload(self._ref_nav)
-        s = _lib.Stats()
-        if self.precision == 'f32':
-            check(lib.ginsim_end_stats_from_traj_f32(self.ctx.handle, self._bufs['traj_' + algo].ptr, self._bufs['ref_nav'].ptr, self.n,
-                                                     self.runs, int(bool(pos_ned)), self._origin().ptr, self._ini_table.shape[0],
-                                                     self._ini_first, C.byref(s)))
-            return StatsResult(s)
-        check(lib.ginsim_end_stats_from_traj(self.ctx.handle, self._bufs['traj_' + algo].ptr, self._bufs['ref_nav'].ptr,
-                                             self.n, self.runs, int(bool(pos_ned)), C.byref(s)))
-        return StatsResult(s)
-
     def end_errors(self, algo, ned=False):
         """(runs, 9) end-point errors [att3 wrapped, pos3, vel3]; ned=True: the NED record (end_ned=True)."""
         return self.ctx.download(self._bufs[('endned_' if ned else 'end_') + algo], (9, self.runs)).T.copy()
 
-    def _gather(self, ptr, ncomp, run_ids, series_major=False):
-        ids = np.ascontiguousarray(np.asarray(run_ids, dtype=np.int64).reshape(-1))
-        out = np.empty((ids.size, self.n, ncomp))
+    def _gather_runs(self, ptr, ncomp, run_ids, series_major=False):
         fn = lib.ginsim_gather_runs_f32 if self.precision == 'f32' else (lib.ginsim_gather_series if series_major else lib.ginsim_gather_runs)
-        check(self.ctx.retry_oom(lambda: fn(self.ctx.handle, ptr, ncomp, self.n, self.runs, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            ids.size, dptr(out))))
-        return out
+        return self._gather(ptr, self.n, ncomp, run_ids, fn)
 
     def sensors(self, name, run_ids):
         """Sensor series of selected runs: 'accel'/'gyro' -> (k,n,3); 'odo' -> (k,n)."""
@@ -1012,8 +935,8 @@ class MonteCarloJob(object):
             raise ValueError('sensor series were not kept (keep_sensors=False)')
         sm = self.sensor_layout == 'series'
         if name == 'odo':
-            return self._gather(self._bufs['odo'].ptr, 1, run_ids, sm)[:, :, 0]
-        return self._gather(self._bufs[name].ptr, 3, run_ids, sm)
+            return self._gather_runs(self._bufs['odo'].ptr, 1, run_ids, sm)[:, :, 0]
+        return self._gather_runs(self._bufs[name].ptr, 3, run_ids, sm)
 
     def trajectories(self, algo, run_ids, displacement=False):
         """(att, pos, vel) of selected runs, each (k,n,3).  displacement=True (fp32 jobs): the position series as the kernel
@@ -1022,7 +945,7 @@ class MonteCarloJob(object):
             raise ValueError('trajectories were not kept (keep_traj=False)')
         base = self._bufs['traj_' + algo].ptr
         plane = self.n * self.runs * self._esize
-        att, pos, vel = (self._gather(base + 3 * k * plane, 3, run_ids) for k in range(3))
+        att, pos, vel = (self._gather_runs(base + 3 * k * plane, 3, run_ids) for k in range(3))
         if self.precision == 'f32' and not displacement:         # the device series is the displacement from the run's initial position
             from gnss_ins_sim.geoparams import geoparams
             ids = np.asarray(run_ids, dtype=np.int64).reshape(-1)
@@ -1053,13 +976,8 @@ class MonteCarloJob(object):
         self.psd_given_on_grid = getattr(self, 'psd_given_on_grid', False) or on_grid
         return v
 
-    def release(self):
-        for b in self._bufs.values():
-            b.free()
-        self._bufs = {}
 
-
-class AuxSensorJob(object):
+class AuxSensorJob(BatchJob):
     """GPS / magnetometer measurements of a Monte-Carlo batch (pathgen.gps_gen, mag_gen), kept in HBM as
     gps[6][m][runs] and mag[3][n][runs].  Same Philox streams as the reference-injection shim (oracle/ref_shim.py)."""
 
@@ -1101,17 +1019,8 @@ class AuxSensorJob(object):
 
     def series(self, name, run_ids):
         """'gps' -> (k, m, 6); 'mag' -> (k, n, 3)."""
-        ids = np.ascontiguousarray(np.asarray(run_ids, dtype=np.int64).reshape(-1))
         ncomp, length = (6, self.m) if name == 'gps' else (3, self.n)
-        out = np.empty((ids.size, length, ncomp))
-        check(self.ctx.retry_oom(lambda: lib.ginsim_gather_runs(self.ctx.handle, self._bufs[name].ptr, ncomp, length, self.runs,
-                                                                ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size, dptr(out))))
-        return out
-
-    def release(self):
-        for b in self._bufs.values():
-            b.free()
-        self._bufs = {}
+        return self._gather(self._bufs[name].ptr, length, ncomp, run_ids)
 
 
 def pinned_empty(ctx, shape, dtype=np.float64):

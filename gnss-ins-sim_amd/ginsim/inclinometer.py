@@ -18,14 +18,15 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check
-from .engine import DeviceView, StatsResult, sensor_model, vibration
+from .engine import DeviceView, StatsResult
+from .job import BatchJob
 
 INCL_BITS = {'mahony': _lib.INCL_MAHONY, 'tilt': _lib.INCL_TILT}
 INCL_SLOT = {'mahony': 0, 'tilt': 1}
 MAHONY_DEFAULTS = dict(kp_high=1.0, kp_low=0.01, ki_high=0.5, ki_low=0.001, innovation_limit=0.1)   # inclinometer_mahony.py:35-40
 
 
-class InclinometerJob(object):
+class InclinometerJob(BatchJob):
     """One batch of runs of the inclinometer plugins on one device.
 
     truth: dict with 'ref_accel', 'ref_gyro' (n, 3) and, for statistics, 'ref_att' (n, 3); the other keys MonteCarloJob takes
@@ -41,7 +42,6 @@ class InclinometerJob(object):
     """
 
     keep_traj = False           # as a statistics job of Sim's _McResults: the statistics are the online ones
-    precision = 'f64'
     proc_ned = False
 
     def __init__(self, ctx, fs, truth, accel_err, gyro_err, runs, algos=('mahony', 'tilt'), gains=None, dt=None, bias0=(0.0, 0.0, 0.0),
@@ -62,27 +62,13 @@ class InclinometerJob(object):
         self.launched = []          # runs launched per pass
         self._bufs = {}
         m = self.mc = _lib.McParams()
-        m.n, m.runs, m.run_offset, m.seed = self.n, self.runs, int(run_offset), int(seed) & (2 ** 64 - 1)
-        m.fs, m.block_threads = float(fs), int(block_threads)
+        self._fill_batch(m, fs, run_offset, seed)
+        m.block_threads = int(block_threads)
+        self._sensor_source(m, fs, accel_err, gyro_err, vib_accel, vib_gyro, given, (('accel', 3, self.n), ('gyro', 3, self.n)), 'inclinometer')
         if given is None:
-            m.accel = sensor_model(accel_err, 'vrw', fs)
-            m.gyro = sensor_model(gyro_err, 'arw', fs)
-            for v in (vib_accel, vib_gyro):
-                if v is not None and str(v['type']).lower() == 'psd':
-                    raise NotImplementedError("the 'psd' vibration is not a term of the inclinometer kernel (random and sinusoidal are)")
-            m.vib_accel = vibration(vib_accel, float(fs), False)
-            m.vib_gyro = vibration(vib_gyro, float(fs), True)
             self._bufs['inputs'] = ctx.upload(np.concatenate([np.asarray(truth['ref_accel'], dtype=np.float64).reshape(-1),
                                                               np.asarray(truth['ref_gyro'], dtype=np.float64).reshape(-1)]))
             m.ref_accel, m.ref_gyro = self._bufs['inputs'].ptr, self._bufs['inputs'].at(3 * self.n * 8)
-        else:
-            if vib_accel is not None or vib_gyro is not None:
-                raise ValueError('given sensors: a vibration model cannot be added to sensor series that already exist')
-            for k in ('accel', 'gyro'):
-                if k not in given or given[k].nbytes < 3 * self.n * self.runs * 8 or getattr(given[k], 'layout', 'runs') != 'runs':
-                    raise ValueError('given sensors: %r missing, too small or not [axis][sample][run]' % (k,))
-            m.given_sensors, m.in_accel, m.in_gyro = 1, given['accel'].ptr, given['gyro'].ptr
-            self._given = given
         p = self.params = _lib.InclParams()
         p.algo_mask = sum(INCL_BITS[a] for a in self.algos)
         g = dict(MAHONY_DEFAULTS, **(gains or {}))
@@ -113,9 +99,7 @@ class InclinometerJob(object):
             if 'mahony' in self.algos:
                 names += [('wb', 3), ('ab', 3)]
             total = sum(c for _, c in names) * plane
-            use_placed = (total >= ctx.PLACED_MIN_JOB) if placed is None else bool(placed)
-            use_placed = bool(use_placed and ctx.placed_reserve(total))
-            self._bufs['series'] = ctx.malloc(total, placed=use_placed)
+            self._bufs['series'] = ctx.malloc(total, placed=self._use_placed(placed, total))
             off = 0
             for nm, c in names:
                 self._bufs[nm] = DeviceView(self._bufs['series'], off, c * plane)
@@ -141,15 +125,10 @@ class InclinometerJob(object):
 
     def _launch(self, ids=None):
         p = self.params
-        if ids is None:
-            p.run_list, p.n_list = None, self.runs
-        else:
-            ids = np.ascontiguousarray(ids, dtype=np.int64)
-            check(lib.ginsim_memcpy_h2d(self.ctx.handle, self._list, ids.ctypes.data, ids.nbytes))
-            p.run_list, p.n_list = self._list, ids.size
+        count = self._put_run_list(p, ids)
         check(self.ctx.retry_oom(lambda: lib.ginsim_incl_run(self.ctx.handle, C.byref(self.mc), C.byref(p))))
         self.passes += 1
-        self.launched.append(self.runs if ids is None else int(ids.size))
+        self.launched.append(count)
 
     def _put_start(self, start):
         a = np.ascontiguousarray(start.T)                           # (R, 3) -> [3][R]
@@ -227,20 +206,7 @@ class InclinometerJob(object):
         """Kept series of selected runs: 'quat_<algo>' (k, n, 4), 'euler_<algo>', 'wb', 'ab' (k, n, 3)."""
         if not self.keep:
             raise ValueError('the series were not kept (keep=True)')
-        C_ = 4 if name.startswith('quat_') else 3
-        ids = np.ascontiguousarray(np.asarray(run_ids, dtype=np.int64).reshape(-1))
-        out = np.empty((ids.size, self.n, C_))
-        check(self.ctx.retry_oom(lambda: lib.ginsim_gather_runs(self.ctx.handle, self._bufs[name].ptr, C_, self.n, self.runs,
-                                                                ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size, _lib.dptr(out))))
-        return out
-
-    def buffer(self, name):
-        return self._bufs[name]
-
-    def release(self):
-        for b in self._bufs.values():
-            b.free()
-        self._bufs = {}
+        return self._gather(self._bufs[name].ptr, self.n, 4 if name.startswith('quat_') else 3, run_ids)
 
 
 def ctx_memset(ctx, buf, nbytes):

@@ -13,8 +13,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import lib, check, dptr
-from .engine import DeviceView, StatsResult, CurveResult, ConsistencyResult, ini_table, sensor_model, vibration
+from ._lib import lib, check
+from .engine import DeviceView, StatsResult, ConsistencyResult, ini_table
+from .job import BatchJob
 
 P0_FLOOR = (1e-3, 1e-3, 1e-5, 1e-7, 1e-5)      # m, m/s, rad, rad/s, m/s^2
 
@@ -105,7 +106,7 @@ def aiding_model(odo_err, aid):
     return out
 
 
-class InsLooseJob(object):
+class InsLooseJob(BatchJob):
     """One batch of runs of the loosely coupled filter on one device.
 
     truth: dict with 'ref_accel', 'ref_gyro', 'ref_att', 'ref_pos', 'ref_vel' (n, 3) and 'ref_gps' (m, 6), 'gps_time' (m,)
@@ -125,7 +126,6 @@ class InsLooseJob(object):
     across its runs (consistency()): the filter's P against its error in its own coordinates.  Not together with proc_first.
     """
 
-    precision = 'f64'
     algos = ('loose',)
 
     def __init__(self, ctx, fs, ref_frame, truth, accel_err, gyro_err, gps_err, ini, runs, seed=0, run_offset=0, ini_first=0,
@@ -143,8 +143,8 @@ class InsLooseJob(object):
         self._bufs = {}
         self._ref_frame = int(ref_frame)
         m = self.mc = _lib.McParams()
-        m.n, m.runs, m.run_offset, m.seed = self.n, self.runs, int(run_offset), int(seed) & (2 ** 64 - 1)
-        m.fs, m.ref_frame, m.earth_rot, m.end_pos_ned = float(fs), int(ref_frame), int(bool(earth_rot)), int(bool(end_pos_ned))
+        self._fill_batch(m, fs, run_offset, seed)
+        m.ref_frame, m.earth_rot, m.end_pos_ned = int(ref_frame), int(bool(earth_rot)), int(bool(end_pos_ned))
         table, has_g = ini_table(ini)
         m.n_ini, m.ini_first, m.ini_has_g = table.shape[0], int(ini_first), int(has_g)
         ref_gps = np.ascontiguousarray(truth['ref_gps'], dtype=np.float64).reshape(-1, 6) if 'ref_gps' in truth else np.zeros((0, 6))
@@ -169,14 +169,9 @@ class InsLooseJob(object):
         self._ref_nav = np.ascontiguousarray(np.concatenate([truth['ref_att'], truth['ref_pos'], truth['ref_vel']], axis=1))
         m.ref_end[:] = [float(x) for x in self._ref_nav[-1]]
         parts = [table.reshape(-1)]
+        need = (('accel', 3, self.n), ('gyro', 3, self.n), ('gps', 6, self.m)) + ((('odo', 1, self.n),) if use_odo else ())
+        self._sensor_source(m, fs, accel_err, gyro_err, vib_accel, vib_gyro, given, need, 'filter')
         if given is None:
-            m.accel = sensor_model(accel_err, 'vrw', fs)
-            m.gyro = sensor_model(gyro_err, 'arw', fs)
-            for v in (vib_accel, vib_gyro):
-                if v is not None and str(v['type']).lower() == 'psd':
-                    raise NotImplementedError("the 'psd' vibration is not a term of the filter kernel (random and sinusoidal are)")
-            m.vib_accel = vibration(vib_accel, float(fs), False)
-            m.vib_gyro = vibration(vib_gyro, float(fs), True)
             parts += [np.asarray(truth['ref_accel'], dtype=np.float64).reshape(-1), np.asarray(truth['ref_gyro'], dtype=np.float64).reshape(-1),
                       ref_gps.reshape(-1)]
             if self.m:
@@ -190,16 +185,9 @@ class InsLooseJob(object):
                 m.odo_scale, m.odo_stdv = float(odo_err['scale']), float(odo_err['stdv'])
                 parts.append(ref_odo)
         else:
-            if vib_accel is not None or vib_gyro is not None:
-                raise ValueError('given sensors: a vibration model cannot be added to sensor series that already exist')
-            for k, c, length in (('accel', 3, self.n), ('gyro', 3, self.n), ('gps', 6, self.m)) + ((('odo', 1, self.n),) if use_odo else ()):
-                if length and (k not in given or given[k].nbytes < c * length * self.runs * 8 or getattr(given[k], 'layout', 'runs') != 'runs'):
-                    raise ValueError('given sensors: %r missing, too small or not [component][sample][run]' % (k,))
-            m.given_sensors, m.in_accel, m.in_gyro = 1, given['accel'].ptr, given['gyro'].ptr
             p.in_gps = given['gps'].ptr if self.m else None
             if use_odo:
                 m.in_odo = given['odo'].ptr
-            self._given = given
         offs = np.cumsum([0] + [q.size for q in parts]) * 8
         self._bufs['inputs'] = ctx.upload(np.concatenate(parts))
         m.ini = self._bufs['inputs'].at(offs[0])
@@ -220,16 +208,13 @@ class InsLooseJob(object):
                 raise ValueError('proc_first must be a sample index of the run')
             if proc_ned and int(ref_frame) != 0:
                 raise ValueError('NED position errors exist in ref_frame 0 only')
-            self._bufs['ref_nav'] = ctx.upload(self._ref_nav)
+            m.ref_nav, m.proc_first, m.proc_pos_ned = self._nav(), int(proc_first), int(bool(proc_ned))
             self._bufs['proc'] = ctx.malloc(27 * R * 8)
-            m.ref_nav, m.proc_first, m.proc_pos_ned = self._bufs['ref_nav'].ptr, int(proc_first), int(bool(proc_ned))
             p.out_proc = self._bufs['proc'].ptr
         if self.keep_traj:
             plane = self.n * R * 8
             total = 15 * plane
-            use_placed = (total >= ctx.PLACED_MIN_JOB) if placed is None else bool(placed)
-            use_placed = bool(use_placed and ctx.placed_reserve(total))
-            self._bufs['series'] = ctx.malloc(total, placed=use_placed)
+            self._bufs['series'] = ctx.malloc(total, placed=self._use_placed(placed, total))
             self._bufs['traj_loose'] = DeviceView(self._bufs['series'], 0, 9 * plane)
             self._bufs['wb'] = DeviceView(self._bufs['series'], 9 * plane, 3 * plane)
             self._bufs['ab'] = DeviceView(self._bufs['series'], 12 * plane, 3 * plane)
@@ -270,12 +255,7 @@ class InsLooseJob(object):
         """Enqueue the kernel (asynchronous).  ids: launch these runs only (lane i filters run ids[i]); the others keep what they hold,
         and the consistency record is over the listed runs."""
         p = self.params
-        if ids is None:
-            p.run_list, p.n_list = None, self.runs
-        else:
-            ids = np.ascontiguousarray(ids, dtype=np.int64)
-            check(lib.ginsim_memcpy_h2d(self.ctx.handle, self._list, ids.ctypes.data, ids.nbytes))
-            p.run_list, p.n_list = self._list, ids.size
+        self._put_run_list(p, ids)
         if self.cons is not None:
             check(self.ctx.retry_oom(lambda: lib.ginsim_loose_cons_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.cons))))
         else:
@@ -306,15 +286,6 @@ class InsLooseJob(object):
         """(runs, 9) end-point errors [att3 wrapped, pos3, vel3]; ned=True: the NED record (end_ned=True)."""
         return self.ctx.download(self._end_ptr(ned), (9, self.runs)).T.copy()
 
-    def stats_from_traj(self, algo='loose', pos_ned=False):
-        """End-point statistics recomputed on the device from the kept trajectories (extra_opt='ned')."""
-        if not self.keep_traj:
-            raise ValueError('needs the trajectories (keep_traj=True)')
-        s = _lib.Stats()
-        check(lib.ginsim_end_stats_from_traj(self.ctx.handle, self._bufs['traj_loose'].ptr, self._nav(), self.n, self.runs,
-                                             int(bool(pos_ned)), C.byref(s)))
-        return StatsResult(s)
-
     def process_stats_online(self, algo='loose'):
         """(runs, 3, 9) = max|e|, mean, std of the error over samples >= proc_first."""
         if self.proc_first is None:
@@ -343,61 +314,15 @@ class InsLooseJob(object):
         rec = self.ctx.download(self._bufs['cons'], (self._cons_samples.size, _lib.CONS_RECORD))
         return ConsistencyResult(rec[self._cons_back])
 
-    def _gather(self, ptr, ncomp, run_ids):
-        ids = np.ascontiguousarray(np.asarray(run_ids, dtype=np.int64).reshape(-1))
-        out = np.empty((ids.size, self.n, ncomp))
-        check(self.ctx.retry_oom(lambda: lib.ginsim_gather_runs(self.ctx.handle, ptr, ncomp, self.n, self.runs,
-                                                                ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size, dptr(out))))
-        return out
-
     def series(self, name, run_ids):
         """Kept series of selected runs, each (k, n, 3): 'att', 'pos', 'vel', 'wb', 'ab'."""
         if not self.keep_traj:
             raise ValueError('the series were not kept (keep_traj=True)')
         plane = self.n * self.runs * 8
         if name in ('wb', 'ab'):
-            return self._gather(self._bufs[name].ptr, 3, run_ids)
+            return self._gather(self._bufs[name].ptr, self.n, 3, run_ids)
         k = ('att', 'pos', 'vel').index(name)
-        return self._gather(self._bufs['traj_loose'].ptr + 3 * k * plane, 3, run_ids)
+        return self._gather(self._bufs['traj_loose'].ptr + 3 * k * plane, self.n, 3, run_ids)
 
     def trajectories(self, algo='loose', run_ids=(0,), displacement=False):
         return tuple(self.series(k, run_ids) for k in ('att', 'pos', 'vel'))
-
-    def _nav(self):
-        if 'ref_nav' not in self._bufs:
-            self._bufs['ref_nav'] = self.ctx.upload(self._ref_nav)
-        return self._bufs['ref_nav'].ptr
-
-    def process_stats(self, algo='loose', first_sample=0, pos_ned=False):
-        """(runs, 3, 9) from the kept trajectories (ginsim_process_stats)."""
-        if not self.keep_traj:
-            raise ValueError('process-error statistics need the trajectories (keep_traj=True)')
-        out = np.empty((self.runs, 3, 9))
-        check(lib.ginsim_process_stats(self.ctx.handle, self._bufs['traj_loose'].ptr, self._nav(), self.n, self.runs, int(first_sample),
-                                       int(bool(pos_ned)), dptr(out)))
-        return out
-
-    def error_curve(self, algo='loose', samples=None, pos_ned=False):
-        """The across-run record (CurveResult) of the error at each of `samples` (None: every sample), from the kept planes."""
-        if not self.keep_traj:
-            raise ValueError('an error-growth curve needs the trajectories (keep_traj=True): this job kept statistics only')
-        if samples is None:
-            idx, m = None, self.n
-        else:
-            ids = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
-            idx, m = ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size
-        out = np.empty((max(m, 1), 9, 4))
-        traj, ref = self._bufs['traj_loose'].ptr, self._nav()
-        check(self.ctx.retry_oom(lambda: lib.ginsim_error_curve(self.ctx.handle, traj, ref, self.n, self.runs, idx, m,
-                                                                int(bool(pos_ned)), dptr(out))))
-        return CurveResult(out)
-
-    def buffer(self, name):
-        if name not in self._bufs:
-            raise ValueError('%r was not kept by this job' % (name,))
-        return self._bufs[name]
-
-    def release(self):
-        for b in self._bufs.values():
-            b.free()
-        self._bufs = {}

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check
+from .job import BatchJob
 
 
 def check_segments(segments, n):
@@ -30,7 +31,7 @@ def check_segments(segments, n):
     return [v for ab in seg for v in ab]
 
 
-class MagCalJob(object):
+class MagCalJob(BatchJob):
     """One batch of runs of the magnetometer calibration on one device.
 
     ref_mag: (n, 3) true magnetic field in the body frame [uT] (truth['ref_mag']); mag_err: {'si' (3, 3), 'hi', 'std'} as
@@ -74,9 +75,7 @@ class MagCalJob(object):
         p.out_si, p.out_hi = self._bufs['results'].ptr, self._bufs['results'].at(9 * R * 8)
         if keep:
             total = 3 * self.rows * R * 8
-            use_placed = (total >= ctx.PLACED_MIN_JOB) if placed is None else bool(placed)
-            use_placed = bool(use_placed and ctx.placed_reserve(total))
-            self._bufs['mag_cal'] = ctx.malloc(total, placed=use_placed)
+            self._bufs['mag_cal'] = ctx.malloc(total, placed=self._use_placed(placed, total))
             p.out_cal = self._bufs['mag_cal'].ptr
 
     @property
@@ -114,11 +113,7 @@ class MagCalJob(object):
         """(k, nx + ny + nz, 3): the calibrated rows of selected runs, the three ranges stacked (kept jobs)."""
         if not self.keep:
             raise ValueError('mag_cal was not kept (keep=True)')
-        ids = np.ascontiguousarray(np.asarray(run_ids, dtype=np.int64).reshape(-1))
-        out = np.empty((ids.size, self.rows, 3))
-        check(self.ctx.retry_oom(lambda: lib.ginsim_gather_runs(self.ctx.handle, self._bufs['mag_cal'].ptr, 3, self.rows, self.runs,
-                                                                ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size, _lib.dptr(out))))
-        return out
+        return self._gather(self._bufs['mag_cal'].ptr, self.rows, 3, run_ids)
 
     def stats(self):
         """{'soft_iron': {'mean', 'std', 'min', 'max': (3, 3)}, 'hard_iron': {...: (4,)}} over the runs (std with ddof 0).  Host
@@ -130,11 +125,3 @@ class MagCalJob(object):
             out[name] = {'mean': a.mean(axis=1).reshape(shape), 'std': a.std(axis=1).reshape(shape),
                          'min': a.min(axis=1).reshape(shape), 'max': a.max(axis=1).reshape(shape)}
         return out
-
-    def buffer(self, name):
-        return self._bufs[name]
-
-    def release(self):
-        for b in self._bufs.values():
-            b.free()
-        self._bufs = {}
