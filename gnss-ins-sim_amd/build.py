@@ -54,6 +54,9 @@ SOURCES = [
     # the same lane once more with consistency checkpoints (ins_loose.hpp, CONS): the same flags, its own resource report
     # (tests/test_ins_loose_cons_oracle.py reads it)
     ('ins_loose_cons.hip', MC_FLAGS),
+    # the same lane with the magnetometer block (ins_loose.hpp, MAG): the same flags -- the magnetometer synthesis must give
+    # aux_mag_kernel's bits (mag_synth.hpp, -ffp-contract=on) -- and its own resource report (tests/test_ins_loose_mag_oracle.py reads it)
+    ('ins_loose_mag.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),

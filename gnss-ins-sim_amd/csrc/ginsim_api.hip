@@ -602,9 +602,11 @@ int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_para
     return GINSIM_OK;
 }
 
-// The launch of the filter, with checkpoints when cons is not NULL (checked by the caller).  The stamps and the visibility flags of
+// The launch of the filter, with checkpoints when cons is not NULL or with the magnetometer block when mag is not NULL (at most one
+// of the two; both checked by the caller).  The stamps and the visibility flags of
 // the fixes and the checkpoint samples are copied next to each other into the context's scratch.
-static int loose_launch(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons) {
+static int loose_launch(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
+                        const ginsim_loose_mag_params* mag = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
     int64_t* d_stamp = nullptr;
     int32_t* d_vis = nullptr;
@@ -628,6 +630,7 @@ static int loose_launch(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_
         }
     }
     if (cons) HIP_TRY(launch_loose_cons(*mc, *p, *cons, d_stamp, d_vis, d_cons, c->stream, nullptr, 0));
+    else if (mag) HIP_TRY(launch_loose_mag(*mc, *p, *mag, d_stamp, d_vis, c->stream, nullptr, 0));
     else HIP_TRY(launch_loose(*mc, *p, d_stamp, d_vis, c->stream, nullptr, 0));
     return GINSIM_OK;
 }
@@ -676,6 +679,50 @@ int ginsim_loose_cons_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsi
     rc = check_loose_cons(mc, p, cons);
     if (rc) return rc;
     return loose_launch(c, mc, p, cons->cons_m > 0 ? cons : nullptr);
+}
+
+// the magnetometer block of a launch whose other two blocks passed check_loose_params
+static int check_loose_mag(const ginsim_mc_params* m, const ginsim_loose_mag_params* g) {
+    REQUIRE(g, "loose_mag_run: NULL argument");
+    REQUIRE(g->mag_every >= 0, "loose_mag_run: mag_every=%lld must be >= 0", (long long)g->mag_every);
+    if (g->mag_every == 0) return GINSIM_OK;
+    if (m->given_sensors) {
+        REQUIRE(g->in_mag, "loose_mag_run: the magnetometer block with given_sensors needs in_mag");
+    } else {
+        REQUIRE(g->ref_mag, "loose_mag_run: the magnetometer block needs ref_mag");
+        for (int k = 0; k < 9; ++k) REQUIRE(std::isfinite(g->mag_si[k]), "loose_mag_run: mag_si must be finite");
+        for (int k = 0; k < 3; ++k)
+            REQUIRE(std::isfinite(g->mag_hi[k]) && std::isfinite(g->mag_std[k]), "loose_mag_run: mag_hi / mag_std must be finite");
+    }
+    for (int k = 0; k < 9; ++k) REQUIRE(std::isfinite(g->cal_si[k]), "loose_mag_run: cal_si must be finite");
+    for (int k = 0; k < 3; ++k) {
+        REQUIRE(std::isfinite(g->mag_n[k]) && std::isfinite(g->cal_hi[k]), "loose_mag_run: mag_n / cal_hi must be finite");
+        REQUIRE(std::isfinite(g->r_mag[k]) && g->r_mag[k] > 0.0, "loose_mag_run: r_mag must be positive");
+    }
+    REQUIRE(g->mag_n[0] != 0.0 || g->mag_n[1] != 0.0 || g->mag_n[2] != 0.0, "loose_mag_run: mag_n must not be the zero vector");
+    return GINSIM_OK;
+}
+
+int ginsim_loose_mag_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
+                                 char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_mag_kernel_name: bad arguments");
+    int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    rc = check_loose_mag(mc, mag);
+    if (rc) return rc;
+    buf[0] = 0;
+    if (mag->mag_every > 0) (void)launch_loose_mag(*mc, *p, *mag, nullptr, nullptr, nullptr, buf, cap);
+    else (void)launch_loose(*mc, *p, nullptr, nullptr, nullptr, buf, cap);
+    return GINSIM_OK;
+}
+
+int ginsim_loose_mag_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag) {
+    REQUIRE(c, "loose_mag_run: NULL argument");
+    int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    rc = check_loose_mag(mc, mag);
+    if (rc) return rc;
+    return loose_launch(c, mc, p, nullptr, mag->mag_every > 0 ? mag : nullptr);
 }
 
 int ginsim_aux_sensors(ginsim_ctx* c, const ginsim_aux_params* p) {

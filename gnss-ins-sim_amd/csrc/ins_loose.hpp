@@ -3,6 +3,7 @@
 // the feedback both end with, and the time loop (loose_body), whose AID = false form is loose_kernel as it was; and, for
 // ins_loose_cons.hip's loose_cons_kernel, the consistency checkpoint (loose_checkpoint) behind the flag CONS.  The account of
 // the register budget that put P into LDS is in ins_loose.hip's header; the aiding block's equations are in ins_loose_aided.hip's.
+// For ins_loose_mag.hip's loose_mag_kernel: the magnetometer block (loose_mag) behind the flag MAG; its equations are in that file's header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
@@ -10,6 +11,7 @@
 #include "philox.hpp"
 #include "sensor_synth.hpp"
 #include "gps_synth.hpp"
+#include "mag_synth.hpp"
 #include "nav.hpp"
 
 namespace ginsim {
@@ -153,6 +155,24 @@ struct Cov {
             for (int c = a; c < kLooseStates; ++c) at(a, c) -= ph[a] * ph[c] * inv;
         }
     }
+    // the same with the row h on the psi states 6-8 only (the magnetometer rows): three products per element of Ph
+    __device__ __forceinline__ void update_row_psi(const double (&h)[3], double z, double rv, double (&x)[kLooseStates]) {
+        double ph[kLooseStates];
+#pragma unroll
+        for (int k = 0; k < kLooseStates; ++k) ph[k] = get(k, 6) * h[0] + get(k, 7) * h[1] + get(k, 8) * h[2];
+        double s = rv, hx = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { s += h[c] * ph[6 + c]; hx += h[c] * x[6 + c]; }
+        const double inv = 1.0 / s;
+        const double g = (z - hx) * inv;
+#pragma unroll
+        for (int k = 0; k < kLooseStates; ++k) x[k] += ph[k] * g;
+#pragma unroll
+        for (int a = 0; a < kLooseStates; ++a) {
+#pragma unroll
+            for (int c = a; c < kLooseStates; ++c) at(a, c) -= ph[a] * ph[c] * inv;
+        }
+    }
 };
 
 // C = body -> navigation of the attitude (the matrix of Att::to_nav)
@@ -169,6 +189,18 @@ __device__ __forceinline__ loose_ptr loose_params() {
     bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
     return (loose_ptr)(p + sizeof(ginsim_mc_params));
+}
+
+// loose_mag_kernel's fifth argument, the magnetometer block by value: it follows the two parameter blocks and the two pointers
+// (stamp, visible) in the kernarg segment
+typedef const ginsim_loose_mag_params __attribute__((address_space(4))) * loose_mag_ptr;
+static_assert(sizeof(ginsim_mc_params) % 8 == 0 && sizeof(ginsim_loose_params) % 8 == 0 && alignof(ginsim_loose_mag_params) == 8,
+              "the kernarg offsets of loose_params() / loose_mag_params()");
+__device__ __forceinline__ loose_mag_ptr loose_mag_params() {
+    typedef const char __attribute__((address_space(4))) * bytes_ptr;
+    bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (loose_mag_ptr)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
 }
 
 // P <- Phi P Phi^T + Qd for the step from the attitude with body -> navigation matrix C and bias-corrected specific force f^n
@@ -288,6 +320,40 @@ __device__ __forceinline__ void loose_aid(Cov& P, Nav& s, Vec3& bg, Vec3& ba, do
     loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
 }
 
+// One magnetometer block (ins_loose_mag.hip's header): the three rows in ascending order from x = 0; then the feedback.
+// D = C^T, z and every row are formed from the state before the first row.  mag: the raw sample of this lane.
+template <int RF>
+__device__ __forceinline__ void loose_mag(Cov& P, Nav& s, Vec3& bg, Vec3& ba, const double (&mag)[3]) {
+    const loose_mag_ptr mp = loose_mag_params();
+    double C[3][3];
+    body_to_nav(s.att, C);
+    const double m[3] = {mp->mag_n[0], mp->mag_n[1], mp->mag_n[2]};
+    double h[3][3], z[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {               // row i of D is column i of C; the psi part is -(D [m x])[i,:] = m x D[i,:]
+        const double d0 = C[0][i], d1 = C[1][i], d2 = C[2][i];
+        h[i][0] = m[1] * d2 - m[2] * d1;
+        h[i][1] = m[2] * d0 - m[0] * d2;
+        h[i][2] = m[0] * d1 - m[1] * d0;
+        const double cal = mp->cal_si[3 * i] * mag[0] + mp->cal_si[3 * i + 1] * mag[1] + mp->cal_si[3 * i + 2] * mag[2] - mp->cal_hi[i];
+        z[i] = (d0 * m[0] + d1 * m[1] + d2 * m[2]) - cal;
+    }
+    double mlat = 1.0, mlon = 1.0;
+    if (RF == 0) {
+        const Geo e = geo_param_sc(s.sl, s.cl, s.pos.z);
+        mlat = e.rm + s.pos.z;
+        mlon = (e.rn + s.pos.z) * e.cl;
+    }
+    double x[kLooseStates];
+#pragma unroll
+    for (int k = 0; k < kLooseStates; ++k) x[k] = 0.0;
+    phase_fence();
+    P.update_row_psi(h[0], z[0], loose_mag_params()->r_mag[0], x); phase_fence();
+    P.update_row_psi(h[1], z[1], loose_mag_params()->r_mag[1], x); phase_fence();
+    P.update_row_psi(h[2], z[2], loose_mag_params()->r_mag[2], x); phase_fence();
+    loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
+}
+
 // ---- consistency checkpoints (ins_loose_cons.hip)
 // What loose_cons_kernel passes to the lane next to the two parameter blocks: the DEVICE copy of the checkpoint samples, their
 // number and the wavefronts' partial records [wave][checkpoint][GINSIM_CONS_RECORD].  Not read unless CONS.
@@ -400,7 +466,10 @@ __device__ __forceinline__ void put3(double* base, int64_t plane, int64_t off, c
 // j > 0 with j % aid_every == 0, after a fix of the same sample and before the row is stored.  ntab: the kernel's static LDS for
 // the normal tables.  CONS: consistency checkpoints (loose_checkpoint) at the samples cq.sample[0 .. cq.m), on the state that row j reports:
 // after a fix and an aiding block of the same sample, before the row is stored.  CONS = false is the lane as it was.
-template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false>
+// MAG: the magnetometer block (loose_mag) at every sample j > 0 with j % mag_every == 0, after a fix and an aiding block of the same
+// sample, before a checkpoint and before the row is stored; its numbers are the kernel's fifth argument (loose_mag_params).  With
+// MAG an aid_mask of 0 fires no aiding block at all.  MAG = false is the lane as it was.
+template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false, bool MAG = false>
 __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const ginsim_loose_params& b, const int64_t* __restrict__ stamp,
                                            const int32_t* __restrict__ visible, uint32_t* ntab, const ConsArgs& cq = ConsArgs{}) {
     NormalTables tab{};
@@ -448,8 +517,11 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
     const bool ned = a.proc_pos_ned != 0;
     int64_t kf = 0;         // the next fix (wave-uniform)
     // the next aiding block (wave-uniform); a period of n or more never fires
-    const int64_t every = AID ? (b.aid_every < n ? b.aid_every : n) : 0;
+    const int64_t every = AID ? ((b.aid_every < n && !(MAG && b.aid_mask == 0)) ? b.aid_every : n) : 0;
     int64_t ja = every;
+    // the next magnetometer block (wave-uniform), a counter of its own; a period of n or more never fires
+    // (the period is read again from the kernarg segment at every block: one wave-uniform counter is all the loop holds)
+    int64_t jm = MAG ? (loose_mag_params()->mag_every < n ? loose_mag_params()->mag_every : n) : 0;
     int64_t kc = 0;         // the next checkpoint (wave-uniform)
 
     for (int64_t j = 0; j < n; ++j) {
@@ -488,6 +560,27 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
                 }
                 phase_fence();
                 loose_aid<RF>(P, s, bg, ba, odo, mask);
+                phase_fence();
+            }
+        }
+        if (MAG) {
+            if (j == jm) {
+                const loose_mag_ptr mp = loose_mag_params();
+                jm += mp->mag_every < n ? mp->mag_every : n;
+                double mag[3];
+                if (GIVEN) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) mag[c] = mp->in_mag[(c * n + j) * runs + r];
+                } else {                // the sample ginsim_aux_sensors stores in out_mag (aux_sensors.hip, mag_synth.hpp)
+                    double z[3];
+                    mag_normals(key, (uint32_t)j, tab, z);
+                    const uniform_ptr rm = as_uniform(mp->ref_mag);
+                    const double v[3] = {rm[3 * j] + mp->mag_hi[0], rm[3 * j + 1] + mp->mag_hi[1], rm[3 * j + 2] + mp->mag_hi[2]};
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) mag[c] = mag_axis(mp->mag_si + 3 * c, v, mp->mag_std[c], z[c]);
+                }
+                phase_fence();
+                loose_mag<RF>(P, s, bg, ba, mag);
                 phase_fence();
             }
         }

@@ -45,6 +45,10 @@ hipError_t launch_loose_aided(const ginsim_mc_params& p, const ginsim_loose_para
 hipError_t launch_loose_cons(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_cons_params& c, const int64_t* stamp,
                              const int32_t* visible, const int64_t* samples, hipStream_t stream, char* name, size_t cap);
 
+// ins_loose_mag.hip: the filter with the magnetometer block (g.mag_every > 0)
+hipError_t launch_loose_mag(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_mag_params& g, const int64_t* stamp,
+                            const int32_t* visible, hipStream_t stream, char* name, size_t cap);
+
 // aux_sensors.hip
 hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s);
 

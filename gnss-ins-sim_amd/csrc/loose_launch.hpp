@@ -1,4 +1,4 @@
-// The host-side launch of the loose family (ins_loose.hip, ins_loose_aided.hip, ins_loose_cons.hip): each file defines its own
+// The host-side launch of the loose family (ins_loose.hip, ins_loose_aided.hip, ins_loose_cons.hip, ins_loose_mag.hip): each file defines its own
 // __global__ wrapper of loose_body and hands its instantiations to launch_loose_trio in threes.
 #pragma once
 #include <hip/hip_runtime.h>

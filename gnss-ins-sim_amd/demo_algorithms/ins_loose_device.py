@@ -8,7 +8,8 @@ every lane making its own IMU samples and GPS fixes; ``run(set_of_input)`` on on
 The checkout's own stub (demo_algorithms.ins_loose) stays hosted.  fp64 only.
 
     InsLoose(ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None,
-             odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None)
+             odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None,
+             mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None)
 
 ini_pos_vel_att: the initial states FreeIntegration takes ((9|10,) or (9|10, k)); None under a Sim: the motion definition's.
 imu: the IMU model the filter is tuned to (its accel_err, gyro_err, gps_err); None under a Sim: the Sim's own.  ref_frame is the
@@ -21,6 +22,12 @@ odo=True uses the odometer (``input`` gains a trailing 'odo'; the IMU model need
 (no sideways and no vertical body velocity), both every odo_every IMU samples.  odo_std [m/s]: 1 sigma of the scaled odometer
 sample (default: the IMU model's odo_err['stdv'] / scale); nhc_std [m/s]: the constraints' pseudo-noise; odo_scale: the scale
 factor the filter assumes (default: the IMU model's odo_err['scale']).
+
+The magnetometer (csrc/ins_loose_mag.hip; as NumPy in tests/ins_loose_mag_ref.py): mag=True observes the attitude
+error with the three axes of the calibrated magnetometer sample every mag_every IMU samples (``input`` gains a trailing 'mag', after
+'odo'; the IMU model needs axis=9).  mag_std [uT]: 1 sigma of the raw sample per axis; mag_si (3, 3), mag_hi (3,): the soft- and
+hard-iron calibration the filter assumes (defaults: the IMU model's mag_err; MagCal's result can be passed).  geo_mag_n [uT, NED]:
+the field the filter assumes; None under a Sim: the Sim's own.  ``run`` on a logged series needs it.
 """
 import numpy as np
 
@@ -34,9 +41,10 @@ class InsLoose(object):
     mc_algo = 'loose'
 
     def __init__(self, ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None,
-                 odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None):
-        self.odo, self.nhc = bool(odo), bool(nhc)
-        self.input = ['fs', 'gyro', 'accel', 'time', 'gps_time', 'gps'] + (['odo'] if self.odo else [])
+                 odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None,
+                 mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None):
+        self.odo, self.nhc, self.mag = bool(odo), bool(nhc), bool(mag)
+        self.input = ['fs', 'gyro', 'accel', 'time', 'gps_time', 'gps'] + (['odo'] if self.odo else []) + (['mag'] if self.mag else [])
         self.output = ['pos', 'vel', 'att_euler', 'wb', 'ab']
         self.batch = True
         self.results = None
@@ -58,6 +66,23 @@ class InsLoose(object):
         self.odo_every, self.nhc_std = int(odo_every), float(nhc_std)
         self.odo_std = None if odo_std is None else float(odo_std)
         self.odo_scale = None if odo_scale is None else float(odo_scale)
+        if int(mag_every) != mag_every or int(mag_every) < 1:
+            raise ValueError('mag_every must be an integer >= 1')
+        self.mag_every = int(mag_every)
+
+        def numbers(name, v, size, positive=False):
+            if v is None:
+                return None
+            v = np.asarray(v, dtype=np.float64)
+            v = v * np.ones(3) if (positive and v.size == 1) else v
+            if v.size != size or not np.all(np.isfinite(v)) or (positive and not np.all(v > 0.0)):
+                raise ValueError('%s must be %d finite%s numbers' % (name, size, ', positive' if positive else ''))
+            return v.copy()
+        self.mag_std = numbers('mag_std', mag_std, 3, True)
+        self.mag_si = numbers('mag_si', mag_si, 9)
+        self.mag_si = None if self.mag_si is None else self.mag_si.reshape(3, 3)
+        self.mag_hi = numbers('mag_hi', mag_hi, 3)
+        self.geo_mag_n = numbers('geo_mag_n', geo_mag_n, 3)
         self.run_times = 0
 
     def aid(self):
@@ -67,6 +92,12 @@ class InsLoose(object):
         return {'odo': self.odo, 'nhc': self.nhc, 'every': self.odo_every, 'odo_std': self.odo_std, 'nhc_std': self.nhc_std,
                 'scale': self.odo_scale}
 
+    def mag_options(self):
+        """The magnetometer options ginsim.InsLooseJob takes (ginsim.ins_loose.mag_model), or None without the magnetometer."""
+        if not self.mag:
+            return None
+        return {'every': self.mag_every, 'std': self.mag_std, 'si': self.mag_si, 'hi': self.mag_hi}
+
     def finish(self, pos, vel, att, wb, ab):
         """State the plugin holds after a run: the last run's series, each (n, 3), in the order of `output`."""
         self.results = [pos, vel, att, wb, ab]
@@ -74,8 +105,8 @@ class InsLoose(object):
     def run(self, set_of_input):
         '''
         set_of_input: [fs, gyro (n, 3), accel (n, 3), time (n,), gps_time (m,), gps (m, 6 | 7)], as the reference's run; a seventh
-        gps column is the visibility; with InsLoose(odo=True) a seventh element, odo (n,).  Needs InsLoose(ini_pos_vel_att=...,
-        ref_frame=..., imu=...).
+        gps column is the visibility; with InsLoose(odo=True) a seventh element, odo (n,); with InsLoose(mag=True) the next
+        element, mag (n, 3), and geo_mag_n= on the plugin.  Needs InsLoose(ini_pos_vel_att=..., ref_frame=..., imu=...).
         '''
         import ginsim
         from ginsim.ins_loose import InsLooseJob
@@ -98,6 +129,17 @@ class InsLoose(object):
             odo = np.ascontiguousarray(np.asarray(set_of_input[6], dtype=np.float64).reshape(-1))
             if odo.shape[0] != n:
                 raise ValueError('odo must be an (n,) array')
+        mag = None
+        if self.mag:
+            at = 7 if self.odo else 6
+            if len(set_of_input) <= at:
+                raise ValueError("InsLoose(mag=True).run needs the magnetometer series as element %d ('mag')" % (at + 1))
+            if self.geo_mag_n is None:
+                raise ValueError('InsLoose(mag=True).run on a logged series needs InsLoose(geo_mag_n=[bx, by, bz] uT): there is no Sim '
+                                 'to take the field from')
+            mag = np.ascontiguousarray(np.asarray(set_of_input[at], dtype=np.float64))
+            if mag.shape != (n, 3):
+                raise ValueError('mag must be an (n, 3) array')
         t0 = time[0] if time.size else 0.0
         truth = {'ref_accel': accel, 'ref_gyro': gyro, 'ref_att': np.zeros((n, 3)), 'ref_pos': np.zeros((n, 3)), 'ref_vel': np.zeros((n, 3)),
                  'ref_gps': np.ascontiguousarray(gps[:, 0:6]), 'gps_time': gps_time - t0,
@@ -107,11 +149,14 @@ class InsLoose(object):
                 'gps': ctx.upload(np.ascontiguousarray(gps[:, 0:6].T))}
         if odo is not None:
             bufs['odo'] = ctx.upload(odo)                                                                                   # [n][1]
+        if mag is not None:
+            bufs['mag'] = ctx.upload(np.ascontiguousarray(mag.T))                                                           # [3][n][1]
         job = None
         try:
             job = InsLooseJob(ctx, fs, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, self.imu.gps_err, self.ini, 1,
                               ini_first=self.run_times, earth_rot=self.earth_rot, given=bufs, q_scale=self.q_scale, p0=self.p0,
-                              keep_traj=True, odo_err=getattr(self.imu, 'odo_err', None), aid=self.aid()).run()
+                              keep_traj=True, odo_err=getattr(self.imu, 'odo_err', None), aid=self.aid(),
+                              **self._mag_arguments()).run()
             self.finish(*[job.series(k, [0])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab')])
         finally:
             if job is not None:
@@ -119,6 +164,9 @@ class InsLoose(object):
             for b in bufs.values():
                 b.free()
         self.run_times += 1
+
+    def _mag_arguments(self):
+        return {} if not self.mag else {'mag_err': getattr(self.imu, 'mag_err', None), 'geo_mag_n': self.geo_mag_n, 'mag': self.mag_options()}
 
     def get_results(self):
         return self.results

@@ -110,6 +110,13 @@ class LooseConsParams(C.Structure):
     _fields_ = [('cons_sample', C.c_void_p), ('cons_m', C.c_int64), ('out_cons', C.c_void_p), ('cons_work', C.c_void_p)]
 
 
+class LooseMagParams(C.Structure):
+    """ginsim_loose_mag_params: the magnetometer aiding block of a filter launch (csrc/ins_loose_mag.hip)."""
+    _fields_ = [('mag_every', C.c_int64), ('ref_mag', C.c_void_p), ('mag_si', C.c_double * 9), ('mag_hi', C.c_double * 3),
+                ('mag_std', C.c_double * 3), ('in_mag', C.c_void_p), ('mag_n', C.c_double * 3), ('cal_si', C.c_double * 9),
+                ('cal_hi', C.c_double * 3), ('r_mag', C.c_double * 3)]
+
+
 class PathgenParams(C.Structure):
     _fields_ = [('ini_pva', C.c_double * 9), ('mobility', C.c_double * 3), ('fs', C.c_double),
                 ('fs_gps', C.c_double), ('ref_frame', C.c_int32), ('enable_gps', C.c_int32),
@@ -183,6 +190,9 @@ _SIGS = {
     'ginsim_loose_cons_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseConsParams)]),
     'ginsim_loose_cons_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseConsParams), C.c_char_p,
                                                 C.c_size_t]),
+    'ginsim_loose_mag_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseMagParams)]),
+    'ginsim_loose_mag_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseMagParams), C.c_char_p,
+                                               C.c_size_t]),
     'ginsim_end_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     'ginsim_end_stats_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     'ginsim_end_stats_finish': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Stats)]),

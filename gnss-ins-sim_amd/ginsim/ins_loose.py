@@ -6,7 +6,8 @@ MonteCarloJob and AuxSensorJob would store), mechanises them with the free-integ
 With aid=... the filter also uses the odometer and the non-holonomic constraints of a land vehicle (csrc/ins_loose_aided.hip,
 aiding_model; restated by tests/ins_loose_aided_ref.py).  With cons_samples=... the launch also reduces, across its runs, the
 filter's covariance and its actual error at those samples (csrc/ins_loose_cons.hip, consistency(); restated by
-tests/ins_loose_cons_ref.py).
+tests/ins_loose_cons_ref.py).  With mag=... the filter also uses the magnetometer, a three-row block on the attitude error
+(csrc/ins_loose_mag.hip, mag_model; restated by tests/ins_loose_mag_ref.py).
 """
 import ctypes as C
 
@@ -106,6 +107,69 @@ def aiding_model(odo_err, aid):
     return out
 
 
+def mag_field(geo_mag_n, ref_frame):
+    """The geomagnetic field [uT] in the navigation frame of ref_frame, (3,): the NED vector in ref_frame 0; in ref_frame 1 the
+    virtual-inertial x axis points along the horizontal field, (hypot(bx, by), 0, bz), as pathgen forms it (pathgen.py:169-171)."""
+    g = np.asarray(geo_mag_n, dtype=np.float64).reshape(-1)
+    if g.size != 3 or not np.all(np.isfinite(g)):
+        raise ValueError('geo_mag_n must be three finite numbers [uT]')
+    if int(ref_frame) == 1:
+        g = np.array([np.hypot(g[0], g[1]), 0.0, g[2]])
+    return g.copy()
+
+
+def mag_model(mag_err, geo_mag_n, ref_frame, mag=None):
+    """The numbers of the magnetometer block of ginsim_loose_mag_params that describe the FILTER,
+    {'mag_every', 'mag_n', 'cal_si', 'cal_hi', 'r_mag'}, from the magnetometer's error dict {'si', 'hi', 'std'} (None: every
+    number must come from the options), the geomagnetic field geo_mag_n [uT, NED] and the options
+    mag = {'every': int, 'std': 3 floats | float, 'si': (3, 3), 'hi': (3,), 'field': (3,)}:
+
+      mag_every  'every': a block every so many IMU samples; default 1
+      cal_si     inv('si'), cal_hi = 'hi': the calibration the filter ASSUMES, m_cal = cal_si . mag - cal_hi; default mag_err's own
+                 soft- and hard-iron.  Parameters, not states (as the odometer's scale factor): MagCal's result can be passed here
+      r_mag      diag(cal_si diag('std'^2) cal_si^T) [uT^2]; 'std' defaults to mag_err['std'].  The calibrated sample's noise
+                 covariance is that full matrix; the rows are processed as independent scalars, so its off-diagonal terms are
+                 dropped.  The expression is exact for a diagonal soft-iron matrix
+      mag_n      'field': the field the filter assumes in the navigation frame; default geo_mag_n in the frame's form
+                 (mag_field: as it is in ref_frame 0, (hypot(bx, by), 0, bz) in ref_frame 1)
+    """
+    mag = dict(mag or {})
+    unknown = set(mag) - {'every', 'std', 'si', 'hi', 'field'}
+    if unknown:
+        raise ValueError('mag: unknown keys %s' % sorted(unknown))
+    every = mag.get('every', 1)
+    if int(every) != every or int(every) < 1:
+        raise ValueError("mag['every'] must be an integer >= 1")
+
+    def pick(name, size):
+        v = mag.get(name)
+        if v is None:
+            if mag_err is None:
+                raise ValueError("mag[%r] is needed without mag_err={'si', 'hi', 'std'}" % (name,))
+            v = mag_err[name]
+        v = np.asarray(v, dtype=np.float64)
+        v = v * np.ones(3) if (name != 'si' and v.size == 1) else v
+        if v.size != size or not np.all(np.isfinite(v)):
+            raise ValueError('mag[%r] must be %d finite numbers' % (name, size))
+        return v.reshape(-1)
+    si, hi, std = pick('si', 9).reshape(3, 3), pick('hi', 3), pick('std', 3)
+    if not np.all(std > 0.0):
+        raise ValueError("mag['std'] must be positive and finite")
+    if not abs(np.linalg.det(si)) > 1e-12 * max(np.abs(si).max(), np.finfo(np.float64).tiny) ** 3:
+        raise ValueError("mag['si'] is singular: the filter cannot undo that soft-iron matrix")
+    cal_si = np.linalg.inv(si)
+    field = mag.get('field')
+    if field is None:
+        if geo_mag_n is None:
+            raise ValueError("the magnetometer block needs the geomagnetic field: geo_mag_n or mag['field']")
+        field = mag_field(geo_mag_n, ref_frame)
+    field = np.asarray(field, dtype=np.float64).reshape(-1)
+    if field.size != 3 or not np.all(np.isfinite(field)) or not np.any(field != 0.0):
+        raise ValueError("mag['field'] must be three finite numbers, not all zero")
+    return {'mag_every': int(every), 'mag_n': field.copy(), 'cal_si': cal_si, 'cal_hi': hi.copy(),
+            'r_mag': np.einsum('ik,k,ik->i', cal_si, std * std, cal_si)}
+
+
 class InsLooseJob(BatchJob):
     """One batch of runs of the loosely coupled filter on one device.
 
@@ -124,6 +188,10 @@ class InsLooseJob(BatchJob):
     placed: as MonteCarloJob (kept planes of Context.PLACED_MIN_JOB bytes or more come from the placed arena).
     cons_samples: None, or the IMU sample indices (any order, repeats allowed) at which the launch reduces the consistency record
     across its runs (consistency()): the filter's P against its error in its own coordinates.  Not together with proc_first.
+    mag_err, geo_mag_n, mag: the magnetometer's error dict {'si', 'hi', 'std'}, the geomagnetic field [uT, NED] and the options of
+    mag_model() (csrc/ins_loose_mag.hip; mag None: the filter without the magnetometer block; {} takes every default).  The
+    generated form needs truth['ref_mag'] (n, 3) and mag_err: the lane makes the magnetometer sample AuxSensorJob would store for
+    the same seed and run ids.  The given form reads given['mag'] [3][n][runs].  Not together with cons_samples.
     """
 
     algos = ('loose',)
@@ -131,7 +199,7 @@ class InsLooseJob(BatchJob):
     def __init__(self, ctx, fs, ref_frame, truth, accel_err, gyro_err, gps_err, ini, runs, seed=0, run_offset=0, ini_first=0,
                  earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
                  end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None,
-                 cons_samples=None):
+                 cons_samples=None, mag_err=None, geo_mag_n=None, mag=None):
         self.ctx = ctx
         self.n, self.runs = int(truth['ref_accel'].shape[0]), int(runs)
         if self.runs < 1:
@@ -166,10 +234,20 @@ class InsLooseJob(BatchJob):
         for k, v in self.aid.items():
             setattr(p, k, v)
         use_odo = bool(self.aid['aid_mask'] & 1)
+        self.mag, self.magp = None, None
+        if mag is not None:
+            if cons_samples is not None:
+                raise ValueError('cons_samples: consistency checkpoints of the magnetometer-aided filter are not built (mag=...)')
+            self.mag = mag_model(mag_err, geo_mag_n, ref_frame, mag)
+            g = self.magp = _lib.LooseMagParams()
+            g.mag_every = self.mag['mag_every']
+            for k in ('mag_n', 'cal_si', 'cal_hi', 'r_mag'):
+                getattr(g, k)[:] = [float(x) for x in np.asarray(self.mag[k], dtype=np.float64).reshape(-1)]
         self._ref_nav = np.ascontiguousarray(np.concatenate([truth['ref_att'], truth['ref_pos'], truth['ref_vel']], axis=1))
         m.ref_end[:] = [float(x) for x in self._ref_nav[-1]]
         parts = [table.reshape(-1)]
-        need = (('accel', 3, self.n), ('gyro', 3, self.n), ('gps', 6, self.m)) + ((('odo', 1, self.n),) if use_odo else ())
+        need = (('accel', 3, self.n), ('gyro', 3, self.n), ('gps', 6, self.m)) + ((('odo', 1, self.n),) if use_odo else ()) + \
+            ((('mag', 3, self.n),) if self.mag is not None else ())
         self._sensor_source(m, fs, accel_err, gyro_err, vib_accel, vib_gyro, given, need, 'filter')
         if given is None:
             parts += [np.asarray(truth['ref_accel'], dtype=np.float64).reshape(-1), np.asarray(truth['ref_gyro'], dtype=np.float64).reshape(-1),
@@ -184,10 +262,23 @@ class InsLooseJob(BatchJob):
                     raise ValueError("truth['ref_odo'] must have one value per IMU sample")
                 m.odo_scale, m.odo_stdv = float(odo_err['scale']), float(odo_err['stdv'])
                 parts.append(ref_odo)
+            if self.mag is not None:
+                if 'ref_mag' not in truth or mag_err is None:
+                    raise ValueError("mag in the generated form needs truth['ref_mag'] and mag_err")
+                ref_mag = np.asarray(truth['ref_mag'], dtype=np.float64)
+                if ref_mag.shape != (self.n, 3):
+                    raise ValueError("truth['ref_mag'] must be (n, 3): one row per IMU sample")
+                g = self.magp
+                g.mag_si[:] = [float(x) for x in np.asarray(mag_err['si'], dtype=np.float64).reshape(9)]
+                g.mag_hi[:] = [float(x) for x in np.asarray(mag_err['hi'], dtype=np.float64) * np.ones(3)]
+                g.mag_std[:] = [float(x) for x in np.asarray(mag_err['std'], dtype=np.float64) * np.ones(3)]
+                parts.append(ref_mag.reshape(-1))
         else:
             p.in_gps = given['gps'].ptr if self.m else None
             if use_odo:
                 m.in_odo = given['odo'].ptr
+            if self.mag is not None:
+                self.magp.in_mag = given['mag'].ptr
         offs = np.cumsum([0] + [q.size for q in parts]) * 8
         self._bufs['inputs'] = ctx.upload(np.concatenate(parts))
         m.ini = self._bufs['inputs'].at(offs[0])
@@ -196,6 +287,8 @@ class InsLooseJob(BatchJob):
             p.ref_gps = self._bufs['inputs'].at(offs[3]) if self.m else None
             if use_odo:
                 m.ref_odo = self._bufs['inputs'].at(offs[4])
+            if self.mag is not None:
+                self.magp.ref_mag = self._bufs['inputs'].at(offs[5 if use_odo else 4])
         R = self.runs
         # end [9][R], bias_end [6][R], pdiag_end [15][R], run list [R], the NED end record [9][R]
         self._bufs['small'] = ctx.malloc((9 + 6 + 15 + 1 + 9) * R * 8)
@@ -242,6 +335,8 @@ class InsLooseJob(BatchJob):
         buf = C.create_string_buffer(256)
         if self.cons is not None:
             check(lib.ginsim_loose_cons_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.cons), buf, 256))
+        elif self.magp is not None:
+            check(lib.ginsim_loose_mag_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.magp), buf, 256))
         else:
             check(lib.ginsim_loose_kernel_name(C.byref(self.mc), C.byref(self.params), buf, 256))
         return buf.value.decode()
@@ -258,6 +353,8 @@ class InsLooseJob(BatchJob):
         self._put_run_list(p, ids)
         if self.cons is not None:
             check(self.ctx.retry_oom(lambda: lib.ginsim_loose_cons_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.cons))))
+        elif self.magp is not None:
+            check(self.ctx.retry_oom(lambda: lib.ginsim_loose_mag_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.magp))))
         else:
             check(self.ctx.retry_oom(lambda: lib.ginsim_loose_run(self.ctx.handle, C.byref(self.mc), C.byref(p))))
 

@@ -324,6 +324,8 @@ def _plugin_roles(sim, kinds):
     for i in loose:
         if getattr(sim.amgr.algo[i], 'odo', False) and not sim.imu.odo:
             raise ValueError("algorithm %d needs 'odo' but the IMU model has no odometer" % i)
+        if getattr(sim.amgr.algo[i], 'mag', False) and not sim.imu.magnetometer:
+            raise ValueError("algorithm %d needs 'mag' but the IMU model has no magnetometer (IMU(axis=9))" % i)
     if loose and sim.precision != 'f64':
         raise NotImplementedError("the loosely coupled filter (InsLoose of demo_algorithms.ins_loose_device) runs in fp64 only: "
                                   "use precision='f64'")
@@ -464,13 +466,24 @@ class _Jobs(object):
                            seed=self.seed, run_offset=self.first + off, ini_first=kw.pop('ini_first', algo.run_times + self.first + off),
                            earth_rot=algo.earth_rot, keep_traj=keep, placed=sim.placed,
                            model=filter_model(sim.fs[0], tuned.accel_err, tuned.gyro_err, tuned.gps_err, algo.q_scale, algo.p0),
-                           **self._aiding(algo), **self.vib, **kw)
+                           **self._aiding(algo), **self._mag_aiding(algo, truth), **self.vib, **kw)
 
     def _aiding(self, algo):
         """The aiding arguments of an InsLooseJob: none for a plugin without aiding.  The odometer SAMPLES are the Sim's
         (truth['ref_odo'] and the IMU's odo_err, as the fused job makes them); what the filter assumes of them is the plugin's."""
         aid = algo.aid() if hasattr(algo, 'aid') else None
         return {} if aid is None else {'odo_err': self.sim.imu.odo_err if self.sim.imu.odo else None, 'aid': aid}
+
+    def _mag_aiding(self, algo, truth):
+        """The magnetometer arguments of an InsLooseJob: none for a plugin without the block.  The SAMPLES are the Sim's (ref_mag
+        and the IMU's mag_err, as AuxSensorJob makes them); the field is the plugin's where it names one, else the Sim's; what the
+        filter assumes of the calibration is the plugin's."""
+        mag = algo.mag_options() if hasattr(algo, 'mag_options') else None
+        if mag is None:
+            return {}
+        truth['ref_mag'] = self.sim.dmgr.ref_mag.data
+        field = algo.geo_mag_n if getattr(algo, 'geo_mag_n', None) is not None else self.sim.geo_mag_n
+        return {'mag_err': self.sim.imu.mag_err, 'geo_mag_n': field, 'mag': mag}
 
     def inclinometer(self, group, runs, keep, start_bias=None, stats=True, proc_first=0, off=0):
         """An InclinometerJob of `runs` runs from run `off` of this rank for the plugins of `group`; the MahonyFilter's gains and
@@ -1281,6 +1294,10 @@ class Sim(object):
         if samples.size == 0 or samples.min() < 0 or samples.max() >= n:
             raise ValueError('consistency_curve: samples must be indices in [0, %d), at least one' % n)
         out = {'time': t[samples], 'states': ['%s_%s' % (b, a) for b in ('dr', 'dv', 'psi', 'dbg', 'dba') for a in 'xyz']}
+        for a, (_, job, _) in zip(names, getattr(self, 'loose_jobs', ())):
+            if getattr(job, 'mag', None) is not None:
+                raise NotImplementedError('consistency_curve: %s is aided by the magnetometer (InsLoose(mag=True)), and the consistency '
+                                          'checkpoints of that filter are not built' % a)
         for a in names:
             c = mc.consistency(a, samples)
             out[a] = {'count': c.count, 'sigma': c.sigma, 'rms': c.rms, 'ratio': c.ratio, 'nees': c.nees}

@@ -429,6 +429,35 @@ int ginsim_loose_cons_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const gin
 int ginsim_loose_cons_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
                                   char* buf, size_t cap);
 
+/* ---- magnetometer aiding of the filter (csrc/ins_loose_mag.hip): a three-row heading block on psi.  Added without
+ *      a change of GINSIM_ABI_VERSION and as a block of its own: ginsim_loose_params and ginsim_loose_run are exactly what they were.
+ *      With D = C_est^T (navigation -> body) of the reported attitude, m_n = mag_n and the calibrated sample
+ *      m_cal = cal_si . mag_j - cal_hi, to first order D_est m_n = m_b - D [m_n x] psi, so body axis i = 0, 1, 2 gives
+ *        z_i = D[i,:] . m_n - m_cal[i],   h_i = [0, 0, m_n x D[i,:], 0, 0],   variance r_mag[i].
+ *      One block runs the three rows in ascending order from x = 0 (D, z and the rows from the state before the first one) and
+ *      ends with the feedback of a GPS fix.  It runs at every IMU sample j > 0 with j % mag_every == 0 on the state that sample's
+ *      row reports: after a fix and after an odometer / non-holonomic block of the same sample, before the row is stored.
+ *      mag_j is what ginsim_aux_sensors writes to out_mag for the same seed and run (ref_mag, mag_si, mag_hi, mag_std; never
+ *      stored), or in_mag[(c n + j) runs + r] with given_sensors.  aid_mask of the loose block may be 0 or not. */
+typedef struct {
+    int64_t  mag_every;      /* 0: none -- the call is ginsim_loose_run (nothing else is read); >= 1: a block every mag_every samples (n or more: never) */
+    const double* ref_mag;   /* device [n][3]: generated form */
+    double   mag_si[9], mag_hi[3], mag_std[3];   /* generation, as ginsim_aux_params */
+    const double* in_mag;    /* device [3][n][runs]: given form (with given_sensors) */
+    double   mag_n[3];       /* the field the FILTER assumes in the navigation frame, uT */
+    double   cal_si[9];      /* row major: m_cal = cal_si . mag - cal_hi */
+    double   cal_hi[3];
+    double   r_mag[3];       /* variances of the calibrated sample per body axis, uT^2; finite, > 0 */
+} ginsim_loose_mag_params;
+
+/* ginsim_loose_run with the magnetometer block: launches loose_mag_kernel.  Everything ginsim_loose_run refuses is refused, and:
+ * mag_every < 0; with mag_every > 0 a missing ref_mag (generated form) or in_mag (given form), a non-finite mag_si, mag_hi,
+ * mag_std, mag_n, cal_si or cal_hi, an r_mag that is not positive and finite, |mag_n| = 0. */
+int ginsim_loose_mag_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag);
+/* the NAME of the kernel it launches (e.g. "ginsim::loose_mag_kernel<1, false, false, false>" = RF, GIVEN, VIB, PS) */
+int ginsim_loose_mag_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
+                                 char* buf, size_t cap);
+
 /* ---- auxiliary sensors of a Monte-Carlo batch: pathgen.gps_gen (pathgen.py:596-625) and pathgen.mag_gen (:643-661).
  *      FreeIntegration does not consume them, so they are generated only when they are to be kept. */
 typedef struct {

@@ -5,6 +5,7 @@
     python tools/bench_ins_loose.py [--runs 65536] [--reps 5] [--out profiles/ins_loose_timing.json]
     python tools/bench_ins_loose.py --aided [--reps 20] [--out profiles/ins_loose_aided_timing.json]
     python tools/bench_ins_loose.py --cons [--reps 20] [--out profiles/ins_loose_cons_timing.json]
+    python tools/bench_ins_loose.py --mag [--reps 20] [--out profiles/ins_loose_mag_timing.json]
 
 Workload: 65 536 runs x the 1000 samples of the 90-degree turn at 100 Hz (BASELINE config C2's shape) with GPS at 10 Hz, ref_frame 1,
 'mid-accuracy' IMU; statistics only (nothing but the per-run end records is written) and with everything kept (trajectory, wb, ab).
@@ -27,7 +28,11 @@ times after one warm-up each, so that a drift of the clocks falls on all three a
 --cons: the consistency checkpoints of csrc/ins_loose_cons.hip on the same case, statistics only: the unaided launch
 without checkpoints, with one every 100 samples and with one at every sample, launched in turn --reps times after one warm-up each.
 The times with checkpoints include the kernel that adds the wavefronts' partial records.  A checkpoint's cost is printed in steps:
-(time with m checkpoints - time without) / m over the time of one step of the launch without."""
+(time with m checkpoints - time without) / m over the time of one step of the launch without.
+
+--mag: the magnetometer block of csrc/ins_loose_mag.hip on the same case, statistics only: the unaided launch, the
+magnetometer block at mag_every 1 and 10, and aid_mask 7 together with the magnetometer (both at every sample), launched in turn
+--reps times after one warm-up each (field (30, -3, 40) uT, no soft or hard iron, noise 0.01 uT)."""
 import argparse
 import json
 import os
@@ -164,6 +169,47 @@ def time_aided(runs, reps, unaided_only=False):
     return out
 
 
+def time_mag(runs, reps):
+    """{leg: {'kernel', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the unaided launch, the magnetometer block at mag_every 1 and
+    10 and aid_mask 7 together with the magnetometer, interleaved."""
+    import numpy as np
+    import ginsim
+    from ginsim import workloads
+    fs, rf, geo = 100.0, 1, (30.0, -3.0, 40.0)
+    ini, truth, _ = workloads.truth_from_profile('turn_90deg', fs, rf, fs_gps=10.0, gps=True)
+    ini_m, seg = workloads.parse_motion(workloads.profile_path('turn_90deg'))
+    raw = ginsim.pathgen(ini_m, seg, fs, 10.0, workloads.HIGH_MOBILITY, rf, gps=True, geo_mag_n=geo)
+    n = int(truth['ref_accel'].shape[0])
+    truth = dict(truth, ref_mag=np.ascontiguousarray(raw['mag'][:n, 1:4]))
+    acc, gyr = workloads.imu_grade('mid-accuracy')
+    gps_err = {'stdp': np.array([5.0, 5.0, 7.0]), 'stdv': np.array([0.05, 0.05, 0.05])}
+    odo_err = {'scale': 0.99, 'stdv': 0.1}
+    mag_err = {'si': np.eye(3), 'hi': np.zeros(3), 'std': np.array([0.01, 0.01, 0.01])}
+    ctx = ginsim.Context(0)
+    out = {'device': ctx.name(), 'runs': runs, 'samples': n, 'fixes': int(truth['ref_gps'].shape[0]), 'library': os.path.basename(ginsim.LIB_PATH)}
+    mag = lambda every: {'mag_err': mag_err, 'geo_mag_n': geo, 'mag': {'every': every}}
+    legs = [('unaided', {}), ('mag_every1', mag(1)), ('mag_every10', mag(10)),
+            ('aided_mask7_mag_every1', dict(mag(1), odo_err=odo_err, aid={'odo': True, 'nhc': True, 'every': 1}))]
+    jobs = [(label, ginsim.InsLooseJob(ctx, fs, rf, truth, acc, gyr, gps_err, ini, runs, seed=1, keep_traj=False, **kw)) for label, kw in legs]
+    ms = {label: [] for label, _ in jobs}
+    for _, job in jobs:
+        job.run()                                       # warm-up: code object, LDS attribute
+    for _ in range(reps):
+        for label, job in jobs:
+            ctx.timer_begin()
+            job.launch()
+            ms[label].append(ctx.timer_end())
+    for label, job in jobs:
+        t = ms[label]
+        out[label] = {'kernel': job.kernel_name(), 'ms_median': float(np.median(t)), 'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)),
+                      'ms_all': [float(x) for x in t]}
+        job.release()
+    for label, _ in jobs[1:]:
+        out[label]['over_unaided'] = out[label]['ms_median'] / out['unaided']['ms_median']
+    ctx.close()
+    return out
+
+
 def time_cons(runs, reps):
     """{leg: {'kernel', 'checkpoints', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the unaided launch without checkpoints, with one
     every 100 samples and with one at every sample, interleaved; and what one checkpoint costs, in steps."""
@@ -207,6 +253,7 @@ def main():
     ap.add_argument('--aided', action='store_true', help='the aided leg: unaided, aid_mask 7 at aid_every 1 and 10')
     ap.add_argument('--unaided-only', action='store_true', help='with --aided: the unaided launch alone')
     ap.add_argument('--cons', action='store_true', help='the checkpoint leg: none, one every 100 samples, one at every sample')
+    ap.add_argument('--mag', action='store_true', help='the magnetometer leg: unaided, mag_every 1 and 10, aid_mask 7 with the magnetometer')
     ap.add_argument('--runs', type=int, default=65536)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ops', type=int, default=0, help='fp64 instructions per step, instead of the count from the ISA')
@@ -216,8 +263,8 @@ def main():
         for k, (n, f, span) in sorted(isa_counts().items()):
             print('%s: %d fp64 VALU instructions (%d fused multiply-adds) in a time loop of %d lines' % (k, n, f, span))
         return
-    if a.aided or a.cons:
-        res = time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
+    if a.aided or a.cons or a.mag:
+        res = time_mag(a.runs, a.reps) if a.mag else time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
         print(json.dumps(res))
         if a.out:
             with open(a.out, 'w') as f:
