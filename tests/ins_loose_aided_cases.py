@@ -14,6 +14,7 @@ NHC_STD = 0.05
 # own model with np.random.default_rng(ins_loose_cases.CONSISTENCY_SEED) (accel, gyro, GPS as the unaided case draws them, then the
 # odometer), the outage profile at 20 Hz with 2 Hz GPS, 'mid-accuracy' IMU, ODO_ERR, NHC_STD, a block at every sample, ref_frame 1.
 # RMS end error over sqrt(mean pdiag_end) for the 15 states.  Mask 1 lies in [0.7, 1.4]; mask 7 is bounded above only (see the test).
+# ref_frame 1, the LEVEL outage profile only; for the tilted profile and ref_frame 0 see ins_loose_mag_cases.CONSISTENCY_BY_PROFILE.
 CONSISTENCY_RATIOS = {
     1: (1.016, 1.016, 0.931, 1.009, 0.986, 0.941, 0.951, 0.980, 1.014, 1.017, 1.014, 0.999, 0.999, 0.972, 0.980),
     7: (0.981, 0.911, 0.475, 0.946, 0.832, 0.694, 0.855, 0.903, 0.992, 1.005, 1.011, 1.005, 0.998, 0.972, 0.978),
@@ -28,12 +29,12 @@ OUTAGE_TABLE = {
 
 
 @functools.lru_cache(maxsize=None)
-def outage_truth(fs, ref_frame, fs_gps, n=None):
+def outage_truth(fs, ref_frame, fs_gps, n=None, profile=cs.OUTAGE_CSV):
     """ins_loose_cases.outage_truth with 'ref_odo' (n,), the truth forward speed."""
     import ginsim
     from ginsim import workloads
-    ini, truth, stamps = cs.outage_truth(fs, ref_frame, fs_gps, n)
-    ini_m, seg = workloads.parse_motion(cs.OUTAGE_CSV)
+    ini, truth, stamps = cs.outage_truth(fs, ref_frame, fs_gps, n, profile)
+    ini_m, seg = workloads.parse_motion(profile)
     raw = ginsim.pathgen(ini_m, seg, fs, fs_gps, workloads.HIGH_MOBILITY, ref_frame, gps=True)
     truth = dict(truth, ref_odo=np.ascontiguousarray(raw['odo'][:truth['ref_accel'].shape[0], 2]))
     truth['ref_odo'].setflags(write=False)

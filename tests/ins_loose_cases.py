@@ -7,21 +7,27 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUTAGE_CSV = os.path.join(REPO, 'tests', 'golden', 'ins_loose', 'motion_def_outage.csv')
+# 41 S, 150 W, 300 m; yaw 165 deg through +-180 deg twice, pitch 20 -> -20 -> 20 deg, roll -15 -> 15 -> -15 deg, climbing and descending,
+# vb = (vx, 0, 0) throughout; 40 s with a 10 s GPS outage (tests/test_ins_loose_attitude_oracle.py, tests/test_gpu_ins_loose_attitude.py)
+TILTED_CSV = os.path.join(REPO, 'tests', 'golden', 'ins_loose', 'motion_def_tilted.csv')
 GPS_ERR = {'stdp': np.array([5.0, 5.0, 7.0]), 'stdv': np.array([0.05, 0.05, 0.05])}       # imu_model.py's gps_low_accuracy
 
 # Consistency of the restatement, measured by tests/test_ins_loose_oracle.py::test_restatement_consistency (1024 runs sampled from the
 # filter's own model with np.random.default_rng(20260117), the outage profile at 20 Hz with 2 Hz GPS, 'mid-accuracy' IMU, ref_frame 1):
 # RMS end error over sqrt(mean pdiag_end) for the 15 states.  A consistent filter has 1; the band the issue allows is [0.7, 1.4].
+# This table is for ref_frame 1 on the LEVEL outage profile only; the tilted profile's and what ref_frame 0 carries instead
+# (a deterministic offset) are in ins_loose_mag_cases.CONSISTENCY_BY_PROFILE and E0_OVER_SIGMA.
 CONSISTENCY_FS, CONSISTENCY_FS_GPS, CONSISTENCY_RUNS, CONSISTENCY_SEED = 20.0, 2.0, 1024, 20260117
 CONSISTENCY_RATIOS = (0.988, 0.982, 0.942, 1.022, 0.963, 0.950, 0.941, 0.960, 1.015, 1.010, 1.013, 0.996, 0.999, 0.972, 0.980)
 
 
 @functools.lru_cache(maxsize=None)
-def outage_truth(fs, ref_frame, fs_gps, n=None):
-    """(ini_pva, truth dict, gps stamps int64) of the outage profile, cut to the first n samples (and the fixes inside them)."""
+def outage_truth(fs, ref_frame, fs_gps, n=None, profile=OUTAGE_CSV):
+    """(ini_pva, truth dict, gps stamps int64) of a motion profile (default: the outage profile), cut to the first n samples (and
+    the fixes inside them)."""
     import ginsim
     from ginsim import workloads
-    ini, seg = workloads.parse_motion(OUTAGE_CSV)
+    ini, seg = workloads.parse_motion(profile)
     raw = ginsim.pathgen(ini, seg, fs, fs_gps, workloads.HIGH_MOBILITY, ref_frame, gps=True)
     n = raw['imu'].shape[0] if n is None else int(n)
     stamps = np.rint(raw['gps'][:, 0]).astype(np.int64)

@@ -32,10 +32,10 @@ class Dump(object):
     """The device's own sensors and fixes of `runs` runs (ginsim_mc_run, ginsim_aux_sensors), on the device and on the host, with
     the free-integration trajectories of the same launch."""
 
-    def __init__(self, ctx, rf, n, runs, seed=77, run_offset=0, fs=FS, fs_gps=FS_GPS, **bias):
+    def __init__(self, ctx, rf, n, runs, seed=77, run_offset=0, fs=FS, fs_gps=FS_GPS, profile=cs.OUTAGE_CSV, **bias):
         import ginsim
         self.rf, self.fs, self.runs, self.seed, self.run_offset = rf, fs, runs, seed, run_offset
-        self.ini, self.truth, self.stamps = cs.outage_truth(fs, rf, fs_gps, n)
+        self.ini, self.truth, self.stamps = cs.outage_truth(fs, rf, fs_gps, n, profile)
         self.acc_e, self.gyr_e = cs.imu_errors(**bias)
         self.mc = ginsim.MonteCarloJob(ctx, fs, rf, self.truth, self.acc_e, self.gyr_e, self.ini, runs=runs, algos=('free',), seed=seed,
                                        run_offset=run_offset, keep_sensors=True, keep_traj=True).run()

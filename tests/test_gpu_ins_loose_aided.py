@@ -37,10 +37,10 @@ class Dump(object):
     """The device's own accel, gyro, odometer (ginsim_mc_run) and fixes (ginsim_aux_sensors) of `runs` runs, on the device and on
     the host.  vbx0: the initial forward speed the FILTER starts from (None: the profile's)."""
 
-    def __init__(self, ctx, rf, n, runs, seed=77, run_offset=0, fs=FS, fs_gps=FS_GPS, gps=True, vbx0=None):
+    def __init__(self, ctx, rf, n, runs, seed=77, run_offset=0, fs=FS, fs_gps=FS_GPS, gps=True, vbx0=None, profile=cs.OUTAGE_CSV):
         import ginsim
         self.rf, self.fs, self.runs, self.seed, self.run_offset = rf, fs, runs, seed, run_offset
-        self.ini, truth, self.stamps = ac.outage_truth(fs, rf, fs_gps, n)
+        self.ini, truth, self.stamps = ac.outage_truth(fs, rf, fs_gps, n, profile)
         if vbx0 is not None:
             self.ini = np.array(self.ini, dtype=np.float64)
             self.ini[3] = vbx0
