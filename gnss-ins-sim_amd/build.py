@@ -57,6 +57,9 @@ SOURCES = [
     # the same lane with the magnetometer block (ins_loose.hpp, MAG): the same flags -- the magnetometer synthesis must give
     # aux_mag_kernel's bits (mag_synth.hpp, -ffp-contract=on) -- and its own resource report (tests/test_ins_loose_mag_oracle.py reads it)
     ('ins_loose_mag.hip', MC_FLAGS),
+    # the aided lane with 16 states, the odometer's scale factor the last (ins_loose.hpp, NS): the same flags, its own resource
+    # report (tests/test_ins_loose_scale_oracle.py reads it)
+    ('ins_loose_scale.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),

@@ -602,11 +602,11 @@ int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_para
     return GINSIM_OK;
 }
 
-// The launch of the filter, with checkpoints when cons is not NULL or with the magnetometer block when mag is not NULL (at most one
-// of the two; both checked by the caller).  The stamps and the visibility flags of
+// The launch of the filter, with checkpoints when cons is not NULL, with the magnetometer block when mag is not NULL or with the
+// scale-factor state when scale is not NULL (at most one of the three; each checked by the caller).  The stamps and the visibility flags of
 // the fixes and the checkpoint samples are copied next to each other into the context's scratch.
 static int loose_launch(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
-                        const ginsim_loose_mag_params* mag = nullptr) {
+                        const ginsim_loose_mag_params* mag = nullptr, const ginsim_loose_scale_params* scale = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
     int64_t* d_stamp = nullptr;
     int32_t* d_vis = nullptr;
@@ -631,6 +631,7 @@ static int loose_launch(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_
     }
     if (cons) HIP_TRY(launch_loose_cons(*mc, *p, *cons, d_stamp, d_vis, d_cons, c->stream, nullptr, 0));
     else if (mag) HIP_TRY(launch_loose_mag(*mc, *p, *mag, d_stamp, d_vis, c->stream, nullptr, 0));
+    else if (scale) HIP_TRY(launch_loose_scale(*mc, *p, *scale, d_stamp, d_vis, c->stream, nullptr, 0));
     else HIP_TRY(launch_loose(*mc, *p, d_stamp, d_vis, c->stream, nullptr, 0));
     return GINSIM_OK;
 }
@@ -723,6 +724,37 @@ int ginsim_loose_mag_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim
     rc = check_loose_mag(mc, mag);
     if (rc) return rc;
     return loose_launch(c, mc, p, nullptr, mag->mag_every > 0 ? mag : nullptr);
+}
+
+// the scale-factor block of a launch whose other two blocks passed check_loose_params (fp32 among what that refuses)
+static int check_loose_scale(const ginsim_loose_params* p, const ginsim_loose_scale_params* q) {
+    REQUIRE(q, "loose_scale_run: NULL argument");
+    REQUIRE((p->aid_mask & 1) != 0, "loose_scale_run: aid_mask=%d has no bit 0: a scale-factor state without the odometer is refused", (int)p->aid_mask);
+    REQUIRE(std::isfinite(q->scale0) && q->scale0 > 0.0, "loose_scale_run: scale0 must be positive");
+    REQUIRE(std::isfinite(q->p0_scale) && q->p0_scale >= 0.0, "loose_scale_run: p0_scale must be finite and not negative");
+    REQUIRE(std::isfinite(q->q_k) && q->q_k >= 0.0, "loose_scale_run: q_k must be finite and not negative");
+    return GINSIM_OK;
+}
+
+int ginsim_loose_scale_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale,
+                                   char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_scale_kernel_name: bad arguments");
+    int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    rc = check_loose_scale(p, scale);
+    if (rc) return rc;
+    buf[0] = 0;
+    (void)launch_loose_scale(*mc, *p, *scale, nullptr, nullptr, nullptr, buf, cap);
+    return GINSIM_OK;
+}
+
+int ginsim_loose_scale_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale) {
+    REQUIRE(c, "loose_scale_run: NULL argument");
+    int rc = check_loose_params(mc, p);
+    if (rc) return rc;
+    rc = check_loose_scale(p, scale);
+    if (rc) return rc;
+    return loose_launch(c, mc, p, nullptr, nullptr, scale);
 }
 
 int ginsim_aux_sensors(ginsim_ctx* c, const ginsim_aux_params* p) {

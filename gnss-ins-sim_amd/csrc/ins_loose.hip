@@ -49,7 +49,7 @@ int loose_variant(const ginsim_mc_params& p) { return p.given_sensors ? 1 : 0; }
 template <int RF, bool PS>
 static hipError_t launch_loose_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
                                  hipStream_t stream, char* name, size_t cap) {
-    return launch_loose_trio<&loose_kernel<RF, true, false, PS>, &loose_kernel<RF, false, true, PS>, &loose_kernel<RF, false, false, PS>>(
+    return launch_loose_trio<kLooseCovLds, &loose_kernel<RF, true, false, PS>, &loose_kernel<RF, false, true, PS>, &loose_kernel<RF, false, false, PS>>(
         "loose_kernel", RF, PS, p, b, stamp, visible, stream, name, cap);
 }
 

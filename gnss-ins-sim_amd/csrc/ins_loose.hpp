@@ -4,6 +4,9 @@
 // ins_loose_cons.hip's loose_cons_kernel, the consistency checkpoint (loose_checkpoint) behind the flag CONS.  The account of
 // the register budget that put P into LDS is in ins_loose.hip's header; the aiding block's equations are in ins_loose_aided.hip's.
 // For ins_loose_mag.hip's loose_mag_kernel: the magnetometer block (loose_mag) behind the flag MAG; its equations are in that file's header.
+// The covariance and everything that touches it is generic in the number of states NS (CovT<NS>; Cov = CovT<15> is the filter of the
+// four files above).  ins_loose_scale.hip's loose_scale_kernel is the lane with NS = 16: state 15 is the odometer's scale-factor
+// error; what it adds is behind `NS == kLooseStates + 1` and compiles to nothing for NS = 15.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
@@ -16,12 +19,15 @@
 
 namespace ginsim {
 
-constexpr int kLooseStates = 15;
-constexpr int kLooseTri = kLooseStates * (kLooseStates + 1) / 2;
+constexpr int kLooseStates = 15;                                    // dr, dv, psi, dbg, dba: the states every filter has
+constexpr int kLooseScaleStates = kLooseStates + 1;                 // and the odometer's scale-factor error, state 15
+__host__ __device__ constexpr int loose_tri(int ns) { return ns * (ns + 1) / 2; }
+constexpr int kLooseTri = loose_tri(kLooseStates);
 
-// index of element (i, j) of the symmetric matrix in its upper triangle, row by row
+// index of element (i, j) of the symmetric NS x NS matrix in its upper triangle, row by row
+template <int NS = kLooseStates>
 __host__ __device__ constexpr int tri(int i, int j) {
-    return i <= j ? i * kLooseStates - i * (i - 1) / 2 + (j - i) : j * kLooseStates - j * (j - 1) / 2 + (i - j);
+    return i <= j ? i * NS - i * (i - 1) / 2 + (j - i) : j * NS - j * (j - 1) / 2 + (i - j);
 }
 __host__ __device__ constexpr bool in_block(int k, int b) { return k >= b && k < b + 3; }
 // Between the fully unrolled phases of a step: without a fence the scheduler interleaves them for instruction-level parallelism,
@@ -33,7 +39,9 @@ constexpr int kLooseBlock = 64;                                     // lanes per
 
 // P lives in LDS as [element][lane] doubles, 120 x 64 per wavefront (60 KB: two single-wavefront workgroups per CU): a lane's
 // column, no bank conflict, every byte offset a 16-bit immediate.  See the register budget in ins_loose.hip's header.
-constexpr size_t kLooseCovLds = sizeof(double) * kLooseTri * kLooseBlock;
+// With 16 states: 136 x 64 (68 KB; with the 8 KB of normal tables two workgroups are 152 KB of the CU's 160 KB).
+__host__ __device__ constexpr size_t loose_cov_lds(int ns) { return sizeof(double) * loose_tri(ns) * kLooseBlock; }
+constexpr size_t kLooseCovLds = loose_cov_lds(kLooseStates);
 __device__ __forceinline__ double* cov_lds() {
     extern __shared__ double loose_lds[];
     return loose_lds;
@@ -41,9 +49,10 @@ __device__ __forceinline__ double* cov_lds() {
 
 constexpr int kAidFirst = 3, kAidSupport = 6;       // an aiding row is non-zero on dv and psi (states 3-8) only
 
-struct Cov {
-    __device__ __forceinline__ double& at(int i, int j) { return cov_lds()[tri(i, j) * kLooseBlock + threadIdx.x]; }
-    __device__ __forceinline__ double get(int i, int j) const { return cov_lds()[tri(i, j) * kLooseBlock + threadIdx.x]; }
+template <int NS>
+struct CovT {
+    __device__ __forceinline__ double& at(int i, int j) { return cov_lds()[tri<NS>(i, j) * kLooseBlock + threadIdx.x]; }
+    __device__ __forceinline__ double get(int i, int j) const { return cov_lds()[tri<NS>(i, j) * kLooseBlock + threadIdx.x]; }
 
     // P <- T P T^T, T = I + B E(I, J): block row I gains B times block row J (I != J), B a 3x3 matrix
     template <int I, int J>
@@ -58,7 +67,7 @@ struct Cov {
             }
         }
 #pragma unroll
-        for (int k = 0; k < kLooseStates; ++k) {
+        for (int k = 0; k < NS; ++k) {
             if (in_block(k, I)) continue;
             const double t0 = get(J, k), t1 = get(J + 1, k), t2 = get(J + 2, k);
 #pragma unroll
@@ -81,7 +90,7 @@ struct Cov {
             for (int c = 0; c < 3; ++c) W[a][c] = s * get(J + a, I + c);
         }
 #pragma unroll
-        for (int k = 0; k < kLooseStates; ++k) {
+        for (int k = 0; k < NS; ++k) {
             if (in_block(k, I)) continue;
 #pragma unroll
             for (int a = 0; a < 3; ++a) at(I + a, k) += s * get(J + a, k);
@@ -98,7 +107,7 @@ struct Cov {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
 #pragma unroll
-            for (int k = 0; k < kLooseStates; ++k) {
+            for (int k = 0; k < NS; ++k) {
                 if (in_block(k, I)) continue;
                 at(I + a, k) *= d[a];
             }
@@ -117,63 +126,74 @@ struct Cov {
     }
     // scalar measurement of state I with variance rv and innovation-before-state z: x and P updated
     template <int I>
-    __device__ __forceinline__ void update(double z, double rv, double (&x)[kLooseStates]) {
-        double col[kLooseStates];
+    __device__ __forceinline__ void update(double z, double rv, double (&x)[NS]) {
+        double col[NS];
 #pragma unroll
-        for (int k = 0; k < kLooseStates; ++k) col[k] = get(k, I);
+        for (int k = 0; k < NS; ++k) col[k] = get(k, I);
         const double inv = 1.0 / (col[I] + rv);
         const double g = (z - x[I]) * inv;
 #pragma unroll
-        for (int k = 0; k < kLooseStates; ++k) x[k] += col[k] * g;
+        for (int k = 0; k < NS; ++k) x[k] += col[k] * g;
 #pragma unroll
-        for (int a = 0; a < kLooseStates; ++a) {
+        for (int a = 0; a < NS; ++a) {
 #pragma unroll
-            for (int c = a; c < kLooseStates; ++c) at(a, c) -= col[a] * col[c] * inv;
+            for (int c = a; c < NS; ++c) at(a, c) -= col[a] * col[c] * inv;
         }
     }
     // scalar measurement with the row h on states kAidFirst .. kAidFirst + 5 (zero elsewhere), variance rv and
     // innovation-before-state z: Ph = P h, s = h.Ph + rv, g = (z - h.x) / s, x += Ph g, P -= Ph Ph^T / s
-    __device__ __forceinline__ void update_row(const double (&h)[kAidSupport], double z, double rv, double (&x)[kLooseStates]) {
-        double ph[kLooseStates];
+    // LAST: the row has a seventh entry hl on the last state, NS - 1 (the odometer row of the scale-factor filter)
+    template <bool LAST>
+    __device__ __forceinline__ void update_row_impl(const double (&h)[kAidSupport], double hl, double z, double rv, double (&x)[NS]) {
+        double ph[NS];
 #pragma unroll
-        for (int k = 0; k < kLooseStates; ++k) {
+        for (int k = 0; k < NS; ++k) {
             double t = get(k, kAidFirst) * h[0];
 #pragma unroll
             for (int c = 1; c < kAidSupport; ++c) t += get(k, kAidFirst + c) * h[c];
+            if (LAST) t += get(k, NS - 1) * hl;
             ph[k] = t;
         }
         double s = rv, hx = 0.0;
 #pragma unroll
         for (int c = 0; c < kAidSupport; ++c) { s += h[c] * ph[kAidFirst + c]; hx += h[c] * x[kAidFirst + c]; }
+        if (LAST) { s += hl * ph[NS - 1]; hx += hl * x[NS - 1]; }
         const double inv = 1.0 / s;
         const double g = (z - hx) * inv;
 #pragma unroll
-        for (int k = 0; k < kLooseStates; ++k) x[k] += ph[k] * g;
+        for (int k = 0; k < NS; ++k) x[k] += ph[k] * g;
 #pragma unroll
-        for (int a = 0; a < kLooseStates; ++a) {
+        for (int a = 0; a < NS; ++a) {
 #pragma unroll
-            for (int c = a; c < kLooseStates; ++c) at(a, c) -= ph[a] * ph[c] * inv;
+            for (int c = a; c < NS; ++c) at(a, c) -= ph[a] * ph[c] * inv;
         }
     }
+    __device__ __forceinline__ void update_row(const double (&h)[kAidSupport], double z, double rv, double (&x)[NS]) {
+        update_row_impl<false>(h, 0.0, z, rv, x);
+    }
+    __device__ __forceinline__ void update_row(const double (&h)[kAidSupport], double hl, double z, double rv, double (&x)[NS]) {
+        update_row_impl<true>(h, hl, z, rv, x);
+    }
     // the same with the row h on the psi states 6-8 only (the magnetometer rows): three products per element of Ph
-    __device__ __forceinline__ void update_row_psi(const double (&h)[3], double z, double rv, double (&x)[kLooseStates]) {
-        double ph[kLooseStates];
+    __device__ __forceinline__ void update_row_psi(const double (&h)[3], double z, double rv, double (&x)[NS]) {
+        double ph[NS];
 #pragma unroll
-        for (int k = 0; k < kLooseStates; ++k) ph[k] = get(k, 6) * h[0] + get(k, 7) * h[1] + get(k, 8) * h[2];
+        for (int k = 0; k < NS; ++k) ph[k] = get(k, 6) * h[0] + get(k, 7) * h[1] + get(k, 8) * h[2];
         double s = rv, hx = 0.0;
 #pragma unroll
         for (int c = 0; c < 3; ++c) { s += h[c] * ph[6 + c]; hx += h[c] * x[6 + c]; }
         const double inv = 1.0 / s;
         const double g = (z - hx) * inv;
 #pragma unroll
-        for (int k = 0; k < kLooseStates; ++k) x[k] += ph[k] * g;
+        for (int k = 0; k < NS; ++k) x[k] += ph[k] * g;
 #pragma unroll
-        for (int a = 0; a < kLooseStates; ++a) {
+        for (int a = 0; a < NS; ++a) {
 #pragma unroll
-            for (int c = a; c < kLooseStates; ++c) at(a, c) -= ph[a] * ph[c] * inv;
+            for (int c = a; c < NS; ++c) at(a, c) -= ph[a] * ph[c] * inv;
         }
     }
 };
+using Cov = CovT<kLooseStates>;
 
 // C = body -> navigation of the attitude (the matrix of Att::to_nav)
 __device__ __forceinline__ void body_to_nav(const Att& t, double (&C)[3][3]) {
@@ -203,8 +223,20 @@ __device__ __forceinline__ loose_mag_ptr loose_mag_params() {
     return (loose_mag_ptr)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
 }
 
+// loose_scale_kernel's fifth argument, the scale-factor block by value, where loose_mag_kernel has the magnetometer block
+typedef const ginsim_loose_scale_params __attribute__((address_space(4))) * loose_scale_ptr;
+static_assert(alignof(ginsim_loose_scale_params) == 8, "the kernarg offset of loose_scale_params()");
+__device__ __forceinline__ loose_scale_ptr loose_scale_params() {
+    typedef const char __attribute__((address_space(4))) * bytes_ptr;
+    bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (loose_scale_ptr)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
+}
+
 // P <- Phi P Phi^T + Qd for the step from the attitude with body -> navigation matrix C and bias-corrected specific force f^n
-__device__ __forceinline__ void loose_propagate(Cov& P, const double (&C)[3][3], double fx, double fy, double fz, double dt) {
+// (NS = 16: Phi is the identity on state 15, whose row takes part in every congruence as a column; P[15][15] += q_k)
+template <int NS>
+__device__ __forceinline__ void loose_propagate(CovT<NS>& P, const double (&C)[3][3], double fx, double fy, double fz, double dt) {
     const double A[3][3] = {{0.0, -fz * dt, fy * dt}, {fz * dt, 0.0, -fx * dt}, {-fy * dt, fx * dt, 0.0}};      // [f^n x] dt
     double Cp[3][3], Cm[3][3];
 #pragma unroll
@@ -212,25 +244,27 @@ __device__ __forceinline__ void loose_propagate(Cov& P, const double (&C)[3][3],
 #pragma unroll
         for (int c = 0; c < 3; ++c) { Cp[a][c] = C[a][c] * dt; Cm[a][c] = -Cp[a][c]; }
     }
-    P.congruence<0, 3>(dt); phase_fence();         // T_r
-    P.congruence<3, 6>(A); phase_fence();          // T_v
-    P.congruence<3, 12>(Cm); phase_fence();
-    P.congruence<6, 9>(Cp); phase_fence();         // T_psi
+    P.template congruence<0, 3>(dt); phase_fence();         // T_r
+    P.template congruence<3, 6>(A); phase_fence();          // T_v
+    P.template congruence<3, 12>(Cm); phase_fence();
+    P.template congruence<6, 9>(Cp); phase_fence();         // T_psi
     const loose_ptr lp = loose_params();
     const double dg[3] = {lp->decay_g[0], lp->decay_g[1], lp->decay_g[2]}, da[3] = {lp->decay_a[0], lp->decay_a[1], lp->decay_a[2]};
-    P.scale<9>(dg); phase_fence();                 // D
-    P.scale<12>(da); phase_fence();
+    P.template scale<9>(dg); phase_fence();                 // D
+    P.template scale<12>(da); phase_fence();
     const double qv[3] = {lp->q_v[0], lp->q_v[1], lp->q_v[2]}, qp[3] = {lp->q_psi[0], lp->q_psi[1], lp->q_psi[2]};
-    P.add_rotated<3>(C, qv); phase_fence();
-    P.add_rotated<6>(C, qp); phase_fence();
+    P.template add_rotated<3>(C, qv); phase_fence();
+    P.template add_rotated<6>(C, qp); phase_fence();
 #pragma unroll
     for (int a = 0; a < 3; ++a) { P.at(9 + a, 9 + a) += lp->q_bg[a]; P.at(12 + a, 12 + a) += lp->q_ba[a]; }
+    if (NS == kLooseScaleStates) P.at(kLooseStates, kLooseStates) += loose_scale_params()->q_k;
 }
 
 // The feedback of the error state x into the mechanisation and the bias estimates (truth = estimate - error).  mlat, mlon:
-// metres per radian of latitude / longitude at the state before the feedback (ref_frame 0)
-template <int RF>
-__device__ __forceinline__ void loose_feedback(Nav& s, Vec3& bg, Vec3& ba, const double (&x)[kLooseStates], double mlat, double mlon) {
+// metres per radian of latitude / longitude at the state before the feedback (ref_frame 0).  x[15] of the scale-factor filter is
+// fed back by the caller (k_est -= x[15])
+template <int RF, int NS>
+__device__ __forceinline__ void loose_feedback(Nav& s, Vec3& bg, Vec3& ba, const double (&x)[NS], double mlat, double mlon) {
     if (RF == 0) {
         s.pos.x -= x[0] / mlat;
         s.pos.y -= x[1] / mlon;
@@ -257,9 +291,9 @@ __device__ __forceinline__ void loose_feedback(Nav& s, Vec3& bg, Vec3& ba, const
     ba.x -= x[12]; ba.y -= x[13]; ba.z -= x[14];
 }
 
-// One fix: six scalar updates, then the feedback
-template <int RF>
-__device__ __forceinline__ void loose_correct(Cov& P, Nav& s, Vec3& bg, Vec3& ba, const double (&fix)[6]) {
+// One fix: six scalar updates, then the feedback.  kest: the scale-factor estimate (NS = 16; not touched otherwise)
+template <int RF, int NS>
+__device__ __forceinline__ void loose_correct(CovT<NS>& P, Nav& s, Vec3& bg, Vec3& ba, const double (&fix)[6], double& kest) {
     const loose_ptr lp = loose_params();
     double z[6], mlat = 1.0, mlon = 1.0;
     if (RF == 0) {          // LLA difference -> NED metres
@@ -273,22 +307,25 @@ __device__ __forceinline__ void loose_correct(Cov& P, Nav& s, Vec3& bg, Vec3& ba
         z[0] = s.pos.x - fix[0]; z[1] = s.pos.y - fix[1]; z[2] = s.pos.z - fix[2];
     }
     z[3] = s.vel.x - fix[3]; z[4] = s.vel.y - fix[4]; z[5] = s.vel.z - fix[5];
-    double x[kLooseStates];
+    double x[NS];
 #pragma unroll
-    for (int k = 0; k < kLooseStates; ++k) x[k] = 0.0;
-    P.update<0>(z[0], lp->r_diag[0], x); phase_fence();
-    P.update<1>(z[1], lp->r_diag[1], x); phase_fence();
-    P.update<2>(z[2], lp->r_diag[2], x); phase_fence();
-    P.update<3>(z[3], lp->r_diag[3], x); phase_fence();
-    P.update<4>(z[4], lp->r_diag[4], x); phase_fence();
-    P.update<5>(z[5], lp->r_diag[5], x); phase_fence();
+    for (int k = 0; k < NS; ++k) x[k] = 0.0;
+    P.template update<0>(z[0], lp->r_diag[0], x); phase_fence();
+    P.template update<1>(z[1], lp->r_diag[1], x); phase_fence();
+    P.template update<2>(z[2], lp->r_diag[2], x); phase_fence();
+    P.template update<3>(z[3], lp->r_diag[3], x); phase_fence();
+    P.template update<4>(z[4], lp->r_diag[4], x); phase_fence();
+    P.template update<5>(z[5], lp->r_diag[5], x); phase_fence();
     loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
+    if (NS == kLooseScaleStates) kest -= x[NS - 1];
 }
 
 // One aiding block (ins_loose_aided.hip's header): the rows `mask` selects, in ascending order, from x = 0; then the feedback.
 // D = C^T, v_b = D v and every row are formed from the state before the first row.  mask is wave-uniform.
-template <int RF>
-__device__ __forceinline__ void loose_aid(Cov& P, Nav& s, Vec3& bg, Vec3& ba, double odo, int mask) {
+// NS = 16: the odometer is divided by the estimate kest, not by odo_scale_f, and its row has the seventh entry
+// h[15] = v_b[0] / kest; the block ends with kest -= x[15].  kest is not touched otherwise.
+template <int RF, int NS>
+__device__ __forceinline__ void loose_aid(CovT<NS>& P, Nav& s, Vec3& bg, Vec3& ba, double odo, int mask, double& kest) {
     const loose_ptr lp = loose_params();
     double C[3][3];
     body_to_nav(s.att, C);
@@ -303,21 +340,32 @@ __device__ __forceinline__ void loose_aid(Cov& P, Nav& s, Vec3& bg, Vec3& ba, do
         h[i][5] = v[0] * d1 - v[1] * d0;
         z[i] = d0 * v[0] + d1 * v[1] + d2 * v[2];
     }
-    z[0] -= odo / lp->odo_scale_f;
+    double hk = 0.0;
+    if (NS == kLooseScaleStates) {
+        hk = z[0] / kest;
+        z[0] -= odo / kest;
+    } else {
+        z[0] -= odo / lp->odo_scale_f;
+    }
     double mlat = 1.0, mlon = 1.0;
     if (RF == 0) {
         const Geo e = geo_param_sc(s.sl, s.cl, s.pos.z);
         mlat = e.rm + s.pos.z;
         mlon = (e.rn + s.pos.z) * e.cl;
     }
-    double x[kLooseStates];
+    double x[NS];
 #pragma unroll
-    for (int k = 0; k < kLooseStates; ++k) x[k] = 0.0;
+    for (int k = 0; k < NS; ++k) x[k] = 0.0;
     phase_fence();
-    if (mask & 1) { P.update_row(h[0], z[0], lp->r_odo, x); phase_fence(); }
+    if (mask & 1) {
+        if (NS == kLooseScaleStates) P.update_row(h[0], hk, z[0], lp->r_odo, x);
+        else P.update_row(h[0], z[0], lp->r_odo, x);
+        phase_fence();
+    }
     if (mask & 2) { P.update_row(h[1], z[1], lp->r_nhc, x); phase_fence(); }
     if (mask & 4) { P.update_row(h[2], z[2], lp->r_nhc, x); phase_fence(); }
     loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
+    if (NS == kLooseScaleStates) kest -= x[NS - 1];
 }
 
 // One magnetometer block (ins_loose_mag.hip's header): the three rows in ascending order from x = 0; then the feedback.
@@ -469,9 +517,12 @@ __device__ __forceinline__ void put3(double* base, int64_t plane, int64_t off, c
 // MAG: the magnetometer block (loose_mag) at every sample j > 0 with j % mag_every == 0, after a fix and an aiding block of the same
 // sample, before a checkpoint and before the row is stored; its numbers are the kernel's fifth argument (loose_mag_params).  With
 // MAG an aid_mask of 0 fires no aiding block at all.  MAG = false is the lane as it was.
-template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false, bool MAG = false>
+// NS: the number of states.  16 (with AID, without CONS and MAG): the odometer's scale factor is state 15 and its estimate kest a
+// value of the lane; its numbers and outputs are the kernel's fifth argument (loose_scale_params).  NS = 15 is the lane as it was.
+template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false, bool MAG = false, int NS = kLooseStates>
 __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const ginsim_loose_params& b, const int64_t* __restrict__ stamp,
                                            const int32_t* __restrict__ visible, uint32_t* ntab, const ConsArgs& cq = ConsArgs{}) {
+    static_assert(NS == kLooseStates || (NS == kLooseScaleStates && AID && !CONS && !MAG), "16 states: the aided lane only");
     NormalTables tab{};
     if (!GIVEN) {
         tab = fill_normal_tables(ntab, threadIdx.x, blockDim.x);
@@ -505,11 +556,17 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
     MathConsts mk;
     mk.init<false>();
     Vec3 bg{0.0, 0.0, 0.0}, ba{0.0, 0.0, 0.0};
-    Cov P;
+    CovT<NS> P;
 #pragma unroll
     for (int i = 0; i < kLooseStates; ++i) {
 #pragma unroll
-        for (int k = i; k < kLooseStates; ++k) P.at(i, k) = i == k ? b.p0[i / 3] * b.p0[i / 3] : 0.0;
+        for (int k = i; k < NS; ++k) P.at(i, k) = i == k ? b.p0[i / 3] * b.p0[i / 3] : 0.0;
+    }
+    double kest = 0.0;      // the scale-factor estimate (NS = 16 only)
+    if (NS == kLooseScaleStates) {
+        const loose_scale_ptr sp = loose_scale_params();
+        kest = sp->scale0;
+        P.at(kLooseStates, kLooseStates) = sp->p0_scale * sp->p0_scale;
     }
     Proc<1> ps;
     if (PS) ps.clear();
@@ -539,7 +596,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
                 } else {
                     gps_fix(as_uniform(lb->ref_gps) + 6 * kf, loose_params()->gps_sigma, key, (uint32_t)kf, tab, fix);
                 }
-                loose_correct<RF>(P, s, bg, ba, fix);
+                loose_correct<RF>(P, s, bg, ba, fix, kest);
             }
             ++kf;
         }
@@ -559,11 +616,11 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
                     }
                 }
                 phase_fence();
-                loose_aid<RF>(P, s, bg, ba, odo, mask);
+                loose_aid<RF>(P, s, bg, ba, odo, mask, kest);
                 phase_fence();
             }
         }
-        if (MAG) {
+        if constexpr (MAG) {
             if (j == jm) {
                 const loose_mag_ptr mp = loose_mag_params();
                 jm += mp->mag_every < n ? mp->mag_every : n;
@@ -584,7 +641,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
                 phase_fence();
             }
         }
-        if (CONS) {
+        if constexpr (CONS) {
             if (kc < cq.m && cq.sample[kc] == j) {
                 phase_fence();
                 loose_checkpoint<RF>(P, s, nav_truth + 9 * j, live, cq.work + ((int64_t)blockIdx.x * cq.m + kc) * GINSIM_CONS_RECORD);
@@ -595,6 +652,10 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
         if (lb->out_traj) store9(lb->out_traj, plane, off, s);
         put3(lb->out_wb, plane, off, bg);
         put3(lb->out_ab, plane, off, ba);
+        if (NS == kLooseScaleStates) {
+            double* const ks = loose_scale_params()->out_scale;
+            if (ks) ks[off] = kest;
+        }
         if (PS) {
             if (j >= ka->proc_first) {
                 const uniform_ptr q = nav_truth + 9 * j;
@@ -652,6 +713,16 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
     if (b.out_pdiag_end) {
 #pragma unroll
         for (int k = 0; k < kLooseStates; ++k) b.out_pdiag_end[k * runs + r] = P.get(k, k);
+    }
+    if (NS == kLooseScaleStates) {
+        const loose_scale_ptr sp = loose_scale_params();
+        double* const se = sp->out_scale_end;
+        double* const pc = sp->out_pcross_end;
+        if (se) { se[r] = kest; se[runs + r] = P.get(kLooseStates, kLooseStates); }
+        if (pc) {
+#pragma unroll
+            for (int k = 0; k < kLooseStates; ++k) pc[k * runs + r] = P.get(k, kLooseStates);
+        }
     }
 }
 

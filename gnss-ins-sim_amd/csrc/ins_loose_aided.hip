@@ -36,7 +36,7 @@ loose_aided_kernel(const ginsim_mc_params a, const ginsim_loose_params b, const 
 template <int RF, bool PS>
 static hipError_t launch_aided_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
                                  hipStream_t stream, char* name, size_t cap) {
-    return launch_loose_trio<&loose_aided_kernel<RF, true, false, PS>, &loose_aided_kernel<RF, false, true, PS>,
+    return launch_loose_trio<kLooseCovLds, &loose_aided_kernel<RF, true, false, PS>, &loose_aided_kernel<RF, false, true, PS>,
                              &loose_aided_kernel<RF, false, false, PS>>("loose_aided_kernel", RF, PS, p, b, stamp, visible, stream, name, cap);
 }
 

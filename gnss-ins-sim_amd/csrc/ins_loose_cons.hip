@@ -55,7 +55,7 @@ static hipError_t launch_cons_a(const ginsim_mc_params& p, const ginsim_loose_pa
     cq.sample = samples;
     cq.m = c.cons_m;
     cq.work = c.cons_work;
-    const hipError_t e = launch_loose_trio<&loose_cons_kernel<RF, true, false, AID>, &loose_cons_kernel<RF, false, true, AID>,
+    const hipError_t e = launch_loose_trio<kLooseCovLds, &loose_cons_kernel<RF, true, false, AID>, &loose_cons_kernel<RF, false, true, AID>,
                                            &loose_cons_kernel<RF, false, false, AID>>("loose_cons_kernel", RF, AID, p, b, stamp, visible, stream,
                                                                                       name, cap, cq);
     if (name || e != hipSuccess) return e;

@@ -43,7 +43,7 @@ loose_mag_kernel(const ginsim_mc_params a, const ginsim_loose_params b, const in
 template <int RF, bool PS>
 static hipError_t launch_mag_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_mag_params& g, const int64_t* stamp,
                                const int32_t* visible, hipStream_t stream, char* name, size_t cap) {
-    return launch_loose_trio<&loose_mag_kernel<RF, true, false, PS>, &loose_mag_kernel<RF, false, true, PS>,
+    return launch_loose_trio<kLooseCovLds, &loose_mag_kernel<RF, true, false, PS>, &loose_mag_kernel<RF, false, true, PS>,
                              &loose_mag_kernel<RF, false, false, PS>>("loose_mag_kernel", RF, PS, p, b, stamp, visible, stream, name, cap, g);
 }
 

@@ -49,6 +49,10 @@ hipError_t launch_loose_cons(const ginsim_mc_params& p, const ginsim_loose_param
 hipError_t launch_loose_mag(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_mag_params& g, const int64_t* stamp,
                             const int32_t* visible, hipStream_t stream, char* name, size_t cap);
 
+// ins_loose_scale.hip: the aided filter with the odometer's scale factor as a 16th state (b.aid_mask has bit 0)
+hipError_t launch_loose_scale(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_scale_params& g, const int64_t* stamp,
+                              const int32_t* visible, hipStream_t stream, char* name, size_t cap);
+
 // aux_sensors.hip
 hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s);
 

@@ -1,4 +1,4 @@
-// The host-side launch of the loose family (ins_loose.hip, ins_loose_aided.hip, ins_loose_cons.hip, ins_loose_mag.hip): each file defines its own
+// The host-side launch of the loose family (ins_loose.hip, ins_loose_aided.hip, ins_loose_cons.hip, ins_loose_mag.hip, ins_loose_scale.hip): each file defines its own
 // __global__ wrapper of loose_body and hands its instantiations to launch_loose_trio in threes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,8 +13,9 @@ namespace ginsim {
 // GIVEN / VIB / PLAIN: the instantiations <RF, true, false, F>, <RF, false, true, F> and <RF, false, false, F> of one kernel template
 // (samples from in_accel / in_gyro; generated with a vibration term; generated without).  kernel, rf, flag: the template's name and
 // the values of RF and F, for the printed name.  tail: the kernel's arguments after (p, b, stamp, visible).
+// LDS: the bytes of dynamic LDS the family's covariance takes (loose_cov_lds of its number of states), for the attribute and the launch.
 // name != NULL: report the kernel's name, do not launch.
-template <auto GIVEN, auto VIB, auto PLAIN, class... Tail>
+template <size_t LDS, auto GIVEN, auto VIB, auto PLAIN, class... Tail>
 hipError_t launch_loose_trio(const char* kernel, int rf, bool flag, const ginsim_mc_params& p, const ginsim_loose_params& b,
                              const int64_t* stamp, const int32_t* visible, hipStream_t stream, char* name, size_t cap, Tail... tail) {
     const dim3 grid((unsigned)((b.n_list + kLooseBlock - 1) / kLooseBlock)), block((unsigned)kLooseBlock);
@@ -26,9 +27,9 @@ hipError_t launch_loose_trio(const char* kernel, int rf, bool flag, const ginsim
     static PerDeviceOnce once;          // one per trio.  More than 64 KB of dynamic LDS: the attribute, on every device that launches
     once.run([] {
         for (auto k : {GIVEN, VIB, PLAIN})
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLooseCovLds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
     });
-    hipLaunchKernelGGL(given ? GIVEN : (vib ? VIB : PLAIN), grid, block, kLooseCovLds, stream, p, b, stamp, visible, tail...);
+    hipLaunchKernelGGL(given ? GIVEN : (vib ? VIB : PLAIN), grid, block, LDS, stream, p, b, stamp, visible, tail...);
     return hipGetLastError();
 }
 

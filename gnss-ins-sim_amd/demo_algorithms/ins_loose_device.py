@@ -9,7 +9,8 @@ The checkout's own stub (demo_algorithms.ins_loose) stays hosted.  fp64 only.
 
     InsLoose(ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None,
              odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None,
-             mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None)
+             mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None,
+             odo_scale_state=False, odo_scale0=1.0, odo_scale_p0=0.02, odo_scale_q=0.0)
 
 ini_pos_vel_att: the initial states FreeIntegration takes ((9|10,) or (9|10, k)); None under a Sim: the motion definition's.
 imu: the IMU model the filter is tuned to (its accel_err, gyro_err, gps_err); None under a Sim: the Sim's own.  ref_frame is the
@@ -28,6 +29,12 @@ error with the three axes of the calibrated magnetometer sample every mag_every 
 'odo'; the IMU model needs axis=9).  mag_std [uT]: 1 sigma of the raw sample per axis; mag_si (3, 3), mag_hi (3,): the soft- and
 hard-iron calibration the filter assumes (defaults: the IMU model's mag_err; MagCal's result can be passed).  geo_mag_n [uT, NED]:
 the field the filter assumes; None under a Sim: the Sim's own.  ``run`` on a logged series needs it.
+
+The odometer's scale factor as a state (csrc/ins_loose_scale.hip; as NumPy in tests/ins_loose_scale_ref.py):
+odo_scale_state=True (needs odo=True) makes the scale factor the filter's 16th state instead of a number the user must know: the
+estimate starts at odo_scale0 with the 1 sigma odo_scale_p0, is learnt while GPS is visible and used through an outage;
+odo_scale_q [1/sqrt(s)] lets it wander (default 0: a constant).  ``output`` gains a trailing 'odo_scale', the estimate at every
+sample.  odo_scale= belongs to the filter without the state and is an error with it; not together with mag=True.
 """
 import numpy as np
 
@@ -42,10 +49,23 @@ class InsLoose(object):
 
     def __init__(self, ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None,
                  odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None,
-                 mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None):
+                 mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None,
+                 odo_scale_state=False, odo_scale0=1.0, odo_scale_p0=0.02, odo_scale_q=0.0):
         self.odo, self.nhc, self.mag = bool(odo), bool(nhc), bool(mag)
+        self.odo_scale_state = bool(odo_scale_state)
+        if self.odo_scale_state:
+            if not self.odo:
+                raise ValueError('odo_scale_state=True needs odo=True: a scale-factor state without the odometer is refused')
+            if odo_scale is not None:
+                raise ValueError('odo_scale= is the scale factor the filter WITHOUT the state assumes; with odo_scale_state=True the '
+                                 'filter estimates it: give the starting value as odo_scale0=')
+            if self.mag:
+                raise ValueError('odo_scale_state=True together with mag=True is not built')
+            from ginsim.ins_loose import scale_model
+            scale_model(None, {'scale0': odo_scale0, 'p0': odo_scale_p0, 'q': odo_scale_q}, 1.0)        # the errors of the three numbers
+        self.odo_scale0, self.odo_scale_p0, self.odo_scale_q = float(odo_scale0), float(odo_scale_p0), float(odo_scale_q)
         self.input = ['fs', 'gyro', 'accel', 'time', 'gps_time', 'gps'] + (['odo'] if self.odo else []) + (['mag'] if self.mag else [])
-        self.output = ['pos', 'vel', 'att_euler', 'wb', 'ab']
+        self.output = ['pos', 'vel', 'att_euler', 'wb', 'ab'] + (['odo_scale'] if self.odo_scale_state else [])
         self.batch = True
         self.results = None
         self.ini = None if ini_pos_vel_att is None else np.array(ini_pos_vel_att, dtype=np.float64)
@@ -98,9 +118,16 @@ class InsLoose(object):
             return None
         return {'every': self.mag_every, 'std': self.mag_std, 'si': self.mag_si, 'hi': self.mag_hi}
 
-    def finish(self, pos, vel, att, wb, ab):
-        """State the plugin holds after a run: the last run's series, each (n, 3), in the order of `output`."""
-        self.results = [pos, vel, att, wb, ab]
+    def scale_options(self):
+        """The options of the scale-factor state ginsim.InsLooseJob takes (ginsim.ins_loose.scale_model), or None without it."""
+        if not self.odo_scale_state:
+            return None
+        return {'scale0': self.odo_scale0, 'p0': self.odo_scale_p0, 'q': self.odo_scale_q}
+
+    def finish(self, pos, vel, att, wb, ab, odo_scale=None):
+        """State the plugin holds after a run: the last run's series, each (n, 3), in the order of `output`; with
+        odo_scale_state the estimate's series (n,) the last."""
+        self.results = [pos, vel, att, wb, ab] + ([odo_scale] if self.odo_scale_state else [])
 
     def run(self, set_of_input):
         '''
@@ -156,8 +183,8 @@ class InsLoose(object):
             job = InsLooseJob(ctx, fs, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, self.imu.gps_err, self.ini, 1,
                               ini_first=self.run_times, earth_rot=self.earth_rot, given=bufs, q_scale=self.q_scale, p0=self.p0,
                               keep_traj=True, odo_err=getattr(self.imu, 'odo_err', None), aid=self.aid(),
-                              **self._mag_arguments()).run()
-            self.finish(*[job.series(k, [0])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab')])
+                              **self._mag_arguments(), **self._scale_arguments()).run()
+            self.finish(*[job.series(k, [0])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab') + (('odo_scale',) if self.odo_scale_state else ())])
         finally:
             if job is not None:
                 job.release()
@@ -167,6 +194,9 @@ class InsLoose(object):
 
     def _mag_arguments(self):
         return {} if not self.mag else {'mag_err': getattr(self.imu, 'mag_err', None), 'geo_mag_n': self.geo_mag_n, 'mag': self.mag_options()}
+
+    def _scale_arguments(self):
+        return {} if not self.odo_scale_state else {'odo_scale_state': self.scale_options(), 'keep_scale': True}
 
     def get_results(self):
         return self.results

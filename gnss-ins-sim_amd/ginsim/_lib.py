@@ -117,6 +117,12 @@ class LooseMagParams(C.Structure):
                 ('cal_hi', C.c_double * 3), ('r_mag', C.c_double * 3)]
 
 
+class LooseScaleParams(C.Structure):
+    """ginsim_loose_scale_params: the odometer's scale factor as a 16th state of a filter launch (csrc/ins_loose_scale.hip)."""
+    _fields_ = [('scale0', C.c_double), ('p0_scale', C.c_double), ('q_k', C.c_double), ('out_scale', C.c_void_p),
+                ('out_scale_end', C.c_void_p), ('out_pcross_end', C.c_void_p)]
+
+
 class PathgenParams(C.Structure):
     _fields_ = [('ini_pva', C.c_double * 9), ('mobility', C.c_double * 3), ('fs', C.c_double),
                 ('fs_gps', C.c_double), ('ref_frame', C.c_int32), ('enable_gps', C.c_int32),
@@ -193,6 +199,9 @@ _SIGS = {
     'ginsim_loose_mag_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseMagParams)]),
     'ginsim_loose_mag_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseMagParams), C.c_char_p,
                                                C.c_size_t]),
+    'ginsim_loose_scale_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseScaleParams)]),
+    'ginsim_loose_scale_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseScaleParams), C.c_char_p,
+                                                 C.c_size_t]),
     'ginsim_end_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     'ginsim_end_stats_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     'ginsim_end_stats_finish': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Stats)]),

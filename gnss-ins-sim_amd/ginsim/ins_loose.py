@@ -7,7 +7,8 @@ With aid=... the filter also uses the odometer and the non-holonomic constraints
 aiding_model; restated by tests/ins_loose_aided_ref.py).  With cons_samples=... the launch also reduces, across its runs, the
 filter's covariance and its actual error at those samples (csrc/ins_loose_cons.hip, consistency(); restated by
 tests/ins_loose_cons_ref.py).  With mag=... the filter also uses the magnetometer, a three-row block on the attitude error
-(csrc/ins_loose_mag.hip, mag_model; restated by tests/ins_loose_mag_ref.py).
+(csrc/ins_loose_mag.hip, mag_model; restated by tests/ins_loose_mag_ref.py).  With odo_scale_state=... the odometer's scale factor is
+a 16th state that the filter estimates (csrc/ins_loose_scale.hip, scale_model; restated by tests/ins_loose_scale_ref.py).
 """
 import ctypes as C
 
@@ -72,7 +73,8 @@ def aiding_model(odo_err, aid):
 
       aid_mask     bit 0 'odo' (z = v_b[0] - odo / scale), bits 1 and 2 'nhc' (z = v_b[1], v_b[2])
       odo_scale_f  'scale': the scale factor the FILTER assumes; default odo_err['scale'].  It is a parameter, not a state: a
-                   filter that assumes 1.0 of an odometer that reads 0.99 is inconsistent by a factor of tens
+                   filter that assumes 1.0 of an odometer that reads 0.99 is inconsistent by a factor of tens (DESIGN 4.11b);
+                   InsLooseJob(odo_scale_state=...) estimates it instead (scale_model)
       r_odo        'odo_std'^2 [m/s]: of the SCALED sample; default odo_err['stdv'] / scale
       r_nhc        'nhc_std'^2 [m/s]; default 0.05: a pseudo-noise, how far the vehicle may slide
       aid_every    'every': a block every so many IMU samples; default 1
@@ -170,6 +172,33 @@ def mag_model(mag_err, geo_mag_n, ref_frame, mag=None):
             'r_mag': np.einsum('ik,k,ik->i', cal_si, std * std, cal_si)}
 
 
+def scale_model(odo_err, opts, fs=None):
+    """The three numbers of ginsim_loose_scale_params that describe the FILTER, {'scale0', 'p0_scale', 'q_k'}, from the odometer's
+    error dict {'scale', 'stdv'} (not read: the filter does not know the odometer's scale -- that is the point of the state) and
+    the options opts = {'scale0': float, 'p0': float, 'q': float}:
+
+      scale0    the scale factor the filter starts from; default 1.0
+      p0_scale  'p0': the initial 1 sigma of the scale-factor error; default 0.02; 0 (with q 0) is the filter that assumes scale0
+      q_k       'q'^2 / fs: 'q' [1/sqrt(s)] is the random walk of the scale factor; default 0, a constant.  'q' > 0 needs fs
+    opts None: no scale state (None is returned); {} or True takes every default."""
+    if opts is None or opts is False:
+        return None
+    opts = {} if opts is True else dict(opts)
+    unknown = set(opts) - {'scale0', 'p0', 'q'}
+    if unknown:
+        raise ValueError('odo_scale_state: unknown keys %s' % sorted(unknown))
+    scale0, p0, q = float(opts.get('scale0', 1.0)), float(opts.get('p0', 0.02)), float(opts.get('q', 0.0))
+    if not (scale0 > 0.0 and np.isfinite(scale0)):
+        raise ValueError("odo_scale_state['scale0'] must be positive and finite")
+    if not (p0 >= 0.0 and np.isfinite(p0)):
+        raise ValueError("odo_scale_state['p0'] must be finite and not negative")
+    if not (q >= 0.0 and np.isfinite(q)):
+        raise ValueError("odo_scale_state['q'] must be finite and not negative")
+    if q > 0.0 and fs is None:
+        raise ValueError("odo_scale_state['q'] > 0 needs the sample rate fs")
+    return {'scale0': scale0, 'p0_scale': p0, 'q_k': q * q / float(fs) if q > 0.0 else 0.0}
+
+
 class InsLooseJob(BatchJob):
     """One batch of runs of the loosely coupled filter on one device.
 
@@ -192,6 +221,10 @@ class InsLooseJob(BatchJob):
     mag_model() (csrc/ins_loose_mag.hip; mag None: the filter without the magnetometer block; {} takes every default).  The
     generated form needs truth['ref_mag'] (n, 3) and mag_err: the lane makes the magnetometer sample AuxSensorJob would store for
     the same seed and run ids.  The given form reads given['mag'] [3][n][runs].  Not together with cons_samples.
+    odo_scale_state: None, or the options of scale_model() ({} takes every default): the odometer's scale factor is the filter's
+    16th state (csrc/ins_loose_scale.hip).  Needs aid['odo']; aid['scale'] is then not read (the filter starts from 'scale0'), and
+    r_odo defaults to (odo_err['stdv'] / scale0)^2.  Not together with mag, cons_samples or fp32.  keep_scale: materialise the
+    k_est series ([n][runs]; series('odo_scale', ...)).
     """
 
     algos = ('loose',)
@@ -199,7 +232,7 @@ class InsLooseJob(BatchJob):
     def __init__(self, ctx, fs, ref_frame, truth, accel_err, gyro_err, gps_err, ini, runs, seed=0, run_offset=0, ini_first=0,
                  earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
                  end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None,
-                 cons_samples=None, mag_err=None, geo_mag_n=None, mag=None):
+                 cons_samples=None, mag_err=None, geo_mag_n=None, mag=None, odo_scale_state=None, keep_scale=False):
         self.ctx = ctx
         self.n, self.runs = int(truth['ref_accel'].shape[0]), int(runs)
         if self.runs < 1:
@@ -230,6 +263,22 @@ class InsLooseJob(BatchJob):
         p.gps_stamp, p.gps_visible = self._stamps.ctypes.data, self._visible.ctypes.data
         for k in ('r_diag', 'p0', 'q_v', 'q_psi', 'q_bg', 'q_ba', 'decay_g', 'decay_a'):
             getattr(p, k)[:] = [float(x) for x in np.asarray(self.model[k], dtype=np.float64).reshape(-1)]
+        self.scale, self.scalep = scale_model(odo_err, odo_scale_state, fs), None
+        self.keep_scale = bool(keep_scale)
+        if self.scale is None and self.keep_scale:
+            raise ValueError('keep_scale: the scale-factor series exists with odo_scale_state=... only')
+        if self.scale is not None:
+            if mag is not None:
+                raise ValueError('odo_scale_state: the scale-factor state together with the magnetometer block (mag=...) is not built')
+            if cons_samples is not None:
+                raise ValueError('odo_scale_state: consistency checkpoints (cons_samples=...) of the filter with the scale-factor '
+                                 'state are not built')
+            if not (aid and aid.get('odo')):
+                raise ValueError("odo_scale_state: a scale-factor state without the odometer (aid['odo']) is refused")
+            # what the 15-state filter is told (aid['scale']) the 16-state filter starts from (scale0); r_odo's default follows it
+            aid = dict(aid, scale=self.scale['scale0'])
+            if aid.get('odo_std') is None and odo_err is None:
+                raise ValueError("odo_scale_state needs odo_err={'scale', 'stdv'} or aid['odo_std']")
         self.aid = aiding_model(odo_err, aid)
         for k, v in self.aid.items():
             setattr(p, k, v)
@@ -312,6 +361,14 @@ class InsLooseJob(BatchJob):
             self._bufs['wb'] = DeviceView(self._bufs['series'], 9 * plane, 3 * plane)
             self._bufs['ab'] = DeviceView(self._bufs['series'], 12 * plane, 3 * plane)
             p.out_traj, p.out_wb, p.out_ab = self._bufs['traj_loose'].ptr, self._bufs['wb'].ptr, self._bufs['ab'].ptr
+        if self.scale is not None:
+            g = self.scalep = _lib.LooseScaleParams()
+            g.scale0, g.p0_scale, g.q_k = self.scale['scale0'], self.scale['p0_scale'], self.scale['q_k']
+            # scale_end [2][R], pcross_end [15][R], and the kept series [n][R]
+            self._bufs['scale'] = ctx.malloc((17 + (self.n if self.keep_scale else 0)) * R * 8)
+            g.out_scale_end, g.out_pcross_end = self._bufs['scale'].ptr, self._bufs['scale'].at(2 * R * 8)
+            if self.keep_scale:
+                g.out_scale = self._bufs['scale'].at(17 * R * 8)
         p.n_list = R
         self.cons = None
         if cons_samples is not None:
@@ -337,6 +394,8 @@ class InsLooseJob(BatchJob):
             check(lib.ginsim_loose_cons_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.cons), buf, 256))
         elif self.magp is not None:
             check(lib.ginsim_loose_mag_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.magp), buf, 256))
+        elif self.scalep is not None:
+            check(lib.ginsim_loose_scale_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.scalep), buf, 256))
         else:
             check(lib.ginsim_loose_kernel_name(C.byref(self.mc), C.byref(self.params), buf, 256))
         return buf.value.decode()
@@ -355,6 +414,8 @@ class InsLooseJob(BatchJob):
             check(self.ctx.retry_oom(lambda: lib.ginsim_loose_cons_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.cons))))
         elif self.magp is not None:
             check(self.ctx.retry_oom(lambda: lib.ginsim_loose_mag_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.magp))))
+        elif self.scalep is not None:
+            check(self.ctx.retry_oom(lambda: lib.ginsim_loose_scale_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.scalep))))
         else:
             check(self.ctx.retry_oom(lambda: lib.ginsim_loose_run(self.ctx.handle, C.byref(self.mc), C.byref(p))))
 
@@ -399,8 +460,25 @@ class InsLooseJob(BatchJob):
         return self.ctx.download(self.params.out_pdiag_end, (15, self.runs)).T.copy()
 
     def final_sigmas(self):
-        """(runs, 15): the 1 sigma of every state at the last sample, sqrt(final_pdiag())."""
-        return np.sqrt(self.final_pdiag())
+        """(runs, 15): the 1 sigma of every state at the last sample, sqrt(final_pdiag()); (runs, 16) with odo_scale_state, the
+        scale-factor error the last."""
+        sig = np.sqrt(self.final_pdiag())
+        return sig if self.scalep is None else np.concatenate([sig, self.final_scale()[1][:, None]], axis=1)
+
+    def _need_scale(self):
+        if self.scalep is None:
+            raise ValueError('the filter has no scale-factor state (odo_scale_state=...)')
+
+    def final_scale(self):
+        """(k_est, sigma), each (runs,): the scale-factor estimate at the last sample and its 1 sigma, sqrt(P[15][15])."""
+        self._need_scale()
+        a = self.ctx.download(self.scalep.out_scale_end, (2, self.runs))
+        return a[0].copy(), np.sqrt(a[1])
+
+    def final_pcross(self):
+        """(runs, 15): P[k][15], the covariance of the scale-factor error with the 15 other states, at the last sample."""
+        self._need_scale()
+        return self.ctx.download(self.scalep.out_pcross_end, (15, self.runs)).T.copy()
 
     def consistency(self):
         """ConsistencyResult of the last launch at cons_samples, in the caller's order: across the runs launched, the filter's
@@ -412,7 +490,12 @@ class InsLooseJob(BatchJob):
         return ConsistencyResult(rec[self._cons_back])
 
     def series(self, name, run_ids):
-        """Kept series of selected runs, each (k, n, 3): 'att', 'pos', 'vel', 'wb', 'ab'."""
+        """Kept series of selected runs, each (k, n, 3): 'att', 'pos', 'vel', 'wb', 'ab'; 'odo_scale' (k, n): k_est (keep_scale)."""
+        if name == 'odo_scale':
+            self._need_scale()
+            if not self.keep_scale:
+                raise ValueError('the scale-factor series was not kept (keep_scale=True)')
+            return self._gather(self.scalep.out_scale, self.n, 1, run_ids)[:, :, 0]
         if not self.keep_traj:
             raise ValueError('the series were not kept (keep_traj=True)')
         plane = self.n * self.runs * 8

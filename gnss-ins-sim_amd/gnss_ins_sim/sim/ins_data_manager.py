@@ -59,6 +59,7 @@ _REGISTRY = [
     ('att_euler', 'simulation attitude (Euler, ZYX) from algo', _ANG, _ANG_OUT, ['Yaw', 'Pitch', 'Roll'], {}),
     ('wb', 'gyro bias estimation', _RATE, _RATE_OUT, ['gyro_bias_x', 'gyro_bias_y', 'gyro_bias_z'], {}),
     ('ab', 'accel bias estimation', _ACC, None, ['accel_bias_x', 'accel_bias_y', 'accel_bias_z'], {}),
+    ('odo_scale', 'odometer scale factor estimation', [''], None, ['odo_scale'], {}),
     ('ad_gyro', 'Allan deviation of gyro', _RATE, _RATE_OUT, ['AD_wx', 'AD_wy', 'AD_wz'], {'logx': True, 'logy': True}),
     ('ad_accel', 'Allan deviation of accel', _ACC, None, ['AD_ax', 'AD_ay', 'AD_az'], {'logx': True, 'logy': True}),
 ]

@@ -466,13 +466,19 @@ class _Jobs(object):
                            seed=self.seed, run_offset=self.first + off, ini_first=kw.pop('ini_first', algo.run_times + self.first + off),
                            earth_rot=algo.earth_rot, keep_traj=keep, placed=sim.placed,
                            model=filter_model(sim.fs[0], tuned.accel_err, tuned.gyro_err, tuned.gps_err, algo.q_scale, algo.p0),
-                           **self._aiding(algo), **self._mag_aiding(algo, truth), **self.vib, **kw)
+                           **self._aiding(algo), **self._mag_aiding(algo, truth), **self._scale_state(algo, keep), **self.vib, **kw)
 
     def _aiding(self, algo):
         """The aiding arguments of an InsLooseJob: none for a plugin without aiding.  The odometer SAMPLES are the Sim's
         (truth['ref_odo'] and the IMU's odo_err, as the fused job makes them); what the filter assumes of them is the plugin's."""
         aid = algo.aid() if hasattr(algo, 'aid') else None
         return {} if aid is None else {'odo_err': self.sim.imu.odo_err if self.sim.imu.odo else None, 'aid': aid}
+
+    def _scale_state(self, algo, keep):
+        """The scale-factor arguments of an InsLooseJob: none for a plugin without the state; the estimate's series is kept where the
+        trajectories are."""
+        opts = algo.scale_options() if hasattr(algo, 'scale_options') else None
+        return {} if opts is None else {'odo_scale_state': opts, 'keep_scale': bool(keep)}
 
     def _mag_aiding(self, algo, truth):
         """The magnetometer arguments of an InsLooseJob: none for a plugin without the block.  The SAMPLES are the Sim's (ref_mag
@@ -905,7 +911,8 @@ class Sim(object):
                 job = jobs.loose(algo, count, False, end_ned=plan.end_ned, **kw).run()
                 kept = jobs.loose(algo, kcount, True).run() if kcount > 0 else None
             last, pos = (kept, count - 1) if (plan.keep or kcount == count) else (jobs.loose(algo, 1, True, off=count - 1).run(), 0)
-            algo.finish(*[last.series(k, [pos])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab')])
+            names = ('pos', 'vel', 'att', 'wb', 'ab') + (('odo_scale',) if getattr(algo, 'odo_scale_state', False) else ())
+            algo.finish(*[last.series(k, [pos])[0] for k in names])
             if last is not kept:
                 last.release()
             out.append((i, job, kept))
@@ -991,7 +998,8 @@ class Sim(object):
             return
         if count <= 0:
             for out_name in ('att_euler',) + (('att_quat',) if incl else ()) + (('pos', 'vel') if nav else ()) + \
-                    (('wb', 'ab') if with_bias else ()):
+                    (('wb', 'ab') if with_bias else ()) + \
+                    (('odo_scale',) if any(getattr(a, 'odo_scale_state', False) for a in self.amgr.algo or []) else ()):
                 d.add_data(out_name, {})
             return
 
@@ -1008,6 +1016,9 @@ class Sim(object):
                                            [(nm, ser(j, 'quat_' + k)) for nm, j, k in incl], first, count))
         for out_name in ('wb', 'ab') if with_bias else ():
             d.add_data(out_name, _keyed_view([(nm, ser(j, out_name)) for nm, j in with_bias], first, count))
+        with_scale = [(nm, j) for nm, j in loose if getattr(j, 'keep_scale', False)]     # InsLoose(odo_scale_state=True)
+        if with_scale:
+            d.add_data('odo_scale', _keyed_view([(nm, ser(j, 'odo_scale')) for nm, j in with_scale], first, count))
 
     def _publish_results(self, plan, jobs, run, incl_groups, kinds, group, xdev, loose_jobs=()):
         """sim.mc: the statistics and kept jobs of every fused and inclinometer plugin, and how to build the jobs that statistics
@@ -1298,6 +1309,9 @@ class Sim(object):
             if getattr(job, 'mag', None) is not None:
                 raise NotImplementedError('consistency_curve: %s is aided by the magnetometer (InsLoose(mag=True)), and the consistency '
                                           'checkpoints of that filter are not built' % a)
+            if getattr(job, 'scale', None) is not None:
+                raise NotImplementedError('consistency_curve: %s estimates the odometer\'s scale factor (InsLoose(odo_scale_state=True)), '
+                                          'and the consistency checkpoints of that filter are not built' % a)
         for a in names:
             c = mc.consistency(a, samples)
             out[a] = {'count': c.count, 'sigma': c.sigma, 'rms': c.rms, 'ratio': c.ratio, 'nees': c.nees}

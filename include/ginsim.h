@@ -458,6 +458,31 @@ int ginsim_loose_mag_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const gins
 int ginsim_loose_mag_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
                                  char* buf, size_t cap);
 
+/* ---- the odometer's scale factor as a 16th state of the filter (csrc/ins_loose_scale.hip).  Added without a
+ *      change of GINSIM_ABI_VERSION and as a block of its own: ginsim_loose_params and ginsim_loose_run are exactly what they were.
+ *      State 15 is dk = k_est - k, k the true scale of odo_j = k v_b[0] + stdv z.  k_est starts at scale0 with
+ *      P[15][15] = p0_scale^2 and no correlation; Phi is the identity on it and P[15][15] += q_k per IMU sample.  The odometer
+ *      row becomes z0 = v_b[0] - odo_j / k_est with the seventh entry h[15] = v_b[0] / k_est (v_b of the state before the first
+ *      row) and the variance r_odo as it is; the constraint rows and the GPS rows have no entry on state 15.  Every block that ran a
+ *      row (a fix, an aiding block) ends with k_est -= x[15] next to the feedback of the other states.  odo_scale_f is checked as
+ *      ginsim_loose_run checks it and not read. */
+typedef struct {
+    double   scale0;          /* k_est at sample 0; finite, > 0 */
+    double   p0_scale;        /* initial 1 sigma of dk; finite, >= 0 (0 with q_k = 0: k_est stays scale0, the 15-state filter) */
+    double   q_k;             /* added to P[15][15] per IMU sample (odo_scale_q^2 dt); finite, >= 0 */
+    double*  out_scale;       /* [n][runs] k_est of every stored row, or NULL */
+    double*  out_scale_end;   /* [2][runs] k_est and P[15][15] at the last sample, or NULL */
+    double*  out_pcross_end;  /* [15][runs] P[k][15], k = 0 .. 14, at the last sample, or NULL */
+} ginsim_loose_scale_params;
+
+/* ginsim_loose_run with the scale-factor state: launches loose_scale_kernel.  Everything ginsim_loose_run refuses is refused (fp32
+ * among it), and: an aid_mask without bit 0 (a scale state without the odometer), scale0 that is not positive and finite,
+ * p0_scale or q_k negative or not finite.  out_pdiag_end stays [15][runs]: the 16th diagonal entry is out_scale_end[1]. */
+int ginsim_loose_scale_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale);
+/* the NAME of the kernel it launches (e.g. "ginsim::loose_scale_kernel<1, false, false, false>" = RF, GIVEN, VIB, PS) */
+int ginsim_loose_scale_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale,
+                                   char* buf, size_t cap);
+
 /* ---- auxiliary sensors of a Monte-Carlo batch: pathgen.gps_gen (pathgen.py:596-625) and pathgen.mag_gen (:643-661).
  *      FreeIntegration does not consume them, so they are generated only when they are to be kept. */
 typedef struct {

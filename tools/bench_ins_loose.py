@@ -6,6 +6,7 @@
     python tools/bench_ins_loose.py --aided [--reps 20] [--out profiles/ins_loose_aided_timing.json]
     python tools/bench_ins_loose.py --cons [--reps 20] [--out profiles/ins_loose_cons_timing.json]
     python tools/bench_ins_loose.py --mag [--reps 20] [--out profiles/ins_loose_mag_timing.json]
+    python tools/bench_ins_loose.py --odo-scale [--reps 20] [--out profiles/ins_loose_scale_timing.json]
 
 Workload: 65 536 runs x the 1000 samples of the 90-degree turn at 100 Hz (BASELINE config C2's shape) with GPS at 10 Hz, ref_frame 1,
 'mid-accuracy' IMU; statistics only (nothing but the per-run end records is written) and with everything kept (trajectory, wb, ab).
@@ -32,7 +33,11 @@ The times with checkpoints include the kernel that adds the wavefronts' partial 
 
 --mag: the magnetometer block of csrc/ins_loose_mag.hip on the same case, statistics only: the unaided launch, the
 magnetometer block at mag_every 1 and 10, and aid_mask 7 together with the magnetometer (both at every sample), launched in turn
---reps times after one warm-up each (field (30, -3, 40) uT, no soft or hard iron, noise 0.01 uT)."""
+--reps times after one warm-up each (field (30, -3, 40) uT, no soft or hard iron, noise 0.01 uT).
+
+--odo-scale: the odometer's scale factor as a 16th state (csrc/ins_loose_scale.hip) on the same case, statistics only:
+the 15-state aided launch (aid_mask 7) and the 16-state launch, each at aid_every 1 and 10, launched in turn --reps times after one
+warm-up each.  The price is the 16-state time over the 15-state time of the same library; the arithmetic on P grows by 136/120."""
 import argparse
 import json
 import os
@@ -210,6 +215,43 @@ def time_mag(runs, reps):
     return out
 
 
+def time_scale(runs, reps):
+    """{leg: {'kernel', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the 15-state aided launch and the 16-state launch at
+    aid_every 1 and 10, interleaved; 'over_aided': the 16-state leg over the 15-state leg of the same period."""
+    import numpy as np
+    import ginsim
+    from ginsim import workloads
+    fs, rf = 100.0, 1
+    ini, truth, _ = workloads.truth_from_profile('turn_90deg', fs, rf, fs_gps=10.0, gps=True)
+    acc, gyr = workloads.imu_grade('mid-accuracy')
+    gps_err = {'stdp': np.array([5.0, 5.0, 7.0]), 'stdv': np.array([0.05, 0.05, 0.05])}
+    odo_err = {'scale': 0.99, 'stdv': 0.1}
+    ctx = ginsim.Context(0)
+    out = {'device': ctx.name(), 'runs': runs, 'samples': int(truth['ref_accel'].shape[0]), 'fixes': int(truth['ref_gps'].shape[0]),
+           'library': os.path.basename(ginsim.LIB_PATH)}
+    aid = lambda every: {'odo_err': odo_err, 'aid': {'odo': True, 'nhc': True, 'every': every}}
+    legs = [('aided_mask7_every1', aid(1)), ('scale_mask7_every1', dict(aid(1), odo_scale_state={})),
+            ('aided_mask7_every10', aid(10)), ('scale_mask7_every10', dict(aid(10), odo_scale_state={}))]
+    jobs = [(label, ginsim.InsLooseJob(ctx, fs, rf, truth, acc, gyr, gps_err, ini, runs, seed=1, keep_traj=False, **kw)) for label, kw in legs]
+    ms = {label: [] for label, _ in jobs}
+    for _, job in jobs:
+        job.run()                                       # warm-up: code object, LDS attribute
+    for _ in range(reps):
+        for label, job in jobs:
+            ctx.timer_begin()
+            job.launch()
+            ms[label].append(ctx.timer_end())
+    for label, job in jobs:
+        t = ms[label]
+        out[label] = {'kernel': job.kernel_name(), 'ms_median': float(np.median(t)), 'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)),
+                      'ms_all': [float(x) for x in t]}
+        job.release()
+    for every in (1, 10):
+        out['scale_mask7_every%d' % every]['over_aided'] = out['scale_mask7_every%d' % every]['ms_median'] / out['aided_mask7_every%d' % every]['ms_median']
+    ctx.close()
+    return out
+
+
 def time_cons(runs, reps):
     """{leg: {'kernel', 'checkpoints', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the unaided launch without checkpoints, with one
     every 100 samples and with one at every sample, interleaved; and what one checkpoint costs, in steps."""
@@ -254,6 +296,7 @@ def main():
     ap.add_argument('--unaided-only', action='store_true', help='with --aided: the unaided launch alone')
     ap.add_argument('--cons', action='store_true', help='the checkpoint leg: none, one every 100 samples, one at every sample')
     ap.add_argument('--mag', action='store_true', help='the magnetometer leg: unaided, mag_every 1 and 10, aid_mask 7 with the magnetometer')
+    ap.add_argument('--odo-scale', action='store_true', help='the scale-factor leg: aid_mask 7 with 15 and with 16 states, aid_every 1 and 10')
     ap.add_argument('--runs', type=int, default=65536)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ops', type=int, default=0, help='fp64 instructions per step, instead of the count from the ISA')
@@ -263,8 +306,8 @@ def main():
         for k, (n, f, span) in sorted(isa_counts().items()):
             print('%s: %d fp64 VALU instructions (%d fused multiply-adds) in a time loop of %d lines' % (k, n, f, span))
         return
-    if a.aided or a.cons or a.mag:
-        res = time_mag(a.runs, a.reps) if a.mag else time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
+    if a.aided or a.cons or a.mag or a.odo_scale:
+        res = time_scale(a.runs, a.reps) if a.odo_scale else time_mag(a.runs, a.reps) if a.mag else time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
         print(json.dumps(res))
         if a.out:
             with open(a.out, 'w') as f:
