@@ -593,56 +593,6 @@ int ginsim_loose_variant(const ginsim_mc_params* mc, const ginsim_loose_params* 
     return GINSIM_OK;
 }
 
-int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, char* buf, size_t cap) {
-    REQUIRE(buf && cap > 0, "loose_kernel_name: bad arguments");
-    const int rc = check_loose_params(mc, p);
-    if (rc) return rc;
-    buf[0] = 0;
-    (void)launch_loose(*mc, *p, nullptr, nullptr, nullptr, buf, cap);
-    return GINSIM_OK;
-}
-
-// The launch of the filter, with checkpoints when cons is not NULL, with the magnetometer block when mag is not NULL or with the
-// scale-factor state when scale is not NULL (at most one of the three; each checked by the caller).  The stamps and the visibility flags of
-// the fixes and the checkpoint samples are copied next to each other into the context's scratch.
-static int loose_launch(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
-                        const ginsim_loose_mag_params* mag = nullptr, const ginsim_loose_scale_params* scale = nullptr) {
-    HIP_TRY(hipSetDevice(c->device));
-    int64_t* d_stamp = nullptr;
-    int32_t* d_vis = nullptr;
-    int64_t* d_cons = nullptr;
-    const size_t sb = sizeof(int64_t) * (size_t)p->m, vb = (sizeof(int32_t) * (size_t)p->m + 7) / 8 * 8;
-    const size_t cb = cons ? sizeof(int64_t) * (size_t)cons->cons_m : 0;
-    if (sb + cb > 0) {
-        void* ws = nullptr;
-        HIP_TRY(scratch(c, 3, sb + vb + cb, &ws));
-        if (p->m > 0) {
-            d_stamp = reinterpret_cast<int64_t*>(ws);
-            HIP_TRY(hipMemcpyAsync(d_stamp, p->gps_stamp, sb, hipMemcpyHostToDevice, c->stream));
-            if (p->gps_visible) {
-                d_vis = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + sb);
-                HIP_TRY(hipMemcpyAsync(d_vis, p->gps_visible, sizeof(int32_t) * (size_t)p->m, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-        if (cb > 0) {
-            d_cons = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ws) + sb + vb);
-            HIP_TRY(hipMemcpyAsync(d_cons, cons->cons_sample, cb, hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    if (cons) HIP_TRY(launch_loose_cons(*mc, *p, *cons, d_stamp, d_vis, d_cons, c->stream, nullptr, 0));
-    else if (mag) HIP_TRY(launch_loose_mag(*mc, *p, *mag, d_stamp, d_vis, c->stream, nullptr, 0));
-    else if (scale) HIP_TRY(launch_loose_scale(*mc, *p, *scale, d_stamp, d_vis, c->stream, nullptr, 0));
-    else HIP_TRY(launch_loose(*mc, *p, d_stamp, d_vis, c->stream, nullptr, 0));
-    return GINSIM_OK;
-}
-
-int ginsim_loose_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p) {
-    REQUIRE(c, "loose_run: NULL argument");
-    const int rc = check_loose_params(mc, p);
-    if (rc) return rc;
-    return loose_launch(c, mc, p, nullptr);
-}
-
 // the checkpoint block of a launch whose other two blocks passed check_loose_params
 static int check_loose_cons(const ginsim_mc_params* m, const ginsim_loose_params* p, const ginsim_loose_cons_params* q) {
     REQUIRE(q, "loose_cons_run: NULL argument");
@@ -658,28 +608,6 @@ static int check_loose_cons(const ginsim_mc_params* m, const ginsim_loose_params
         REQUIRE(k == 0 || s > (long long)q->cons_sample[k - 1], "loose_cons_run: the checkpoints are not strictly increasing at %lld", (long long)k);
     }
     return GINSIM_OK;
-}
-
-int ginsim_loose_cons_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
-                                  char* buf, size_t cap) {
-    REQUIRE(buf && cap > 0, "loose_cons_kernel_name: bad arguments");
-    int rc = check_loose_params(mc, p);
-    if (rc) return rc;
-    rc = check_loose_cons(mc, p, cons);
-    if (rc) return rc;
-    buf[0] = 0;
-    if (cons->cons_m > 0) (void)launch_loose_cons(*mc, *p, *cons, nullptr, nullptr, nullptr, nullptr, buf, cap);
-    else (void)launch_loose(*mc, *p, nullptr, nullptr, nullptr, buf, cap);
-    return GINSIM_OK;
-}
-
-int ginsim_loose_cons_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons) {
-    REQUIRE(c, "loose_cons_run: NULL argument");
-    int rc = check_loose_params(mc, p);
-    if (rc) return rc;
-    rc = check_loose_cons(mc, p, cons);
-    if (rc) return rc;
-    return loose_launch(c, mc, p, cons->cons_m > 0 ? cons : nullptr);
 }
 
 // the magnetometer block of a launch whose other two blocks passed check_loose_params
@@ -704,28 +632,6 @@ static int check_loose_mag(const ginsim_mc_params* m, const ginsim_loose_mag_par
     return GINSIM_OK;
 }
 
-int ginsim_loose_mag_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
-                                 char* buf, size_t cap) {
-    REQUIRE(buf && cap > 0, "loose_mag_kernel_name: bad arguments");
-    int rc = check_loose_params(mc, p);
-    if (rc) return rc;
-    rc = check_loose_mag(mc, mag);
-    if (rc) return rc;
-    buf[0] = 0;
-    if (mag->mag_every > 0) (void)launch_loose_mag(*mc, *p, *mag, nullptr, nullptr, nullptr, buf, cap);
-    else (void)launch_loose(*mc, *p, nullptr, nullptr, nullptr, buf, cap);
-    return GINSIM_OK;
-}
-
-int ginsim_loose_mag_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag) {
-    REQUIRE(c, "loose_mag_run: NULL argument");
-    int rc = check_loose_params(mc, p);
-    if (rc) return rc;
-    rc = check_loose_mag(mc, mag);
-    if (rc) return rc;
-    return loose_launch(c, mc, p, nullptr, mag->mag_every > 0 ? mag : nullptr);
-}
-
 // the scale-factor block of a launch whose other two blocks passed check_loose_params (fp32 among what that refuses)
 static int check_loose_scale(const ginsim_loose_params* p, const ginsim_loose_scale_params* q) {
     REQUIRE(q, "loose_scale_run: NULL argument");
@@ -736,25 +642,104 @@ static int check_loose_scale(const ginsim_loose_params* p, const ginsim_loose_sc
     return GINSIM_OK;
 }
 
+// The family of a launch of the filter, in one order: checkpoints, magnetometer, scale-factor state, aiding, plain.
+static hipError_t launch_loose(const LooseLaunch& L) {
+    if (L.b->n_list <= 0 && !L.name) return hipSuccess;
+    if (L.cons) return launch_loose_cons(L);
+    if (L.mag) return launch_loose_mag(L);
+    if (L.scale) return launch_loose_scale(L);
+    return L.b->aid_mask != 0 ? launch_loose_aided(L) : launch_loose_plain(L);
+}
+
+// What every entry point of the loose family does with its blocks: L.mc, L.b and, for the entry points of family `who`, that
+// family's block (the other two are NULL).  The one place that orders the checks: the base blocks, then the family's own; a
+// degenerate block (cons_m == 0, mag_every == 0) is then no block.  L.name != NULL (c is not read): the kernel's name.  Otherwise
+// the stamps, the visibility flags (padded to 8 bytes) and the checkpoint samples are copied next to each other into the context's
+// scratch and the family is launched.
+enum LooseFamily { LOOSE_PLAIN, LOOSE_CONS, LOOSE_MAG, LOOSE_SCALE };
+
+static int loose_entry(LooseFamily who, ginsim_ctx* c, LooseLaunch L) {
+    int rc = check_loose_params(L.mc, L.b);
+    if (rc) return rc;
+    rc = who == LOOSE_CONS ? check_loose_cons(L.mc, L.b, L.cons) : who == LOOSE_MAG ? check_loose_mag(L.mc, L.mag)
+       : who == LOOSE_SCALE ? check_loose_scale(L.b, L.scale) : GINSIM_OK;
+    if (rc) return rc;
+    if (L.cons && L.cons->cons_m == 0) L.cons = nullptr;
+    if (L.mag && L.mag->mag_every == 0) L.mag = nullptr;
+    if (L.name) {
+        L.name[0] = 0;
+        (void)launch_loose(L);
+        return GINSIM_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const ginsim_loose_params* p = L.b;
+    const size_t sb = sizeof(int64_t) * (size_t)p->m, vb = (sizeof(int32_t) * (size_t)p->m + 7) / 8 * 8;
+    const size_t cb = L.cons ? sizeof(int64_t) * (size_t)L.cons->cons_m : 0;
+    if (sb + cb > 0) {
+        void* ws = nullptr;
+        HIP_TRY(scratch(c, 3, sb + vb + cb, &ws));
+        if (p->m > 0) {
+            int64_t* d_stamp = reinterpret_cast<int64_t*>(ws);
+            HIP_TRY(hipMemcpyAsync(d_stamp, p->gps_stamp, sb, hipMemcpyHostToDevice, c->stream));
+            L.stamp = d_stamp;
+            if (p->gps_visible) {
+                int32_t* d_vis = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + sb);
+                HIP_TRY(hipMemcpyAsync(d_vis, p->gps_visible, sizeof(int32_t) * (size_t)p->m, hipMemcpyHostToDevice, c->stream));
+                L.visible = d_vis;
+            }
+        }
+        if (cb > 0) {
+            int64_t* d_cons = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ws) + sb + vb);
+            HIP_TRY(hipMemcpyAsync(d_cons, L.cons->cons_sample, cb, hipMemcpyHostToDevice, c->stream));
+            L.samples = d_cons;
+        }
+    }
+    L.stream = c->stream;
+    HIP_TRY(launch_loose(L));
+    return GINSIM_OK;
+}
+
+int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_kernel_name: bad arguments");
+    return loose_entry(LOOSE_PLAIN, nullptr, LooseLaunch{mc, p, nullptr, nullptr, nullptr, buf, cap});
+}
+
+int ginsim_loose_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p) {
+    REQUIRE(c, "loose_run: NULL argument");
+    return loose_entry(LOOSE_PLAIN, c, LooseLaunch{mc, p});
+}
+
+int ginsim_loose_cons_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
+                                  char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_cons_kernel_name: bad arguments");
+    return loose_entry(LOOSE_CONS, nullptr, LooseLaunch{mc, p, cons, nullptr, nullptr, buf, cap});
+}
+
+int ginsim_loose_cons_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons) {
+    REQUIRE(c, "loose_cons_run: NULL argument");
+    return loose_entry(LOOSE_CONS, c, LooseLaunch{mc, p, cons});
+}
+
+int ginsim_loose_mag_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
+                                 char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_mag_kernel_name: bad arguments");
+    return loose_entry(LOOSE_MAG, nullptr, LooseLaunch{mc, p, nullptr, mag, nullptr, buf, cap});
+}
+
+int ginsim_loose_mag_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag) {
+    REQUIRE(c, "loose_mag_run: NULL argument");
+    return loose_entry(LOOSE_MAG, c, LooseLaunch{mc, p, nullptr, mag});
+}
+
 int ginsim_loose_scale_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale,
                                    char* buf, size_t cap) {
     REQUIRE(buf && cap > 0, "loose_scale_kernel_name: bad arguments");
-    int rc = check_loose_params(mc, p);
-    if (rc) return rc;
-    rc = check_loose_scale(p, scale);
-    if (rc) return rc;
-    buf[0] = 0;
-    (void)launch_loose_scale(*mc, *p, *scale, nullptr, nullptr, nullptr, buf, cap);
-    return GINSIM_OK;
+    return loose_entry(LOOSE_SCALE, nullptr, LooseLaunch{mc, p, nullptr, nullptr, scale, buf, cap});
 }
 
 int ginsim_loose_scale_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale) {
     REQUIRE(c, "loose_scale_run: NULL argument");
-    int rc = check_loose_params(mc, p);
-    if (rc) return rc;
-    rc = check_loose_scale(p, scale);
-    if (rc) return rc;
-    return loose_launch(c, mc, p, nullptr, nullptr, scale);
+    return loose_entry(LOOSE_SCALE, c, LooseLaunch{mc, p, nullptr, nullptr, scale});
 }
 
 int ginsim_aux_sensors(ginsim_ctx* c, const ginsim_aux_params* p) {

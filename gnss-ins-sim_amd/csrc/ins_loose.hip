@@ -25,7 +25,7 @@
 // registers.
 // What loose_aided_kernel (ins_loose_aided.hip) shares with this file -- Cov, the propagation, the correction, the time loop -- is
 // in ins_loose.hpp; the host side that launches an instantiation of either, or of loose_cons_kernel (ins_loose_cons.hip), is
-// launch_loose_trio (loose_launch.hpp): this file keeps the choice of <RF, PS> and hands over to the aided kernel.
+// launch_loose_family (loose_launch.hpp) on the file's trait; which family a launch takes is decided in ginsim_api.hip (launch_loose).
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
 #include "ins_loose.hpp"
@@ -46,22 +46,12 @@ loose_kernel(const ginsim_mc_params a, const ginsim_loose_params b, const int64_
 
 int loose_variant(const ginsim_mc_params& p) { return p.given_sensors ? 1 : 0; }
 
-template <int RF, bool PS>
-static hipError_t launch_loose_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
-                                 hipStream_t stream, char* name, size_t cap) {
-    return launch_loose_trio<kLooseCovLds, &loose_kernel<RF, true, false, PS>, &loose_kernel<RF, false, true, PS>, &loose_kernel<RF, false, false, PS>>(
-        "loose_kernel", RF, PS, p, b, stamp, visible, stream, name, cap);
-}
+struct PlainFamily {
+    static constexpr const char* name = "loose_kernel";
+    static constexpr size_t lds = kLooseCovLds;
+    template <int RF, bool GIVEN, bool VIB, bool PS> static constexpr auto kernel = &loose_kernel<RF, GIVEN, VIB, PS>;
+};
 
-// name != NULL: report the kernel's name, do not launch.  stamp / visible: DEVICE copies of b.gps_stamp / b.gps_visible.
-// aid_mask != 0: loose_aided_kernel
-hipError_t launch_loose(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
-                        hipStream_t stream, char* name, size_t cap) {
-    if (b.n_list <= 0 && !name) return hipSuccess;
-    if (b.aid_mask != 0) return launch_loose_aided(p, b, stamp, visible, stream, name, cap);
-    const bool ps = b.out_proc != nullptr;
-    if (p.ref_frame == 1) return ps ? launch_loose_a<1, true>(p, b, stamp, visible, stream, name, cap) : launch_loose_a<1, false>(p, b, stamp, visible, stream, name, cap);
-    return ps ? launch_loose_a<0, true>(p, b, stamp, visible, stream, name, cap) : launch_loose_a<0, false>(p, b, stamp, visible, stream, name, cap);
-}
+hipError_t launch_loose_plain(const LooseLaunch& L) { return launch_loose_family<PlainFamily>(L, L.b->out_proc != nullptr); }
 
 }  // namespace ginsim

@@ -14,7 +14,7 @@
 // counter j (the bits ginsim_mc_run writes to out_odo) or read from in_odo[j runs + r] (given_sensors).
 // aid_mask and aid_every are wave-uniform kernel arguments, not template parameters: 12 instantiations as loose_kernel's.
 //
-// The launch is launch_loose_trio (loose_launch.hpp); launch_loose_aided chooses <RF, PS>.
+// The launch is launch_loose_family (loose_launch.hpp) on the file's trait, with PS as the flag.
 // Built with ins_loose.hip's flags; P stays in LDS as [120][64], one wavefront per workgroup.  The build's resource report
 // (build/ins_loose_aided.resources.txt, read by tests/test_ins_loose_aided_oracle.py): 0 bytes of scratch in all 12.
 #include <hip/hip_runtime.h>
@@ -33,19 +33,12 @@ loose_aided_kernel(const ginsim_mc_params a, const ginsim_loose_params b, const 
     loose_body<RF, GIVEN, VIB, PS, true>(a, b, stamp, visible, ntab);
 }
 
-template <int RF, bool PS>
-static hipError_t launch_aided_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
-                                 hipStream_t stream, char* name, size_t cap) {
-    return launch_loose_trio<kLooseCovLds, &loose_aided_kernel<RF, true, false, PS>, &loose_aided_kernel<RF, false, true, PS>,
-                             &loose_aided_kernel<RF, false, false, PS>>("loose_aided_kernel", RF, PS, p, b, stamp, visible, stream, name, cap);
-}
+struct AidedFamily {
+    static constexpr const char* name = "loose_aided_kernel";
+    static constexpr size_t lds = kLooseCovLds;
+    template <int RF, bool GIVEN, bool VIB, bool PS> static constexpr auto kernel = &loose_aided_kernel<RF, GIVEN, VIB, PS>;
+};
 
-// name != NULL: report the kernel's name, do not launch.  stamp / visible: DEVICE copies of b.gps_stamp / b.gps_visible
-hipError_t launch_loose_aided(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
-                              hipStream_t stream, char* name, size_t cap) {
-    const bool ps = b.out_proc != nullptr;
-    if (p.ref_frame == 1) return ps ? launch_aided_a<1, true>(p, b, stamp, visible, stream, name, cap) : launch_aided_a<1, false>(p, b, stamp, visible, stream, name, cap);
-    return ps ? launch_aided_a<0, true>(p, b, stamp, visible, stream, name, cap) : launch_aided_a<0, false>(p, b, stamp, visible, stream, name, cap);
-}
+hipError_t launch_loose_aided(const LooseLaunch& L) { return launch_loose_family<AidedFamily>(L, L.b->out_proc != nullptr); }
 
 }  // namespace ginsim

@@ -18,8 +18,8 @@
 // list again and weigh 0.
 // The errors of the six bias states are left out (they carry P_kk only): the given form has no bias truth.
 // PS is false here: online process statistics and checkpoints in one launch are refused.  12 instantiations, <RF, GIVEN, VIB, AID>.
-// The filter's launch is launch_loose_trio (loose_launch.hpp) with the checkpoint arguments behind the filter's own;
-// launch_loose_cons chooses <RF, AID> and launches cons_final_kernel after it.
+// The filter's launch is launch_loose_family (loose_launch.hpp) on the file's trait, with AID as the flag and the checkpoint
+// arguments behind the filter's own; launch_loose_cons launches cons_final_kernel after it.
 // Built with ins_loose.hip's flags; the build's resource report is build/ins_loose_cons.resources.txt
 // (tests/test_ins_loose_cons_oracle.py reads it).
 #include <hip/hip_runtime.h>
@@ -48,30 +48,20 @@ __global__ void __launch_bounds__(256) cons_final_kernel(const double* __restric
     out[i] = acc;
 }
 
-template <int RF, bool AID>
-static hipError_t launch_cons_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_cons_params& c,
-                                const int64_t* stamp, const int32_t* visible, const int64_t* samples, hipStream_t stream, char* name, size_t cap) {
-    ConsArgs cq;
-    cq.sample = samples;
-    cq.m = c.cons_m;
-    cq.work = c.cons_work;
-    const hipError_t e = launch_loose_trio<kLooseCovLds, &loose_cons_kernel<RF, true, false, AID>, &loose_cons_kernel<RF, false, true, AID>,
-                                           &loose_cons_kernel<RF, false, false, AID>>("loose_cons_kernel", RF, AID, p, b, stamp, visible, stream,
-                                                                                      name, cap, cq);
-    if (name || e != hipSuccess) return e;
-    const int64_t waves = (b.n_list + kLooseBlock - 1) / kLooseBlock, len = c.cons_m * GINSIM_CONS_RECORD;
-    hipLaunchKernelGGL(cons_final_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, stream, c.cons_work, waves, len, c.out_cons);
-    return hipGetLastError();
-}
+struct ConsFamily {
+    static constexpr const char* name = "loose_cons_kernel";
+    static constexpr size_t lds = kLooseCovLds;
+    template <int RF, bool GIVEN, bool VIB, bool AID> static constexpr auto kernel = &loose_cons_kernel<RF, GIVEN, VIB, AID>;
+};
 
-// name != NULL: report the kernel's name, do not launch.  stamp / visible / samples: DEVICE copies of b.gps_stamp / b.gps_visible /
-// c.cons_sample.  c.cons_m > 0 (ginsim_api.hip checks it and sends cons_m == 0 to launch_loose)
-hipError_t launch_loose_cons(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_cons_params& c, const int64_t* stamp,
-                             const int32_t* visible, const int64_t* samples, hipStream_t stream, char* name, size_t cap) {
-    if (b.n_list <= 0 && !name) return hipSuccess;
-    const bool aid = b.aid_mask != 0;
-    if (p.ref_frame == 1) return aid ? launch_cons_a<1, true>(p, b, c, stamp, visible, samples, stream, name, cap) : launch_cons_a<1, false>(p, b, c, stamp, visible, samples, stream, name, cap);
-    return aid ? launch_cons_a<0, true>(p, b, c, stamp, visible, samples, stream, name, cap) : launch_cons_a<0, false>(p, b, c, stamp, visible, samples, stream, name, cap);
+// L.cons->cons_m > 0 (ginsim_api.hip checks it and takes cons_m == 0 for no checkpoint block)
+hipError_t launch_loose_cons(const LooseLaunch& L) {
+    const ginsim_loose_cons_params& c = *L.cons;
+    const hipError_t e = launch_loose_family<ConsFamily>(L, L.b->aid_mask != 0, ConsArgs{L.samples, c.cons_m, c.cons_work});
+    if (L.name || e != hipSuccess) return e;
+    const int64_t waves = (L.b->n_list + kLooseBlock - 1) / kLooseBlock, len = c.cons_m * GINSIM_CONS_RECORD;
+    hipLaunchKernelGGL(cons_final_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, L.stream, c.cons_work, waves, len, c.out_cons);
+    return hipGetLastError();
 }
 
 }  // namespace ginsim

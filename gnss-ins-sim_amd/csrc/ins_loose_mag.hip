@@ -19,7 +19,7 @@
 // The magnetometer block's numbers are the kernel's fifth argument, a ginsim_loose_mag_params by value: the lane reads them from
 // the kernarg segment where they are used (loose_mag_params() of ins_loose.hpp), as it reads the two blocks before them.
 //
-// The launch is launch_loose_trio (loose_launch.hpp); launch_loose_mag chooses <RF, PS>.
+// The launch is launch_loose_family (loose_launch.hpp) on the file's trait, with PS as the flag and the block as the tail argument.
 // Built with ins_loose.hip's flags; P stays in LDS as [120][64], one wavefront per workgroup, nothing new in LDS.  The build's
 // resource report (build/ins_loose_mag.resources.txt, read by tests/test_ins_loose_mag_oracle.py): 0 bytes of scratch in all 12.
 #include <hip/hip_runtime.h>
@@ -40,21 +40,13 @@ loose_mag_kernel(const ginsim_mc_params a, const ginsim_loose_params b, const in
     loose_body<RF, GIVEN, VIB, PS, true, false, true>(a, b, stamp, visible, ntab);
 }
 
-template <int RF, bool PS>
-static hipError_t launch_mag_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_mag_params& g, const int64_t* stamp,
-                               const int32_t* visible, hipStream_t stream, char* name, size_t cap) {
-    return launch_loose_trio<kLooseCovLds, &loose_mag_kernel<RF, true, false, PS>, &loose_mag_kernel<RF, false, true, PS>,
-                             &loose_mag_kernel<RF, false, false, PS>>("loose_mag_kernel", RF, PS, p, b, stamp, visible, stream, name, cap, g);
-}
+struct MagFamily {
+    static constexpr const char* name = "loose_mag_kernel";
+    static constexpr size_t lds = kLooseCovLds;
+    template <int RF, bool GIVEN, bool VIB, bool PS> static constexpr auto kernel = &loose_mag_kernel<RF, GIVEN, VIB, PS>;
+};
 
-// name != NULL: report the kernel's name, do not launch.  stamp / visible: DEVICE copies of b.gps_stamp / b.gps_visible.
-// g.mag_every > 0 (ginsim_api.hip checks it and sends mag_every == 0 to launch_loose)
-hipError_t launch_loose_mag(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_mag_params& g, const int64_t* stamp,
-                            const int32_t* visible, hipStream_t stream, char* name, size_t cap) {
-    if (b.n_list <= 0 && !name) return hipSuccess;
-    const bool ps = b.out_proc != nullptr;
-    if (p.ref_frame == 1) return ps ? launch_mag_a<1, true>(p, b, g, stamp, visible, stream, name, cap) : launch_mag_a<1, false>(p, b, g, stamp, visible, stream, name, cap);
-    return ps ? launch_mag_a<0, true>(p, b, g, stamp, visible, stream, name, cap) : launch_mag_a<0, false>(p, b, g, stamp, visible, stream, name, cap);
-}
+// L.mag->mag_every > 0 (ginsim_api.hip checks it and takes mag_every == 0 for no magnetometer block)
+hipError_t launch_loose_mag(const LooseLaunch& L) { return launch_loose_family<MagFamily>(L, L.b->out_proc != nullptr, *L.mag); }
 
 }  // namespace ginsim

@@ -19,7 +19,7 @@
 // ginsim_loose_scale_params by value, read from the kernarg segment where they are used (loose_scale_params() of ins_loose.hpp).
 // k_est and everything else of a lane is written with ordinary per-lane (vector) stores.
 //
-// The launch is launch_loose_trio (loose_launch.hpp) with 68 KB of dynamic LDS: P is [136][64] doubles, one wavefront per
+// The launch is launch_loose_family (loose_launch.hpp) on the file's trait with 68 KB of dynamic LDS: P is [136][64] doubles, one wavefront per
 // workgroup; with the 8 KB of normal tables of the generating forms two workgroups fit a CU's 160 KB.
 // Built with ins_loose.hip's flags; the build's resource report is build/ins_loose_scale.resources.txt (read by
 // tests/test_ins_loose_scale_oracle.py).
@@ -41,21 +41,13 @@ loose_scale_kernel(const ginsim_mc_params a, const ginsim_loose_params b, const 
     loose_body<RF, GIVEN, VIB, PS, true, false, false, kLooseScaleStates>(a, b, stamp, visible, ntab);
 }
 
-template <int RF, bool PS>
-static hipError_t launch_scale_a(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_scale_params& g, const int64_t* stamp,
-                                 const int32_t* visible, hipStream_t stream, char* name, size_t cap) {
-    return launch_loose_trio<loose_cov_lds(kLooseScaleStates), &loose_scale_kernel<RF, true, false, PS>, &loose_scale_kernel<RF, false, true, PS>,
-                             &loose_scale_kernel<RF, false, false, PS>>("loose_scale_kernel", RF, PS, p, b, stamp, visible, stream, name, cap, g);
-}
+struct ScaleFamily {
+    static constexpr const char* name = "loose_scale_kernel";
+    static constexpr size_t lds = loose_cov_lds(kLooseScaleStates);
+    template <int RF, bool GIVEN, bool VIB, bool PS> static constexpr auto kernel = &loose_scale_kernel<RF, GIVEN, VIB, PS>;
+};
 
-// name != NULL: report the kernel's name, do not launch.  stamp / visible: DEVICE copies of b.gps_stamp / b.gps_visible.
-// b.aid_mask has bit 0 (ginsim_api.hip checks it)
-hipError_t launch_loose_scale(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_scale_params& g, const int64_t* stamp,
-                              const int32_t* visible, hipStream_t stream, char* name, size_t cap) {
-    if (b.n_list <= 0 && !name) return hipSuccess;
-    const bool ps = b.out_proc != nullptr;
-    if (p.ref_frame == 1) return ps ? launch_scale_a<1, true>(p, b, g, stamp, visible, stream, name, cap) : launch_scale_a<1, false>(p, b, g, stamp, visible, stream, name, cap);
-    return ps ? launch_scale_a<0, true>(p, b, g, stamp, visible, stream, name, cap) : launch_scale_a<0, false>(p, b, g, stamp, visible, stream, name, cap);
-}
+// L.b->aid_mask has bit 0 (ginsim_api.hip checks it)
+hipError_t launch_loose_scale(const LooseLaunch& L) { return launch_loose_family<ScaleFamily>(L, L.b->out_proc != nullptr, *L.scale); }
 
 }  // namespace ginsim

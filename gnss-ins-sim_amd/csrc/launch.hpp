@@ -32,26 +32,28 @@ hipError_t launch_series(const ginsim_mc_params& p, double* carry, hipStream_t s
 hipError_t launch_incl(const ginsim_mc_params& p, const ginsim_incl_params& b, hipStream_t stream, char* name, size_t cap);
 int incl_variant(const ginsim_mc_params& p);
 
-// ins_loose.hip
-hipError_t launch_loose(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
-                        hipStream_t stream, char* name, size_t cap);      // stamp / visible: device copies of b.gps_stamp / b.gps_visible
+// One launch of the loose family, as ginsim_api.hip (loose_entry) describes it to the family's launcher.
+struct LooseLaunch {
+    const ginsim_mc_params* mc;                 // the two base blocks, checked
+    const ginsim_loose_params* b;
+    const ginsim_loose_cons_params* cons;       // the family blocks, checked: NULL when absent or degenerate (cons_m == 0,
+    const ginsim_loose_mag_params* mag;         // mag_every == 0); launch_loose (ginsim_api.hip) picks the family from them
+    const ginsim_loose_scale_params* scale;
+    char* name; size_t cap;                     // name != NULL: report the kernel's name into name[cap], do not launch
+    const int64_t* stamp;                       // DEVICE copies of b->gps_stamp, b->gps_visible and cons->cons_sample
+    const int32_t* visible;
+    const int64_t* samples;
+    hipStream_t stream;
+};
+
+// ins_loose.hip, ins_loose_aided.hip (b->aid_mask != 0), ins_loose_cons.hip (cons), ins_loose_mag.hip (mag), ins_loose_scale.hip
+// (scale; b->aid_mask has bit 0): each chooses its <RF, flag> and launches, or names, one instantiation of its kernel
+hipError_t launch_loose_plain(const LooseLaunch& L);
+hipError_t launch_loose_aided(const LooseLaunch& L);
+hipError_t launch_loose_cons(const LooseLaunch& L);
+hipError_t launch_loose_mag(const LooseLaunch& L);
+hipError_t launch_loose_scale(const LooseLaunch& L);
 int loose_variant(const ginsim_mc_params& p);
-
-// ins_loose_aided.hip: what launch_loose calls when b.aid_mask != 0
-hipError_t launch_loose_aided(const ginsim_mc_params& p, const ginsim_loose_params& b, const int64_t* stamp, const int32_t* visible,
-                              hipStream_t stream, char* name, size_t cap);
-
-// ins_loose_cons.hip: the filter with consistency checkpoints (c.cons_m > 0); samples: the device copy of c.cons_sample
-hipError_t launch_loose_cons(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_cons_params& c, const int64_t* stamp,
-                             const int32_t* visible, const int64_t* samples, hipStream_t stream, char* name, size_t cap);
-
-// ins_loose_mag.hip: the filter with the magnetometer block (g.mag_every > 0)
-hipError_t launch_loose_mag(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_mag_params& g, const int64_t* stamp,
-                            const int32_t* visible, hipStream_t stream, char* name, size_t cap);
-
-// ins_loose_scale.hip: the aided filter with the odometer's scale factor as a 16th state (b.aid_mask has bit 0)
-hipError_t launch_loose_scale(const ginsim_mc_params& p, const ginsim_loose_params& b, const ginsim_loose_scale_params& g, const int64_t* stamp,
-                              const int32_t* visible, hipStream_t stream, char* name, size_t cap);
 
 // aux_sensors.hip
 hipError_t launch_aux(const ginsim_aux_params& p, hipStream_t s);

@@ -1,5 +1,6 @@
-// The host-side launch of the loose family (ins_loose.hip, ins_loose_aided.hip, ins_loose_cons.hip, ins_loose_mag.hip, ins_loose_scale.hip): each file defines its own
-// __global__ wrapper of loose_body and hands its instantiations to launch_loose_trio in threes.
+// The host-side launch of the loose family (ins_loose.hip, ins_loose_aided.hip, ins_loose_cons.hip, ins_loose_mag.hip,
+// ins_loose_scale.hip): each file defines its own __global__ wrapper of loose_body, describes it by a trait and hands a LooseLaunch
+// (launch.hpp) to launch_loose_family, which chooses <RF, flag> and gives the three instantiations to launch_loose_trio.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -31,6 +32,24 @@ hipError_t launch_loose_trio(const char* kernel, int rf, bool flag, const ginsim
     });
     hipLaunchKernelGGL(given ? GIVEN : (vib ? VIB : PLAIN), grid, block, LDS, stream, p, b, stamp, visible, tail...);
     return hipGetLastError();
+}
+
+// The choice of <RF, FLAG> for a family.  Family: a struct with
+//   static constexpr const char* name      the kernel template's name, as printed
+//   static constexpr size_t lds            the bytes of dynamic LDS of its covariance
+//   kernel<RF, GIVEN, VIB, FLAG>           a static constexpr variable template: the address of that instantiation
+// flag: the value of the kernel's fourth template argument for this launch.  tail: the kernel's arguments after the four common ones.
+template <class Family, int RF, bool FLAG, class... Tail>
+hipError_t launch_loose_as(const LooseLaunch& L, Tail... tail) {
+    return launch_loose_trio<Family::lds, Family::template kernel<RF, true, false, FLAG>, Family::template kernel<RF, false, true, FLAG>,
+                             Family::template kernel<RF, false, false, FLAG>>(Family::name, RF, FLAG, *L.mc, *L.b, L.stamp, L.visible, L.stream,
+                                                                              L.name, L.cap, tail...);
+}
+
+template <class Family, class... Tail>
+hipError_t launch_loose_family(const LooseLaunch& L, bool flag, Tail... tail) {
+    if (L.mc->ref_frame == 1) return flag ? launch_loose_as<Family, 1, true>(L, tail...) : launch_loose_as<Family, 1, false>(L, tail...);
+    return flag ? launch_loose_as<Family, 0, true>(L, tail...) : launch_loose_as<Family, 0, false>(L, tail...);
 }
 
 }  // namespace ginsim

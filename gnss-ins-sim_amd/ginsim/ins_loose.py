@@ -9,6 +9,7 @@ filter's covariance and its actual error at those samples (csrc/ins_loose_cons.h
 tests/ins_loose_cons_ref.py).  With mag=... the filter also uses the magnetometer, a three-row block on the attitude error
 (csrc/ins_loose_mag.hip, mag_model; restated by tests/ins_loose_mag_ref.py).  With odo_scale_state=... the odometer's scale factor is
 a 16th state that the filter estimates (csrc/ins_loose_scale.hip, scale_model; restated by tests/ins_loose_scale_ref.py).
+What one launch does not combine is stated once (refuse_combinations); the job records the family it launches once (FAMILIES).
 """
 import ctypes as C
 
@@ -199,6 +200,26 @@ def scale_model(odo_err, opts, fs=None):
     return {'scale0': scale0, 'p0_scale': p0, 'q_k': q * q / float(fs) if q > 0.0 else 0.0}
 
 
+# the family blocks a job can hold, in the order the C glue picks among them: (the job's attribute, the entry points' suffix)
+FAMILIES = (('cons', '_cons'), ('magp', '_mag'), ('scalep', '_scale'))
+
+
+def refuse_combinations(scale, keep_scale, odo, mag, cons, proc):
+    """The options of InsLooseJob that one launch does not combine, stated once: (applies, message), the first row that applies is
+    raised.  Arguments: is the option given (scale: odo_scale_state, odo: aid['odo'], cons: cons_samples, proc: proc_first)."""
+    rows = (
+        (keep_scale and not scale, 'keep_scale: the scale-factor series exists with odo_scale_state=... only'),
+        (scale and mag, 'odo_scale_state: the scale-factor state together with the magnetometer block (mag=...) is not built'),
+        (scale and cons, 'odo_scale_state: consistency checkpoints (cons_samples=...) of the filter with the scale-factor state are not built'),
+        (scale and not odo, "odo_scale_state: a scale-factor state without the odometer (aid['odo']) is refused"),
+        (mag and cons, 'cons_samples: consistency checkpoints of the magnetometer-aided filter are not built (mag=...)'),
+        (cons and proc, 'cons_samples: online process statistics (proc_first) and checkpoints in one launch are refused'),
+    )
+    for applies, text in rows:
+        if applies:
+            raise ValueError(text)
+
+
 class InsLooseJob(BatchJob):
     """One batch of runs of the loosely coupled filter on one device.
 
@@ -233,15 +254,33 @@ class InsLooseJob(BatchJob):
                  earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
                  end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None,
                  cons_samples=None, mag_err=None, geo_mag_n=None, mag=None, odo_scale_state=None, keep_scale=False):
-        self.ctx = ctx
+        self.ctx, self._bufs = ctx, {}
+        self.keep_traj, self.keep_scale = bool(keep_traj), bool(keep_scale)
+        self.proc_first, self.proc_ned, self.end_ned = proc_first, bool(proc_ned), bool(end_ned)
+        table, ref_gps = self._sizes_and_stamps(fs, ref_frame, truth, ini, runs, seed, run_offset, ini_first, earth_rot, end_pos_ned,
+                                                gps_stamps)
+        self.model = model if model is not None else filter_model(fs, accel_err, gyro_err, gps_err, q_scale, p0)
+        self.scale = scale_model(odo_err, odo_scale_state, fs)
+        refuse_combinations(scale=self.scale is not None, keep_scale=self.keep_scale, odo=bool(aid and aid.get('odo')),
+                            mag=mag is not None, cons=cons_samples is not None, proc=proc_first is not None)
+        for k in ('r_diag', 'p0', 'q_v', 'q_psi', 'q_bg', 'q_ba', 'decay_g', 'decay_a'):     # the filter numbers
+            getattr(self.params, k)[:] = [float(x) for x in np.asarray(self.model[k], dtype=np.float64).reshape(-1)]
+        self._family_blocks(ref_frame, odo_err, aid, mag_err, geo_mag_n, mag)
+        self._inputs(table, ref_gps, truth, fs, accel_err, gyro_err, gps_err, odo_err, mag_err, vib_accel, vib_gyro, given)
+        self._outputs(placed)
+        self._checkpoints(cons_samples)
+        # the family the job launches, once: the first block of FAMILIES that the job has (the order of the C glue), else the plain entry
+        self._family = next(((suffix, getattr(self, attr)) for attr, suffix in FAMILIES if getattr(self, attr) is not None), ('', None))
+
+    # ------------------------------------------------------------------ the constructor's steps
+    def _sizes_and_stamps(self, fs, ref_frame, truth, ini, runs, seed, run_offset, ini_first, earth_rot, end_pos_ned, gps_stamps):
+        """n, runs, m and the fields of the two base blocks that say which runs a launch makes and when its fixes arrive (the stamps
+        and the visibility flags stay host arrays: every launch copies them).  Returns the initial-state table and ref_gps (m, 6)."""
         self.n, self.runs = int(truth['ref_accel'].shape[0]), int(runs)
         if self.runs < 1:
             raise ValueError('runs must be >= 1')
-        self.keep_traj = bool(keep_traj)
-        self.proc_first, self.proc_ned, self.end_ned = proc_first, bool(proc_ned), bool(end_ned)
-        if end_ned and int(ref_frame) != 0:
+        if self.end_ned and int(ref_frame) != 0:
             raise ValueError('end_ned: ref_frame 0 only')
-        self._bufs = {}
         self._ref_frame = int(ref_frame)
         m = self.mc = _lib.McParams()
         self._fill_batch(m, fs, run_offset, seed)
@@ -257,147 +296,147 @@ class InsLooseJob(BatchJob):
         self._visible = np.ascontiguousarray(np.asarray(vis) != 0, dtype=np.int32).reshape(-1)
         if self._stamps.size != self.m or self._visible.size != self.m:
             raise ValueError('gps_time / gps_visibility do not match ref_gps')
-        self.model = model if model is not None else filter_model(fs, accel_err, gyro_err, gps_err, q_scale, p0)
         p = self.params = _lib.LooseParams()
-        p.m = self.m
+        p.m, p.n_list = self.m, self.runs
         p.gps_stamp, p.gps_visible = self._stamps.ctypes.data, self._visible.ctypes.data
-        for k in ('r_diag', 'p0', 'q_v', 'q_psi', 'q_bg', 'q_ba', 'decay_g', 'decay_a'):
-            getattr(p, k)[:] = [float(x) for x in np.asarray(self.model[k], dtype=np.float64).reshape(-1)]
-        self.scale, self.scalep = scale_model(odo_err, odo_scale_state, fs), None
-        self.keep_scale = bool(keep_scale)
-        if self.scale is None and self.keep_scale:
-            raise ValueError('keep_scale: the scale-factor series exists with odo_scale_state=... only')
+        return table, ref_gps
+
+    def _family_blocks(self, ref_frame, odo_err, aid, mag_err, geo_mag_n, mag):
+        """The numbers of the aiding fields (aid), of the scale-factor block (scale, scalep) and of the magnetometer block (mag, magp);
+        their device pointers come with the inputs and the outputs."""
+        self.scalep = self.mag = self.magp = None
         if self.scale is not None:
-            if mag is not None:
-                raise ValueError('odo_scale_state: the scale-factor state together with the magnetometer block (mag=...) is not built')
-            if cons_samples is not None:
-                raise ValueError('odo_scale_state: consistency checkpoints (cons_samples=...) of the filter with the scale-factor '
-                                 'state are not built')
-            if not (aid and aid.get('odo')):
-                raise ValueError("odo_scale_state: a scale-factor state without the odometer (aid['odo']) is refused")
             # what the 15-state filter is told (aid['scale']) the 16-state filter starts from (scale0); r_odo's default follows it
             aid = dict(aid, scale=self.scale['scale0'])
             if aid.get('odo_std') is None and odo_err is None:
                 raise ValueError("odo_scale_state needs odo_err={'scale', 'stdv'} or aid['odo_std']")
+            g = self.scalep = _lib.LooseScaleParams()
+            g.scale0, g.p0_scale, g.q_k = self.scale['scale0'], self.scale['p0_scale'], self.scale['q_k']
         self.aid = aiding_model(odo_err, aid)
         for k, v in self.aid.items():
-            setattr(p, k, v)
-        use_odo = bool(self.aid['aid_mask'] & 1)
-        self.mag, self.magp = None, None
+            setattr(self.params, k, v)
         if mag is not None:
-            if cons_samples is not None:
-                raise ValueError('cons_samples: consistency checkpoints of the magnetometer-aided filter are not built (mag=...)')
             self.mag = mag_model(mag_err, geo_mag_n, ref_frame, mag)
             g = self.magp = _lib.LooseMagParams()
             g.mag_every = self.mag['mag_every']
             for k in ('mag_n', 'cal_si', 'cal_hi', 'r_mag'):
                 getattr(g, k)[:] = [float(x) for x in np.asarray(self.mag[k], dtype=np.float64).reshape(-1)]
+
+    def _inputs(self, table, ref_gps, truth, fs, accel_err, gyro_err, gps_err, odo_err, mag_err, vib_accel, vib_gyro, given):
+        """Where the lanes take their samples from, and the one upload of what they read: the initial-state table and, in the generated
+        form, the truth's series behind it."""
+        m, p, use_odo = self.mc, self.params, bool(self.aid['aid_mask'] & 1)
         self._ref_nav = np.ascontiguousarray(np.concatenate([truth['ref_att'], truth['ref_pos'], truth['ref_vel']], axis=1))
         m.ref_end[:] = [float(x) for x in self._ref_nav[-1]]
-        parts = [table.reshape(-1)]
         need = (('accel', 3, self.n), ('gyro', 3, self.n), ('gps', 6, self.m)) + ((('odo', 1, self.n),) if use_odo else ()) + \
             ((('mag', 3, self.n),) if self.mag is not None else ())
         self._sensor_source(m, fs, accel_err, gyro_err, vib_accel, vib_gyro, given, need, 'filter')
+        parts = [(m, 'ini', table.reshape(-1))]             # (block, pointer field, host array) of everything uploaded, in order
         if given is None:
-            parts += [np.asarray(truth['ref_accel'], dtype=np.float64).reshape(-1), np.asarray(truth['ref_gyro'], dtype=np.float64).reshape(-1),
-                      ref_gps.reshape(-1)]
-            if self.m:
-                p.gps_sigma[:] = [float(x) for x in gps_sigma(gps_err, ref_gps, int(ref_frame))]
-            if use_odo:
-                if 'ref_odo' not in truth or odo_err is None:
-                    raise ValueError("aid['odo'] in the generated form needs truth['ref_odo'] and odo_err")
-                ref_odo = np.asarray(truth['ref_odo'], dtype=np.float64).reshape(-1)
-                if ref_odo.size != self.n:
-                    raise ValueError("truth['ref_odo'] must have one value per IMU sample")
-                m.odo_scale, m.odo_stdv = float(odo_err['scale']), float(odo_err['stdv'])
-                parts.append(ref_odo)
-            if self.mag is not None:
-                if 'ref_mag' not in truth or mag_err is None:
-                    raise ValueError("mag in the generated form needs truth['ref_mag'] and mag_err")
-                ref_mag = np.asarray(truth['ref_mag'], dtype=np.float64)
-                if ref_mag.shape != (self.n, 3):
-                    raise ValueError("truth['ref_mag'] must be (n, 3): one row per IMU sample")
-                g = self.magp
-                g.mag_si[:] = [float(x) for x in np.asarray(mag_err['si'], dtype=np.float64).reshape(9)]
-                g.mag_hi[:] = [float(x) for x in np.asarray(mag_err['hi'], dtype=np.float64) * np.ones(3)]
-                g.mag_std[:] = [float(x) for x in np.asarray(mag_err['std'], dtype=np.float64) * np.ones(3)]
-                parts.append(ref_mag.reshape(-1))
+            parts += self._truth_series(truth, ref_gps, gps_err, odo_err, mag_err, use_odo)
         else:
             p.in_gps = given['gps'].ptr if self.m else None
             if use_odo:
                 m.in_odo = given['odo'].ptr
             if self.mag is not None:
                 self.magp.in_mag = given['mag'].ptr
-        offs = np.cumsum([0] + [q.size for q in parts]) * 8
-        self._bufs['inputs'] = ctx.upload(np.concatenate(parts))
-        m.ini = self._bufs['inputs'].at(offs[0])
-        if given is None:
-            m.ref_accel, m.ref_gyro = self._bufs['inputs'].at(offs[1]), self._bufs['inputs'].at(offs[2])
-            p.ref_gps = self._bufs['inputs'].at(offs[3]) if self.m else None
-            if use_odo:
-                m.ref_odo = self._bufs['inputs'].at(offs[4])
-            if self.mag is not None:
-                self.magp.ref_mag = self._bufs['inputs'].at(offs[5 if use_odo else 4])
-        R = self.runs
+        buf = self._bufs['inputs'] = self.ctx.upload(np.concatenate([q for _, _, q in parts]))
+        offs = np.cumsum([0] + [q.size for _, _, q in parts]) * 8
+        for (block, field, q), o in zip(parts, offs):
+            setattr(block, field, buf.at(o) if q.size else None)
+
+    def _truth_series(self, truth, ref_gps, gps_err, odo_err, mag_err, use_odo):
+        """The generated form: [(block, pointer field, flat host array)] of the truth's series the lanes make their samples from, in
+        upload order, and the numbers of the sensors that only this form has (gps_sigma, the odometer's and the magnetometer's model)."""
+        m, p = self.mc, self.params
+        parts = [(m, 'ref_accel', np.asarray(truth['ref_accel'], dtype=np.float64).reshape(-1)),
+                 (m, 'ref_gyro', np.asarray(truth['ref_gyro'], dtype=np.float64).reshape(-1)), (p, 'ref_gps', ref_gps.reshape(-1))]
+        if self.m:
+            p.gps_sigma[:] = [float(x) for x in gps_sigma(gps_err, ref_gps, self._ref_frame)]
+        if use_odo:
+            if 'ref_odo' not in truth or odo_err is None:
+                raise ValueError("aid['odo'] in the generated form needs truth['ref_odo'] and odo_err")
+            ref_odo = np.asarray(truth['ref_odo'], dtype=np.float64).reshape(-1)
+            if ref_odo.size != self.n:
+                raise ValueError("truth['ref_odo'] must have one value per IMU sample")
+            m.odo_scale, m.odo_stdv = float(odo_err['scale']), float(odo_err['stdv'])
+            parts.append((m, 'ref_odo', ref_odo))
+        if self.mag is not None:
+            if 'ref_mag' not in truth or mag_err is None:
+                raise ValueError("mag in the generated form needs truth['ref_mag'] and mag_err")
+            ref_mag = np.asarray(truth['ref_mag'], dtype=np.float64)
+            if ref_mag.shape != (self.n, 3):
+                raise ValueError("truth['ref_mag'] must be (n, 3): one row per IMU sample")
+            g = self.magp
+            g.mag_si[:] = [float(x) for x in np.asarray(mag_err['si'], dtype=np.float64).reshape(9)]
+            g.mag_hi[:] = [float(x) for x in np.asarray(mag_err['hi'], dtype=np.float64) * np.ones(3)]
+            g.mag_std[:] = [float(x) for x in np.asarray(mag_err['std'], dtype=np.float64) * np.ones(3)]
+            parts.append((g, 'ref_mag', ref_mag.reshape(-1)))
+        return parts
+
+    def _outputs(self, placed):
+        """The device buffers a launch writes: the per-run end records, the online process statistics (proc_first), the kept series
+        (keep_traj) and the records of the scale-factor state."""
+        m, p, R = self.mc, self.params, self.runs
         # end [9][R], bias_end [6][R], pdiag_end [15][R], run list [R], the NED end record [9][R]
-        self._bufs['small'] = ctx.malloc((9 + 6 + 15 + 1 + 9) * R * 8)
-        small = self._bufs['small']
-        if end_ned:
+        small = self._bufs['small'] = self.ctx.malloc((9 + 6 + 15 + 1 + 9) * R * 8)
+        if self.end_ned:
             p.out_end_ned = small.at(31 * R * 8)
         p.out_end, p.out_bias_end, p.out_pdiag_end, self._list = small.ptr, small.at(9 * R * 8), small.at(15 * R * 8), small.at(30 * R * 8)
-        if proc_first is not None:
-            if not 0 <= int(proc_first) < self.n:
+        if self.proc_first is not None:
+            if not 0 <= int(self.proc_first) < self.n:
                 raise ValueError('proc_first must be a sample index of the run')
-            if proc_ned and int(ref_frame) != 0:
+            if self.proc_ned and self._ref_frame != 0:
                 raise ValueError('NED position errors exist in ref_frame 0 only')
-            m.ref_nav, m.proc_first, m.proc_pos_ned = self._nav(), int(proc_first), int(bool(proc_ned))
-            self._bufs['proc'] = ctx.malloc(27 * R * 8)
+            m.ref_nav, m.proc_first, m.proc_pos_ned = self._nav(), int(self.proc_first), int(self.proc_ned)
+            self._bufs['proc'] = self.ctx.malloc(27 * R * 8)
             p.out_proc = self._bufs['proc'].ptr
         if self.keep_traj:
             plane = self.n * R * 8
             total = 15 * plane
-            self._bufs['series'] = ctx.malloc(total, placed=self._use_placed(placed, total))
+            self._bufs['series'] = self.ctx.malloc(total, placed=self._use_placed(placed, total))
             self._bufs['traj_loose'] = DeviceView(self._bufs['series'], 0, 9 * plane)
             self._bufs['wb'] = DeviceView(self._bufs['series'], 9 * plane, 3 * plane)
             self._bufs['ab'] = DeviceView(self._bufs['series'], 12 * plane, 3 * plane)
             p.out_traj, p.out_wb, p.out_ab = self._bufs['traj_loose'].ptr, self._bufs['wb'].ptr, self._bufs['ab'].ptr
-        if self.scale is not None:
-            g = self.scalep = _lib.LooseScaleParams()
-            g.scale0, g.p0_scale, g.q_k = self.scale['scale0'], self.scale['p0_scale'], self.scale['q_k']
+        if self.scalep is not None:
+            g = self.scalep
             # scale_end [2][R], pcross_end [15][R], and the kept series [n][R]
-            self._bufs['scale'] = ctx.malloc((17 + (self.n if self.keep_scale else 0)) * R * 8)
+            self._bufs['scale'] = self.ctx.malloc((17 + (self.n if self.keep_scale else 0)) * R * 8)
             g.out_scale_end, g.out_pcross_end = self._bufs['scale'].ptr, self._bufs['scale'].at(2 * R * 8)
             if self.keep_scale:
                 g.out_scale = self._bufs['scale'].at(17 * R * 8)
-        p.n_list = R
+
+    def _checkpoints(self, cons_samples):
+        """The checkpoint block (cons) and its record and work buffers."""
         self.cons = None
-        if cons_samples is not None:
-            if proc_first is not None:
-                raise ValueError('cons_samples: online process statistics (proc_first) and checkpoints in one launch are refused')
-            asked = np.asarray(cons_samples, dtype=np.int64).reshape(-1)
-            if asked.size == 0 or asked.min() < 0 or asked.max() >= self.n:
-                raise ValueError('cons_samples must be sample indices in [0, %d), at least one' % self.n)
-            # the kernel walks a strictly increasing list; _cons_back maps its records to the caller's order
-            self._cons_samples, self._cons_back = np.unique(asked, return_inverse=True)
-            self._cons_samples = np.ascontiguousarray(self._cons_samples, dtype=np.int64)
-            mu, waves = self._cons_samples.size, (R + 63) // 64
-            self._bufs['cons'] = ctx.malloc((1 + waves) * mu * _lib.CONS_RECORD * 8)
-            m.ref_nav = self._nav()
-            c = self.cons = _lib.LooseConsParams()
-            c.cons_sample, c.cons_m = self._cons_samples.ctypes.data, mu
-            c.out_cons, c.cons_work = self._bufs['cons'].ptr, self._bufs['cons'].at(mu * _lib.CONS_RECORD * 8)
+        if cons_samples is None:
+            return
+        asked = np.asarray(cons_samples, dtype=np.int64).reshape(-1)
+        if asked.size == 0 or asked.min() < 0 or asked.max() >= self.n:
+            raise ValueError('cons_samples must be sample indices in [0, %d), at least one' % self.n)
+        # the kernel walks a strictly increasing list; _cons_back maps its records to the caller's order
+        self._cons_samples, self._cons_back = np.unique(asked, return_inverse=True)
+        self._cons_samples = np.ascontiguousarray(self._cons_samples, dtype=np.int64)
+        mu, waves = self._cons_samples.size, (self.runs + 63) // 64
+        self._bufs['cons'] = self.ctx.malloc((1 + waves) * mu * _lib.CONS_RECORD * 8)
+        self.mc.ref_nav = self._nav()
+        c = self.cons = _lib.LooseConsParams()
+        c.cons_sample, c.cons_m = self._cons_samples.ctypes.data, mu
+        c.out_cons, c.cons_work = self._bufs['cons'].ptr, self._bufs['cons'].at(mu * _lib.CONS_RECORD * 8)
 
     # ------------------------------------------------------------------ launches
+    def _entry(self, what, *head):
+        """The family's entry point ginsim_loose[_cons | _mag | _scale]_<what> and its arguments: head, the two base blocks, the
+        family's block."""
+        suffix, block = self._family
+        args = head + (C.byref(self.mc), C.byref(self.params)) + (() if block is None else (C.byref(block),))
+        return getattr(lib, 'ginsim_loose%s_%s' % (suffix, what)), args
+
     def kernel_name(self):
         buf = C.create_string_buffer(256)
-        if self.cons is not None:
-            check(lib.ginsim_loose_cons_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.cons), buf, 256))
-        elif self.magp is not None:
-            check(lib.ginsim_loose_mag_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.magp), buf, 256))
-        elif self.scalep is not None:
-            check(lib.ginsim_loose_scale_kernel_name(C.byref(self.mc), C.byref(self.params), C.byref(self.scalep), buf, 256))
-        else:
-            check(lib.ginsim_loose_kernel_name(C.byref(self.mc), C.byref(self.params), buf, 256))
+        fn, args = self._entry('kernel_name')
+        check(fn(*(args + (buf, 256))))
         return buf.value.decode()
 
     def variant(self):
@@ -408,16 +447,9 @@ class InsLooseJob(BatchJob):
     def launch(self, ids=None):
         """Enqueue the kernel (asynchronous).  ids: launch these runs only (lane i filters run ids[i]); the others keep what they hold,
         and the consistency record is over the listed runs."""
-        p = self.params
-        self._put_run_list(p, ids)
-        if self.cons is not None:
-            check(self.ctx.retry_oom(lambda: lib.ginsim_loose_cons_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.cons))))
-        elif self.magp is not None:
-            check(self.ctx.retry_oom(lambda: lib.ginsim_loose_mag_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.magp))))
-        elif self.scalep is not None:
-            check(self.ctx.retry_oom(lambda: lib.ginsim_loose_scale_run(self.ctx.handle, C.byref(self.mc), C.byref(p), C.byref(self.scalep))))
-        else:
-            check(self.ctx.retry_oom(lambda: lib.ginsim_loose_run(self.ctx.handle, C.byref(self.mc), C.byref(p))))
+        self._put_run_list(self.params, ids)
+        fn, args = self._entry('run', self.ctx.handle)
+        check(self.ctx.retry_oom(lambda: fn(*args)))
 
     def run(self, ids=None):
         self.launch(ids)

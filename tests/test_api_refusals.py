@@ -1,14 +1,16 @@
-"""CPU: what check_mc_params, check_incl_params, check_loose_params and check_loose_cons (csrc/ginsim_api.hip) refuse, in which
-order, and the dispatch table of the loose family -- through the name queries ginsim_mc_kernel_name, ginsim_incl_kernel_name,
-ginsim_loose_kernel_name and ginsim_loose_cons_kernel_name, which run the same checks as the launches and need no device.
+"""CPU: what check_mc_params, check_incl_params, check_loose_params, check_loose_cons, check_loose_mag and check_loose_scale
+(csrc/ginsim_api.hip) refuse, in which order, and the dispatch table of the loose family -- through the name queries
+ginsim_mc_kernel_name, ginsim_incl_kernel_name, ginsim_loose_kernel_name, ginsim_loose_cons_kernel_name,
+ginsim_loose_mag_kernel_name and ginsim_loose_scale_kernel_name, which run the same checks as the launches and need no device.
 
 Every case starts from one valid block per entry point (dummy non-NULL pointers: a name query reads host memory only) and breaks
 one field per REQUIRE of those functions; 'a + b' breaks two, which pins the ORDER of the checks where the functions share
 helpers: sizes before the sensor source, the sensor source before the vibration, the vibration before what follows it.
 
 tests/golden/api_refusals.json holds (return code, full message) of every case, recorded from commit 89d973d (each function with
-its own copy of every check) by this file run with GINSIM_RECORD_REFUSALS=1.  It is the definition of "the same refusals" for any
-later shape of those functions and is not regenerated from changed code."""
+its own copy of every check) by this file run with GINSIM_RECORD_REFUSALS=1; the 'mag' and 'scale' entries were added to it from
+commit 20487e3 (the last one in which every entry point of the loose family orders its checks itself).  It is the definition of
+"the same refusals" for any later shape of those functions and is not regenerated from changed code."""
 import ctypes
 import itertools
 import json
@@ -26,7 +28,8 @@ TOO_MANY_RUNS = 0x7FFFFFFF * 64 + 1
 
 
 class Blocks(object):
-    """The valid parameter blocks of one entry point: mc (ginsim_mc_params), p (the kernel's own block), q (the checkpoint block)."""
+    """The valid parameter blocks of one entry point: mc (ginsim_mc_params), p (the kernel's own block), q (the family's block:
+    checkpoints, magnetometer or scale-factor state)."""
 
     def __init__(self, entry, given):
         from ginsim import _lib as L
@@ -57,6 +60,15 @@ class Blocks(object):
                 q = self.q = L.LooseConsParams()
                 q.cons_sample, q.cons_m, q.out_cons, q.cons_work = self.samples.ctypes.data, 3, d, d
                 m.ref_nav = d
+            elif entry == 'mag':
+                q = self.q = L.LooseMagParams()
+                q.mag_every, q.in_mag, q.ref_mag = 1, (d if given else None), (None if given else d)
+                q.mag_si[:], q.cal_si[:] = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0], [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+                q.mag_std[:], q.mag_n[:], q.r_mag[:] = [0.01] * 3, [30.0, -3.0, 40.0], [1e-4] * 3
+            elif entry == 'scale':
+                q = self.q = L.LooseScaleParams()
+                q.scale0, q.p0_scale, q.q_k = 1.0, 0.02, 0.0
+                p.aid_mask, p.aid_every, p.r_odo, p.odo_scale_f = 1, 1, 0.01, 1.0
 
     def name(self):
         """(return code, kernel name or the refusal's message)"""
@@ -70,7 +82,9 @@ class Blocks(object):
         elif self.entry == 'loose':
             rc = L.lib.ginsim_loose_kernel_name(ref(self.mc), ref(self.p), buf, 256)
         else:
-            rc = L.lib.ginsim_loose_cons_kernel_name(ref(self.mc), ref(self.p), ref(self.q), buf, 256)
+            fn = {'cons': L.lib.ginsim_loose_cons_kernel_name, 'mag': L.lib.ginsim_loose_mag_kernel_name,
+                  'scale': L.lib.ginsim_loose_scale_kernel_name}[self.entry]
+            rc = fn(ref(self.mc), ref(self.p), ref(self.q), buf, 256)
         return [rc, (buf.value if rc == L.OK else L.lib.ginsim_last_error()).decode()]
 
 
@@ -230,6 +244,34 @@ SINGLE = {
         },
         'given': {'in_gps NULL': _set('p.in_gps', None), 'checkpoint n': _stamp('samples', 2, N)},
     },
+    'mag': {
+        'gen': {
+            'q NULL': _drop('q'), 'mag_every=-1': _set('q.mag_every', -1), 'mag_every=0 is legal: the plain launch': _set('q.mag_every', 0),
+            'mag_every=0 is legal: the aided launch': _all(_set('q.mag_every', 0), _set('p.aid_mask', 6), _set('p.aid_every', 1), _set('p.r_nhc', 0.0025)),
+            'mag_every=0 is legal and reads nothing else': _all(_set('q.mag_every', 0), _set('q.ref_mag', None), _set('q.r_mag', 0.0, 0), _set('q.mag_n', NAN, 1)),
+            'ref_mag NULL': _set('q.ref_mag', None), 'mag_si nan': _set('q.mag_si', NAN, 4), 'mag_hi inf': _set('q.mag_hi', INF, 2),
+            'mag_std nan': _set('q.mag_std', NAN, 0), 'cal_si inf': _set('q.cal_si', INF, 8), 'mag_n nan': _set('q.mag_n', NAN, 1),
+            'cal_hi -inf': _set('q.cal_hi', -INF, 0), 'r_mag=0': _set('q.r_mag', 0.0, 1), 'r_mag nan': _set('q.r_mag', NAN, 2),
+            'mag_n zero': _all(_set('q.mag_n', 0.0, 0), _set('q.mag_n', 0.0, 1), _set('q.mag_n', 0.0, 2)),
+            'runs=0': SIZES['runs=0'], 'ref_gps NULL': _set('p.ref_gps', None), 'vib_accel psd': VIB['vib_accel psd'], 'aid_mask=8': _set('p.aid_mask', 8),
+        },
+        'given': {
+            'in_mag NULL': _set('q.in_mag', None), 'ref_mag NULL is legal': _set('q.ref_mag', None), 'mag_si nan is not read': _set('q.mag_si', NAN, 0),
+            'mag_std inf is not read': _set('q.mag_std', INF, 1), 'cal_si nan': _set('q.cal_si', NAN, 0), 'r_mag=0': _set('q.r_mag', 0.0, 0),
+            'in_gps NULL': _set('p.in_gps', None),
+        },
+    },
+    'scale': {
+        'gen': {
+            'q NULL': _drop('q'), 'aid_mask without bit 0': _all(_set('p.aid_mask', 6), _set('p.r_nhc', 0.0025)), 'aid_mask=0': _set('p.aid_mask', 0),
+            'scale0=0': _set('q.scale0', 0.0), 'scale0 nan': _set('q.scale0', NAN), 'scale0 inf': _set('q.scale0', INF),
+            'p0_scale<0': _set('q.p0_scale', -1e-300), 'p0_scale inf': _set('q.p0_scale', INF), 'p0_scale=0 is legal': _set('q.p0_scale', 0.0),
+            'q_k<0': _set('q.q_k', -1.0), 'q_k nan': _set('q.q_k', NAN), 'q_k>0 is legal': _set('q.q_k', 1e-8),
+            'runs=0': SIZES['runs=0'], 'vib_accel psd': VIB['vib_accel psd'], 'aid_mask=8': _set('p.aid_mask', 8), 'r_odo=0': _set('p.r_odo', 0.0),
+            'odo without ref_odo': _set('mc.ref_odo', None), 'precision=1': _set('mc.precision', 1),
+        },
+        'given': {'odo without in_odo': _set('mc.in_odo', None), 'scale0 nan': _set('q.scale0', NAN), 'in_gps NULL': _set('p.in_gps', None)},
+    },
 }
 
 # two violations at once: the message is that of the check that comes first
@@ -257,6 +299,15 @@ PAIRS = [
     ('mc', 'gen', 'vib_gyro omega_dt inf', 'precision=2'), ('incl', 'gen', 'vib_gyro omega_dt inf', 'out_end without ref_nav'),
     ('incl', 'gen', 'vib_accel psd', 'out_wb without mahony'), ('loose', 'gen', 'vib_gyro omega_dt inf', 'r_diag=0'), ('loose', 'gen', 'vib_gyro type 9', 'aid_mask=8'),
     ('loose', 'given', 'vib_gyro sinusoidal', 'odo without in_odo'),
+    # the filter's block before the magnetometer's, and the order inside the magnetometer's
+    ('mag', 'gen', 'aid_mask=8', 'mag_every=-1'), ('mag', 'gen', 'vib_accel psd', 'q NULL'), ('mag', 'gen', 'runs=0', 'ref_mag NULL'),
+    ('mag', 'gen', 'ref_gps NULL', 'r_mag=0'), ('mag', 'given', 'in_gps NULL', 'in_mag NULL'), ('mag', 'gen', 'ref_mag NULL', 'mag_si nan'),
+    ('mag', 'gen', 'mag_hi inf', 'cal_si inf'), ('mag', 'gen', 'cal_si inf', 'mag_n nan'), ('mag', 'gen', 'r_mag=0', 'mag_n zero'),
+    ('mag', 'given', 'in_mag NULL', 'cal_si nan'),
+    # the filter's block before the scale-factor state's, and the order inside the state's
+    ('scale', 'gen', 'aid_mask=8', 'scale0=0'), ('scale', 'gen', 'vib_accel psd', 'q NULL'), ('scale', 'gen', 'r_odo=0', 'q_k<0'),
+    ('scale', 'gen', 'precision=1', 'p0_scale inf'), ('scale', 'given', 'odo without in_odo', 'scale0 nan'),
+    ('scale', 'gen', 'aid_mask without bit 0', 'scale0 nan'), ('scale', 'gen', 'scale0=0', 'p0_scale<0'), ('scale', 'gen', 'p0_scale inf', 'q_k nan'),
     # the filter's block before the checkpoints'
     ('cons', 'gen', 'aid_mask=8', 'cons_m=-1'), ('cons', 'gen', 'vib_accel psd', 'q NULL'), ('cons', 'gen', 'ref_nav NULL', 'out_proc'),
     ('cons', 'gen', 'cons_work NULL', 'ref_nav NULL'), ('cons', 'given', 'in_gps NULL', 'checkpoint n'),
@@ -314,7 +365,8 @@ def test_every_refusal_is_an_argument_error_with_its_entry_point_s_prefix(record
         if name.endswith('valid') or 'legal' in name or 'not read' in name or 'cons_m=0' in name:
             assert rc == L.OK and text.startswith('ginsim::'), name
         else:
-            assert rc == L.ERR_ARG and text.split(':')[0] in ('mc_kernel_name', 'mc_run', 'incl_run', 'loose_run', 'loose_cons_run'), name
+            assert rc == L.ERR_ARG and text.split(':')[0] in ('mc_kernel_name', 'mc_run', 'incl_run', 'loose_run', 'loose_cons_run', 'loose_mag_run',
+                                                               'loose_scale_run'), name
             refused += 1
     assert refused >= 150
 
@@ -324,11 +376,11 @@ TF = {False: 'false', True: 'true'}
 
 
 @pytest.mark.parametrize('rf, source, flag, kind', list(itertools.product((0, 1), ('gen', 'vib', 'given'), (False, True),
-                                                                          ('plain', 'aided', 'cons'))))
+                                                                          ('plain', 'aided', 'cons', 'mag', 'scale'))))
 def test_loose_family_dispatch(rf, source, flag, kind):
-    """36 names: <RF, GIVEN, VIB, F> with F = online process statistics (out_proc) for loose_kernel and loose_aided_kernel (aid_mask
-    != 0), F = aiding for loose_cons_kernel (cons_m > 0)."""
-    b = Blocks('cons' if kind == 'cons' else 'loose', source == 'given')
+    """60 names: <RF, GIVEN, VIB, F> with F = online process statistics (out_proc) for loose_kernel, loose_aided_kernel (aid_mask
+    != 0), loose_mag_kernel (mag_every > 0) and loose_scale_kernel, F = aiding for loose_cons_kernel (cons_m > 0)."""
+    b = Blocks(kind if kind in ('cons', 'mag', 'scale') else 'loose', source == 'given')
     b.mc.ref_frame = rf
     if source == 'vib':
         b.mc.vib_gyro.type = 1
@@ -337,6 +389,7 @@ def test_loose_family_dispatch(rf, source, flag, kind):
         b.p.aid_mask, b.p.aid_every, b.p.r_nhc = 6, 3, 0.0025
     if kind != 'cons' and flag:
         b.p.out_proc, b.mc.ref_nav = b.d, b.d
-    kernel = {'plain': 'loose_kernel', 'aided': 'loose_aided_kernel', 'cons': 'loose_cons_kernel'}[kind]
+    kernel = {'plain': 'loose_kernel', 'aided': 'loose_aided_kernel', 'cons': 'loose_cons_kernel', 'mag': 'loose_mag_kernel',
+              'scale': 'loose_scale_kernel'}[kind]
     want = 'ginsim::%s<%d, %s, %s, %s>' % (kernel, rf, TF[source == 'given'], TF[source == 'vib'], TF[flag])
     assert b.name() == [0, want]
