@@ -60,6 +60,9 @@ SOURCES = [
     # the aided lane with 16 states, the odometer's scale factor the last (ins_loose.hpp, NS): the same flags, its own resource
     # report (tests/test_ins_loose_scale_oracle.py reads it)
     ('ins_loose_scale.hip', MC_FLAGS),
+    # the aided lane with the standstill block, ZUPT and ZARU (ins_loose.hpp, STILL): the same flags, its own resource report
+    # (tests/test_ins_loose_still_oracle.py reads it)
+    ('ins_loose_still.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),

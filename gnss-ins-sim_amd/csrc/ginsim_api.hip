@@ -642,30 +642,46 @@ static int check_loose_scale(const ginsim_loose_params* p, const ginsim_loose_sc
     return GINSIM_OK;
 }
 
-// The family of a launch of the filter, in one order: checkpoints, magnetometer, scale-factor state, aiding, plain.
+// the standstill block of a launch whose other two blocks passed check_loose_params (fp32 among what that refuses)
+static int check_loose_still(const ginsim_mc_params* m, const ginsim_loose_still_params* q) {
+    REQUIRE(q, "loose_still_run: NULL argument");
+    REQUIRE(q->still_mask >= 0 && q->still_mask <= 3, "loose_still_run: still_mask=%d must lie in 0 .. 3", (int)q->still_mask);
+    if (q->still_mask == 0) return GINSIM_OK;
+    REQUIRE(m->precision == 0, "loose_still_run: the standstill block is fp64 only");
+    REQUIRE(q->still_every >= 1, "loose_still_run: still_every=%lld must be >= 1", (long long)q->still_every);
+    REQUIRE((q->still_mask & 1) == 0 || (std::isfinite(q->r_zupt) && q->r_zupt > 0.0), "loose_still_run: r_zupt must be positive");
+    for (int k = 0; k < 3; ++k)
+        REQUIRE((q->still_mask & 2) == 0 || (std::isfinite(q->r_zaru[k]) && q->r_zaru[k] > 0.0), "loose_still_run: r_zaru must be positive");
+    REQUIRE(q->still_flags, "loose_still_run: still_flags missing");
+    return GINSIM_OK;
+}
+
+// The family of a launch of the filter, in one order: checkpoints, magnetometer, scale-factor state, standstill, aiding, plain.
 static hipError_t launch_loose(const LooseLaunch& L) {
     if (L.b->n_list <= 0 && !L.name) return hipSuccess;
     if (L.cons) return launch_loose_cons(L);
     if (L.mag) return launch_loose_mag(L);
     if (L.scale) return launch_loose_scale(L);
+    if (L.still) return launch_loose_still(L);
     return L.b->aid_mask != 0 ? launch_loose_aided(L) : launch_loose_plain(L);
 }
 
 // What every entry point of the loose family does with its blocks: L.mc, L.b and, for the entry points of family `who`, that
-// family's block (the other two are NULL).  The one place that orders the checks: the base blocks, then the family's own; a
-// degenerate block (cons_m == 0, mag_every == 0) is then no block.  L.name != NULL (c is not read): the kernel's name.  Otherwise
+// family's block (the others are NULL).  The one place that orders the checks: the base blocks, then the family's own; a
+// degenerate block (cons_m == 0, mag_every == 0, still_mask == 0) is then no block.  L.name != NULL (c is not read): the kernel's name.  Otherwise
 // the stamps, the visibility flags (padded to 8 bytes) and the checkpoint samples are copied next to each other into the context's
 // scratch and the family is launched.
-enum LooseFamily { LOOSE_PLAIN, LOOSE_CONS, LOOSE_MAG, LOOSE_SCALE };
+enum LooseFamily { LOOSE_PLAIN, LOOSE_CONS, LOOSE_MAG, LOOSE_SCALE, LOOSE_STILL };
 
 static int loose_entry(LooseFamily who, ginsim_ctx* c, LooseLaunch L) {
     int rc = check_loose_params(L.mc, L.b);
     if (rc) return rc;
     rc = who == LOOSE_CONS ? check_loose_cons(L.mc, L.b, L.cons) : who == LOOSE_MAG ? check_loose_mag(L.mc, L.mag)
-       : who == LOOSE_SCALE ? check_loose_scale(L.b, L.scale) : GINSIM_OK;
+       : who == LOOSE_SCALE ? check_loose_scale(L.b, L.scale) : who == LOOSE_STILL ? check_loose_still(L.mc, L.still) : GINSIM_OK;
     if (rc) return rc;
     if (L.cons && L.cons->cons_m == 0) L.cons = nullptr;
     if (L.mag && L.mag->mag_every == 0) L.mag = nullptr;
+    if (L.still && L.still->still_mask == 0) L.still = nullptr;
     if (L.name) {
         L.name[0] = 0;
         (void)launch_loose(L);
@@ -701,7 +717,7 @@ static int loose_entry(LooseFamily who, ginsim_ctx* c, LooseLaunch L) {
 
 int ginsim_loose_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, char* buf, size_t cap) {
     REQUIRE(buf && cap > 0, "loose_kernel_name: bad arguments");
-    return loose_entry(LOOSE_PLAIN, nullptr, LooseLaunch{mc, p, nullptr, nullptr, nullptr, buf, cap});
+    return loose_entry(LOOSE_PLAIN, nullptr, LooseLaunch{mc, p, nullptr, nullptr, nullptr, nullptr, buf, cap});
 }
 
 int ginsim_loose_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p) {
@@ -712,7 +728,7 @@ int ginsim_loose_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loo
 int ginsim_loose_cons_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons,
                                   char* buf, size_t cap) {
     REQUIRE(buf && cap > 0, "loose_cons_kernel_name: bad arguments");
-    return loose_entry(LOOSE_CONS, nullptr, LooseLaunch{mc, p, cons, nullptr, nullptr, buf, cap});
+    return loose_entry(LOOSE_CONS, nullptr, LooseLaunch{mc, p, cons, nullptr, nullptr, nullptr, buf, cap});
 }
 
 int ginsim_loose_cons_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_cons_params* cons) {
@@ -723,7 +739,7 @@ int ginsim_loose_cons_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsi
 int ginsim_loose_mag_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
                                  char* buf, size_t cap) {
     REQUIRE(buf && cap > 0, "loose_mag_kernel_name: bad arguments");
-    return loose_entry(LOOSE_MAG, nullptr, LooseLaunch{mc, p, nullptr, mag, nullptr, buf, cap});
+    return loose_entry(LOOSE_MAG, nullptr, LooseLaunch{mc, p, nullptr, mag, nullptr, nullptr, buf, cap});
 }
 
 int ginsim_loose_mag_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag) {
@@ -734,12 +750,23 @@ int ginsim_loose_mag_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim
 int ginsim_loose_scale_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale,
                                    char* buf, size_t cap) {
     REQUIRE(buf && cap > 0, "loose_scale_kernel_name: bad arguments");
-    return loose_entry(LOOSE_SCALE, nullptr, LooseLaunch{mc, p, nullptr, nullptr, scale, buf, cap});
+    return loose_entry(LOOSE_SCALE, nullptr, LooseLaunch{mc, p, nullptr, nullptr, scale, nullptr, buf, cap});
 }
 
 int ginsim_loose_scale_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale) {
     REQUIRE(c, "loose_scale_run: NULL argument");
     return loose_entry(LOOSE_SCALE, c, LooseLaunch{mc, p, nullptr, nullptr, scale});
+}
+
+int ginsim_loose_still_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_still_params* still,
+                                   char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_still_kernel_name: bad arguments");
+    return loose_entry(LOOSE_STILL, nullptr, LooseLaunch{mc, p, nullptr, nullptr, nullptr, still, buf, cap});
+}
+
+int ginsim_loose_still_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_still_params* still) {
+    REQUIRE(c, "loose_still_run: NULL argument");
+    return loose_entry(LOOSE_STILL, c, LooseLaunch{mc, p, nullptr, nullptr, nullptr, still});
 }
 
 int ginsim_aux_sensors(ginsim_ctx* c, const ginsim_aux_params* p) {

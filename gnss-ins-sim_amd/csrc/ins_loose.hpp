@@ -7,6 +7,8 @@
 // The covariance and everything that touches it is generic in the number of states NS (CovT<NS>; Cov = CovT<15> is the filter of the
 // four files above).  ins_loose_scale.hip's loose_scale_kernel is the lane with NS = 16: state 15 is the odometer's scale-factor
 // error; what it adds is behind `NS == kLooseStates + 1` and compiles to nothing for NS = 15.
+// For ins_loose_still.hip's loose_still_kernel: the standstill block (loose_still) behind the flag STILL; its equations are in that
+// file's header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
@@ -233,6 +235,21 @@ __device__ __forceinline__ loose_scale_ptr loose_scale_params() {
     return (loose_scale_ptr)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
 }
 
+// loose_still_kernel's fifth argument, the standstill block by value, where loose_mag_kernel has the magnetometer block
+typedef const ginsim_loose_still_params __attribute__((address_space(4))) * loose_still_ptr;
+static_assert(alignof(ginsim_loose_still_params) == 8, "the kernarg offset of loose_still_params()");
+__device__ __forceinline__ loose_still_ptr loose_still_params() {
+    typedef const char __attribute__((address_space(4))) * bytes_ptr;
+    bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (loose_still_ptr)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
+}
+// the standstill signal of sample j (wave-uniform: a scalar load, as visible[kf])
+__device__ __forceinline__ bool still_flag(const int32_t* flags, int64_t j) {
+    typedef const int32_t __attribute__((address_space(4))) * flags_ptr;
+    return ((flags_ptr)(uintptr_t)flags)[j] != 0;
+}
+
 // P <- Phi P Phi^T + Qd for the step from the attitude with body -> navigation matrix C and bias-corrected specific force f^n
 // (NS = 16: Phi is the identity on state 15, whose row takes part in every congruence as a column; P[15][15] += q_k)
 template <int NS>
@@ -402,6 +419,41 @@ __device__ __forceinline__ void loose_mag(Cov& P, Nav& s, Vec3& bg, Vec3& ba, co
     loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
 }
 
+// One standstill block (ins_loose_still.hip's header): the rows `mask` selects (bit 0: dv, states 3-5; bit 1: dbg, states 9-11) in
+// ascending state order from x = 0; then the feedback.  Every z is formed from the state before the first row.  gyro_prev: the raw
+// gyro sample the lane integrated last (j - 1), before the bias was subtracted.  mask is wave-uniform.
+template <int RF>
+__device__ __forceinline__ void loose_still(Cov& P, Nav& s, Vec3& bg, Vec3& ba, const Vec3& gyro_prev, int mask) {
+    // the rate the mechanisation assumes of a body at rest (nav_step with v = 0): earth rate in the body axes of the estimate
+    Vec3 wr{0.0, 0.0, 0.0};
+    if (RF == 0) {
+        if (kernarg_params()->earth_rot) wr = s.att.to_body(Vec3{kWie * s.cl, 0.0, -kWie * s.sl});
+    }
+    const double zv[3] = {s.vel.x, s.vel.y, s.vel.z};
+    const double zg[3] = {bg.x + wr.x - gyro_prev.x, bg.y + wr.y - gyro_prev.y, bg.z + wr.z - gyro_prev.z};
+    double mlat = 1.0, mlon = 1.0;
+    if (RF == 0) {
+        const Geo e = geo_param_sc(s.sl, s.cl, s.pos.z);
+        mlat = e.rm + s.pos.z;
+        mlon = (e.rn + s.pos.z) * e.cl;
+    }
+    double x[kLooseStates];
+#pragma unroll
+    for (int k = 0; k < kLooseStates; ++k) x[k] = 0.0;
+    phase_fence();
+    if (mask & 1) {
+        P.template update<3>(zv[0], loose_still_params()->r_zupt, x); phase_fence();
+        P.template update<4>(zv[1], loose_still_params()->r_zupt, x); phase_fence();
+        P.template update<5>(zv[2], loose_still_params()->r_zupt, x); phase_fence();
+    }
+    if (mask & 2) {
+        P.template update<9>(zg[0], loose_still_params()->r_zaru[0], x); phase_fence();
+        P.template update<10>(zg[1], loose_still_params()->r_zaru[1], x); phase_fence();
+        P.template update<11>(zg[2], loose_still_params()->r_zaru[2], x); phase_fence();
+    }
+    loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
+}
+
 // ---- consistency checkpoints (ins_loose_cons.hip)
 // What loose_cons_kernel passes to the lane next to the two parameter blocks: the DEVICE copy of the checkpoint samples, their
 // number and the wavefronts' partial records [wave][checkpoint][GINSIM_CONS_RECORD].  Not read unless CONS.
@@ -519,10 +571,15 @@ __device__ __forceinline__ void put3(double* base, int64_t plane, int64_t off, c
 // MAG an aid_mask of 0 fires no aiding block at all.  MAG = false is the lane as it was.
 // NS: the number of states.  16 (with AID, without CONS and MAG): the odometer's scale factor is state 15 and its estimate kest a
 // value of the lane; its numbers and outputs are the kernel's fifth argument (loose_scale_params).  NS = 15 is the lane as it was.
-template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false, bool MAG = false, int NS = kLooseStates>
+// STILL: the standstill block (loose_still) at every sample j > 0 with j % still_every == 0 and still_flags[j] != 0, after a fix and an
+// aiding block of the same sample, before the row is stored (the magnetometer block's place; with AID, without CONS and MAG, NS = 15);
+// its numbers are the kernel's fifth argument (loose_still_params).  The lane carries the raw gyro sample it integrated last.  With
+// STILL an aid_mask of 0 fires no aiding block at all.  STILL = false is the lane as it was.
+template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false, bool MAG = false, int NS = kLooseStates, bool STILL = false>
 __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const ginsim_loose_params& b, const int64_t* __restrict__ stamp,
                                            const int32_t* __restrict__ visible, uint32_t* ntab, const ConsArgs& cq = ConsArgs{}) {
     static_assert(NS == kLooseStates || (NS == kLooseScaleStates && AID && !CONS && !MAG), "16 states: the aided lane only");
+    static_assert(!STILL || (AID && !CONS && !MAG && NS == kLooseStates), "the standstill block: the aided lane with 15 states only");
     NormalTables tab{};
     if (!GIVEN) {
         tab = fill_normal_tables(ntab, threadIdx.x, blockDim.x);
@@ -574,12 +631,16 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
     const bool ned = a.proc_pos_ned != 0;
     int64_t kf = 0;         // the next fix (wave-uniform)
     // the next aiding block (wave-uniform); a period of n or more never fires
-    const int64_t every = AID ? ((b.aid_every < n && !(MAG && b.aid_mask == 0)) ? b.aid_every : n) : 0;
+    const int64_t every = AID ? ((b.aid_every < n && !((MAG || STILL) && b.aid_mask == 0)) ? b.aid_every : n) : 0;
     int64_t ja = every;
     // the next magnetometer block (wave-uniform), a counter of its own; a period of n or more never fires
     // (the period is read again from the kernarg segment at every block: one wave-uniform counter is all the loop holds)
     int64_t jm = MAG ? (loose_mag_params()->mag_every < n ? loose_mag_params()->mag_every : n) : 0;
     int64_t kc = 0;         // the next checkpoint (wave-uniform)
+    // the next sample at which a standstill block can fire (wave-uniform), a counter of its own as jm; and the raw gyro sample the
+    // lane integrated last (STILL only: nothing reads it otherwise)
+    int64_t js = STILL ? (loose_still_params()->still_every < n ? loose_still_params()->still_every : n) : 0;
+    Vec3 gyro_prev{0.0, 0.0, 0.0};
 
     for (int64_t j = 0; j < n; ++j) {
         const int64_t off = j * runs + r;
@@ -641,6 +702,17 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
                 phase_fence();
             }
         }
+        if constexpr (STILL) {
+            if (j == js) {
+                const loose_still_ptr sp = loose_still_params();
+                js += sp->still_every < n ? sp->still_every : n;
+                if (still_flag(sp->still_flags, j)) {
+                    phase_fence();
+                    loose_still<RF>(P, s, bg, ba, gyro_prev, sp->still_mask);
+                    phase_fence();
+                }
+            }
+        }
         if constexpr (CONS) {
             if (kc < cq.m && cq.sample[kc] == j) {
                 phase_fence();
@@ -690,6 +762,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
                 gyr = add_vibration<S_GYR_VIB_XY>(gyr, &kernarg_params()->vib_gyro, key, jj, tab, vpg, nopsd);
             }
         }
+        if constexpr (STILL) gyro_prev = gyr;       // raw: before the bias is subtracted
         acc = Vec3{acc.x - ba.x, acc.y - ba.y, acc.z - ba.z};
         gyr = Vec3{gyr.x - bg.x, gyr.y - bg.y, gyr.z - bg.z};
         // what the propagation needs of the state BEFORE the step: C and f^n = C f

@@ -39,6 +39,7 @@ struct LooseLaunch {
     const ginsim_loose_cons_params* cons;       // the family blocks, checked: NULL when absent or degenerate (cons_m == 0,
     const ginsim_loose_mag_params* mag;         // mag_every == 0); launch_loose (ginsim_api.hip) picks the family from them
     const ginsim_loose_scale_params* scale;
+    const ginsim_loose_still_params* still;     // NULL when absent or degenerate (still_mask == 0)
     char* name; size_t cap;                     // name != NULL: report the kernel's name into name[cap], do not launch
     const int64_t* stamp;                       // DEVICE copies of b->gps_stamp, b->gps_visible and cons->cons_sample
     const int32_t* visible;
@@ -47,12 +48,13 @@ struct LooseLaunch {
 };
 
 // ins_loose.hip, ins_loose_aided.hip (b->aid_mask != 0), ins_loose_cons.hip (cons), ins_loose_mag.hip (mag), ins_loose_scale.hip
-// (scale; b->aid_mask has bit 0): each chooses its <RF, flag> and launches, or names, one instantiation of its kernel
+// (scale; b->aid_mask has bit 0), ins_loose_still.hip (still): each chooses its <RF, flag> and launches, or names, one instantiation of its kernel
 hipError_t launch_loose_plain(const LooseLaunch& L);
 hipError_t launch_loose_aided(const LooseLaunch& L);
 hipError_t launch_loose_cons(const LooseLaunch& L);
 hipError_t launch_loose_mag(const LooseLaunch& L);
 hipError_t launch_loose_scale(const LooseLaunch& L);
+hipError_t launch_loose_still(const LooseLaunch& L);
 int loose_variant(const ginsim_mc_params& p);
 
 // aux_sensors.hip

@@ -10,7 +10,9 @@ The checkout's own stub (demo_algorithms.ins_loose) stays hosted.  fp64 only.
     InsLoose(ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None,
              odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None,
              mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None,
-             odo_scale_state=False, odo_scale0=1.0, odo_scale_p0=0.02, odo_scale_q=0.0)
+             odo_scale_state=False, odo_scale0=1.0, odo_scale_p0=0.02, odo_scale_q=0.0,
+             zupt=False, zaru=False, still_every=1, still_speed=0.01, still_rate=2e-4, zupt_std=0.02, zaru_std=None,
+             standstill=None)
 
 ini_pos_vel_att: the initial states FreeIntegration takes ((9|10,) or (9|10, k)); None under a Sim: the motion definition's.
 imu: the IMU model the filter is tuned to (its accel_err, gyro_err, gps_err); None under a Sim: the Sim's own.  ref_frame is the
@@ -35,6 +37,14 @@ odo_scale_state=True (needs odo=True) makes the scale factor the filter's 16th s
 estimate starts at odo_scale0 with the 1 sigma odo_scale_p0, is learnt while GPS is visible and used through an outage;
 odo_scale_q [1/sqrt(s)] lets it wander (default 0: a constant).  ``output`` gains a trailing 'odo_scale', the estimate at every
 sample.  odo_scale= belongs to the filter without the state and is an error with it; not together with mag=True.
+
+Standstill (csrc/ins_loose_still.hip; as NumPy in tests/ins_loose_still_ref.py): zupt=True tells the filter that
+the velocity is zero, zaru=True that the gyroscope reads its own bias (plus the earth rate the mechanisation assumes), at every
+still_every-th IMU sample that the standstill signal marks.  The signal is standstill= (n,), one flag per IMU sample (a vehicle's
+own signal), or, under a Sim, the Sim's truth: |velocity| <= still_speed [m/s] and |angular rate| <= still_rate [rad/s].  ``run`` on
+a logged series has no truth and needs standstill=.  zupt_std [m/s], zaru_std [rad/s, per axis or one number]: the 1 sigma of the
+two pseudo-measurements (zaru_std default: the per-sample gyro noise of the filter's own model).  ``input`` and ``output`` are
+unchanged.  Not together with mag=True or odo_scale_state=True.
 """
 import numpy as np
 
@@ -50,8 +60,20 @@ class InsLoose(object):
     def __init__(self, ini_pos_vel_att=None, earth_rot=True, ref_frame=None, imu=None, q_scale=1.0, p0=None,
                  odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None,
                  mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None,
-                 odo_scale_state=False, odo_scale0=1.0, odo_scale_p0=0.02, odo_scale_q=0.0):
+                 odo_scale_state=False, odo_scale0=1.0, odo_scale_p0=0.02, odo_scale_q=0.0,
+                 zupt=False, zaru=False, still_every=1, still_speed=0.01, still_rate=2e-4, zupt_std=0.02, zaru_std=None, standstill=None):
         self.odo, self.nhc, self.mag = bool(odo), bool(nhc), bool(mag)
+        self.zupt, self.zaru = bool(zupt), bool(zaru)
+        self.still = {'zupt': self.zupt, 'zaru': self.zaru, 'every': still_every, 'speed': still_speed, 'rate': still_rate,
+                      'zupt_std': zupt_std, 'zaru_std': zaru_std}
+        self.standstill = None if standstill is None else np.ascontiguousarray(np.asarray(standstill).reshape(-1) != 0, dtype=np.int32)
+        if self.zupt or self.zaru:
+            if self.mag:
+                raise ValueError('zupt / zaru together with mag=True is not built')
+            if odo_scale_state:
+                raise ValueError('zupt / zaru together with odo_scale_state=True is not built')
+            from ginsim.ins_loose import still_model
+            still_model({'q_psi': np.ones(3)}, 1.0, self.still)         # the errors of the numbers
         self.odo_scale_state = bool(odo_scale_state)
         if self.odo_scale_state:
             if not self.odo:
@@ -124,6 +146,13 @@ class InsLoose(object):
             return None
         return {'scale0': self.odo_scale0, 'p0': self.odo_scale_p0, 'q': self.odo_scale_q}
 
+    def still_options(self):
+        """The standstill options ginsim.InsLooseJob takes (ginsim.ins_loose.still_model), or None without zupt and zaru; 'flags' is
+        the plugin's standstill= (None: the job derives the signal from its truth)."""
+        if not (self.zupt or self.zaru):
+            return None
+        return dict(self.still, flags=self.standstill)
+
     def finish(self, pos, vel, att, wb, ab, odo_scale=None):
         """State the plugin holds after a run: the last run's series, each (n, 3), in the order of `output`; with
         odo_scale_state the estimate's series (n,) the last."""
@@ -133,13 +162,17 @@ class InsLoose(object):
         '''
         set_of_input: [fs, gyro (n, 3), accel (n, 3), time (n,), gps_time (m,), gps (m, 6 | 7)], as the reference's run; a seventh
         gps column is the visibility; with InsLoose(odo=True) a seventh element, odo (n,); with InsLoose(mag=True) the next
-        element, mag (n, 3), and geo_mag_n= on the plugin.  Needs InsLoose(ini_pos_vel_att=..., ref_frame=..., imu=...).
+        element, mag (n, 3), and geo_mag_n= on the plugin.  Needs InsLoose(ini_pos_vel_att=..., ref_frame=..., imu=...), and with
+        zupt / zaru InsLoose(standstill=...) (n,).
         '''
         import ginsim
         from ginsim.ins_loose import InsLooseJob
         if self.ini is None or self.ref_frame not in (0, 1) or self.imu is None:
             raise ValueError('InsLoose.run on a logged series needs InsLoose(ini_pos_vel_att=..., ref_frame=0 | 1, imu=...): '
                              'there is no Sim to take them from')
+        if (self.zupt or self.zaru) and self.standstill is None:
+            raise ValueError('InsLoose(zupt / zaru).run on a logged series needs InsLoose(standstill=flags (n,)): there is no truth to '
+                             'derive the standstill signal from')
         fs = float(np.asarray(set_of_input[0]).reshape(-1)[0])
         gyro = np.ascontiguousarray(np.asarray(set_of_input[1], dtype=np.float64))
         accel = np.ascontiguousarray(np.asarray(set_of_input[2], dtype=np.float64))
@@ -183,7 +216,7 @@ class InsLoose(object):
             job = InsLooseJob(ctx, fs, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, self.imu.gps_err, self.ini, 1,
                               ini_first=self.run_times, earth_rot=self.earth_rot, given=bufs, q_scale=self.q_scale, p0=self.p0,
                               keep_traj=True, odo_err=getattr(self.imu, 'odo_err', None), aid=self.aid(),
-                              **self._mag_arguments(), **self._scale_arguments()).run()
+                              **self._mag_arguments(), **self._scale_arguments(), **self._still_arguments()).run()
             self.finish(*[job.series(k, [0])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab') + (('odo_scale',) if self.odo_scale_state else ())])
         finally:
             if job is not None:
@@ -194,6 +227,9 @@ class InsLoose(object):
 
     def _mag_arguments(self):
         return {} if not self.mag else {'mag_err': getattr(self.imu, 'mag_err', None), 'geo_mag_n': self.geo_mag_n, 'mag': self.mag_options()}
+
+    def _still_arguments(self):
+        return {} if not (self.zupt or self.zaru) else {'still': self.still_options()}
 
     def _scale_arguments(self):
         return {} if not self.odo_scale_state else {'odo_scale_state': self.scale_options(), 'keep_scale': True}

@@ -8,4 +8,4 @@ from .engine import (Context, DeviceBuffer, MonteCarloJob, AuxSensorJob, StatsRe
                      sensor_model, ini_table, free_integration_host, rng_normals, normal_transform, default_context, allan_var, allan_var_host)
 from .inclinometer import InclinometerJob  # noqa: F401,E402
 from .magcal import MagCalJob  # noqa: F401,E402
-from .ins_loose import InsLooseJob, filter_model, aiding_model, mag_model, scale_model  # noqa: F401,E402
+from .ins_loose import InsLooseJob, filter_model, aiding_model, mag_model, scale_model, still_model, standstill_flags  # noqa: F401,E402

@@ -123,6 +123,12 @@ class LooseScaleParams(C.Structure):
                 ('out_scale_end', C.c_void_p), ('out_pcross_end', C.c_void_p)]
 
 
+class LooseStillParams(C.Structure):
+    """ginsim_loose_still_params: the standstill block (ZUPT / ZARU) of a filter launch (csrc/ins_loose_still.hip)."""
+    _fields_ = [('still_mask', C.c_int32), ('reserved', C.c_int32), ('still_every', C.c_int64), ('still_flags', C.c_void_p),
+                ('r_zupt', C.c_double), ('r_zaru', C.c_double * 3)]
+
+
 class PathgenParams(C.Structure):
     _fields_ = [('ini_pva', C.c_double * 9), ('mobility', C.c_double * 3), ('fs', C.c_double),
                 ('fs_gps', C.c_double), ('ref_frame', C.c_int32), ('enable_gps', C.c_int32),
@@ -201,6 +207,9 @@ _SIGS = {
                                                C.c_size_t]),
     'ginsim_loose_scale_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseScaleParams)]),
     'ginsim_loose_scale_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseScaleParams), C.c_char_p,
+                                                 C.c_size_t]),
+    'ginsim_loose_still_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseStillParams)]),
+    'ginsim_loose_still_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseStillParams), C.c_char_p,
                                                  C.c_size_t]),
     'ginsim_end_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     'ginsim_end_stats_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

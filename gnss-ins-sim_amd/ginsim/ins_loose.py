@@ -9,6 +9,8 @@ filter's covariance and its actual error at those samples (csrc/ins_loose_cons.h
 tests/ins_loose_cons_ref.py).  With mag=... the filter also uses the magnetometer, a three-row block on the attitude error
 (csrc/ins_loose_mag.hip, mag_model; restated by tests/ins_loose_mag_ref.py).  With odo_scale_state=... the odometer's scale factor is
 a 16th state that the filter estimates (csrc/ins_loose_scale.hip, scale_model; restated by tests/ins_loose_scale_ref.py).
+With still=... the filter also uses what it may assume while the vehicle stands still, the zero-velocity and the zero-angular-rate
+update (csrc/ins_loose_still.hip, still_model, standstill_flags; restated by tests/ins_loose_still_ref.py).
 What one launch does not combine is stated once (refuse_combinations); the job records the family it launches once (FAMILIES).
 """
 import ctypes as C
@@ -200,13 +202,74 @@ def scale_model(odo_err, opts, fs=None):
     return {'scale0': scale0, 'p0_scale': p0, 'q_k': q * q / float(fs) if q > 0.0 else 0.0}
 
 
+STILL_KEYS = ('zupt', 'zaru', 'every', 'speed', 'rate', 'zupt_std', 'zaru_std', 'flags')
+
+
+def still_model(model, fs, still=None):
+    """The numbers of ginsim_loose_still_params that describe the FILTER, {'still_mask', 'still_every', 'r_zupt', 'r_zaru'}, and the
+    two thresholds of standstill_flags, {'speed', 'rate'}, from the filter's model (filter_model: 'q_psi' is read), the sample rate
+    and the options still = {'zupt': bool, 'zaru': bool, 'every': int, 'speed': float, 'rate': float, 'zupt_std': float,
+    'zaru_std': 3 floats | float, 'flags': (n,)}:
+
+      still_mask   bit 0 'zupt' (z = vel, on dv), bit 1 'zaru' (z = bg_est + w_rest - gyro, on dbg); default both
+      still_every  'every': a block is possible every so many IMU samples; default 1
+      speed, rate  the standstill signal of standstill_flags: |ref_vel| <= speed [m/s] and |ref_gyro| <= rate [rad/s]; defaults
+                   0.01 and 2e-4.  Not read when 'flags' gives the signal (the job reads 'flags', not this function)
+      r_zupt       'zupt_std'^2 [m/s]; default 0.02: twice the largest true speed the default flags admit
+      r_zaru       'zaru_std'^2 [rad/s] per body axis; default sqrt(q_psi) fs: the per-sample rate noise the filter already believes in
+    still None: no block (None is returned); {} or True takes every default."""
+    if still is None or still is False:
+        return None
+    still = {} if still is True else dict(still)
+    unknown = set(still) - set(STILL_KEYS)
+    if unknown:
+        raise ValueError('still: unknown keys %s' % sorted(unknown))
+    zupt, zaru = bool(still.get('zupt', True)), bool(still.get('zaru', True))
+    every = still.get('every', 1)
+    if int(every) != every or int(every) < 1:
+        raise ValueError("still['every'] must be an integer >= 1")
+
+    def positive(name, v, size=1, zero=False):
+        v = np.asarray(v, dtype=np.float64).reshape(-1)
+        v = v * np.ones(size) if v.size == 1 else v
+        if v.size != size or not np.all(np.isfinite(v)) or not np.all(v >= 0.0 if zero else v > 0.0):
+            raise ValueError('still[%r] must be %s%s and finite' % (name, '%d numbers, ' % size if size > 1 else '',
+                                                                   'not negative' if zero else 'positive'))
+        return v
+    speed, rate = positive('speed', still.get('speed', 0.01), zero=True)[0], positive('rate', still.get('rate', 2e-4), zero=True)[0]
+    out = {'still_mask': (1 if zupt else 0) | (2 if zaru else 0), 'still_every': int(every), 'speed': float(speed), 'rate': float(rate),
+           'r_zupt': 0.0, 'r_zaru': np.zeros(3)}
+    if zupt:
+        out['r_zupt'] = float(positive('zupt_std', still.get('zupt_std', 0.02))[0]) ** 2
+    if zaru:
+        std = still.get('zaru_std')
+        if std is None:
+            std = np.sqrt(np.asarray(model['q_psi'], dtype=np.float64) * np.ones(3)) * float(fs)
+        out['r_zaru'] = positive('zaru_std', std, 3) ** 2
+    return out
+
+
+def standstill_flags(truth, speed=0.01, rate=2e-4):
+    """(n,) int32: flag[j] = |ref_vel[j]| <= speed and |ref_gyro[j]| <= rate, from the truth's 'ref_vel' and 'ref_gyro' (n, 3): the
+    standstill signal a vehicle would supply, one per IMU sample for all runs.  A detector on each run's own noisy sensors would
+    differ from lane to lane and is not built."""
+    speed, rate = float(speed), float(rate)
+    if not (speed >= 0.0 and np.isfinite(speed) and rate >= 0.0 and np.isfinite(rate)):
+        raise ValueError('standstill_flags: speed and rate must be finite and not negative')
+    vel, gyro = np.asarray(truth['ref_vel'], dtype=np.float64), np.asarray(truth['ref_gyro'], dtype=np.float64)
+    if vel.ndim != 2 or vel.shape[1] != 3 or gyro.shape != vel.shape:
+        raise ValueError("standstill_flags: truth['ref_vel'] and truth['ref_gyro'] must be (n, 3)")
+    return np.ascontiguousarray((np.linalg.norm(vel, axis=1) <= speed) & (np.linalg.norm(gyro, axis=1) <= rate), dtype=np.int32)
+
+
 # the family blocks a job can hold, in the order the C glue picks among them: (the job's attribute, the entry points' suffix)
-FAMILIES = (('cons', '_cons'), ('magp', '_mag'), ('scalep', '_scale'))
+FAMILIES = (('cons', '_cons'), ('magp', '_mag'), ('scalep', '_scale'), ('stillp', '_still'))
 
 
-def refuse_combinations(scale, keep_scale, odo, mag, cons, proc):
+def refuse_combinations(scale, keep_scale, odo, mag, cons, proc, still=False):
     """The options of InsLooseJob that one launch does not combine, stated once: (applies, message), the first row that applies is
-    raised.  Arguments: is the option given (scale: odo_scale_state, odo: aid['odo'], cons: cons_samples, proc: proc_first)."""
+    raised.  Arguments: is the option given (scale: odo_scale_state, odo: aid['odo'], cons: cons_samples, proc: proc_first,
+    still: still)."""
     rows = (
         (keep_scale and not scale, 'keep_scale: the scale-factor series exists with odo_scale_state=... only'),
         (scale and mag, 'odo_scale_state: the scale-factor state together with the magnetometer block (mag=...) is not built'),
@@ -214,6 +277,9 @@ def refuse_combinations(scale, keep_scale, odo, mag, cons, proc):
         (scale and not odo, "odo_scale_state: a scale-factor state without the odometer (aid['odo']) is refused"),
         (mag and cons, 'cons_samples: consistency checkpoints of the magnetometer-aided filter are not built (mag=...)'),
         (cons and proc, 'cons_samples: online process statistics (proc_first) and checkpoints in one launch are refused'),
+        (still and mag, 'still: the standstill block together with the magnetometer block (mag=...) is not built'),
+        (still and cons, 'still: consistency checkpoints (cons_samples=...) of the filter with the standstill block are not built'),
+        (still and scale, 'still: the standstill block together with the scale-factor state (odo_scale_state=...) is not built'),
     )
     for applies, text in rows:
         if applies:
@@ -246,6 +312,10 @@ class InsLooseJob(BatchJob):
     16th state (csrc/ins_loose_scale.hip).  Needs aid['odo']; aid['scale'] is then not read (the filter starts from 'scale0'), and
     r_odo defaults to (odo_err['stdv'] / scale0)^2.  Not together with mag, cons_samples or fp32.  keep_scale: materialise the
     k_est series ([n][runs]; series('odo_scale', ...)).
+    still: None, or the options of still_model() ({} takes every default): the zero-velocity and the zero-angular-rate update at the
+    samples the standstill signal marks (csrc/ins_loose_still.hip).  The signal is still['flags'] (n,), or standstill_flags() of the
+    truth with still['speed'] and still['rate']; it is the job's own device array in the generated and in the given form (nothing
+    is read from `given`).  Not together with mag, cons_samples or odo_scale_state.
     """
 
     algos = ('loose',)
@@ -253,7 +323,7 @@ class InsLooseJob(BatchJob):
     def __init__(self, ctx, fs, ref_frame, truth, accel_err, gyro_err, gps_err, ini, runs, seed=0, run_offset=0, ini_first=0,
                  earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
                  end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None,
-                 cons_samples=None, mag_err=None, geo_mag_n=None, mag=None, odo_scale_state=None, keep_scale=False):
+                 cons_samples=None, mag_err=None, geo_mag_n=None, mag=None, odo_scale_state=None, keep_scale=False, still=None):
         self.ctx, self._bufs = ctx, {}
         self.keep_traj, self.keep_scale = bool(keep_traj), bool(keep_scale)
         self.proc_first, self.proc_ned, self.end_ned = proc_first, bool(proc_ned), bool(end_ned)
@@ -261,11 +331,13 @@ class InsLooseJob(BatchJob):
                                                 gps_stamps)
         self.model = model if model is not None else filter_model(fs, accel_err, gyro_err, gps_err, q_scale, p0)
         self.scale = scale_model(odo_err, odo_scale_state, fs)
+        self.still = still_model(self.model, fs, still)
         refuse_combinations(scale=self.scale is not None, keep_scale=self.keep_scale, odo=bool(aid and aid.get('odo')),
-                            mag=mag is not None, cons=cons_samples is not None, proc=proc_first is not None)
+                            mag=mag is not None, cons=cons_samples is not None, proc=proc_first is not None, still=self.still is not None)
         for k in ('r_diag', 'p0', 'q_v', 'q_psi', 'q_bg', 'q_ba', 'decay_g', 'decay_a'):     # the filter numbers
             getattr(self.params, k)[:] = [float(x) for x in np.asarray(self.model[k], dtype=np.float64).reshape(-1)]
         self._family_blocks(ref_frame, odo_err, aid, mag_err, geo_mag_n, mag)
+        self._standstill(truth, still)
         self._inputs(table, ref_gps, truth, fs, accel_err, gyro_err, gps_err, odo_err, mag_err, vib_accel, vib_gyro, given)
         self._outputs(placed)
         self._checkpoints(cons_samples)
@@ -321,6 +393,25 @@ class InsLooseJob(BatchJob):
             g.mag_every = self.mag['mag_every']
             for k in ('mag_n', 'cal_si', 'cal_hi', 'r_mag'):
                 getattr(g, k)[:] = [float(x) for x in np.asarray(self.mag[k], dtype=np.float64).reshape(-1)]
+
+    def _standstill(self, truth, still):
+        """The standstill block (still, stillp) and the device copy of its signal: the caller's still['flags'] or standstill_flags()
+        of the truth."""
+        self.stillp = self.still_flags = None
+        if self.still is None:
+            return
+        flags = None if still is True else dict(still).get('flags')
+        if flags is None:
+            flags = standstill_flags(truth, self.still['speed'], self.still['rate'])
+        flags = np.asarray(flags)
+        if flags.shape != (self.n,):
+            raise ValueError("still['flags'] must be (n,): one standstill signal per IMU sample")
+        self.still_flags = np.ascontiguousarray(flags != 0, dtype=np.int32)
+        self._bufs['still_flags'] = self.ctx.upload(self.still_flags)
+        g = self.stillp = _lib.LooseStillParams()
+        g.still_mask, g.still_every, g.r_zupt = self.still['still_mask'], self.still['still_every'], self.still['r_zupt']
+        g.r_zaru[:] = [float(x) for x in self.still['r_zaru']]
+        g.still_flags = self._bufs['still_flags'].ptr
 
     def _inputs(self, table, ref_gps, truth, fs, accel_err, gyro_err, gps_err, odo_err, mag_err, vib_accel, vib_gyro, given):
         """Where the lanes take their samples from, and the one upload of what they read: the initial-state table and, in the generated
@@ -427,7 +518,7 @@ class InsLooseJob(BatchJob):
 
     # ------------------------------------------------------------------ launches
     def _entry(self, what, *head):
-        """The family's entry point ginsim_loose[_cons | _mag | _scale]_<what> and its arguments: head, the two base blocks, the
+        """The family's entry point ginsim_loose[_cons | _mag | _scale | _still]_<what> and its arguments: head, the two base blocks, the
         family's block."""
         suffix, block = self._family
         args = head + (C.byref(self.mc), C.byref(self.params)) + (() if block is None else (C.byref(block),))

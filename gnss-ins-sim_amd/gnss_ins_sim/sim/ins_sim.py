@@ -466,13 +466,19 @@ class _Jobs(object):
                            seed=self.seed, run_offset=self.first + off, ini_first=kw.pop('ini_first', algo.run_times + self.first + off),
                            earth_rot=algo.earth_rot, keep_traj=keep, placed=sim.placed,
                            model=filter_model(sim.fs[0], tuned.accel_err, tuned.gyro_err, tuned.gps_err, algo.q_scale, algo.p0),
-                           **self._aiding(algo), **self._mag_aiding(algo, truth), **self._scale_state(algo, keep), **self.vib, **kw)
+                           **self._aiding(algo), **self._mag_aiding(algo, truth), **self._scale_state(algo, keep), **self._standstill(algo), **self.vib, **kw)
 
     def _aiding(self, algo):
         """The aiding arguments of an InsLooseJob: none for a plugin without aiding.  The odometer SAMPLES are the Sim's
         (truth['ref_odo'] and the IMU's odo_err, as the fused job makes them); what the filter assumes of them is the plugin's."""
         aid = algo.aid() if hasattr(algo, 'aid') else None
         return {} if aid is None else {'odo_err': self.sim.imu.odo_err if self.sim.imu.odo else None, 'aid': aid}
+
+    def _standstill(self, algo):
+        """The standstill arguments of an InsLooseJob: none for a plugin without zupt and zaru.  The signal is the plugin's
+        standstill= where it has one; else the job derives it from the Sim's truth."""
+        opts = algo.still_options() if hasattr(algo, 'still_options') else None
+        return {} if opts is None else {'still': opts}
 
     def _scale_state(self, algo, keep):
         """The scale-factor arguments of an InsLooseJob: none for a plugin without the state; the estimate's series is kept where the
@@ -1312,6 +1318,9 @@ class Sim(object):
             if getattr(job, 'scale', None) is not None:
                 raise NotImplementedError('consistency_curve: %s estimates the odometer\'s scale factor (InsLoose(odo_scale_state=True)), '
                                           'and the consistency checkpoints of that filter are not built' % a)
+            if getattr(job, 'still', None) is not None:
+                raise NotImplementedError('consistency_curve: %s is aided at standstill (InsLoose(zupt=True) / InsLoose(zaru=True)), and '
+                                          'the consistency checkpoints of that filter are not built' % a)
         for a in names:
             c = mc.consistency(a, samples)
             out[a] = {'count': c.count, 'sigma': c.sigma, 'rms': c.rms, 'ratio': c.ratio, 'nees': c.nees}

@@ -483,6 +483,35 @@ int ginsim_loose_scale_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const gi
 int ginsim_loose_scale_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_scale_params* scale,
                                    char* buf, size_t cap);
 
+/* ---- standstill aiding of the filter (csrc/ins_loose_still.hip): what the filter may assume while the vehicle
+ *      stands still.  Added without a change of GINSIM_ABI_VERSION and as a block of its own: ginsim_loose_params and
+ *      ginsim_loose_run are exactly what they were.  With x = estimate - truth every row observes one state, H = e_I:
+ *        bit 0, the zero-velocity update, I = 3, 4, 5:     z_i = vel_i (the mechanised velocity, the coordinates of dv), R = r_zupt
+ *        bit 1, the zero-angular-rate update, I = 9, 10, 11: z_i = bg_est_i + w_rest_i - gyro_i, R = r_zaru[i]; gyro is the RAW
+ *               sample j - 1 (the last one the lane integrated), w_rest the rate the mechanisation assumes of a body at rest:
+ *               C_est^T (W cos lat, 0, -W sin lat) in ref_frame 0 with earth_rot, zero otherwise.  The dependence of w_rest on
+ *               psi (about 7e-5 psi) is neglected in H, as earth rate is neglected in F.
+ *      One block runs the selected rows in ascending state order from x = 0 (every z from the state before the first row) and
+ *      ends with the feedback of a GPS fix.  It runs at every IMU sample j > 0 with j % still_every == 0 and still_flags[j] != 0
+ *      on the state that sample's row reports: after a fix and after an odometer / non-holonomic block of the same sample, before
+ *      the row is stored.  aid_mask of the loose block may be 0 or not. */
+typedef struct {
+    int32_t  still_mask;     /* 0: none -- the call is ginsim_loose_run (nothing else is read); bit 0 ZUPT, bit 1 ZARU */
+    int32_t  reserved;
+    int64_t  still_every;    /* >= 1: a block is possible every still_every samples (n or more: never) */
+    const int32_t* still_flags;  /* device [n]: the standstill signal per IMU sample, the same for every run */
+    double   r_zupt;         /* (m/s)^2; finite, > 0 with bit 0 */
+    double   r_zaru[3];      /* (rad/s)^2 per body axis; finite, > 0 with bit 1 */
+} ginsim_loose_still_params;
+
+/* ginsim_loose_run with the standstill block: launches loose_still_kernel.  Everything ginsim_loose_run refuses is refused (fp32
+ * among it), and: a still_mask outside 0 .. 3; with still_mask != 0 still_every < 1, an r_zupt / r_zaru that is not positive and
+ * finite where its bit is set, still_flags NULL. */
+int ginsim_loose_still_run(ginsim_ctx* ctx, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_still_params* still);
+/* the NAME of the kernel it launches (e.g. "ginsim::loose_still_kernel<1, false, false, false>" = RF, GIVEN, VIB, PS) */
+int ginsim_loose_still_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_still_params* still,
+                                   char* buf, size_t cap);
+
 /* ---- auxiliary sensors of a Monte-Carlo batch: pathgen.gps_gen (pathgen.py:596-625) and pathgen.mag_gen (:643-661).
  *      FreeIntegration does not consume them, so they are generated only when they are to be kept. */
 typedef struct {
