@@ -177,6 +177,8 @@ struct CovT {
         update_row_impl<true>(h, hl, z, rv, x);
     }
     // the same with the row h on the psi states 6-8 only (the magnetometer rows): three products per element of Ph
+    // (not update_row_impl with another first column and width: under -ffp-contract=on the one expression below rounds the
+    // product with h[1] and fuses the other two, the loop there rounds the product with h[0]; the kernel's bits would move)
     __device__ __forceinline__ void update_row_psi(const double (&h)[3], double z, double rv, double (&x)[NS]) {
         double ph[NS];
 #pragma unroll
@@ -213,37 +215,24 @@ __device__ __forceinline__ loose_ptr loose_params() {
     return (loose_ptr)(p + sizeof(ginsim_mc_params));
 }
 
-// loose_mag_kernel's fifth argument, the magnetometer block by value: it follows the two parameter blocks and the two pointers
-// (stamp, visible) in the kernarg segment
+// The fifth argument of loose_mag_kernel, loose_scale_kernel and loose_still_kernel, the family's block T by value: it follows the
+// two parameter blocks and the two pointers (stamp, visible) in the kernarg segment
+template <class T>
+__device__ __forceinline__ const T __attribute__((address_space(4))) * loose_tail_params() {
+    static_assert(sizeof(ginsim_mc_params) % 8 == 0 && sizeof(ginsim_loose_params) % 8 == 0 && alignof(T) == 8,
+                  "the kernarg offsets of loose_params() / loose_tail_params()");
+    typedef const char __attribute__((address_space(4))) * bytes_ptr;
+    bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (const T __attribute__((address_space(4))) *)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
+}
 typedef const ginsim_loose_mag_params __attribute__((address_space(4))) * loose_mag_ptr;
-static_assert(sizeof(ginsim_mc_params) % 8 == 0 && sizeof(ginsim_loose_params) % 8 == 0 && alignof(ginsim_loose_mag_params) == 8,
-              "the kernarg offsets of loose_params() / loose_mag_params()");
-__device__ __forceinline__ loose_mag_ptr loose_mag_params() {
-    typedef const char __attribute__((address_space(4))) * bytes_ptr;
-    bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return (loose_mag_ptr)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
-}
-
-// loose_scale_kernel's fifth argument, the scale-factor block by value, where loose_mag_kernel has the magnetometer block
 typedef const ginsim_loose_scale_params __attribute__((address_space(4))) * loose_scale_ptr;
-static_assert(alignof(ginsim_loose_scale_params) == 8, "the kernarg offset of loose_scale_params()");
-__device__ __forceinline__ loose_scale_ptr loose_scale_params() {
-    typedef const char __attribute__((address_space(4))) * bytes_ptr;
-    bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return (loose_scale_ptr)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
-}
-
-// loose_still_kernel's fifth argument, the standstill block by value, where loose_mag_kernel has the magnetometer block
 typedef const ginsim_loose_still_params __attribute__((address_space(4))) * loose_still_ptr;
-static_assert(alignof(ginsim_loose_still_params) == 8, "the kernarg offset of loose_still_params()");
-__device__ __forceinline__ loose_still_ptr loose_still_params() {
-    typedef const char __attribute__((address_space(4))) * bytes_ptr;
-    bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return (loose_still_ptr)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
-}
+__device__ __forceinline__ loose_mag_ptr loose_mag_params() { return loose_tail_params<ginsim_loose_mag_params>(); }
+__device__ __forceinline__ loose_scale_ptr loose_scale_params() { return loose_tail_params<ginsim_loose_scale_params>(); }
+__device__ __forceinline__ loose_still_ptr loose_still_params() { return loose_tail_params<ginsim_loose_still_params>(); }
+
 // the standstill signal of sample j (wave-uniform: a scalar load, as visible[kf])
 __device__ __forceinline__ bool still_flag(const int32_t* flags, int64_t j) {
     typedef const int32_t __attribute__((address_space(4))) * flags_ptr;

@@ -1,5 +1,5 @@
 // InsLoose aided by the odometer and the non-holonomic constraints of a land vehicle: loose_kernel's lane (ins_loose.hpp,
-// loose_body) with an aiding block.  DESIGN 4.11b; restated in NumPy by tests/ins_loose_aided_ref.py.
+// loose_body) with an aiding block.  DESIGN 4.11b; restated in NumPy by tests/ins_loose_ref.py.
 //
 // State order, x = estimate - truth and C_est = (I - [psi x]) C as in ins_loose.hip.  With D = C_est^T (navigation -> body) of the
 // reported attitude, v the reported navigation-frame velocity and v_b = D v, to first order v_b,est = v_b + D dv - D [v x] psi:

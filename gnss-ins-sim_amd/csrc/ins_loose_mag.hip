@@ -1,5 +1,5 @@
 // InsLoose aided by the magnetometer: loose_aided_kernel's lane (ins_loose.hpp, loose_body) with a three-row heading block.
-// DESIGN 4.11d; restated in NumPy by tests/ins_loose_mag_ref.py.
+// DESIGN 4.11d; restated in NumPy by tests/ins_loose_ref.py.
 //
 // State order, x = estimate - truth and C_est = (I - [psi x]) C as in ins_loose.hip.  With D = C_est^T (navigation -> body) of the
 // reported attitude, m_n the field the filter assumes in the navigation frame and the calibrated sample

@@ -1,5 +1,5 @@
 // InsLoose aided at standstill: loose_aided_kernel's lane (ins_loose.hpp, loose_body) with the zero-velocity update (ZUPT) and the
-// zero-angular-rate update (ZARU).  DESIGN 4.11g; restated in NumPy by tests/ins_loose_still_ref.py.
+// zero-angular-rate update (ZARU).  DESIGN 4.11g; restated in NumPy by tests/ins_loose_ref.py.
 //
 // State order, x = estimate - truth and C_est = (I - [psi x]) C as in ins_loose.hip.  Every row observes one state, H = e_I, and is
 // the scalar update of a GPS fix, Cov::update<I>(z, R, x):

@@ -20,13 +20,13 @@ Sim's under a Sim and needed by ``run`` on a logged series.
 q_scale multiplies the process noise; p0 = (sigma_r [m], sigma_v [m/s], sigma_psi [rad], sigma_bg [rad/s], sigma_ba [m/s^2]), the
 initial 1 sigma; default (1e-3, 1e-3, 1e-5, 1e-7, 1e-5), the two bias terms raised to the sensor's largest constant bias.
 
-The two aids of a land vehicle (csrc/ins_loose_aided.hip; as NumPy in tests/ins_loose_aided_ref.py):
+The two aids of a land vehicle (csrc/ins_loose_aided.hip; as NumPy in tests/ins_loose_ref.py):
 odo=True uses the odometer (``input`` gains a trailing 'odo'; the IMU model needs odo=True), nhc=True the non-holonomic constraints
 (no sideways and no vertical body velocity), both every odo_every IMU samples.  odo_std [m/s]: 1 sigma of the scaled odometer
 sample (default: the IMU model's odo_err['stdv'] / scale); nhc_std [m/s]: the constraints' pseudo-noise; odo_scale: the scale
 factor the filter assumes (default: the IMU model's odo_err['scale']).
 
-The magnetometer (csrc/ins_loose_mag.hip; as NumPy in tests/ins_loose_mag_ref.py): mag=True observes the attitude
+The magnetometer (csrc/ins_loose_mag.hip; as NumPy in tests/ins_loose_ref.py): mag=True observes the attitude
 error with the three axes of the calibrated magnetometer sample every mag_every IMU samples (``input`` gains a trailing 'mag', after
 'odo'; the IMU model needs axis=9).  mag_std [uT]: 1 sigma of the raw sample per axis; mag_si (3, 3), mag_hi (3,): the soft- and
 hard-iron calibration the filter assumes (defaults: the IMU model's mag_err; MagCal's result can be passed).  geo_mag_n [uT, NED]:
@@ -38,7 +38,7 @@ estimate starts at odo_scale0 with the 1 sigma odo_scale_p0, is learnt while GPS
 odo_scale_q [1/sqrt(s)] lets it wander (default 0: a constant).  ``output`` gains a trailing 'odo_scale', the estimate at every
 sample.  odo_scale= belongs to the filter without the state and is an error with it; not together with mag=True.
 
-Standstill (csrc/ins_loose_still.hip; as NumPy in tests/ins_loose_still_ref.py): zupt=True tells the filter that
+Standstill (csrc/ins_loose_still.hip; as NumPy in tests/ins_loose_ref.py): zupt=True tells the filter that
 the velocity is zero, zaru=True that the gyroscope reads its own bias (plus the earth rate the mechanisation assumes), at every
 still_every-th IMU sample that the standstill signal marks.  The signal is standstill= (n,), one flag per IMU sample (a vehicle's
 own signal), or, under a Sim, the Sim's truth: |velocity| <= still_speed [m/s] and |angular rate| <= still_rate [rad/s].  ``run`` on

@@ -4,13 +4,13 @@ ginsim_loose_run).  One launch: every lane makes its own IMU samples and GPS fix
 MonteCarloJob and AuxSensorJob would store), mechanises them with the free-integration step on bias-corrected samples and runs a
 15-state closed-loop error-state filter next to it.  tests/ins_loose_ref.py restates the arithmetic in NumPy.
 With aid=... the filter also uses the odometer and the non-holonomic constraints of a land vehicle (csrc/ins_loose_aided.hip,
-aiding_model; restated by tests/ins_loose_aided_ref.py).  With cons_samples=... the launch also reduces, across its runs, the
+aiding_model; restated by tests/ins_loose_ref.py).  With cons_samples=... the launch also reduces, across its runs, the
 filter's covariance and its actual error at those samples (csrc/ins_loose_cons.hip, consistency(); restated by
 tests/ins_loose_cons_ref.py).  With mag=... the filter also uses the magnetometer, a three-row block on the attitude error
-(csrc/ins_loose_mag.hip, mag_model; restated by tests/ins_loose_mag_ref.py).  With odo_scale_state=... the odometer's scale factor is
+(csrc/ins_loose_mag.hip, mag_model; restated by tests/ins_loose_ref.py).  With odo_scale_state=... the odometer's scale factor is
 a 16th state that the filter estimates (csrc/ins_loose_scale.hip, scale_model; restated by tests/ins_loose_scale_ref.py).
 With still=... the filter also uses what it may assume while the vehicle stands still, the zero-velocity and the zero-angular-rate
-update (csrc/ins_loose_still.hip, still_model, standstill_flags; restated by tests/ins_loose_still_ref.py).
+update (csrc/ins_loose_still.hip, still_model, standstill_flags; restated by tests/ins_loose_ref.py).
 What one launch does not combine is stated once (refuse_combinations); the job records the family it launches once (FAMILIES).
 """
 import ctypes as C

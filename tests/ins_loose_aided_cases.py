@@ -1,6 +1,6 @@
 """Shared inputs of the aided-InsLoose tests (tests/test_ins_loose_aided_oracle.py on the CPU, tests/test_gpu_ins_loose_aided.py on the
-device): the outage profile's truth with the odometer's, the odometer model, the restatement's own rounding error as the parity bound,
-and the constants the CPU test measures and the device test is held to."""
+device): the outage profile's truth with the odometer's, the odometer model, and the constants the CPU test measures and
+the device test is held to."""
 import functools
 
 import numpy as np
@@ -59,20 +59,3 @@ def aid(mask, every=1, odo_err=ODO_ERR, nhc_std=NHC_STD, **kw):
 def aid_options(mask, every=1, nhc_std=NHC_STD, **kw):
     """The same as the `aid` dict InsLooseJob takes."""
     return dict({'odo': bool(mask & 1), 'nhc': bool(mask & 6), 'every': every, 'nhc_std': nhc_std}, **kw)
-
-
-def restatement_error(ref_frame, fs, gyro, accel, ini, model, gps, stamps, visible, odo, aid_numbers, max_runs=8):
-    """The float64 aided restatement against its np.longdouble evaluation on the first max_runs runs of a case, in the metrics of
-    ins_loose_cases.deviation."""
-    import ins_loose_aided_ref as aref
-    k = min(max_runs, gyro.shape[0])
-    ini = np.asarray(ini)
-    ini = ini[:, :k] if ini.ndim == 2 else ini
-    args = (ref_frame, fs, gyro[:k], accel[:k], ini, model, None if gps is None else gps[:k], stamps, visible)
-    kw = dict(odo=None if odo is None else odo[:k], aid=aid_numbers)
-    return cs.deviation(aref.run(*args, **kw), aref.run(*args, dtype=np.longdouble, **kw))
-
-
-def parity_bound(*args, **kw):
-    """ins_loose_cases.PARITY_MARGIN (16) x restatement_error: what the device may deviate from the restatement, per quantity."""
-    return {k: cs.PARITY_MARGIN * v for k, v in restatement_error(*args, **kw).items()}

@@ -84,16 +84,20 @@ def deviation(a, b):
     return out
 
 
-def restatement_error(ref_frame, fs, gyro, accel, ini, model, gps, stamps, visible, max_runs=8):
+def restatement_error(ref_frame, fs, gyro, accel, ini, model, gps, stamps, visible, max_runs=8, run=None, deviation=deviation, **blocks):
     """The float64 restatement against its np.longdouble evaluation on the first max_runs runs of a case: {quantity: deviation}.
-    The device is allowed PARITY_MARGIN times this (parity_bound)."""
+    The device is allowed PARITY_MARGIN times this (parity_bound).  blocks: the optional blocks' keyword arguments of run
+    (default ins_loose_ref.run): aid, still, flags, mag_model, scale as they are, the per-run series odo and mag cut to the same runs."""
     import ins_loose_ref as ref
     k = min(max_runs, gyro.shape[0])
     ini = np.asarray(ini)
     ini = ini[:, :k] if ini.ndim == 2 else ini
     args = (ref_frame, fs, gyro[:k], accel[:k], ini, model, None if gps is None else gps[:k], stamps, visible)
-    return deviation(ref.run(*args), ref.run(*args, dtype=np.longdouble))
+    kw = {key: v[:k] if key in ('odo', 'mag') and v is not None else v for key, v in blocks.items()}
+    run = run or ref.run
+    return deviation(run(*args, **kw), run(*args, dtype=np.longdouble, **kw))
 
 
 def parity_bound(*args, **kw):
+    """PARITY_MARGIN (16) x restatement_error: what the device may deviate from the restatement, per quantity."""
     return {k: PARITY_MARGIN * v for k, v in restatement_error(*args, **kw).items()}

@@ -1,5 +1,5 @@
-"""NumPy restatement of InsLoose's consistency checkpoints (csrc/ins_loose_cons.hip) on top of tests/ins_loose_ref.py
-and tests/ins_loose_aided_ref.py (imported, not edited): the specification by example of the record ginsim_loose_cons_run reduces.
+"""NumPy restatement of InsLoose's consistency checkpoints (csrc/ins_loose_cons.hip) on top of tests/ins_loose_ref.py:
+the specification by example of the record ginsim_loose_cons_run reduces, taken through the hook of ins_loose_ref.run.
 
 A checkpoint is an IMU sample j of a list.  On the state that row j reports (after a GPS correction and an aiding block of the same
 sample, before the row is stored) every run forms
@@ -15,7 +15,6 @@ e_k^2 / P_kk, [34:37] the three block values, [37:43] reserved zeros.  The bias 
 Every array carries `dtype` (np.float64 or np.longdouble)."""
 import numpy as np
 
-import ins_loose_aided_ref as aref
 import ins_loose_ref as ref
 from oracle import ins_np
 
@@ -82,35 +81,29 @@ def record(f, t):
     return out
 
 
+class _Quiet(ref.LooseFilter):
+    """Runs the checkpoints exclude (a non-finite value) are inputs here: propagate() does not warn about them."""
+
+    def propagate(self, gyro, accel):
+        with np.errstate(all='ignore'):
+            super().propagate(gyro, accel)
+
+
 def run(ref_frame, fs, gyro, accel, ini, model, ref_nav, cons_samples, gps=None, stamps=(), visible=None, earth_rot=True,
         dtype=np.float64, odo=None, aid=None):
-    """ins_loose_aided_ref.run's loop, recording at the checkpoints.  ref_nav (n, 9) = att3, pos3, vel3 of the truth; cons_samples in
-    any order, repeats allowed.  Returns (len(cons_samples), RECORD) sums in `dtype`, in the caller's order."""
-    gyro, accel = np.asarray(gyro).astype(dtype), np.asarray(accel).astype(dtype)
-    R, n, _ = gyro.shape
-    mask, every, scale_f, r_odo, r_nhc = aref.aid_numbers(aid) if aid is not None else (0, 1, 1.0, 1.0, 1.0)
-    if mask & 1:
-        odo = np.asarray(odo).astype(dtype)
-    f = aref.AidedFilter(ref_frame, fs, ini, R, model, earth_rot, dtype)
-    stamps = [int(s) for s in stamps]
-    gps = None if gps is None else np.asarray(gps).astype(dtype)
+    """ins_loose_ref.run, recording at the checkpoints and ending after the last one.  ref_nav (n, 9) = att3, pos3, vel3 of the truth;
+    cons_samples in any order, repeats allowed.  Returns (len(cons_samples), RECORD) sums in `dtype`, in the caller's order."""
     asked = [int(s) for s in cons_samples]
-    want = set(asked)
+    last = max(asked)
     got = {}
-    kf = 0
-    for j in range(n):
-        if kf < len(stamps) and stamps[kf] == j:
-            if visible is None or visible[kf] != 0:
-                f.correct(gps[:, kf])
-            kf += 1
-        if mask and j > 0 and j % every == 0:
-            f.aid(odo[:, j] if mask & 1 else None, mask, scale_f, r_odo, r_nhc)
-        if j in want:
+
+    def hook(f, j):
+        if j in asked:
             got[j] = record(f, ref_nav[j])
-        if j == n - 1 or j >= max(want):
-            break
-        with np.errstate(all='ignore'):
-            f.propagate(gyro[:, j], accel[:, j])
+        return j >= last
+
+    ref.run(ref_frame, fs, gyro, accel, ini, model, gps, stamps, visible, earth_rot, dtype, odo, aid, hook=hook,
+            filt=_Quiet(ref_frame, fs, ini, np.shape(gyro)[0], model, earth_rot, dtype))
     return np.stack([got[j] for j in asked])
 
 

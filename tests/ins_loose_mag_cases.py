@@ -1,6 +1,6 @@
 """Shared inputs of the magnetometer-aided InsLoose tests (tests/test_ins_loose_mag_oracle.py on the CPU,
-tests/test_gpu_ins_loose_mag.py on the device): the outage profile's truth with the magnetometer's, the magnetometer models, the
-restatement's own rounding error as the parity bound, and the constants the CPU test measures and the device test is held to."""
+tests/test_gpu_ins_loose_mag.py on the device): the outage profile's truth with the magnetometer's, the magnetometer models,
+and the constants the CPU test measures and the device test is held to."""
 import functools
 
 import numpy as np
@@ -59,23 +59,6 @@ def model(mag_err, ref_frame, every=1, geo=GEO, **kw):
     return mag_model(mag_err, geo, ref_frame, dict({'every': every}, **kw))
 
 
-def restatement_error(ref_frame, fs, gyro, accel, ini, model, gps, stamps, visible, odo, aid_numbers, mag, mag_numbers, max_runs=8):
-    """The float64 restatement against its np.longdouble evaluation on the first max_runs runs of a case, in the metrics of
-    ins_loose_cases.deviation."""
-    import ins_loose_mag_ref as mref
-    k = min(max_runs, gyro.shape[0])
-    ini = np.asarray(ini)
-    ini = ini[:, :k] if ini.ndim == 2 else ini
-    args = (ref_frame, fs, gyro[:k], accel[:k], ini, model, None if gps is None else gps[:k], stamps, visible)
-    kw = dict(odo=None if odo is None else odo[:k], aid=aid_numbers, mag=None if mag is None else mag[:k], mag_model=mag_numbers)
-    return cs.deviation(mref.run(*args, **kw), mref.run(*args, dtype=np.longdouble, **kw))
-
-
-def parity_bound(*args, **kw):
-    """ins_loose_cases.PARITY_MARGIN (16) x restatement_error: what the device may deviate from the restatement, per quantity."""
-    return {k: cs.PARITY_MARGIN * v for k, v in restatement_error(*args, **kw).items()}
-
-
 # ------------------------------------------------------------------------------------------------- consistency by profile and frame
 # profile name -> (motion CSV, geomagnetic field, magnetometer model): the level outage profile as the tests above use it, and the
 # tilted southern profile with a general calibration
@@ -120,8 +103,6 @@ def consistency_draw(profile, rf, fs, runs, error_free=False):
     """One draw for all four FILTERS: accel, gyro, fixes, odometer, magnetometer in that order from
     np.random.default_rng(ins_loose_cases.CONSISTENCY_SEED), 2 Hz GPS, 'mid-accuracy' IMU.  error_free: ONE run whose sensors, fixes,
     odometer and magnetometer are the truth's (the magnetometer's through its soft and hard iron, which the filter undoes)."""
-    import ins_loose_aided_ref as aref
-    import ins_loose_mag_ref as mref
     import ins_loose_ref as ref
     from ginsim.ins_loose import filter_model
     csv, geo, mag_err = PROFILES[profile]
@@ -138,17 +119,17 @@ def consistency_draw(profile, rf, fs, runs, error_free=False):
     rng = np.random.default_rng(cs.CONSISTENCY_SEED)
     c['accel'], c['gyro'], c['tba'], c['tbg'] = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, runs)
     c['gps'] = cs.sample_gps(rng, truth, rf, runs)
-    c['odo'] = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, runs)
-    c['mag'] = mref.sample_mag(rng, truth['ref_mag'], mag_err, runs)
+    c['odo'] = ref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, runs)
+    c['mag'] = ref.sample_mag(rng, truth['ref_mag'], mag_err, runs)
     c['runs'] = runs
     return c
 
 
 def restate_filter(c, name):
     """The restatement's result of filter FILTERS[name] on a consistency_draw."""
-    import ins_loose_mag_ref as mref
+    import ins_loose_ref as ref
     with_mag, mask = FILTERS[name]
-    return mref.run(c['rf'], c['fs'], c['gyro'], c['accel'], c['ini'], c['model'], c['gps'], c['stamps'], c['truth']['gps_visibility'],
+    return ref.run(c['rf'], c['fs'], c['gyro'], c['accel'], c['ini'], c['model'], c['gps'], c['stamps'], c['truth']['gps_visibility'],
                     odo=c['odo'], aid=ac.aid(mask) if mask else None, mag=c['mag'] if with_mag else None,
                     mag_model=model(c['mag_err'], c['rf'], 1, c['geo']) if with_mag else None)
 

@@ -1,5 +1,5 @@
 """Shared inputs of the tests of InsLoose's scale-factor state (tests/test_ins_loose_scale_oracle.py on the CPU,
-tests/test_gpu_ins_loose_scale.py on the device): the options, the draws, the restatement's own rounding error as the parity bound,
+tests/test_gpu_ins_loose_scale.py on the device): the options, the draws, the metrics of the parity bound (deviation),
 and every number the CPU test measures and records."""
 import numpy as np
 
@@ -66,7 +66,8 @@ def aid(mask, every=1, scale0=SCALE0):
 
 def deviation(a, b):
     """ins_loose_cases.deviation and, for the outputs of the state: k_est (the series) and scale_end (k_est, P[15][15]) relative,
-    pcross_end relative to sqrt(P_kk P[15][15]) of b (a zero reference: absolute)."""
+    pcross_end relative to sqrt(P_kk P[15][15]) of b (a zero reference: absolute).  The family's parity bound is
+    ins_loose_cases.parity_bound(..., run=ins_loose_scale_ref.run, deviation=deviation, odo=, aid=, scale=)."""
     out = cs.deviation(a, b)
     lo = np.longdouble
     for k in ('k_est', 'scale_end'):
@@ -76,22 +77,6 @@ def deviation(a, b):
     s = np.sqrt(np.asarray(b['pdiag_end'], dtype=lo) * np.asarray(b['scale_end'], dtype=lo)[:, 1:2])
     out['pcross_end'] = float(np.max(np.abs(x - y) / np.where(s == 0, 1.0, s)))
     return out
-
-
-def restatement_error(ref_frame, fs, gyro, accel, ini, model, gps, stamps, visible, odo, aid_numbers, scale_numbers, max_runs=8):
-    """The float64 restatement against its np.longdouble evaluation on the first max_runs runs of a case, in the metrics of deviation."""
-    import ins_loose_scale_ref as sref
-    k = min(max_runs, gyro.shape[0])
-    ini = np.asarray(ini)
-    ini = ini[:, :k] if ini.ndim == 2 else ini
-    args = (ref_frame, fs, gyro[:k], accel[:k], ini, model, None if gps is None else gps[:k], stamps, visible)
-    kw = dict(odo=odo[:k], aid=aid_numbers, scale=scale_numbers)
-    return deviation(sref.run(*args, **kw), sref.run(*args, dtype=np.longdouble, **kw))
-
-
-def parity_bound(*args, **kw):
-    """ins_loose_cases.PARITY_MARGIN (16) x restatement_error: what the device may deviate from the restatement, per quantity."""
-    return {k: cs.PARITY_MARGIN * v for k, v in restatement_error(*args, **kw).items()}
 
 
 def draws(runs, seed, ref_frame=1, fs=cs.CONSISTENCY_FS, fs_gps=cs.CONSISTENCY_FS_GPS, scales=None):
@@ -119,7 +104,7 @@ def odometer(d, scales=None):
 
 
 def ratios16(d, o, k_true):
-    """RMS end error over sqrt(mean P_kk) of the 16 states of a result of ins_loose_scale_ref.run (15 of one of ins_loose_aided_ref.run)."""
+    """RMS end error over sqrt(mean P_kk) of the 16 states of a result of ins_loose_scale_ref.run (15 of one of ins_loose_ref.run)."""
     import ins_loose_ref as ref
     t = d['truth']
     e = ref.error_state(d['rf'], o['att'][:, -1], o['pos'][:, -1], o['vel'][:, -1], o['wb'][:, -1], o['ab'][:, -1], t['ref_att'][-1],

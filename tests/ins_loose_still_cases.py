@@ -1,6 +1,6 @@
 """Shared inputs of the standstill-aided InsLoose tests (tests/test_ins_loose_still_oracle.py on the CPU,
-tests/test_gpu_ins_loose_still.py on the device): the stops profile's truth and its standstill windows, the block's numbers, the
-restatement's own rounding error as the parity bound, and the constants the CPU test measures and the device test is held to."""
+tests/test_gpu_ins_loose_still.py on the device): the stops profile's truth and its standstill windows, the block's numbers,
+and the constants the CPU test measures and the device test is held to."""
 import functools
 import os
 
@@ -60,23 +60,6 @@ def model(filter_numbers, fs, mask, every=1, **kw):
     return still_model(filter_numbers, fs, options(mask, every, **kw))
 
 
-def restatement_error(ref_frame, fs, gyro, accel, ini, model, gps, stamps, visible, odo, aid_numbers, still, flags, max_runs=8):
-    """The float64 restatement against its np.longdouble evaluation on the first max_runs runs of a case, in the metrics of
-    ins_loose_cases.deviation."""
-    import ins_loose_still_ref as sref
-    k = min(max_runs, gyro.shape[0])
-    ini = np.asarray(ini)
-    ini = ini[:, :k] if ini.ndim == 2 else ini
-    args = (ref_frame, fs, gyro[:k], accel[:k], ini, model, None if gps is None else gps[:k], stamps, visible)
-    kw = dict(odo=None if odo is None else odo[:k], aid=aid_numbers, still=still, flags=flags)
-    return cs.deviation(sref.run(*args, **kw), sref.run(*args, dtype=np.longdouble, **kw))
-
-
-def parity_bound(*args, **kw):
-    """ins_loose_cases.PARITY_MARGIN (16) x restatement_error: what the device may deviate from the restatement, per quantity."""
-    return {k: cs.PARITY_MARGIN * v for k, v in restatement_error(*args, **kw).items()}
-
-
 def consistency_draw(rf, fs, runs, n=None):
     """One draw for all FILTERS: accel, gyro, fixes in that order from np.random.default_rng(ins_loose_cases.CONSISTENCY_SEED), 2 Hz
     GPS, 'mid-accuracy' IMU, the stops profile cut to its first n samples."""
@@ -95,9 +78,9 @@ def consistency_draw(rf, fs, runs, n=None):
 
 def restate_filter(c, name, keep_pdiag=False):
     """The restatement's result of filter FILTERS[name] on a consistency_draw."""
-    import ins_loose_still_ref as sref
+    import ins_loose_ref as ref
     mask = FILTERS[name]
-    return sref.run(c['rf'], c['fs'], c['gyro'], c['accel'], c['ini'], c['model'], c['gps'], c['stamps'], c['truth']['gps_visibility'],
+    return ref.run(c['rf'], c['fs'], c['gyro'], c['accel'], c['ini'], c['model'], c['gps'], c['stamps'], c['truth']['gps_visibility'],
                     still=model(c['model'], c['fs'], mask) if mask else None, flags=c['flags'], keep_pdiag=keep_pdiag)
 
 

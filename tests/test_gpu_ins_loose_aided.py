@@ -1,11 +1,11 @@
 """GPU: InsLoose aided by the odometer and the non-holonomic constraints (csrc/ins_loose_aided.hip, InsLooseJob(aid=...),
-InsLoose(odo=..., nhc=...), the 'loose' role of Sim) against its NumPy restatement (tests/ins_loose_aided_ref.py), against the
+InsLoose(odo=..., nhc=...), the 'loose' role of Sim) against its NumPy restatement (tests/ins_loose_ref.py), against the
 unaided launch, and against the statistics of its own covariance.  Shapes: 1-257 runs x 100-700 samples (1024 x 1200 for the
 consistency, 257 x 6000 through Sim).  Every test passes an argument the unaided package does not have.
 
 Parity bound, as tests/test_gpu_ins_loose.py: not a recorded constant.  Every comparison with the restatement measures, on its own
 case (the device's dumped sensors, fixes and odometer, the first 8 runs), the float64 aided restatement against its np.longdouble
-evaluation (ins_loose_aided_cases.restatement_error) and allows the device ins_loose_cases.PARITY_MARGIN (16) x that.
+evaluation (ins_loose_cases.restatement_error) and allows the device ins_loose_cases.PARITY_MARGIN (16) x that.
 Measured on the MI355X over the twelve parity cases (700 samples, 65 runs): device against restatement att <= 4.8e-14, pos <= 6.8e-14,
 vel <= 1.6e-13, wb <= 4.3e-12, ab <= 1.1e-11, pdiag_end <= 1.2e-13; the smallest bounds att 3.1e-13, pos 5.2e-14, vel 6.3e-12,
 wb 3.3e-10, ab 5.3e-10, pdiag_end 4.4e-13.  Consistency ratios on the device: the restatement's to three digits for both masks.
@@ -16,7 +16,6 @@ import numpy as np
 import pytest
 
 import ins_loose_aided_cases as ac
-import ins_loose_aided_ref as aref
 import ins_loose_cases as cs
 import ins_loose_ref as ref
 
@@ -77,11 +76,11 @@ class Dump(object):
         return (self.rf, self.fs, self.gyro, self.accel, self.ini, self.model, self.gps, self.stamps, self.truth['gps_visibility'])
 
     def restate(self, mask, every=1):
-        return aref.run(*self._args(), odo=self.odo, aid=ac.aid(mask, every))
+        return ref.run(*self._args(), odo=self.odo, aid=ac.aid(mask, every))
 
     def bound(self, mask, every=1):
         """16 x the aided restatement's own float64 error on this case (its first 8 runs)."""
-        return ac.parity_bound(*self._args(), odo=self.odo, aid_numbers=ac.aid(mask, every))
+        return cs.parity_bound(*self._args(), odo=self.odo, aid=ac.aid(mask, every))
 
     def release(self):
         self.mc.release()
@@ -286,7 +285,7 @@ def drawn(ctx):
     rng = np.random.default_rng(cs.CONSISTENCY_SEED)
     accel, gyro, tba, tbg = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, R)
     gps = cs.sample_gps(rng, truth, 1, R)
-    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
+    odo = ref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
     bufs = {'accel': ctx.upload(np.ascontiguousarray(accel.transpose(2, 1, 0))), 'gyro': ctx.upload(np.ascontiguousarray(gyro.transpose(2, 1, 0))),
             'gps': ctx.upload(np.ascontiguousarray(gps.transpose(2, 1, 0))), 'odo': ctx.upload(np.ascontiguousarray(odo.T))}
     yield ini, truth, acc_e, gyr_e, tba, tbg, bufs
@@ -353,8 +352,8 @@ def test_sim_runs_the_aided_and_the_unaided_filter_on_one_realisation(ctx):
     vis = np.asarray(d.gps_visibility.data)
     model = filter_model(fs, imu.accel_err, imu.gyro_err, imu.gps_err)
     args = (rf, fs, gyro, accel, ini, model, gps, stamps, vis)
-    exp = aref.run(*args, odo=odo, aid=job1.aid)
-    bound = ac.parity_bound(*args, odo=odo, aid_numbers=job1.aid)
+    exp = ref.run(*args, odo=odo, aid=job1.aid)
+    bound = cs.parity_bound(*args, odo=odo, aid=job1.aid)
     got = {k: np.stack([np.asarray(src.data['%s_%d' % (aided, r)]) for r in runs])
            for k, src in (('att', d.att_euler), ('pos', d.pos), ('vel', d.vel), ('wb', d.wb), ('ab', d.ab))}
     got['pdiag_end'] = job1.final_pdiag()[runs]

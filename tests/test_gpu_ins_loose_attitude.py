@@ -28,10 +28,8 @@ import numpy as np
 import pytest
 
 import ins_loose_aided_cases as ac
-import ins_loose_aided_ref as aref
 import ins_loose_cases as cs
 import ins_loose_mag_cases as mc
-import ins_loose_mag_ref as mref
 import ins_loose_ref as ref
 import test_gpu_ins_loose_cons as K
 import test_gpu_ins_loose_mag as M
@@ -70,8 +68,8 @@ def restated(d, kernel, mask, every, dtype=np.float64, runs=slice(None)):
     if kernel == 'loose':
         return ref.run(*args, dtype=dtype)
     if kernel == 'aided':
-        return aref.run(*args, dtype=dtype, odo=d.odo[runs], aid=aid)
-    return mref.run(*args, dtype=dtype, odo=d.odo[runs], aid=aid, mag=d.mag['skew'][runs], mag_model=mc.model(mc.MAG_ERR_SKEW, d.rf, 1, d.geo))
+        return ref.run(*args, dtype=dtype, odo=d.odo[runs], aid=aid)
+    return ref.run(*args, dtype=dtype, odo=d.odo[runs], aid=aid, mag=d.mag['skew'][runs], mag_model=mc.model(mc.MAG_ERR_SKEW, d.rf, 1, d.geo))
 
 
 def job_of(ctx, d, kernel, mask, every, given, **kw):
@@ -179,7 +177,7 @@ def sweep(request):
         out['accel'].append(a[0])
         out['gyro'].append(g[0])
         out['gps'].append(cs.sample_gps(rng, truth, rf, 1)[0])
-        out['mag'].append(mref.sample_mag(rng, raw['mag'][:, 1:4], mc.MAG_ERR_SKEW, 1)[0])
+        out['mag'].append(ref.sample_mag(rng, raw['mag'][:, 1:4], mc.MAG_ERR_SKEW, 1)[0])
         if r == 0:
             first = {'ref_accel': raw['imu'][:, 1:4], 'ref_gyro': raw['imu'][:, 4:7], 'ref_pos': raw['nav'][:, 1:4], 'ref_vel': raw['nav'][:, 4:7],
                      'ref_att': raw['nav'][:, 7:10], 'ref_gps': raw['gps'][:, 1:7], 'gps_time': raw['gps'][:, 0] / FS, 'gps_visibility': raw['gps'][:, 7]}
@@ -212,8 +210,7 @@ def test_a_table_of_initial_states_in_one_launch(ctx, sweep, with_mag):
     job.release()
     args = (rf, FS, s['gyro'], s['accel'], s['table'], s['model'], s['gps'], s['stamps'], s['truth']['gps_visibility'])
     kw = dict(mag=s['mag'], mag_model=mc.model(mc.MAG_ERR_SKEW, rf, 1, mc.GEO_SOUTH)) if with_mag else {}
-    run = mref.run if with_mag else ref.run
-    exp, hi = run(*args, **kw), run(*args, dtype=np.longdouble, **kw)
+    exp, hi = ref.run(*args, **kw), ref.run(*args, dtype=np.longdouble, **kw)
     assert np.all(np.isfinite(dev['att'])) and np.all(np.isfinite(dev['pdiag_end']))
     got, err = cs.deviation(dev, exp), cs.deviation(exp, hi)
     print('sweep rf%d %s: ' % (rf, 'mag' if with_mag else 'loose') + ', '.join('%s %.2e (bound %.2e)' % (k, got[k], cs.PARITY_MARGIN * err[k]) for k in got))

@@ -1,11 +1,11 @@
 """GPU: InsLoose aided by the magnetometer (csrc/ins_loose_mag.hip, InsLooseJob(mag=...), InsLoose(mag=True), the 'loose' role of
-Sim) against its NumPy restatement (tests/ins_loose_mag_ref.py), against the unaided and the odometer-aided launch, against
+Sim) against its NumPy restatement (tests/ins_loose_ref.py), against the unaided and the odometer-aided launch, against
 AuxSensorJob's magnetometer series and against the statistics of its own covariance.  Shapes: 1-129 runs x 200-700 samples
 (1024 x 1200 for the consistency, 257 x 6000 through Sim).  Every test passes an argument the package did not have before.
 
 Parity bound, as tests/test_gpu_ins_loose_aided.py: not a recorded constant.  Every comparison with the restatement measures, on
 its own case (the device's dumped sensors, fixes, odometer and magnetometer, the first 8 runs), the float64 restatement against its
-np.longdouble evaluation (ins_loose_mag_cases.restatement_error) and allows the device ins_loose_cases.PARITY_MARGIN (16) x that.
+np.longdouble evaluation (ins_loose_cases.restatement_error) and allows the device ins_loose_cases.PARITY_MARGIN (16) x that.
 Measured on the MI355X over the twelve parity cases (700 samples, 65 runs, both frames; the largest deviation of the device from
 the restatement, and in brackets the smallest bound any case allowed): att 2.8e-14 (3.3e-13), pos 3.0e-14 (5.6e-14), vel 1.7e-13
 (5.0e-12), wb 5.7e-11 (5.8e-11, in different cases: the closest single case is 1.7e-11 against 7.2e-11), ab 1.3e-11 (8.1e-10),
@@ -18,9 +18,7 @@ import pytest
 import ins_loose_aided_cases as ac
 import ins_loose_cases as cs
 import ins_loose_mag_cases as mc
-import ins_loose_mag_ref as mref
 import ins_loose_ref as ref
-import ins_loose_aided_ref as aref
 
 pytestmark = pytest.mark.gpu
 
@@ -86,11 +84,11 @@ class Dump(object):
 
     def restate(self, which, mask, every):
         series, aid, model = self._kw(which, mask, every)
-        return mref.run(*self._args(), aid=aid, mag_model=model, **series)
+        return ref.run(*self._args(), aid=aid, mag_model=model, **series)
 
     def bound(self, which, mask, every):
         series, aid, model = self._kw(which, mask, every)
-        return mc.parity_bound(*self._args(), odo=series['odo'], aid_numbers=aid, mag=series['mag'], mag_numbers=model)
+        return cs.parity_bound(*self._args(), odo=series['odo'], aid=aid, mag=series['mag'], mag_model=model)
 
     def release(self):
         self.mc.release()
@@ -262,8 +260,8 @@ def drawn(ctx):
     rng = np.random.default_rng(cs.CONSISTENCY_SEED)
     accel, gyro, tba, tbg = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, R)
     gps = cs.sample_gps(rng, truth, 1, R)
-    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
-    mag = mref.sample_mag(rng, truth['ref_mag'], mc.MAG_ERR, R)
+    odo = ref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
+    mag = ref.sample_mag(rng, truth['ref_mag'], mc.MAG_ERR, R)
     bufs = {'accel': ctx.upload(np.ascontiguousarray(accel.transpose(2, 1, 0))), 'gyro': ctx.upload(np.ascontiguousarray(gyro.transpose(2, 1, 0))),
             'gps': ctx.upload(np.ascontiguousarray(gps.transpose(2, 1, 0))), 'odo': ctx.upload(np.ascontiguousarray(odo.T)),
             'mag': ctx.upload(np.ascontiguousarray(mag.transpose(2, 1, 0)))}
@@ -335,8 +333,8 @@ def test_sim_runs_the_magnetometer_aided_and_the_unaided_filter_on_one_realisati
     vis = np.asarray(d.gps_visibility.data)
     model = filter_model(fs, imu.accel_err, imu.gyro_err, imu.gps_err)
     args = (rf, fs, gyro, accel, ini, model, gps, stamps, vis)
-    exp = mref.run(*args, mag=mag, mag_model=job1.mag)
-    bound = mc.parity_bound(*args, odo=None, aid_numbers=None, mag=mag, mag_numbers=job1.mag)
+    exp = ref.run(*args, mag=mag, mag_model=job1.mag)
+    bound = cs.parity_bound(*args, odo=None, aid=None, mag=mag, mag_model=job1.mag)
     got = {k: np.stack([np.asarray(src.data['%s_%d' % (aided, r)]) for r in runs])
            for k, src in (('att', d.att_euler), ('pos', d.pos), ('vel', d.vel), ('wb', d.wb), ('ab', d.ab))}
     got['pdiag_end'] = job1.final_pdiag()[runs]

@@ -6,7 +6,7 @@ the package without the state does not have.
 
 Parity bound, as tests/test_gpu_ins_loose_aided.py: not a recorded constant.  Every comparison with the restatement measures, on its
 own case (the device's dumped sensors, fixes and odometer, the first 8 runs), the float64 restatement against its np.longdouble
-evaluation (ins_loose_scale_cases.restatement_error) and allows the device ins_loose_cases.PARITY_MARGIN (16) x that, per output:
+evaluation (ins_loose_cases.restatement_error) and allows the device ins_loose_cases.PARITY_MARGIN (16) x that, per output:
 att, pos, vel, wb, ab, pdiag_end, the k_est series, scale_end and pcross_end.
 
 Measured on the MI355X (first run: all pass as written).  Largest deviation from the restatement over the eight 257-run parity
@@ -18,8 +18,8 @@ import numpy as np
 import pytest
 
 import ins_loose_aided_cases as ac
-import ins_loose_aided_ref as aref
 import ins_loose_cases as cs
+import ins_loose_ref as ref
 import ins_loose_scale_cases as sc
 import ins_loose_scale_ref as sref
 
@@ -79,7 +79,7 @@ class Dump(object):
         if key not in self._restated:
             kw = dict(odo=self.odo, aid=sc.aid(mask, every, scale0))
             out = sref.run(*self._args(), scale=sc.scale(scale0, p0), **kw)
-            bound = sc.parity_bound(*self._args(), odo=self.odo, aid_numbers=kw['aid'], scale_numbers=sc.scale(scale0, p0))
+            bound = cs.parity_bound(*self._args(), run=sref.run, deviation=sc.deviation, odo=self.odo, aid=kw['aid'], scale=sc.scale(scale0, p0))
             for v in out.values():
                 v.setflags(write=False)
             self._restated[key] = (out, bound)
@@ -323,14 +323,14 @@ def test_sim_runs_both_filters_on_one_realisation_and_the_plugin_on_one_series(c
     published = lambda name: {k: np.stack([np.asarray(src.data['%s_%d' % (name, r)]) for r in runs])
                               for k, src in (('att', d.att_euler), ('pos', d.pos), ('vel', d.vel), ('wb', d.wb), ('ab', d.ab))}
     got0 = dict(published(plain), pdiag_end=job0.final_pdiag()[runs])
-    held('Sim, the 15-state plugin', cs.deviation(got0, aref.run(*args, odo=odo, aid=job0.aid)),
-         ac.parity_bound(*args, odo=odo, aid_numbers=job0.aid))
+    held('Sim, the 15-state plugin', cs.deviation(got0, ref.run(*args, odo=odo, aid=job0.aid)),
+         cs.parity_bound(*args, odo=odo, aid=job0.aid))
     got1 = dict(published(state), pdiag_end=job1.final_pdiag()[runs], pcross_end=job1.final_pcross()[runs])
     got1['k_est'] = np.stack([np.asarray(d.odo_scale.data['%s_%d' % (state, r)]).reshape(-1) for r in runs])
     k_end, sigma = job1.final_scale()
     got1['scale_end'] = np.stack([k_end, sigma ** 2], axis=1)[runs]
     held('Sim, the 16-state plugin', sc.deviation(got1, sref.run(*args, odo=odo, aid=job1.aid, scale=job1.scale)),
-         sc.parity_bound(*args, odo=odo, aid_numbers=job1.aid, scale_numbers=job1.scale))
+         cs.parity_bound(*args, run=sref.run, deviation=sc.deviation, odo=odo, aid=job1.aid, scale=job1.scale))
     assert np.all(np.abs(k_end - imu.odo_err['scale']) < 4 * sigma + 1e-3)
     # the published series are an InsLooseJob's of the same seed
     t = {'ref_accel': np.asarray(d.ref_accel.data), 'ref_gyro': np.asarray(d.ref_gyro.data), 'ref_att': np.asarray(d.ref_att_euler.data),

@@ -1,11 +1,11 @@
 """GPU: InsLoose aided at standstill, ZUPT and ZARU (csrc/ins_loose_still.hip, InsLooseJob(still=...), InsLoose(zupt=True, zaru=True),
-the 'loose' role of Sim) against its NumPy restatement (tests/ins_loose_still_ref.py), against the unaided and the odometer-aided
+the 'loose' role of Sim) against its NumPy restatement (tests/ins_loose_ref.py), against the unaided and the odometer-aided
 launch and against the statistics of its own covariance.  Shapes: the stops profile at 20 Hz, 1100 samples (600 for the bit
 comparisons: the first stop and 13 s after it), 1-257 runs; 1024 runs for the consistency.
 
 Parity bound, as tests/test_gpu_ins_loose_mag.py: not a recorded constant.  Every comparison with the restatement measures, on its
 own case (the device's dumped sensors, fixes and odometer, the first 8 runs), the float64 restatement against its np.longdouble
-evaluation (ins_loose_still_cases.restatement_error) and allows the device ins_loose_cases.PARITY_MARGIN (16) x that.
+evaluation (ins_loose_cases.restatement_error) and allows the device ins_loose_cases.PARITY_MARGIN (16) x that.
 Measured on the MI355X over the twelve 257-run parity cases (the largest deviation of the device from the restatement, and in
 brackets the smallest bound any case allowed): att 5.0e-14 (1.7e-12), pos 6.3e-14 in ref_frame 0 (4.7e-12) and 2.0e-16 in ref_frame 1
 (7.9e-14), vel 2.7e-13 (1.3e-11), wb 1.0e-11 (5.2e-10), ab 7.9e-12 (8.3e-11), pdiag_end 2.5e-13 (9.3e-13).  Every bit comparison holds.
@@ -18,7 +18,6 @@ import ins_loose_aided_cases as ac
 import ins_loose_cases as cs
 import ins_loose_ref as ref
 import ins_loose_still_cases as sc
-import ins_loose_still_ref as sref
 
 pytestmark = pytest.mark.gpu
 
@@ -79,11 +78,11 @@ class Dump(object):
                     flags=self.flags if flags is None else flags)
 
     def restate(self, smask, mask=0, every=1, flags=None):
-        return sref.run(*self._args(), **self._kw(smask, mask, every, flags))
+        return ref.run(*self._args(), **self._kw(smask, mask, every, flags))
 
     def bound(self, smask, mask=0, every=1, flags=None):
         kw = self._kw(smask, mask, every, flags)
-        return sc.parity_bound(*self._args(), odo=kw['odo'], aid_numbers=kw['aid'], still=kw['still'], flags=kw['flags'])
+        return cs.parity_bound(*self._args(), odo=kw['odo'], aid=kw['aid'], still=kw['still'], flags=kw['flags'])
 
     def release(self):
         self.mc.release()
@@ -366,8 +365,8 @@ def test_sim_runs_the_standstill_aided_and_the_unaided_filter_on_one_realisation
     stamps = np.rint(np.asarray(d.gps_time.data) * fs).astype(np.int64)
     vis = np.asarray(d.gps_visibility.data)
     args = (rf, fs, gyro, accel, ini, model, gps, stamps, vis)
-    exp = sref.run(*args, still=job1.still, flags=job1.still_flags)
-    bound = sc.parity_bound(*args, odo=None, aid_numbers=None, still=job1.still, flags=job1.still_flags)
+    exp = ref.run(*args, still=job1.still, flags=job1.still_flags)
+    bound = cs.parity_bound(*args, odo=None, aid=None, still=job1.still, flags=job1.still_flags)
     got = {k: np.stack([np.asarray(src.data['%s_%d' % (aided, r)]) for r in runs])
            for k, src in (('att', d.att_euler), ('pos', d.pos), ('vel', d.vel), ('wb', d.wb), ('ab', d.ab))}
     got['pdiag_end'] = job1.final_pdiag()[runs]

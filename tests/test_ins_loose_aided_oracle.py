@@ -1,5 +1,5 @@
 """CPU: InsLoose's odometer / non-holonomic aiding: the C ABI's appended fields and refusals, the build's resource
-report of loose_aided_kernel, the restatement (tests/ins_loose_aided_ref.py) against the statistics of its own covariance and the
+report of loose_aided_kernel, the restatement (tests/ins_loose_ref.py) against the statistics of its own covariance and the
 benefit it measures through the GPS outage, the plugin's surface and the Sim's refusal.
 
 Recorded in ins_loose_aided_cases (measured by test_restatement_consistency and test_outage_benefit; 1024 runs drawn from the filter's
@@ -14,7 +14,6 @@ import numpy as np
 import pytest
 
 import ins_loose_aided_cases as ac
-import ins_loose_aided_ref as aref
 import ins_loose_cases as cs
 import ins_loose_ref as ref
 from conftest import REPO
@@ -132,17 +131,17 @@ def test_mask_zero_is_the_unaided_restatement_and_a_block_shrinks_p():
     rng = np.random.default_rng(3)
     accel, gyro, _, _ = ref.sample_sensors(rng, 100.0, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, 5)
     gps = cs.sample_gps(rng, truth, 1, 5)
-    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, 5)
+    odo = ref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, 5)
     from ginsim.ins_loose import filter_model
     model = filter_model(100.0, acc_e, gyr_e, cs.GPS_ERR)
     args = (1, 100.0, gyro, accel, ini, model, gps, stamps, truth['gps_visibility'])
-    a, b = ref.run(*args), aref.run(*args, odo=odo, aid=None)
+    a, b = ref.run(*args), ref.run(*args, odo=odo, aid=None)
     for k in cs.PARITY_KEYS:
         assert np.array_equal(a[k], b[k]), k
-    never = aref.run(*args, odo=odo, aid=ac.aid(7, every=400))
+    never = ref.run(*args, odo=odo, aid=ac.aid(7, every=400))
     for k in cs.PARITY_KEYS:
         assert np.array_equal(a[k], never[k]), k
-    c = aref.run(*args, odo=odo, aid=ac.aid(7))
+    c = ref.run(*args, odo=odo, aid=ac.aid(7))
     assert not np.array_equal(a['vel'], c['vel'])
     assert np.all(c['pdiag_end'][:, 3:9] < a['pdiag_end'][:, 3:9])              # dv and psi are what the rows see
     d = c['P_end']
@@ -158,7 +157,7 @@ def test_rows_follow_the_first_order_model():
     from ginsim.ins_loose import filter_model
     acc_e, gyr_e = cs.imu_errors()
     model = filter_model(100.0, acc_e, gyr_e, cs.GPS_ERR)
-    f = aref.AidedFilter(1, 100.0, ini, 1, model)
+    f = ref.LooseFilter(1, 100.0, ini, 1, model)
     for j in range(1400):                                                       # into the first turn: a general attitude
         f.propagate(truth['ref_gyro'][None, j], truth['ref_accel'][None, j])
     D, v = f.D[0], f.vel[0]
@@ -183,12 +182,12 @@ def consistency():
     rng = np.random.default_rng(cs.CONSISTENCY_SEED)
     accel, gyro, tba, tbg = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, R)
     gps = cs.sample_gps(rng, truth, 1, R)
-    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
+    odo = ref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
     model = filter_model(fs, acc_e, gyr_e, cs.GPS_ERR)
     samples = ac.outage_samples(truth, stamps, fs, fs_gps)
     out = {}
     for mask in (0, 1, 7):
-        o = aref.run(1, fs, gyro, accel, ini, model, gps, stamps, truth['gps_visibility'], odo=odo, aid=ac.aid(mask) if mask else None)
+        o = ref.run(1, fs, gyro, accel, ini, model, gps, stamps, truth['gps_visibility'], odo=odo, aid=ac.aid(mask) if mask else None)
         e = ref.error_state(1, o['att'][:, -1], o['pos'][:, -1], o['vel'][:, -1], o['wb'][:, -1], o['ab'][:, -1], truth['ref_att'][-1],
                             truth['ref_pos'][-1], truth['ref_vel'][-1], tbg[:, -1], tba[:, -1])
         ratio = np.sqrt(np.mean(e * e, axis=0)) / np.sqrt(np.mean(o['pdiag_end'], axis=0))

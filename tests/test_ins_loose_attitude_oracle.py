@@ -1,4 +1,4 @@
-"""CPU: the InsLoose restatements (tests/ins_loose_ref.py, ins_loose_aided_ref.py, ins_loose_mag_ref.py, ins_loose_cons_ref.py) against
+"""CPU: the InsLoose restatements (tests/ins_loose_ref.py with its aiding and magnetometer blocks, tests/ins_loose_cons_ref.py) against
 the nonlinear model they linearise, at 200 random attitudes (yaw over +-pi, pitch over +-80 deg, roll over +-pi) with fully
 three-dimensional velocities, specific forces and fields, in np.longdouble where the platform has it.  The rotation the tests hold
 the restatements to (rot_nb: Rx(roll) Ry(pitch) Rz(yaw) from elementary rotations, Rodrigues' formula for the error rotation) is
@@ -44,32 +44,30 @@ import types
 import numpy as np
 import pytest
 
-import ins_loose_aided_ref          # noqa: F401  (family() copies the four restatements from sys.modules)
 import ins_loose_cases as cs
 import ins_loose_cons_ref as cref
 import ins_loose_mag_cases as mc
-import ins_loose_mag_ref            # noqa: F401
-import ins_loose_ref                # noqa: F401
+import ins_loose_ref                # noqa: F401  (family() copies the two restatements from sys.modules)
 from oracle import ins_np
 
 LD = np.longdouble
 N_ATT, PSI_NORM = 200, 1e-4
-ORDER = ['ins_loose_ref', 'ins_loose_aided_ref', 'ins_loose_mag_ref', 'ins_loose_cons_ref']
+ORDER = ['ins_loose_ref', 'ins_loose_cons_ref']
 TRANSPOSE = ('C = np.swapaxes(self.D, 1, 2)', 'C = self.D')
 # name -> {module: [(expression, replacement), ...]}; every expression must occur in its module
 MUTATIONS = {
     'dcm_sp': {'ins_loose_ref': [('m[..., 0, 2] = -sp', 'm[..., 0, 2] = sp')]},
     'dcm_sr': {'ins_loose_ref': [('m[..., 1, 2] = cp * sr', 'm[..., 1, 2] = -cp * sr')]},
-    'transpose_C': {'ins_loose_ref': [TRANSPOSE], 'ins_loose_aided_ref': [TRANSPOSE, ('D, v = self.D, self.vel', 'D, v = np.swapaxes(self.D, 1, 2), self.vel')],
-                    'ins_loose_mag_ref': [TRANSPOSE, ('        D = self.D\n', '        D = np.swapaxes(self.D, 1, 2)\n')],
+    'transpose_C': {'ins_loose_ref': [TRANSPOSE, ('D, v = self.D, self.vel', 'D, v = np.swapaxes(self.D, 1, 2), self.vel'),
+                                      ('        D = self.D\n', '        D = np.swapaxes(self.D, 1, 2)\n')],
                     'ins_loose_cons_ref': [('Ce = np.swapaxes(ref.dcm_zyx(f.att), 1, 2)', 'Ce = ref.dcm_zyx(f.att)'),
                                            ('Ct = ref.dcm_zyx(t[None, 0:3])[0].T', 'Ct = ref.dcm_zyx(t[None, 0:3])[0]')]},
     'negate_skew': {'ins_loose_ref': [('return np.stack([np.stack([z, -v[:, 2], v[:, 1]], 1)', 'return -np.stack([np.stack([z, -v[:, 2], v[:, 1]], 1)')]},
-    'swap_d12_d22': {n: [('np.arctan2(d12, d22)', 'np.arctan2(d22, d12)')] for n in ORDER[:3]},
-    'cross_order': {'ins_loose_aided_ref': [("H[:, :, 6:9] = -np.einsum('rij,rjk->rik', D, ref.skew(v))", "H[:, :, 6:9] = np.einsum('rij,rjk->rik', D, ref.skew(v))")],
-                    'ins_loose_mag_ref': [('np.cross(np.broadcast_to(m_n, D.shape), D)', 'np.cross(D, np.broadcast_to(m_n, D.shape))')],
+    'swap_d12_d22': {'ins_loose_ref': [('np.arctan2(d12, d22)', 'np.arctan2(d22, d12)')]},
+    'cross_order': {'ins_loose_ref': [("H[:, :, 6:9] = -np.einsum('rij,rjk->rik', D, skew(v))", "H[:, :, 6:9] = np.einsum('rij,rjk->rik', D, skew(v))"),
+                                      ('np.cross(np.broadcast_to(m_n, D.shape), D)', 'np.cross(D, np.broadcast_to(m_n, D.shape))')],
                     'ins_loose_cons_ref': [('e[:, 6] = (M[:, 1, 2] - M[:, 2, 1]) / 2', 'e[:, 6] = (M[:, 2, 1] - M[:, 1, 2]) / 2')]},
-    'cal_si_T': {'ins_loose_mag_ref': [("np.einsum('ik,rk->ri', cal_si.reshape(3, 3)", "np.einsum('ki,rk->ri', cal_si.reshape(3, 3)")]},
+    'cal_si_T': {'ins_loose_ref': [("np.einsum('ik,rk->ri', cal_si.reshape(3, 3)", "np.einsum('ki,rk->ri', cal_si.reshape(3, 3)")]},
 }
 # measured residuals of the unmodified restatement (module docstring); the allowance is 10 x
 BASE = {'feedback': 2.6e-8, 'feedback_reverse': 2.6e-8, 'aid_rows': 3.3e-9, 'mag_rows': 1.7e-9, 'mag_block': 2.5e-9,
@@ -78,7 +76,7 @@ LEVEL_BLIND = {'feedback': [], 'rows': ['dcm_sp', 'dcm_sr'], 'phi': [], 'cons': 
 
 
 def family(name=None):
-    """The four restatement modules, compiled again from their source with the mutation `name` applied (None: unchanged copies),
+    """The two restatement modules, compiled again from their source with the mutation `name` applied (None: unchanged copies),
     each importing the copies before it: {module name: module}."""
     edits = MUTATIONS[name] if name else {}
     saved = {n: sys.modules[n] for n in ORDER}
@@ -201,13 +199,12 @@ def model(fs):
     return filter_model(fs, acc_e, gyr_e, cs.GPS_ERR)
 
 
-def make_filter(fam, rf, d, att=None, fs=20.0, cls='LooseFilter'):
+def make_filter(fam, rf, d, att=None, fs=20.0):
     """A filter of N_ATT runs, one per case, at the case's position and navigation-frame velocity with the attitude att."""
-    mod = fam[{'LooseFilter': 'ins_loose_ref', 'AidedFilter': 'ins_loose_aided_ref', 'MagFilter': 'ins_loose_mag_ref'}[cls]]
     att = d['att'] if att is None else att
     vel_b = np.einsum('rij,rj->ri', rot_nb(att), d['vel'])
     ini = np.concatenate([d['lla'], vel_b, att], axis=1).T
-    f = getattr(mod, cls)(rf, fs, np.asarray(ini, dtype=np.float64), N_ATT, model(fs), dtype=LD)
+    f = fam['ins_loose_ref'].LooseFilter(rf, fs, np.asarray(ini, dtype=np.float64), N_ATT, model(fs), dtype=LD)
     # the constructor takes float64: put the long double values in, through the module's own dcm_zyx
     f.att, f.D = att.copy(), fam['ins_loose_ref'].dcm_zyx(att)
     f.vel = d['vel'].copy()
@@ -234,8 +231,8 @@ def check(what, measure, families, names, base):
 
 
 # ------------------------------------------------------------------------------------------------- B1 feedback
-def feedback_residual(fam, kind, reverse=False, which='ins_loose_ref'):
-    """Truth C, estimate C_est = exp(-[psi x]) C; LooseFilter.correct (or the aiding / magnetometer block's copy of the feedback)
+def feedback_residual(fam, kind, reverse=False):
+    """Truth C, estimate C_est = exp(-[psi x]) C; LooseFilter.correct, whose feedback is every block's,
     is driven so that its x[6:9] is psi exactly: P = I with P[0, 6:9] = P[6:9, 0] = psi and a fix whose only innovation is
     z0 = P00 + R0, so the first scalar update has gain 1 on that column and the other five have innovation 0.  Returns the largest
     |psi| left between the fed-back attitude and the truth [rad].  reverse: x[6:9] is what error_state measures on the estimate."""
@@ -288,7 +285,7 @@ def measurement_jacobian(C, vec, with_dv):
 
 
 def aid_rows_residual(fam, kind):
-    """AidedFilter.aid builds its rows inside the block; they are read back from what the block does to P = I with R = 1, one row
+    """LooseFilter.aid builds its rows inside the block; they are read back from what the block does to P = I with R = 1, one row
     at a time: I - P' = h h^T / (|h|^2 + 1).  Compared, as h h^T / |h|^2, with the finite differences' (a row's overall sign is the
     innovation's; the sign of its psi part against its dv part is in the outer product)."""
     d = draw(kind)
@@ -296,7 +293,7 @@ def aid_rows_residual(fam, kind):
     J = measurement_jacobian(C, d['vel'], True)
     worst = 0.0
     for i in range(3):
-        f = make_filter(fam, 1, d, cls='AidedFilter')
+        f = make_filter(fam, 1, d)
         f.P = np.zeros((N_ATT, 15, 15), dtype=LD)
         f.P[:] = np.eye(15, dtype=LD)
         f.aid(np.zeros(N_ATT), 1 << i, 1.0, 1.0, 1.0)
@@ -316,18 +313,18 @@ def mag_rows_residual(fam, kind):
     C = np.swapaxes(rot_nb(d['att']), 1, 2)
     J = measurement_jacobian(C, d['field'], False)[:, :, 3:6]
     D = fam['ins_loose_ref'].dcm_zyx(d['att'])
-    got = np.stack([fam['ins_loose_mag_ref'].mag_rows(D[i:i + 1], d['field'][i])[0] for i in range(N_ATT)])
+    got = np.stack([fam['ins_loose_ref'].mag_rows(D[i:i + 1], d['field'][i])[0] for i in range(N_ATT)])
     return float(np.max(np.abs(got - J) / np.linalg.norm(d['field'], axis=1)[:, None, None]))
 
 
 def mag_block_residual(fam, kind):
-    """MagFilter.mag on the estimate C_est = exp(-[psi x]) C with the error-free sample of the TRUE attitude, generated by a general
+    """LooseFilter.mag on the estimate C_est = exp(-[psi x]) C with the error-free sample of the TRUE attitude, generated by a general
     magnetometer (MAG_ERR_SKEW) and calibrated by the block: with P = I on psi and R -> 0 the block returns the part of psi the
     field makes observable, psi minus its component along m_n.  [rad], relative to nothing: |psi| = 1e-4."""
     d = draw(kind)
     C = np.swapaxes(rot_nb(d['att']), 1, 2)
     att_est = euler_of(np.matmul(error_rotation(d['psi']), C))
-    f = make_filter(fam, 1, d, att_est, cls='MagFilter')
+    f = make_filter(fam, 1, d, att_est)
     f.P = np.zeros((N_ATT, 15, 15), dtype=LD)
     f.P[:, np.arange(6, 9), np.arange(6, 9)] = 1
     si, hi = mc.MAG_ERR_SKEW['si'].astype(LD), mc.MAG_ERR_SKEW['hi'].astype(LD)
@@ -337,7 +334,7 @@ def mag_block_residual(fam, kind):
     cal_si = cal_si + np.matmul(cal_si, np.eye(3, dtype=LD) - np.matmul(si, cal_si))        # one Newton step: the inverse in long double
     x = np.zeros((N_ATT, 15), dtype=LD)
     for i in range(N_ATT):                                                        # the block takes ONE field: row by row
-        g = fam['ins_loose_mag_ref'].MagFilter.__new__(fam['ins_loose_mag_ref'].MagFilter)
+        g = fam['ins_loose_ref'].LooseFilter.__new__(fam['ins_loose_ref'].LooseFilter)
         g.__dict__.update({k: (v[i:i + 1] if isinstance(v, np.ndarray) and v.shape[:1] == (N_ATT,) else v) for k, v in f.__dict__.items()})
         g.R = 1
         x[i] = g.mag(raw[i:i + 1], d['field'][i], cal_si, hi, np.full(3, 1e-12))[0]

@@ -1,5 +1,5 @@
 """CPU: InsLoose's magnetometer aiding: the C ABI's new block, entry points and refusals, the build's resource report of
-loose_mag_kernel, the restatement (tests/ins_loose_mag_ref.py) against the first-order model, against the statistics of its own
+loose_mag_kernel, the restatement (tests/ins_loose_ref.py) against the first-order model, against the statistics of its own
 covariance and the benefit it measures for the heading and through the GPS outage, mag_model, the plugin's surface and the Sim's
 refusal.
 
@@ -15,10 +15,8 @@ import numpy as np
 import pytest
 
 import ins_loose_aided_cases as ac
-import ins_loose_aided_ref as aref
 import ins_loose_cases as cs
 import ins_loose_mag_cases as mc
-import ins_loose_mag_ref as mref
 import ins_loose_ref as ref
 from conftest import REPO
 
@@ -194,7 +192,7 @@ def test_rows_follow_the_first_order_model():
     psi = np.array([1e-5, 2e-5, -3e-5])
     skew = lambda a: np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0.0]])
     C_est = (np.eye(3) - skew(psi)) @ D.T
-    H = mref.mag_rows(Dr, m_n)[0]
+    H = ref.mag_rows(Dr, m_n)[0]
     np.testing.assert_allclose(H, -D @ skew(m_n), rtol=0, atol=1e-12)
     np.testing.assert_allclose(C_est.T @ m_n - D @ m_n, H @ psi, rtol=0, atol=1e-8 * np.linalg.norm(m_n))
     assert np.linalg.norm(H @ psi) > 1e-4                                       # and the change is far above that
@@ -208,21 +206,21 @@ def test_a_block_that_never_fires_is_the_aided_restatement_and_a_block_shrinks_p
     rng = np.random.default_rng(3)
     accel, gyro, _, _ = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, R)
     gps = cs.sample_gps(rng, truth, 1, R)
-    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
-    mag = mref.sample_mag(rng, truth['ref_mag'], mc.MAG_ERR_SKEW, R)
+    odo = ref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
+    mag = ref.sample_mag(rng, truth['ref_mag'], mc.MAG_ERR_SKEW, R)
     from ginsim.ins_loose import filter_model
     model = filter_model(fs, acc_e, gyr_e, cs.GPS_ERR)
     args = (1, fs, gyro, accel, ini, model, gps, stamps, truth['gps_visibility'])
     aid = ac.aid(mask) if mask else None
-    a = aref.run(*args, odo=odo, aid=aid)
+    a = ref.run(*args, odo=odo, aid=aid)
     for every in (n, n + 1, 2 ** 40):
-        never = mref.run(*args, odo=odo, aid=aid, mag=mag, mag_model=mc.model(mc.MAG_ERR_SKEW, 1, every))
+        never = ref.run(*args, odo=odo, aid=aid, mag=mag, mag_model=mc.model(mc.MAG_ERR_SKEW, 1, every))
         for k in cs.PARITY_KEYS + ('P_end',):
             assert np.array_equal(a[k], never[k]), (k, every)
-    none = mref.run(*args, odo=odo, aid=aid)                                    # and so is no block at all
+    none = ref.run(*args, odo=odo, aid=aid)                                     # and so is no block at all
     for k in cs.PARITY_KEYS:
         assert np.array_equal(a[k], none[k]), k
-    c = mref.run(*args, odo=odo, aid=aid, mag=mag, mag_model=mc.model(mc.MAG_ERR_SKEW, 1))
+    c = ref.run(*args, odo=odo, aid=aid, mag=mag, mag_model=mc.model(mc.MAG_ERR_SKEW, 1))
     assert not np.array_equal(a['att'], c['att'])
     assert np.all(c['pdiag_end'][:, 6:9] < a['pdiag_end'][:, 6:9])              # psi is what the rows see
     d = c['P_end']
@@ -230,7 +228,7 @@ def test_a_block_that_never_fires_is_the_aided_restatement_and_a_block_shrinks_p
     assert np.max(np.abs(d - np.swapaxes(d, 1, 2)) / (dd[:, :, None] * dd[:, None, :])) < 1e-12
     assert np.all(np.linalg.eigvalsh(d / (dd[:, :, None] * dd[:, None, :])) > -1e-9)
     # the wrong calibration shows: a filter that forgets the hard iron is dragged off by it
-    wrong = mref.run(*args, odo=odo, aid=aid, mag=mag, mag_model=mc.model(mc.MAG_ERR_SKEW, 1, hi=np.zeros(3)))
+    wrong = ref.run(*args, odo=odo, aid=aid, mag=mag, mag_model=mc.model(mc.MAG_ERR_SKEW, 1, hi=np.zeros(3)))
     yaw = lambda o: np.abs(np.mod(o['att'][:, -1, 0] - truth['ref_att'][-1, 0] + np.pi, 2 * np.pi) - np.pi)
     assert np.all(yaw(wrong) > 10.0 * yaw(c) + 1e-3)
 
@@ -250,13 +248,13 @@ def consistency():
     rng = np.random.default_rng(cs.CONSISTENCY_SEED)
     accel, gyro, tba, tbg = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, R)
     gps = cs.sample_gps(rng, truth, 1, R)
-    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
-    mag = mref.sample_mag(rng, truth['ref_mag'], mc.MAG_ERR, R)
+    odo = ref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
+    mag = ref.sample_mag(rng, truth['ref_mag'], mc.MAG_ERR, R)
     model = filter_model(fs, acc_e, gyr_e, cs.GPS_ERR)
     samples = ac.outage_samples(truth, stamps, fs, fs_gps)
     out = {}
     for key, mask, use_mag in (('gps', 0, False), ('mag', 0, True), ('mag7', 7, True)):
-        o = mref.run(1, fs, gyro, accel, ini, model, gps, stamps, truth['gps_visibility'], odo=odo, aid=ac.aid(mask) if mask else None,
+        o = ref.run(1, fs, gyro, accel, ini, model, gps, stamps, truth['gps_visibility'], odo=odo, aid=ac.aid(mask) if mask else None,
                      mag=mag, mag_model=mc.model(mc.MAG_ERR, 1) if use_mag else None)
         e = ref.error_state(1, o['att'][:, -1], o['pos'][:, -1], o['vel'][:, -1], o['wb'][:, -1], o['ab'][:, -1], truth['ref_att'][-1],
                             truth['ref_pos'][-1], truth['ref_vel'][-1], tbg[:, -1], tba[:, -1])

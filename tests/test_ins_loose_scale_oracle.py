@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 import ins_loose_aided_cases as ac
-import ins_loose_aided_ref as aref
 import ins_loose_cases as cs
+import ins_loose_ref as ref
 import ins_loose_scale_cases as sc
 import ins_loose_scale_ref as sref
 from conftest import REPO
@@ -191,7 +191,7 @@ def _args(d):
 def test_p0_zero_is_the_15_state_restatement_exactly(small, rf, mask):
     d, s = small[rf], 0.99
     assert d['gyro'].shape[1] == 1200 and np.any(d['truth']['gps_visibility'] == 0)
-    a = aref.run(*_args(d), odo=d['odo'], aid=ac.aid(mask, odo_err={'scale': s, 'stdv': sc.ODO_STDV}))
+    a = ref.run(*_args(d), odo=d['odo'], aid=ac.aid(mask, odo_err={'scale': s, 'stdv': sc.ODO_STDV}))
     b = sref.run(*_args(d), odo=d['odo'], aid=sc.aid(mask, scale0=s), scale=sc.scale(s, 0.0, 0.0))
     for k in cs.PARITY_KEYS:
         assert np.array_equal(a[k], b[k]), k                                    # adding 0 * h changes nothing
@@ -222,10 +222,10 @@ def test_the_random_walk_only_adds_to_the_last_diagonal_element(small):
 def test_float64_error_of_the_restatement(small, rf, mask):
     """The float64 restatement against its np.longdouble evaluation, per output (ins_loose_scale_cases.deviation), measured on
     the case: this, times ins_loose_cases.PARITY_MARGIN, is what the device test allows, measured anew on each of its cases (as
-    ins_loose_aided_cases.parity_bound does).  Here every figure is printed and held to 4 x the one recorded in
+    ins_loose_cases.parity_bound does).  Here every figure is printed and held to 4 x the one recorded in
     ins_loose_scale_cases.RESTATEMENT_ERROR, the freedom another NumPy build's order of operations may take."""
     d = small[rf]
-    err = sc.restatement_error(*_args(d), odo=d['odo'], aid_numbers=sc.aid(mask), scale_numbers=sc.scale())
+    err = cs.restatement_error(*_args(d), run=sref.run, deviation=sc.deviation, odo=d['odo'], aid=sc.aid(mask), scale=sc.scale())
     print('rf%d mask %d float64 error: ' % (rf, mask) + ', '.join('%s %.2e' % kv for kv in err.items()))
     assert set(err) == set(sc.PARITY_KEYS)
     for k, v in err.items():
@@ -238,7 +238,7 @@ def consistency():
     d = sc.draws(cs.CONSISTENCY_RUNS, cs.CONSISTENCY_SEED)
     o16 = sref.run(*_args(d), odo=sc.odometer(d), aid=sc.aid(1), scale=sc.scale())
     # the defect: the same runs and noise, an odometer that reads 0.99, the 15-state filter that assumes 1.0
-    o15 = aref.run(*_args(d), odo=sc.odometer(d, sc.READS), aid=sc.aid(1))
+    o15 = ref.run(*_args(d), odo=sc.odometer(d, sc.READS), aid=sc.aid(1))
     return d, sc.ratios16(d, o16, d['scales']), sc.ratios16(d, o15, None), o16
 
 
@@ -276,8 +276,8 @@ def test_payoff_table():
     j = ac.outage_samples(d['truth'], d['stamps'], d['fs'], d['fs_gps'])[1]
     told_aid = ac.aid(7, odo_err={'scale': sc.READS, 'stdv': sc.ODO_STDV})
     wrong_aid = dict(told_aid, odo_scale_f=1.0)                                 # the same r_odo: only the assumed scale differs
-    res = {'wrong': aref.run(*_args(d), odo=odo, aid=wrong_aid, keep_pdiag=True),
-           'told': aref.run(*_args(d), odo=odo, aid=told_aid, keep_pdiag=True),
+    res = {'wrong': ref.run(*_args(d), odo=odo, aid=wrong_aid, keep_pdiag=True),
+           'told': ref.run(*_args(d), odo=odo, aid=told_aid, keep_pdiag=True),
            'state': sref.run(*_args(d), odo=odo, aid=sc.aid(7), scale=sc.scale(), keep_pdiag=True)}
     table = {}
     for k, o in res.items():

@@ -1,5 +1,5 @@
 """CPU: InsLoose's standstill aiding, ZUPT and ZARU: the C ABI's new block, entry points, refusals and dispatch, the
-build's resource report of loose_still_kernel, the restatement (tests/ins_loose_still_ref.py) against the aided restatement, against
+build's resource report of loose_still_kernel, the restatement (tests/ins_loose_ref.py) against the aided restatement, against
 what information can only do to P and against the statistics of its own covariance, still_model, standstill_flags, the job's
 combination refusals, the plugin's surface and the stops profile's windows.
 
@@ -16,11 +16,9 @@ import numpy as np
 import pytest
 
 import ins_loose_aided_cases as ac
-import ins_loose_aided_ref as aref
 import ins_loose_cases as cs
 import ins_loose_ref as ref
 import ins_loose_still_cases as sc
-import ins_loose_still_ref as sref
 from conftest import GOLDEN, REPO
 
 NEW = {'ginsim_loose_still_run', 'ginsim_loose_still_kernel_name'}
@@ -313,7 +311,7 @@ def small(request):
     rng = np.random.default_rng(5)
     accel, gyro, _, _ = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, R)
     gps = cs.sample_gps(rng, truth, rf, R)
-    odo = aref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
+    odo = ref.sample_odo(rng, truth['ref_odo'], ac.ODO_ERR, R)
     model = filter_model(fs, acc_e, gyr_e, cs.GPS_ERR)
     return {'args': (rf, fs, gyro, accel, ini, model, gps, stamps, truth['gps_visibility']), 'kw': dict(odo=odo, aid=ac.aid(mask) if mask else None),
             'model': model, 'fs': fs, 'n': n, 'flags': sc.flags_of(truth), 'truth': truth}
@@ -321,7 +319,7 @@ def small(request):
 
 def test_a_block_that_never_fires_is_the_aided_restatement_bit_for_bit(small):
     n, flags = small['n'], small['flags']
-    a = aref.run(*small['args'], **small['kw'])
+    a = ref.run(*small['args'], **small['kw'])
     still = sc.model(small['model'], small['fs'], 3)
     only_first = np.zeros(n, dtype=np.int32)
     only_first[0] = 1
@@ -330,10 +328,10 @@ def test_a_block_that_never_fires_is_the_aided_restatement_bit_for_bit(small):
                      ('every >= n', dict(still=sc.model(small['model'], small['fs'], 3, every=n), flags=flags)),
                      ('every = 2^40', dict(still=sc.model(small['model'], small['fs'], 3, every=2 ** 40), flags=flags)),
                      ('mask 0', dict(still=dict(still, still_mask=0), flags=flags))):
-        o = sref.run(*small['args'], **dict(small['kw'], **kw))
+        o = ref.run(*small['args'], **dict(small['kw'], **kw))
         for k in cs.PARITY_KEYS + ('P_end',):
             assert np.array_equal(a[k], o[k]), (name, k)
-    c = sref.run(*small['args'], still=still, flags=flags, **small['kw'])
+    c = ref.run(*small['args'], still=still, flags=flags, **small['kw'])
     assert not np.array_equal(a['vel'], c['vel']) and not np.array_equal(a['wb'], c['wb'])
     d, dd = c['P_end'], np.sqrt(c['pdiag_end'])
     assert np.max(np.abs(d - np.swapaxes(d, 1, 2)) / (dd[:, :, None] * dd[:, None, :])) < 1e-12
@@ -346,11 +344,11 @@ def test_one_bit_alone_is_the_full_block_with_the_other_bit_clear(small):
     flags = small['flags']
     both = sc.model(small['model'], small['fs'], 3)
     for mask in (1, 2):
-        alone = sref.run(*small['args'], still=sc.model(small['model'], small['fs'], mask), flags=flags, **small['kw'])
-        cleared = sref.run(*small['args'], still=dict(both, still_mask=mask), flags=flags, **small['kw'])
+        alone = ref.run(*small['args'], still=sc.model(small['model'], small['fs'], mask), flags=flags, **small['kw'])
+        cleared = ref.run(*small['args'], still=dict(both, still_mask=mask), flags=flags, **small['kw'])
         poisoned = dict(both, still_mask=mask, **({'r_zaru': np.full(3, np.nan)} if mask == 1 else {'r_zupt': np.nan}))
-        unread = sref.run(*small['args'], still=poisoned, flags=flags, **small['kw'])
-        full = sref.run(*small['args'], still=both, flags=flags, **small['kw'])
+        unread = ref.run(*small['args'], still=poisoned, flags=flags, **small['kw'])
+        full = ref.run(*small['args'], still=both, flags=flags, **small['kw'])
         for k in cs.PARITY_KEYS + ('P_end',):
             assert np.array_equal(alone[k], cleared[k]) and np.array_equal(alone[k], unread[k]), (mask, k)
         assert not np.array_equal(alone['pdiag_end'], full['pdiag_end'])
@@ -367,7 +365,7 @@ def test_zaru_uses_the_raw_sample_before_and_the_rest_rate():
     ini = np.array([0.6, 2.0, 10.0, 0.0, 0.0, 0.0, 0.7, -0.2, 0.3])
     bias = np.array([[2e-4, -1e-4, 3e-4]])
     for rf, earth in ((0, True), (0, False), (1, True)):
-        f = sref.StillFilter(rf, fs, ini, 1, model, earth)
+        f = ref.LooseFilter(rf, fs, ini, 1, model, earth)
         w = f.rest_rate()
         if rf == 0 and earth:
             want = ref.dcm_zyx(ini[None, 6:9])[0] @ (ins_np.W_IE * np.array([np.cos(0.6), 0.0, -np.sin(0.6)]))
