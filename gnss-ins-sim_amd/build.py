@@ -65,6 +65,9 @@ SOURCES = [
     ('ins_loose_still.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
+    # error_curve.hip's flags: the keys are formed with its error expression (tests/test_error_quantiles_oracle.py reads the
+    # resource report: no scratch)
+    ('error_quantile.hip', ['--offload-arch=' + ARCH]),
     ('allan.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),
     ('vib_psd.hip', ['--offload-arch=' + ARCH]),

@@ -1073,6 +1073,82 @@ int ginsim_curve_merge(const double* parts, int32_t nparts, int64_t m, double* o
     return GINSIM_OK;
 }
 
+// ---- error quantiles across the runs (csrc/error_quantile.hip): the keys of every (sample, run), then the order statistics of key rows
+static int check_keys_args(const char* who, const void* c, const void* traj, const void* ref, int64_t n, int64_t runs,
+                           const int64_t* samples, int64_t m, int32_t which, const void* keys, int64_t row_stride, int64_t col0) {
+    const int rc = check_curve_args(who, c, traj, ref, n, runs, samples, m, keys);
+    if (rc) return rc;
+    REQUIRE(which == 0 || which == 1, "%s: which=%d is neither 0 (position) nor 1 (velocity)", who, (int)which);
+    REQUIRE(col0 >= 0, "%s: col0=%lld is negative", who, (long long)col0);
+    REQUIRE(row_stride >= col0 + runs, "%s: row_stride=%lld is shorter than col0 + runs = %lld + %lld", who, (long long)row_stride,
+            (long long)col0, (long long)runs);
+    return GINSIM_OK;
+}
+
+static int keys_run(ginsim_ctx* c, const void* traj, int f32, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                    int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* keys,
+                    int64_t row_stride, int64_t col0) {
+    HIP_TRY(hipSetDevice(c->device));
+    int64_t* d_samples = nullptr;
+    if (samples) {
+        void* ws = nullptr;
+        HIP_TRY(scratch(c, 2, sizeof(int64_t) * (size_t)m, &ws));
+        d_samples = reinterpret_cast<int64_t*>(ws);
+        HIP_TRY(hipMemcpyAsync(d_samples, samples, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+    }
+    if (f32)
+        HIP_TRY(launch_radial_keys_f32(reinterpret_cast<const float*>(traj), ref, n, runs, d_samples, m, which, pos_ned, keys, row_stride,
+                                       col0, origin, n_ini, ini_first, c->stream));
+    else
+        HIP_TRY(launch_radial_keys(reinterpret_cast<const double*>(traj), ref, n, runs, d_samples, m, which, pos_ned, keys, row_stride,
+                                   col0, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
+int ginsim_radial_keys(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
+                       int32_t which, int32_t pos_ned, double* keys, int64_t row_stride, int64_t col0) {
+    const int rc = check_keys_args("radial_keys", c, traj, ref, n, runs, samples, m, which, keys, row_stride, col0);
+    if (rc) return rc;
+    return keys_run(c, traj, 0, ref, n, runs, samples, m, which, pos_ned, nullptr, 0, 0, keys, row_stride, col0);
+}
+
+int ginsim_radial_keys_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                           int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first,
+                           double* keys, int64_t row_stride, int64_t col0) {
+    const int rc = check_keys_args("radial_keys_f32", c, traj, ref, n, runs, samples, m, which, keys, row_stride, col0);
+    if (rc) return rc;
+    REQUIRE(origin && n_ini >= 1, "radial_keys_f32: the origin table of the displacement series is missing");
+    return keys_run(c, traj, 1, ref, n, runs, samples, m, which, pos_ned, origin, n_ini, ini_first, keys, row_stride, col0);
+}
+
+int ginsim_quantile_rows(ginsim_ctx* c, const double* keys, int64_t rows, int64_t len, int64_t row_stride, const double* probs,
+                         int32_t q, double* host_out, double* host_count) {
+    REQUIRE(c && keys && probs && host_out && host_count, "quantile_rows: NULL argument");
+    REQUIRE(rows >= 1 && len >= 1, "quantile_rows: rows=%lld len=%lld must be >= 1", (long long)rows, (long long)len);
+    REQUIRE(rows <= 0x7FFFFFFFll && len <= 0x7FFFFFFFll, "quantile_rows: too many rows or keys for one call");
+    REQUIRE(row_stride >= len, "quantile_rows: row_stride=%lld is shorter than len=%lld", (long long)row_stride, (long long)len);
+    REQUIRE(q >= 1 && q <= GINSIM_QUANTILE_MAX_PROBS, "quantile_rows: q=%d probabilities (1..%d at once)", (int)q,
+            GINSIM_QUANTILE_MAX_PROBS);
+    for (int i = 0; i < q; ++i)
+        REQUIRE(std::isfinite(probs[i]) && probs[i] > 0.0 && probs[i] <= 1.0, "quantile_rows: probability %g (entry %d) is not in (0, 1]",
+                probs[i], i);
+    HIP_TRY(hipSetDevice(c->device));
+    // scratch: [q probabilities][rows x q results][rows counts]
+    const size_t res = sizeof(double) * (size_t)rows * ((size_t)q + 1);
+    void* ws = nullptr;
+    HIP_TRY(scratch(c, 2, sizeof(double) * (size_t)q + res, &ws));
+    double* d_probs = reinterpret_cast<double*>(ws);
+    double* d_out = d_probs + q;
+    double* d_count = d_out + (size_t)rows * q;
+    HIP_TRY(hipMemcpyAsync(d_probs, probs, sizeof(double) * (size_t)q, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_quantile_rows(keys, rows, len, row_stride, d_probs, q, d_out, d_count, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, d_out, sizeof(double) * (size_t)rows * q, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_count, d_count, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
 int ginsim_stats_merge(const ginsim_stats* parts, int32_t nparts, ginsim_stats* out) {
     REQUIRE(parts && out && nparts >= 1, "stats_merge: bad arguments");
     stats_merge_host(parts, nparts, out);

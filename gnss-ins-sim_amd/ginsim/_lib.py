@@ -236,6 +236,11 @@ _SIGS = {
     'ginsim_error_curve_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
                                          C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, _PD]),
     'ginsim_curve_merge': (C.c_int, [_PD, C.c_int32, C.c_int64, _PD]),
+    'ginsim_radial_keys': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                     C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64]),
+    'ginsim_radial_keys_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_int64, C.c_int64]),
+    'ginsim_quantile_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _PD, C.c_int32, _PD, _PD]),
     'ginsim_gather_runs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                      C.POINTER(C.c_int64), C.c_int32, _PD]),
     'ginsim_gather_series': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,

@@ -7,6 +7,7 @@ Nothing here computes on the CPU: every number a job returns was produced by lib
 import ctypes as C
 import os
 import math
+from collections import namedtuple
 
 import numpy as np
 
@@ -578,6 +579,23 @@ class CurveResult(object):
         out = np.empty(parts.shape[1:])
         check(lib.ginsim_curve_merge(dptr(parts), parts.shape[0], parts.shape[1], dptr(out)))
         return CurveResult(out)
+
+
+QuantileResult = namedtuple('QuantileResult', 'values count')
+QuantileResult.__doc__ = """Order statistics of key rows (ginsim_quantile_rows): values (rows, q), for each row and probability one of the
+row's keys bit for bit (NaN where the row has no finite key); count (rows,), the finite keys of the row."""
+
+
+def quantile_rows(ctx, keys, rows, len, stride, probs):
+    """Exact nearest-rank quantiles (np.quantile(method='inverted_cdf')) of each of `rows` rows of `len` doubles, `stride` doubles
+    apart, in the device buffer (or at the device pointer) `keys`, for up to 8 probabilities in (0, 1] at once; keys that are not
+    finite are left out.  Selected on the device: only the (rows, q) results and the counts come back."""
+    p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    rows = int(rows)
+    values, count = np.empty((max(rows, 1), max(p.size, 1))), np.empty(max(rows, 1))
+    check(ctx.retry_oom(lambda: lib.ginsim_quantile_rows(ctx.handle, getattr(keys, 'ptr', keys), rows, int(len), int(stride), dptr(p),
+                                                        p.size, dptr(values), dptr(count))))
+    return QuantileResult(values, count)
 
 
 class ConsistencyResult(object):

@@ -100,14 +100,15 @@ class BatchJob(object):
 
     def _traj_call(self, fns, algo, what, mid, out):
         """fns = (fp64 entry point, its _f32 twin) on the kept trajectory of algo (None: the job's first algorithm):
-        fn(handle, traj, ref_nav, n, runs, *mid[, origin, n_ini, ini_first], out)."""
+        fn(handle, traj, ref_nav, n, runs, *mid[, origin, n_ini, ini_first], out); a tuple `out`: the arguments that end the call."""
         if not self.keep_traj:
             raise ValueError('%s the trajectories (keep_traj=True)' % what)
         args = (self.ctx.handle, self._bufs['traj_' + (algo or self.algos[0])].ptr, self._nav(), self.n, self.runs) + mid
         fn = fns[0]
         if self.precision == 'f32':     # float series, positions as displacement from the run's initial position
             fn, args = fns[1], args + (self._origin().ptr, self._ini_table.shape[0], self._ini_first)
-        check(self.ctx.retry_oom(lambda: fn(*(args + (out,)))))
+        args += out if isinstance(out, tuple) else (out,)
+        check(self.ctx.retry_oom(lambda: fn(*args)))
 
     def process_stats(self, algo=None, first_sample=0, pos_ned=False):
         """Per-run statistics of the error over time (samples >= first_sample): (runs, 3, 9) = max|e|, mean, std.
@@ -121,15 +122,51 @@ class BatchJob(object):
         """The error-growth curve of this batch: the across-run record (CurveResult) of the error at each of `samples` (sample
         indices in any order, repeats allowed; None: every sample).  Needs the trajectories (keep_traj=True)."""
         from .engine import CurveResult
-        if samples is None:
-            idx, m = None, self.n
-        else:
-            ids = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
-            idx, m = ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size
+        idx, m, _keep = self._sample_arg(samples)
         out = np.empty((max(m, 1), 9, 4))
         self._traj_call((lib.ginsim_error_curve, lib.ginsim_error_curve_f32), algo, 'an error-growth curve needs',
                         (idx, m, int(bool(pos_ned))), dptr(out))
         return CurveResult(out)
+
+    def _sample_arg(self, samples):
+        """(POINTER(c_int64) | None, m, the array that owns the memory) of a sample list (None: every sample)."""
+        if samples is None:
+            return None, self.n, None
+        ids = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
+        return ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size, ids
+
+    def radial_keys(self, algo=None, samples=None, which=0, out=None, col0=0):
+        """The radial error keys of this batch at `samples` (as error_curve takes them): per sample and run the horizontal
+        sqrt(e0^2 + e1^2), vertical |e2| and 3-D sqrt(e0^2 + e1^2 + e2^2) error of the position (which = 0; ref_frame 0: always in
+        local NED metres, ref_frame 1: the frame's own x, y are horizontal and z vertical) or the velocity (which = 1).  They stay
+        on the device: a DeviceBuffer of [3][m][stride] doubles, this job's runs in columns col0 .. col0 + runs of every row.
+        out: such a buffer of another call (stride = out.nbytes / (24 m) >= col0 + runs), so that several jobs fill one row; None: a
+        new one of stride col0 + runs.  Needs the trajectories (keep_traj=True)."""
+        idx, m, _keep = self._sample_arg(samples)
+        col0, own = int(col0), out is None
+        stride = col0 + self.runs if own else out.nbytes // (24 * max(m, 1))
+        if own:                             # sizes the library refuses get a token buffer and its words
+            out = self.ctx.malloc(24 * max(m, 1) * max(stride, 1))
+        try:
+            self._traj_call((lib.ginsim_radial_keys, lib.ginsim_radial_keys_f32), algo, 'the radial error keys need',
+                            (idx, m, int(which), int(self._ref_frame == 0)), (out.ptr, stride, col0))
+        except Exception:
+            if own:
+                out.free()
+            raise
+        return out
+
+    def error_quantiles(self, algo=None, samples=None, which=0, probs=(0.5, 0.95)):
+        """The quantiles `probs` across this batch's runs of the horizontal, vertical and 3-D error (radial_keys) at `samples`:
+        a QuantileResult with values (3, m, q) and count (3, m).  CEP50 / CEP95 are values[0, :, i] of probs (0.5, 0.95)."""
+        from .engine import quantile_rows, QuantileResult
+        keys = self.radial_keys(algo, samples, which)
+        try:
+            m = keys.nbytes // (24 * self.runs)
+            r = quantile_rows(self.ctx, keys, 3 * m, self.runs, self.runs, probs)
+        finally:
+            keys.free()
+        return QuantileResult(r.values.reshape(3, m, -1), r.count.reshape(3, m))
 
     def stats_from_traj(self, algo=None, pos_ned=False):
         """End-point statistics recomputed on the device from the kept trajectories (used for extra_opt='ned')."""

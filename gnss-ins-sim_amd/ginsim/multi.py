@@ -189,6 +189,17 @@ class JobSet(_Parts):
             return CurveResult.zero(self.n if samples is None else np.asarray(samples).size)
         return CurveResult.merge([c.pack() for c in got])
 
+    def radial_keys_host(self, algo, samples=None, which=0):
+        """MonteCarloJob.radial_keys on every device at the same time, brought to the host: (3 m, runs) rows of keys, the
+        devices' columns side by side in run order (24 B per sample and run; the select wants a whole row on one device)."""
+        def keys(j):
+            k = j.radial_keys(algo, samples, which)
+            try:
+                return j.ctx.download(k, (k.nbytes // (8 * j.runs), j.runs))
+            finally:
+                k.free()
+        return np.concatenate([a for a in self._each_part(keys) if a is not None], axis=1)
+
     def part_stats(self, algo, ned=False):
         """The unmerged per-device records (device order; None where a device holds no runs)."""
         return self._each_part(lambda j: j.stats(algo, ned=ned))

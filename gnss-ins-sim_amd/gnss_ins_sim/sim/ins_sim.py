@@ -231,6 +231,39 @@ class _McResults(object):
             self._stats[key] = distributed.allgather_curve(part, self._group, self._device)
         return self._stats[key]
 
+    def error_quantiles(self, name, samples, n, which, probs, budget):
+        """ginsim.QuantileResult (values (3, m, q), count (3, m): horizontal, vertical, 3-D) of algorithm `name` over ALL runs of
+        the Sim at `samples`: one key buffer [3][m][runs] on the selecting device, then one select.  Kept trajectories fill it in
+        one launch; statistics-only runs are integrated again through _blocks and every block writes its column range.  Over
+        several devices every device's key columns come through the host into one buffer on the first device.  Quantiles are not
+        mergeable records: nothing here crosses ranks (Sim.error_quantiles refuses a process group before it gets here)."""
+        key = ('quantiles', name, None if samples is None else samples.tobytes(), int(which), probs.tobytes())
+        if key not in self._stats:
+            import ginsim
+            idx = self.algo_names.index(name)
+            job, kind = self.jobs[idx], self.kinds[idx]
+            m, total = (n if samples is None else samples.size), self.runs_local
+            if not job.keep_traj and 24 * m * total > budget:
+                raise ValueError('error_quantiles: the keys of %d samples x %d runs are %d bytes (24 per sample and run) and must '
+                                 'be on one device at once, more than max_device_bytes = %d: ask for fewer samples (every=, '
+                                 'samples=)' % (m, total, 24 * m * total, budget))
+            blocks = [job] if job.keep_traj else self._blocks(idx)
+            if hasattr(self._ctx, 'contexts'):          # Sim(devices=...): a JobSet per block
+                ctx = self._ctx.contexts[0]
+                buf = ctx.upload(np.concatenate([b.radial_keys_host(kind, samples, which) for b in blocks], axis=1))
+            else:
+                ctx, col = self._ctx, 0
+                buf = ctx.malloc(24 * m * total)
+                for b in blocks:
+                    b.radial_keys(kind, samples, which, out=buf, col0=col)
+                    col += b.runs
+            try:
+                r = ginsim.quantile_rows(ctx, buf, 3 * m, total, total, probs)
+            finally:
+                buf.free()
+            self._stats[key] = ginsim.QuantileResult(r.values.reshape(3, m, -1), r.count.reshape(3, m))
+        return self._stats[key]
+
     def consistency(self, name, samples):
         """ginsim.ConsistencyResult of the InsLoose `name` over ALL runs of the Sim at `samples` (int64 sample indices): one more
         statistics-only launch of the filter with checkpoints (the counter RNG reproduces the same runs; nothing kept is needed),
@@ -1214,6 +1247,22 @@ class Sim(object):
                 except Exception:
                     raise IOError('Unable to save summary to %s.' % data_dir)
 
+    def _samples_of(self, who, every, samples, n):
+        """The sample indices `every` (seconds between instants, from the first sample) or `samples` name, as contiguous int64, or
+        None for every one of the n samples; refusals in the words of `who`."""
+        if every is not None and samples is not None:
+            raise ValueError('%s: give every (seconds) or samples (indices), not both' % who)
+        if every is not None:
+            step = int(round(float(every) * float(self.fs[0])))
+            if step < 1:
+                raise ValueError('%s: every=%r s is shorter than one sample at %g Hz' % (who, every, self.fs[0]))
+            samples = np.arange(0, n, step, dtype=np.int64)
+        if samples is not None:
+            samples = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
+            if samples.size == 0 or samples.min() < 0 or samples.max() >= n:
+                raise ValueError('%s: samples must be indices in [0, %d), at least one' % (who, n))
+        return samples
+
     def error_curve(self, data_names=('att_euler', 'pos', 'vel'), *, every=None, samples=None, extra_opt=''):
         """How the error grows with time: the across-run max |e|, mean and std (ddof 0) of the attitude, position and velocity
         error at each instant -- at sample j what ``results(err_stats_start=-1)`` reports for the series cut after j
@@ -1247,17 +1296,7 @@ class Sim(object):
                                  'planes -- run the Sim with keep_trajectories=True' % a)
         t = np.asarray(d.time.data)
         n = t.shape[0]
-        if every is not None and samples is not None:
-            raise ValueError('error_curve: give every (seconds) or samples (indices), not both')
-        if every is not None:
-            step = int(round(float(every) * float(self.fs[0])))
-            if step < 1:
-                raise ValueError('error_curve: every=%r s is shorter than one sample at %g Hz' % (every, self.fs[0]))
-            samples = np.arange(0, n, step, dtype=np.int64)
-        if samples is not None:
-            samples = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
-            if samples.size == 0 or samples.min() < 0 or samples.max() >= n:
-                raise ValueError('error_curve: samples must be indices in [0, %d), at least one' % n)
+        samples = self._samples_of('error_curve', every, samples, n)
         # one reduction serves every name: the NED form changes the position components only
         use_ned = self.ref_frame == 0 and extra_opt == 'ned' and 'pos' in data_names
         out = {}
@@ -1271,6 +1310,62 @@ class Sim(object):
                 c = mc.error_curve(a, samples, n, ned=use_ned)
                 for stat, arr in (('max', c.maxabs), ('avg', c.mean), ('std', c.std)):
                     res[stat][a] = sim_data.convert_unit(np.ascontiguousarray(arr[:, slices[nm]]), units, out_units)
+            out[nm] = res
+        return out
+
+    def error_quantiles(self, data_names=('pos',), probs=(0.5, 0.95), *, every=None, samples=None):
+        """What share of the runs stays inside which radius: for each probability p of `probs` the horizontal, vertical and 3-D
+        error that holds the share p of the runs at each instant -- CEP50 and CEP95 (R95) are the 'horizontal' columns of
+        probs=(0.5, 0.95).  The across-run moments of ``error_curve`` do not give these numbers: the radial error is not Gaussian,
+        and in ref_frame 0 the across-run mean is not zero.  Exact order statistics (nearest rank,
+        ``np.quantile(method='inverted_cdf')``: the value is the error of one of the runs), selected on the device.
+          data_names 'pos' and / or 'vel'.  The position error of ref_frame 0 is always taken in local NED metres (north and east
+                     horizontal, down vertical); in ref_frame 1 the frame's own x, y are horizontal and z vertical
+          probs      up to 8 probabilities in (0, 1]
+          every      seconds between the instants (from the first sample); None and samples=None: every sample
+          samples    or the sample indices themselves (any order, repeats allowed)
+        Returns {name: {'time': (m,), 'units': ['m'] | ['m/s'], 'probs': (q,), 'count': {algorithm name: (m,) the runs whose
+        error is finite, the others are left out}, 'horizontal' | 'vertical' | '3d': {algorithm name: (m, q)}}}.  Served: the fused
+        free-integration plugins, kept or statistics only (their runs are integrated again in blocks that fit
+        ``max_device_bytes``; the keys, 24 B per sample and run, must fit it at once), over one or several devices of this
+        process, and InsLoose with kept trajectories."""
+        if not self.sim_complete:
+            print("Call Sim.run() to run the simulaltion first.")
+            return None
+        mc = self.mc
+        names = list(getattr(mc, 'nav_names', None) or getattr(mc, 'fused_names', None) or []) \
+            if mc is not None and not self.data_from_files else []
+        if isinstance(data_names, str):
+            data_names = (data_names,)
+        which = {'pos': 0, 'vel': 1}
+        for nm in data_names:
+            if nm not in which:
+                raise ValueError("error_quantiles: %r has no error quantiles (one of 'pos', 'vel')" % (nm,))
+        if not names:
+            raise ValueError('error_quantiles: the quantiles of %s come from the fused free-integration plugins (FreeIntegration, '
+                             'FreeIntegrationOdo) and from InsLoose, and this Sim has none -- inclinometer, MagCal and host plugins '
+                             'are not covered' % (', '.join(data_names),))
+        if mc._group is not None:           # every rank, before any collective
+            raise NotImplementedError('error_quantiles: quantiles are not mergeable records, and the keys of the ranks of a '
+                                      'torch.distributed process group are not gathered yet -- run the Sim in one process '
+                                      '(Sim(devices=...) spreads it over the GPUs of one)')
+        for a in getattr(mc, 'loose_names', ()):
+            if not mc.job_of(a).keep_traj:
+                raise ValueError('error_quantiles: %s (InsLoose) kept statistics only: its keys are read from the kept trajectory '
+                                 'planes -- run the Sim with keep_trajectories=True' % a)
+        probs = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+        t = np.asarray(self.dmgr.time.data)
+        n = t.shape[0]
+        samples = self._samples_of('error_quantiles', every, samples, n)
+        out = {}
+        for nm in data_names:
+            res = {'time': t.copy() if samples is None else t[samples], 'units': ['m'] if nm == 'pos' else ['m/s'],
+                   'probs': probs.copy(), 'count': {}, 'horizontal': {}, 'vertical': {}, '3d': {}}
+            for a in names:
+                r = mc.error_quantiles(a, samples, n, which[nm], probs, self.max_device_bytes)
+                res['count'][a] = r.count[2].copy()         # the 3-D key is finite where all three components are
+                for k, part in enumerate(('horizontal', 'vertical', '3d')):
+                    res[part][a] = r.values[k].copy()
             out[nm] = res
         return out
 
@@ -1298,18 +1393,9 @@ class Sim(object):
                              'this Sim has none -- free integration, inclinometer, MagCal and host plugins carry no covariance')
         t = np.asarray(self.dmgr.time.data)
         n = t.shape[0]
-        if every is not None and samples is not None:
-            raise ValueError('consistency_curve: give every (seconds) or samples (indices), not both')
-        if every is not None:
-            step = int(round(float(every) * float(self.fs[0])))
-            if step < 1:
-                raise ValueError('consistency_curve: every=%r s is shorter than one sample at %g Hz' % (every, self.fs[0]))
-            samples = np.arange(0, n, step, dtype=np.int64)
+        samples = self._samples_of('consistency_curve', every, samples, n)
         if samples is None:
             samples = np.arange(n, dtype=np.int64)
-        samples = np.ascontiguousarray(np.asarray(samples, dtype=np.int64).reshape(-1))
-        if samples.size == 0 or samples.min() < 0 or samples.max() >= n:
-            raise ValueError('consistency_curve: samples must be indices in [0, %d), at least one' % n)
         out = {'time': t[samples], 'states': ['%s_%s' % (b, a) for b in ('dr', 'dv', 'psi', 'dbg', 'dba') for a in 'xyz']}
         for a, (_, job, _) in zip(names, getattr(self, 'loose_jobs', ())):
             if getattr(job, 'mag', None) is not None:

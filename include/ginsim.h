@@ -645,6 +645,31 @@ int ginsim_error_curve_f32(ginsim_ctx* ctx, const float* traj, const double* ref
  * record with the Chan merge of ginsim_stats_merge, in the order given. */
 int ginsim_curve_merge(const double* parts, int32_t nparts, int64_t m, double* out);
 
+/* ---- error quantiles across the runs (csrc/error_quantile.hip): the radius that holds a given share of the runs (CEP50, CEP95 /
+ *      R95) and the same quantiles of the vertical and the 3-D error.  Moments do not give them: the radial error is not Gaussian.
+ *      Added without a change of GINSIM_ABI_VERSION: nothing existing moved.
+ *      ginsim_radial_keys reads kept planes as ginsim_error_curve does (traj: device [9][n][runs]; ref: device [n][9]; samples:
+ *      HOST int64[m] in [0, n), any order, repeats allowed, or NULL = every sample, m must then be n) and forms, for which = 0 the
+ *      position error (components 3..5; pos_ned != 0: in local NED metres, what ref_frame 0 needs for a radius to mean anything)
+ *      or for which = 1 the velocity error (components 6..8; pos_ned is not looked at), with the error expression of
+ *      ginsim_error_curve.  Per (sample s, run r) it writes three non-negative keys, k = 0 horizontal sqrt(e0^2 + e1^2), k = 1
+ *      vertical |e2|, k = 2 3-D sqrt(e0^2 + e1^2 + e2^2), to the DEVICE array keys[(k * m + s) * row_stride + col0 + r]:
+ *      row_stride >= col0 + runs, so that blocks of runs (or devices) fill one row of row_stride keys per (k, s), each at its col0.
+ *      ginsim_quantile_rows: exact order statistics of each of `rows` rows of `len` doubles, row_stride (>= len) apart on the
+ *      device, for q (1..GINSIM_QUANTILE_MAX_PROBS) probabilities in (0, 1] at once.  Keys that are not finite are left out;
+ *      host_count[row] = N, the keys included.  host_out[row][i] is the k-th smallest included key, k = min(max(ceil(probs[i] * N),
+ *      1), N) with probs[i] * N one fp64 product -- nearest rank, np.quantile(method='inverted_cdf') --, one of the keys bit for
+ *      bit (no interpolation; -0.0 orders before +0.0), NaN when N = 0.  The same row gives the same bits at every call. */
+#define GINSIM_QUANTILE_MAX_PROBS 8
+int ginsim_radial_keys(ginsim_ctx* ctx, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                       int64_t m, int32_t which, int32_t pos_ned, double* keys, int64_t row_stride, int64_t col0);
+/* the same over the FLOAT trajectories of the fp32 kernel; origin, n_ini, ini_first as ginsim_error_curve_f32 takes them */
+int ginsim_radial_keys_f32(ginsim_ctx* ctx, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                           int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first,
+                           double* keys, int64_t row_stride, int64_t col0);
+int ginsim_quantile_rows(ginsim_ctx* ctx, const double* keys, int64_t rows, int64_t len, int64_t row_stride, const double* probs,
+                         int32_t q, double* host_out, double* host_count);
+
 /* ---- data access: pull selected runs out of a [ncomp][n][runs] device series into host [nsel][n][ncomp] */
 int ginsim_gather_runs(ginsim_ctx* ctx, const double* series, int32_t ncomp, int64_t n, int64_t runs,
                        const int64_t* run_ids /*host*/, int32_t nsel, double* host_out);
