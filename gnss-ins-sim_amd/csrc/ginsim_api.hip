@@ -1149,6 +1149,55 @@ int ginsim_quantile_rows(ginsim_ctx* c, const double* keys, int64_t rows, int64_
     return GINSIM_OK;
 }
 
+// ---- error covariance across the runs (csrc/error_cov.hip): the record of every requested sample
+// the scratch region: [records and slice records of error_cov.hip][m sample indices]
+static int cov_run(ginsim_ctx* c, const void* traj, int f32, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                   int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first,
+                   double* host_out) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t body = error_cov_scratch_bytes(runs, m);
+    void* ws = nullptr;
+    HIP_TRY(scratch(c, 2, body + sizeof(int64_t) * (size_t)m, &ws));
+    int64_t* d_samples = nullptr;
+    if (samples) {
+        d_samples = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ws) + body);
+        HIP_TRY(hipMemcpyAsync(d_samples, samples, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+    }
+    if (f32)
+        HIP_TRY(launch_error_cov_f32(reinterpret_cast<const float*>(traj), ref, n, runs, d_samples, m, which, pos_ned, ws, origin, n_ini,
+                                     ini_first, c->stream));
+    else
+        HIP_TRY(launch_error_cov(reinterpret_cast<const double*>(traj), ref, n, runs, d_samples, m, which, pos_ned, ws, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, ws, sizeof(double) * GINSIM_COV_RECORD * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
+int ginsim_error_cov(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
+                     int32_t which, int32_t pos_ned, double* host_out) {
+    const int rc = check_curve_args("error_cov", c, traj, ref, n, runs, samples, m, host_out);
+    if (rc) return rc;
+    REQUIRE(which == 0 || which == 1, "error_cov: which=%d is neither 0 (position) nor 1 (velocity)", (int)which);
+    return cov_run(c, traj, 0, ref, n, runs, samples, m, which, pos_ned, nullptr, 0, 0, host_out);
+}
+
+int ginsim_error_cov_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                         int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first,
+                         double* host_out) {
+    const int rc = check_curve_args("error_cov_f32", c, traj, ref, n, runs, samples, m, host_out);
+    if (rc) return rc;
+    REQUIRE(which == 0 || which == 1, "error_cov_f32: which=%d is neither 0 (position) nor 1 (velocity)", (int)which);
+    REQUIRE(origin && n_ini >= 1, "error_cov_f32: the origin table of the displacement series is missing");
+    return cov_run(c, traj, 1, ref, n, runs, samples, m, which, pos_ned, origin, n_ini, ini_first, host_out);
+}
+
+int ginsim_cov_merge(const double* parts, int32_t nparts, int64_t m, double* out) {
+    REQUIRE(parts && out, "cov_merge: NULL argument");
+    REQUIRE(nparts >= 1 && m >= 1, "cov_merge: nparts=%d m=%lld must be >= 1", (int)nparts, (long long)m);
+    cov_merge_host(parts, nparts, m, out);
+    return GINSIM_OK;
+}
+
 int ginsim_stats_merge(const ginsim_stats* parts, int32_t nparts, ginsim_stats* out) {
     REQUIRE(parts && out && nparts >= 1, "stats_merge: bad arguments");
     stats_merge_host(parts, nparts, out);

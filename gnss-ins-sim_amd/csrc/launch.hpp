@@ -115,6 +115,15 @@ hipError_t launch_radial_keys_f32(const float* traj, const double* ref, int64_t 
 hipError_t launch_quantile_rows(const double* keys, int64_t rows, int64_t len, int64_t row_stride, const double* probs, int q,
                                 double* out, double* count, hipStream_t s);
 
+// error_cov.hip
+size_t error_cov_scratch_bytes(int64_t runs, int64_t m);
+hipError_t launch_error_cov(const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
+                            int which, int pos_ned, void* scratch, hipStream_t s);
+hipError_t launch_error_cov_f32(const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
+                                int which, int pos_ned, void* scratch, const double* origin, int64_t n_ini, uint64_t ini_first,
+                                hipStream_t s);
+void cov_merge_host(const double* parts, int nparts, int64_t m, double* out);
+
 // Predicates on a parameter block that the dispatch of several files asks.
 inline int split_policy() {        // GINSIM_SPLIT=0 / 1 forces the plain / wave-specialised kernel (A/B measurements)
     static const int v = [] { const char* e = getenv("GINSIM_SPLIT"); return e ? atoi(e) : -1; }();

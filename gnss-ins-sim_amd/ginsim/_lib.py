@@ -241,6 +241,11 @@ _SIGS = {
     'ginsim_radial_keys_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
                                          C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_int64, C.c_int64]),
     'ginsim_quantile_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _PD, C.c_int32, _PD, _PD]),
+    'ginsim_error_cov': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                   C.c_int32, C.c_int32, _PD]),
+    'ginsim_error_cov_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, _PD]),
+    'ginsim_cov_merge': (C.c_int, [_PD, C.c_int32, C.c_int64, _PD]),
     'ginsim_gather_runs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                      C.POINTER(C.c_int64), C.c_int32, _PD]),
     'ginsim_gather_series': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .engine import StatsResult, CurveResult, ConsistencyResult
+from .engine import StatsResult, CurveResult, CovResult, ConsistencyResult
 
 RECORD = 28
 
@@ -72,6 +72,21 @@ def allgather_curve(part, group=None, device=None):
     rows = [torch.empty_like(mine) for _ in range(world)]
     dist.all_gather(rows, mine, group=group)
     return CurveResult.merge([r.cpu().numpy() for r in rows])
+
+
+def allgather_cov(part, group=None, device=None):
+    """allgather_curve for CovResult records: every rank's packed records are gathered (one all-gather, whatever the backend) and
+    folded in rank order with ginsim_cov_merge -- the same record on every rank.  A rank without runs contributes
+    CovResult.zero(m).  Identity when not distributed."""
+    if group is None:
+        return part
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    mine = torch.from_numpy(np.ascontiguousarray(part.pack()).reshape(-1)).to(device)
+    rows = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(rows, mine, group=group)
+    return CovResult.merge([r.cpu().numpy() for r in rows])
 
 
 def allgather_consistency(part, group=None, device=None):

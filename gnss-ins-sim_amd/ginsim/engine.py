@@ -581,6 +581,85 @@ class CurveResult(object):
         return CurveResult(out)
 
 
+class CovResult(object):
+    """count, mean vector and co-moment sums of a 3-vector error (position or velocity) ACROSS the runs at each of m samples
+    (ginsim_error_cov, GINSIM_COV_RECORD doubles each): count (m,), mean (m, 3), comoment (m, 6) = sum (e_a - mean_a)(e_b - mean_b)
+    in the order 00, 01, 02, 11, 12, 22.  Runs with a non-finite component at a sample did not enter that sample's record; a record
+    without runs has NaN mean and co-moments.  Records of disjoint sets of runs over the same samples merge (ginsim_cov_merge)."""
+    _UPPER = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+
+    def __init__(self, records):
+        r = np.asarray(records, dtype=np.float64).reshape(-1, 10)
+        self.count, self.mean, self.comoment = r[:, 0].copy(), r[:, 1:4].copy(), r[:, 4:10].copy()
+
+    @property
+    def m(self):
+        return self.count.shape[0]
+
+    @staticmethod
+    def zero(m):
+        """The record of a rank that holds no runs (neutral element of the merge)."""
+        return CovResult(np.zeros((int(m), 10)))
+
+    @property
+    def cov(self):
+        """(m, 3, 3) covariance, ddof 0 like every std of the project: comoment / count (NaN where count is 0)."""
+        out = np.empty((self.m, 3, 3))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            c = self.comoment / self.count[:, None]
+        for k, (a, b) in enumerate(self._UPPER):
+            out[:, a, b] = out[:, b, a] = c[:, k]
+        return out
+
+    def pack(self):
+        """(m, 10) records as the library lays them out."""
+        return np.concatenate([self.count[:, None], self.mean, self.comoment], axis=1)
+
+    @staticmethod
+    def unpack(v):
+        return CovResult(v)
+
+    @staticmethod
+    def merge(packed):
+        """Merge packed records (one (m, 10) array per block of runs, device or rank, in that order) with the library's Chan merge
+        (ginsim_cov_merge); records without runs are the neutral element."""
+        parts = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.float64).reshape(-1, 10) for p in packed]))
+        out = np.empty(parts.shape[1:])
+        check(lib.ginsim_cov_merge(dptr(parts), parts.shape[0], parts.shape[1], dptr(out)))
+        return CovResult(out)
+
+
+def track_frame(mean, cov, yaw):
+    """Mean (..., 3) and covariance (..., 3, 3) of an error in the frame's own axes, rotated about the vertical axis by the truth's
+    yaw (radians, (...,) or a scalar) into the track frame: along = cos(yaw) e0 + sin(yaw) e1, cross = -sin(yaw) e0 + cos(yaw) e1,
+    the vertical unchanged.  Returns (R mean, R cov R^T); the vertical row and column of the covariance rotate with it."""
+    mean, cov = np.asarray(mean, dtype=np.float64), np.asarray(cov, dtype=np.float64)
+    yaw = np.broadcast_to(np.asarray(yaw, dtype=np.float64), mean.shape[:-1])
+    R = np.zeros(mean.shape[:-1] + (3, 3))
+    R[..., 0, 0], R[..., 0, 1] = np.cos(yaw), np.sin(yaw)
+    R[..., 1, 0], R[..., 1, 1] = -np.sin(yaw), np.cos(yaw)
+    R[..., 2, 2] = 1.0
+    return np.einsum('...ab,...b->...a', R, mean), np.einsum('...ab,...bc,...dc->...ad', R, cov, R)
+
+
+def error_ellipse(cov2):
+    """(semi_major, semi_minor, azimuth) of the 1-sigma ellipse of a 2x2 covariance block [[a, b], [b, c]] (..., 2, 2): the square
+    roots of the eigenvalues (a + c) / 2 +- hypot((a - c) / 2, b), a smaller root that rounding made negative taken as 0, and the
+    azimuth of the major axis, atan2(2 b, a - c) / 2 in degrees, from axis 0 towards axis 1, in (-90, 90]; 0 for a circle.
+    The ellipse that holds a Gaussian error with probability p has these axes times sqrt(-2 ln(1 - p)): 1 sigma holds 39.3 %,
+    2.4477 sigma 95 %."""
+    cov2 = np.asarray(cov2, dtype=np.float64)
+    a, b, c = cov2[..., 0, 0], cov2[..., 0, 1], cov2[..., 1, 1]
+    mid, rad = (a + c) / 2.0, np.hypot((a - c) / 2.0, b)
+    with np.errstate(invalid='ignore'):
+        major = np.sqrt(mid + rad)
+        lo = mid - rad
+        minor = np.sqrt(np.where(lo < 0.0, 0.0, lo))
+    az = np.degrees(0.5 * np.arctan2(2.0 * b, a - c))
+    az = np.where(az <= -90.0, az + 180.0, az)
+    return major, minor, az
+
+
 QuantileResult = namedtuple('QuantileResult', 'values count')
 QuantileResult.__doc__ = """Order statistics of key rows (ginsim_quantile_rows): values (rows, q), for each row and probability one of the
 row's keys bit for bit (NaN where the row has no finite key); count (rows,), the finite keys of the row."""

@@ -128,6 +128,18 @@ class BatchJob(object):
                         (idx, m, int(bool(pos_ned))), dptr(out))
         return CurveResult(out)
 
+    def error_cov(self, algo=None, samples=None, which=0, pos_ned=False):
+        """The error covariance of this batch: the across-run record (CovResult: count, mean vector, co-moment sums) of the position
+        (which = 0; pos_ned: in local NED metres) or velocity (which = 1) error at each of `samples` (as error_curve takes them).
+        A run with a non-finite component at a sample is left out of that sample's record.  Needs the trajectories
+        (keep_traj=True)."""
+        from .engine import CovResult
+        idx, m, _keep = self._sample_arg(samples)
+        out = np.empty((max(m, 1), 10))
+        self._traj_call((lib.ginsim_error_cov, lib.ginsim_error_cov_f32), algo, 'an error covariance needs',
+                        (idx, m, int(which), int(bool(pos_ned))), dptr(out))
+        return CovResult(out)
+
     def _sample_arg(self, samples):
         """(POINTER(c_int64) | None, m, the array that owns the memory) of a sample list (None: every sample)."""
         if samples is None:

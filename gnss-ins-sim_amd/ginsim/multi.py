@@ -21,7 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from .engine import Context, MonteCarloJob, AuxSensorJob, StatsResult, CurveResult, device_count
+from .engine import Context, MonteCarloJob, AuxSensorJob, StatsResult, CurveResult, CovResult, device_count
 from .distributed import shard
 
 
@@ -188,6 +188,13 @@ class JobSet(_Parts):
         if not got:                     # no device holds runs: the empty curve
             return CurveResult.zero(self.n if samples is None else np.asarray(samples).size)
         return CurveResult.merge([c.pack() for c in got])
+
+    def error_cov(self, algo, samples=None, which=0, pos_ned=False):
+        """MonteCarloJob.error_cov on every device at the same time; the per-device records folded on the host in device order."""
+        got = [c for c in self._each_part(lambda j: j.error_cov(algo, samples, which, pos_ned=pos_ned)) if c is not None]
+        if not got:                     # no device holds runs: the empty record
+            return CovResult.zero(self.n if samples is None else np.asarray(samples).size)
+        return CovResult.merge([c.pack() for c in got])
 
     def radial_keys_host(self, algo, samples=None, which=0):
         """MonteCarloJob.radial_keys on every device at the same time, brought to the host: (3 m, runs) rows of keys, the

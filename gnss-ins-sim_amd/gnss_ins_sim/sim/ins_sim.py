@@ -231,6 +231,26 @@ class _McResults(object):
             self._stats[key] = distributed.allgather_curve(part, self._group, self._device)
         return self._stats[key]
 
+    def error_covariance(self, name, samples, n, which, ned=False):
+        """ginsim.CovResult of algorithm `name` over ALL runs of the Sim: the across-run count, mean vector and co-moment sums of
+        the position (which = 0) or velocity (which = 1) error at each of `samples` (int64 sample indices; None: every one of the
+        n samples).  Shaped like error_curve: kept trajectories in one call, statistics-only runs integrated again through _blocks
+        and folded block by block, merged over devices (JobSet) and ranks; every rank takes the same branches."""
+        key = ('cov', name, None if samples is None else samples.tobytes(), int(which))
+        if key not in self._stats:
+            import ginsim
+            from ginsim import distributed
+            idx = self.algo_names.index(name)
+            job, kind = self.jobs[idx], self.kinds[idx]
+            if job is None:                 # a rank without runs: the empty record, into the same collective
+                part = ginsim.CovResult.zero(n if samples is None else samples.size)
+            elif job.keep_traj:
+                part = job.error_cov(kind, samples, which, pos_ned=ned)
+            else:
+                part = ginsim.CovResult.merge([b.error_cov(kind, samples, which, pos_ned=ned).pack() for b in self._blocks(idx)])
+            self._stats[key] = distributed.allgather_cov(part, self._group, self._device)
+        return self._stats[key]
+
     def error_quantiles(self, name, samples, n, which, probs, budget):
         """ginsim.QuantileResult (values (3, m, q), count (3, m): horizontal, vertical, 3-D) of algorithm `name` over ALL runs of
         the Sim at `samples`: one key buffer [3][m][runs] on the selecting device, then one select.  Kept trajectories fill it in
@@ -1366,6 +1386,69 @@ class Sim(object):
                 res['count'][a] = r.count[2].copy()         # the 3-D key is finite where all three components are
                 for k, part in enumerate(('horizontal', 'vertical', '3d')):
                     res[part][a] = r.values[k].copy()
+            out[nm] = res
+        return out
+
+    def error_covariance(self, data_names=('pos',), *, every=None, samples=None, frame='track'):
+        """Which way the error points: the across-run mean vector and 3x3 covariance (ddof 0) of the position or velocity error at
+        each instant, reduced on the device, and from it the correlation coefficients and the horizontal 1-sigma error ellipse.
+        ``error_curve`` gives per-axis sigmas and ``error_quantiles`` one radius; an odometer-aided filter whose error is a narrow
+        strip across the track looks unremarkable in both.
+          data_names 'pos' and / or 'vel'.  The position error of ref_frame 0 is always taken in local NED metres
+          every      seconds between the instants (from the first sample); None and samples=None: every sample
+          samples    or the sample indices themselves (any order, repeats allowed)
+          frame      'nav': the frame's own axes (north, east, down in ref_frame 0; x, y, z in ref_frame 1); 'track': rotated about
+                     the vertical axis by the truth's yaw at each instant (ginsim.track_frame): along, cross, down
+        Returns {name: {'time': (m,), 'units': ['m'] | ['m/s'], 'frame': frame, 'axes': (three names), 'count': {algorithm name:
+        (m,) the runs that entered: a run with a non-finite component at an instant is left out there}, 'mean': {(m, 3)}, 'cov':
+        {(m, 3, 3)}, 'corr': {(m, 3, 3) correlation coefficients, NaN where a variance is 0}, 'ellipse': {(m, 3): semi-major,
+        semi-minor and azimuth of the major axis in degrees of the horizontal 1-sigma ellipse (ginsim.error_ellipse); the azimuth
+        from north (axis 0) in 'nav', from the track in 'track'}}}.  Served: what ``error_curve`` serves -- the fused
+        free-integration plugins, kept or statistics only (their runs are integrated again in blocks that fit
+        ``max_device_bytes``), several devices, a process group -- and InsLoose with kept trajectories."""
+        if not self.sim_complete:
+            print("Call Sim.run() to run the simulaltion first.")
+            return None
+        import ginsim
+        d, mc = self.dmgr, self.mc
+        names = list(getattr(mc, 'nav_names', None) or getattr(mc, 'fused_names', None) or []) \
+            if mc is not None and not self.data_from_files else []
+        if isinstance(data_names, str):
+            data_names = (data_names,)
+        which = {'pos': 0, 'vel': 1}
+        for nm in data_names:
+            if nm not in which:
+                raise ValueError("error_covariance: %r has no error covariance (one of 'pos', 'vel')" % (nm,))
+        if frame not in ('nav', 'track'):
+            raise ValueError("error_covariance: frame=%r is neither 'nav' nor 'track'" % (frame,))
+        if not names:
+            raise ValueError('error_covariance: the covariance of %s comes from the fused free-integration plugins (FreeIntegration, '
+                             'FreeIntegrationOdo) and from InsLoose, and this Sim has none -- inclinometer, MagCal and host plugins '
+                             'are not covered' % (', '.join(data_names),))
+        for a in getattr(mc, 'loose_names', ()):
+            if not mc.job_of(a).keep_traj:
+                raise ValueError('error_covariance: %s (InsLoose) kept statistics only: its covariance is read from the kept '
+                                 'trajectory planes -- run the Sim with keep_trajectories=True' % a)
+        t = np.asarray(d.time.data)
+        n = t.shape[0]
+        samples = self._samples_of('error_covariance', every, samples, n)
+        yaw = np.asarray(d.ref_att_euler.data, dtype=np.float64)[:, 0]
+        yaw = yaw.copy() if samples is None else yaw[samples]
+        axes = ('along', 'cross', 'down') if frame == 'track' else ('north', 'east', 'down') if self.ref_frame == 0 else ('x', 'y', 'z')
+        out = {}
+        for nm in data_names:
+            res = {'time': t.copy() if samples is None else t[samples], 'units': ['m'] if nm == 'pos' else ['m/s'], 'frame': frame,
+                   'axes': axes, 'count': {}, 'mean': {}, 'cov': {}, 'corr': {}, 'ellipse': {}}
+            for a in names:
+                r = mc.error_covariance(a, samples, n, which[nm], ned=self.ref_frame == 0)
+                mean, cov = r.mean.copy(), r.cov
+                if frame == 'track':
+                    mean, cov = ginsim.track_frame(mean, cov, yaw)
+                sd = np.sqrt(np.einsum('kaa->ka', cov))
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    corr = cov / (sd[:, :, None] * sd[:, None, :])
+                res['count'][a], res['mean'][a], res['cov'][a], res['corr'][a] = r.count.copy(), mean, cov, corr
+                res['ellipse'][a] = np.stack(ginsim.error_ellipse(cov[:, :2, :2]), axis=1)
             out[nm] = res
         return out
 

@@ -670,6 +670,29 @@ int ginsim_radial_keys_f32(ginsim_ctx* ctx, const float* traj, const double* ref
 int ginsim_quantile_rows(ginsim_ctx* ctx, const double* keys, int64_t rows, int64_t len, int64_t row_stride, const double* probs,
                          int32_t q, double* host_out, double* host_count);
 
+/* ---- error covariance across the runs (csrc/error_cov.hip): the mean vector and the 3x3 covariance of the position or velocity
+ *      error at every requested sample -- which way the error points (along / cross track, the error ellipse), what neither the
+ *      per-component moments of ginsim_error_curve nor the radii of ginsim_quantile_rows tell.  Added without a change of
+ *      GINSIM_ABI_VERSION: nothing existing moved.
+ *      traj, ref, n, runs, samples, m as ginsim_radial_keys takes them; which = 0 the position error (components 3..5; pos_ned != 0:
+ *      in local NED metres), which = 1 the velocity error (components 6..8; pos_ned is not looked at), with the error expression of
+ *      ginsim_error_curve; only those three planes are read.  host_out: [m] records of GINSIM_COV_RECORD doubles: count, mean[3],
+ *      C[6] = sum (e_a - mean_a)(e_b - mean_b) over the runs in the order 00, 01, 02, 11, 12, 22; covariance (ddof 0) = C / count.
+ *      A run with ANY of its three components not finite at a sample is left out of that sample's record (unlike
+ *      ginsim_error_curve, which lets it poison the record): count is the number of runs that entered.  count = 0: mean and C are
+ *      NaN; count = 1: the run's error and C exactly 0.  The same (n, runs, m) gives the same bits at every call. */
+#define GINSIM_COV_RECORD 10
+int ginsim_error_cov(ginsim_ctx* ctx, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                     int64_t m, int32_t which, int32_t pos_ned, double* host_out);
+/* the same over the FLOAT trajectories of the fp32 kernel; origin, n_ini, ini_first as ginsim_error_curve_f32 takes them */
+int ginsim_error_cov_f32(ginsim_ctx* ctx, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
+                         int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first,
+                         double* host_out);
+/* Host only: the records of nparts sets of runs (parts: [nparts][m] records; a set without runs is all zeros, or any record of
+ * count 0) folded record by record with C = C_a + C_b + dd^T n_a n_b / n, d = mean_b - mean_a, in the order given; a result
+ * without runs is count 0 with NaN mean and C. */
+int ginsim_cov_merge(const double* parts, int32_t nparts, int64_t m, double* out);
+
 /* ---- data access: pull selected runs out of a [ncomp][n][runs] device series into host [nsel][n][ncomp] */
 int ginsim_gather_runs(ginsim_ctx* ctx, const double* series, int32_t ncomp, int64_t n, int64_t runs,
                        const int64_t* run_ids /*host*/, int32_t nsel, double* host_out);
