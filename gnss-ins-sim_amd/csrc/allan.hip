@@ -941,6 +941,7 @@ bool allan_fuse_applies(const double* in, const AllanLevel& lv, const AllanLevel
     return on != 0 && allan_dma_applies(in, lv) && lv.n_out == lv1.n_in && lv1.n_in > kChunk;
 }
 int allan_fuse_parts(const AllanLevel& lv) { return (lv.nchunks + kFuseChunks - 1) / kFuseChunks; }
+int allan_fuse_chunks() { return kFuseChunks; }
 int allan_fuse_record() { return kFuseRecord; }
 
 hipError_t launch_allan_fused(const double* in, double* out1, double* out2, double* partial0, double* partial1, const AllanLevel& lv,

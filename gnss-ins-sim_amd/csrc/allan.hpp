@@ -45,6 +45,7 @@ hipError_t launch_allan_pair(const double* in, double* out, double* partial, con
 // last workgroup of a series only), out2 = level k+2, partial0 / partial1 = the records of the two levels
 bool allan_fuse_applies(const double* in, const AllanLevel& lv, const AllanLevel& lv1);
 int allan_fuse_parts(const AllanLevel& lv);
+int allan_fuse_chunks();        // chunks of level k per workgroup
 int allan_fuse_record();        // doubles per level-k+1 record (a multiple of 9)
 hipError_t launch_allan_fused(const double* in, double* out1, double* out2, double* partial0, double* partial1, const AllanLevel& lv,
                               const AllanLevel& lv1, int64_t nseries, hipStream_t st);

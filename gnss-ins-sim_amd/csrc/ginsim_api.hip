@@ -42,6 +42,7 @@ struct ginsim_ctx {
     size_t ws_bytes[4] = {0, 0, 0, 0};
     double* allan_host = nullptr;                         // pinned host memory the Allan kernels write their sums into
     size_t allan_host_doubles = 0;
+    int max_grid_y = 65535;                               // the device's maxGridSize[1]: the Allan kernels have the series there
     ginsim::Comm* comm = nullptr;                         // RCCL communicator of this rank (ginsim_comm_init), or nullptr
     double* comm_recv = nullptr;                          // device [8 slots][nranks][28]: the gathered records
     ginsim_stats* comm_host = nullptr;                    // pinned host copy of the same
@@ -121,6 +122,123 @@ static int gather_run(const char* who, ginsim_ctx* c, const void* series, int32_
     return GINSIM_OK;
 }
 
+// What one Allan call runs: the averaging factors of allan.py:29-43, the decade levels, and for every level the kernel form that
+// takes it.  Host arithmetic only; ginsim_allan launches from it and ginsim_allan_plan reports it, so the two cannot differ.
+struct AllanStep { int k; int mode; };     // mode 0: allan_level_kernel, 1: wave-pair LDS-DMA kernel, 2: levels k and k+1 fused
+struct AllanPlan {
+    std::vector<int64_t> mult;             // the averaging factors; empty = the series is shorter than 9 s
+    int levels = 0;
+    std::vector<AllanLevel> lvs;
+    AllanFold fold;
+    int64_t records = 0;
+    std::vector<AllanStep> steps;
+    std::vector<int32_t> mode, chunks_per_block, nparts;       // per level, as ginsim_allan_level reports them
+};
+
+static int allan_plan(const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, AllanPlan& P) {
+    REQUIRE(n >= 1 && nseries >= 1 && series_stride >= n && fs > 0, "allan: bad sizes");
+    // averaging factors exactly as allan.py:29-43
+    const double ts = 1.0 / fs;
+    const int64_t mmax = (int64_t)floor((double)n / 9.0);
+    if ((double)mmax * ts < 1.0) return GINSIM_OK;
+    std::vector<int64_t>& mult = P.mult;
+    const int decades = (int)ceil(log10((double)mmax));
+    double scale = 0.1;
+    for (int i = 0; i < decades; ++i) {
+        scale *= 10;
+        for (int j = 1; j < 10; ++j) {
+            const int64_t m = (int64_t)(j * scale);
+            if (m > mmax) break;
+            mult.push_back(m);
+        }
+    }
+    const int levels = P.levels = decades;
+    // levels of more than one chunk: per-wavefront / per-workgroup partial sums; ONE launch at the end folds them and runs
+    // the levels of at most one chunk (the last three or four).  Where the level's rows are 16-byte aligned the
+    // LDS-DMA wave-pair kernel takes the level, otherwise the register-staged one.
+    std::vector<AllanLevel>& lvs = P.lvs;
+    lvs.resize(levels);
+    AllanFold& fold = P.fold;
+    fold.nlevels = 0;
+    fold.fused_level = -1;
+    fold.pad = 0;
+    for (int j = 0; j < 9; ++j) fold.fused_nb[j] = 0;
+    int64_t& records = P.records;
+    std::vector<AllanStep>& steps = P.steps;
+    P.mode.assign(levels, 4);
+    P.chunks_per_block.assign(levels, 1);
+    P.nparts.assign(levels, 1);
+    {
+        int64_t n_in = n, stride_in = series_stride, pow10 = 1;
+        for (int k = 0; k < levels; ++k) {
+            AllanLevel& lv = lvs[k];
+            lv.n_in = n_in;
+            lv.n_out = (k + 1 < levels) ? n_in / 10 : 0;
+            lv.in_stride = stride_in;
+            lv.out_stride = lv.n_out;
+            for (int j = 1; j <= 9; ++j) lv.nb[j - 1] = (j * pow10 <= mmax) ? n / (j * pow10) : 0;
+            lv.nchunks = allan_chunks(n_in);
+            lv.chunks_per_block = allan_chunks_per_block((int64_t)lv.nchunks * nseries);
+            stride_in = lv.n_out;
+            n_in = lv.n_out;
+            pow10 *= 10;
+        }
+        int k = 0;
+        if (levels >= 2 && lvs[0].n_in > allan_chunk_entries() && allan_fuse_applies(x, lvs[0], lvs[1])) {
+            // levels 0 and 1 in one launch: the entries of level 1 never leave the chip (round 5; csrc/allan.hip)
+            const int parts = allan_fuse_parts(lvs[0]);
+            fold.nparts[0] = parts;
+            fold.offset[0] = records;
+            records += (int64_t)parts * nseries;
+            fold.nparts[1] = parts;
+            fold.offset[1] = records;
+            records += (int64_t)parts * nseries * (allan_fuse_record() / 9);
+            fold.fused_level = 1;
+            for (int j = 0; j < 9; ++j) fold.fused_nb[j] = lvs[1].nb[j];
+            steps.push_back(AllanStep{0, 2});
+            P.mode[0] = 2;
+            P.mode[1] = 3;
+            P.chunks_per_block[0] = allan_fuse_chunks();
+            P.nparts[0] = P.nparts[1] = parts;
+            k = 2;
+        }
+        while (k < levels && lvs[k].n_in > allan_chunk_entries()) {
+            REQUIRE(k < 8, "allan: series too long");
+            AllanLevel& lv = lvs[k];
+            // intermediate levels live in this call's scratch region, whose rows start 256-byte aligned
+            const bool dma = allan_dma_applies(k == 0 ? x : reinterpret_cast<const double*>(uintptr_t(256)), lv);
+            int parts;
+            if (dma) {      // four workgroups per CU: ~1024 in flight; up to 8 chunks each so that the first, exposed load is amortised
+                // a level that fits ONE round of resident workgroups (1024) with at most 16 chunks each runs as one (a second,
+                // partly filled round costs a whole workgroup time: 144 000 entries x 192 series 62 -> 51 us); longer levels
+                // in runs of 8 chunks
+                static const int cap = [] { const char* e = getenv("GINSIM_ALLAN_CPB"); return e && atoi(e) > 0 ? atoi(e) : 8; }();
+                const int64_t total = (int64_t)lv.nchunks * nseries;
+                const int64_t max_parts = nseries <= 1024 ? 1024 / nseries : 1;         // workgroups per series in one round
+                const int64_t fit = (lv.nchunks + max_parts - 1) / max_parts;
+                const bool single = fit <= 16;
+                const int64_t per = single ? fit : total / 4096;
+                const int64_t lim = single ? 16 : cap;
+                lv.chunks_per_block = (int32_t)(per < 1 ? 1 : (per > lim ? lim : per));
+                parts = allan_pair_parts(lv);
+            } else {
+                parts = allan_parts(lv);
+            }
+            fold.nparts[k] = parts;
+            fold.offset[k] = records;
+            records += (int64_t)parts * nseries;
+            steps.push_back(AllanStep{k, dma ? 1 : 0});
+            P.mode[k] = dma ? 1 : 0;
+            P.chunks_per_block[k] = lv.chunks_per_block;
+            P.nparts[k] = parts;
+            ++k;
+        }
+        fold.nlevels = k;
+    }
+    REQUIRE(levels - fold.nlevels <= 4, "allan: internal level plan");
+    return GINSIM_OK;
+}
+
 extern "C" {
 
 int ginsim_abi_version(void) { return GINSIM_ABI_VERSION; }
@@ -155,6 +273,7 @@ int ginsim_create(int device, ginsim_ctx** out) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&c->ev0));
     HIP_TRY(hipEventCreate(&c->ev1));
+    HIP_TRY(hipDeviceGetAttribute(&c->max_grid_y, hipDeviceAttributeMaxGridDimY, device));
     ginsim::placed_context_created(device);
     *out = c;
     return GINSIM_OK;
@@ -1279,104 +1398,51 @@ int ginsim_free_integration(ginsim_ctx* c, int32_t algo, int32_t ref_frame, doub
     return GINSIM_OK;
 }
 
+int ginsim_allan_plan(const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t* ntau, int32_t* nlevels,
+                      ginsim_allan_level* levels, int32_t cap) {
+    REQUIRE(ntau && nlevels && (levels || cap == 0) && cap >= 0, "allan_plan: bad arguments");
+    AllanPlan P;
+    const int rc = allan_plan(x, n, nseries, series_stride, fs, P);
+    if (rc) return rc;
+    *ntau = (int32_t)P.mult.size();
+    *nlevels = P.levels;
+    if (P.levels > cap) { set_error("allan_plan: %d levels but capacity %d", P.levels, cap); return GINSIM_ERR_RANGE; }
+    for (int k = 0; k < P.levels; ++k) {
+        levels[k].n_in = P.lvs[k].n_in;
+        levels[k].in_stride = P.lvs[k].in_stride;
+        levels[k].mode = P.mode[k];
+        levels[k].chunks_per_block = P.chunks_per_block[k];
+        levels[k].nparts = P.nparts[k];
+        levels[k].reserved = 0;
+    }
+    return GINSIM_OK;
+}
+
 int ginsim_allan(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, double* tau,
                  double* avar, int32_t* ntau, int32_t cap) {
     REQUIRE(c && x && tau && avar && ntau, "allan: NULL argument");
-    REQUIRE(n >= 1 && nseries >= 1 && series_stride >= n && fs > 0, "allan: bad sizes");
-    // averaging factors exactly as allan.py:29-43
-    const double ts = 1.0 / fs;
-    const int64_t mmax = (int64_t)floor((double)n / 9.0);
     *ntau = 0;
-    if ((double)mmax * ts < 1.0) return GINSIM_OK;
-    std::vector<int64_t> mult;
-    const int decades = (int)ceil(log10((double)mmax));
-    double scale = 0.1;
-    for (int i = 0; i < decades; ++i) {
-        scale *= 10;
-        for (int j = 1; j < 10; ++j) {
-            const int64_t m = (int64_t)(j * scale);
-            if (m > mmax) break;
-            mult.push_back(m);
-        }
-    }
+    AllanPlan P;
+    const int rc = allan_plan(x, n, nseries, series_stride, fs, P);
+    if (rc) return rc;
+    const std::vector<int64_t>& mult = P.mult;
     const int nt = (int)mult.size();
+    if (nt == 0) return GINSIM_OK;
+    // the three chunked kernels put the series on the grid's y dimension; the finishing launch has them on x
+    if (!P.steps.empty() && nseries > c->max_grid_y) {
+        set_error("allan: %d series on the grid's y dimension but the device takes %d: split the batch into calls of at most %d series",
+                  (int)nseries, c->max_grid_y, c->max_grid_y);
+        return GINSIM_ERR_RANGE;
+    }
     if (nt > cap) { set_error("allan: %d averaging factors but capacity %d", nt, cap); return GINSIM_ERR_RANGE; }
     HIP_TRY(hipSetDevice(c->device));
-    const int levels = decades;
+    const double ts = 1.0 / fs;
+    const int levels = P.levels;
     const int64_t n1 = n / 10;
-    // levels of more than one chunk: per-wavefront / per-workgroup partial sums; ONE launch at the end folds them and runs
-    // the levels of at most one chunk (the last three or four).  Where the level's rows are 16-byte aligned the
-    // LDS-DMA wave-pair kernel takes the level, otherwise the register-staged one.
-    std::vector<AllanLevel> lvs(levels);
-    AllanFold fold;
-    fold.nlevels = 0;
-    fold.fused_level = -1;
-    fold.pad = 0;
-    for (int j = 0; j < 9; ++j) fold.fused_nb[j] = 0;
-    int64_t records = 0;
-    struct Step { int k; int mode; };      // mode 0: allan_level_kernel, 1: wave-pair LDS-DMA kernel, 2: levels k and k+1 fused
-    std::vector<Step> steps;
-    {
-        int64_t n_in = n, stride_in = series_stride, pow10 = 1;
-        for (int k = 0; k < levels; ++k) {
-            AllanLevel& lv = lvs[k];
-            lv.n_in = n_in;
-            lv.n_out = (k + 1 < levels) ? n_in / 10 : 0;
-            lv.in_stride = stride_in;
-            lv.out_stride = lv.n_out;
-            for (int j = 1; j <= 9; ++j) lv.nb[j - 1] = (j * pow10 <= mmax) ? n / (j * pow10) : 0;
-            lv.nchunks = allan_chunks(n_in);
-            lv.chunks_per_block = allan_chunks_per_block((int64_t)lv.nchunks * nseries);
-            stride_in = lv.n_out;
-            n_in = lv.n_out;
-            pow10 *= 10;
-        }
-        int k = 0;
-        if (levels >= 2 && lvs[0].n_in > allan_chunk_entries() && allan_fuse_applies(x, lvs[0], lvs[1])) {
-            // levels 0 and 1 in one launch: the entries of level 1 never leave the chip (round 5; csrc/allan.hip)
-            const int parts = allan_fuse_parts(lvs[0]);
-            fold.nparts[0] = parts;
-            fold.offset[0] = records;
-            records += (int64_t)parts * nseries;
-            fold.nparts[1] = parts;
-            fold.offset[1] = records;
-            records += (int64_t)parts * nseries * (allan_fuse_record() / 9);
-            fold.fused_level = 1;
-            for (int j = 0; j < 9; ++j) fold.fused_nb[j] = lvs[1].nb[j];
-            steps.push_back(Step{0, 2});
-            k = 2;
-        }
-        while (k < levels && lvs[k].n_in > allan_chunk_entries()) {
-            REQUIRE(k < 8, "allan: series too long");
-            AllanLevel& lv = lvs[k];
-            // intermediate levels live in this call's scratch region, whose rows start 256-byte aligned
-            const bool dma = allan_dma_applies(k == 0 ? x : reinterpret_cast<const double*>(uintptr_t(256)), lv);
-            int parts;
-            if (dma) {      // four workgroups per CU: ~1024 in flight; up to 8 chunks each so that the first, exposed load is amortised
-                // a level that fits ONE round of resident workgroups (1024) with at most 16 chunks each runs as one (a second,
-                // partly filled round costs a whole workgroup time: 144 000 entries x 192 series 62 -> 51 us); longer levels
-                // in runs of 8 chunks
-                static const int cap = [] { const char* e = getenv("GINSIM_ALLAN_CPB"); return e && atoi(e) > 0 ? atoi(e) : 8; }();
-                const int64_t total = (int64_t)lv.nchunks * nseries;
-                const int64_t max_parts = nseries <= 1024 ? 1024 / nseries : 1;         // workgroups per series in one round
-                const int64_t fit = (lv.nchunks + max_parts - 1) / max_parts;
-                const bool single = fit <= 16;
-                const int64_t per = single ? fit : total / 4096;
-                const int64_t lim = single ? 16 : cap;
-                lv.chunks_per_block = (int32_t)(per < 1 ? 1 : (per > lim ? lim : per));
-                parts = allan_pair_parts(lv);
-            } else {
-                parts = allan_parts(lv);
-            }
-            fold.nparts[k] = parts;
-            fold.offset[k] = records;
-            records += (int64_t)parts * nseries;
-            steps.push_back(Step{k, dma ? 1 : 0});
-            ++k;
-        }
-        fold.nlevels = k;
-    }
-    REQUIRE(levels - fold.nlevels <= 4, "allan: internal level plan");
+    const std::vector<AllanLevel>& lvs = P.lvs;
+    const AllanFold& fold = P.fold;
+    const int64_t records = P.records;
+    const std::vector<AllanStep>& steps = P.steps;
     struct Region { void* p; double* d() const { return reinterpret_cast<double*>(p); } } ping, pong, partial;
     const size_t b_ping = sizeof(double) * (size_t)nseries * (n1 + 1), b_pong = sizeof(double) * (size_t)nseries * (n1 / 10 + 1);
     const size_t b_part = sizeof(double) * 9 * (size_t)(records + 1), b_sums = 0;
@@ -1387,7 +1453,7 @@ int ginsim_allan(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, int
     partial.p = reinterpret_cast<char*>(pong.p) + ((b_pong + 255) & ~(size_t)255);
     const double* in = x;
     int flip = 0;
-    for (const Step& st : steps) {
+    for (const AllanStep& st : steps) {
         // level k+1 (<= n/10 entries per series) goes to ping, k+2 to pong, ...
         const int k = st.k;
         if (st.mode == 2) {             // level k+1 -> ping (its last workgroup per series only), level k+2 -> pong

@@ -150,6 +150,12 @@ class MagCalParams(C.Structure):
                 ('out_si', C.c_void_p), ('out_hi', C.c_void_p), ('out_cal', C.c_void_p)]
 
 
+class AllanLevel(C.Structure):
+    """ginsim_allan_level: one decade level of an Allan call as ginsim_allan_plan reports it."""
+    _fields_ = [('n_in', C.c_int64), ('in_stride', C.c_int64), ('mode', C.c_int32), ('chunks_per_block', C.c_int32),
+                ('nparts', C.c_int32), ('reserved', C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [('count', C.c_double), ('mean', C.c_double * 9), ('m2', C.c_double * 9),
                 ('maxabs', C.c_double * 9)]
@@ -257,6 +263,8 @@ _SIGS = {
                                           _PD, _PD, _PD]),
     'ginsim_allan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, _PD, _PD,
                                C.POINTER(C.c_int32), C.c_int32]),
+    'ginsim_allan_plan': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), C.POINTER(AllanLevel), C.c_int32]),
     'ginsim_runs_to_series': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     'ginsim_normal_transform': (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64, _PD, _PD]),
     'ginsim_rng_normals': (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int64, _PD, _PD,

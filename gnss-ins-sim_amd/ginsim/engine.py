@@ -1197,6 +1197,21 @@ def allan_var(ctx, x, n, nseries, series_stride, fs, cap=128):
     return np.ascontiguousarray(avar[:, :nt.value]), tau[:nt.value].copy()
 
 
+ALLAN_MODES = ('level', 'pair', 'fused0', 'fused1', 'tail')      # ginsim_allan_level.mode 0..4
+
+
+def allan_plan(x, n, nseries, series_stride, fs):
+    """What ``allan_var`` with these arguments runs, from the library's own planning code (ginsim_allan_plan: host only, no
+    context, nothing launched; of `x` only the address modulo 16 counts).  Returns (ntau, levels), one dict per decade level
+    with n_in, in_stride, mode (index into ALLAN_MODES), chunks_per_block and nparts."""
+    ptr = getattr(x, 'ptr', x)
+    lv = (_lib.AllanLevel * 16)()
+    nt, nl = C.c_int32(0), C.c_int32(0)
+    check(lib.ginsim_allan_plan(ptr, int(n), int(nseries), int(series_stride), float(fs), C.byref(nt), C.byref(nl), lv, 16))
+    return nt.value, [dict(n_in=l.n_in, in_stride=l.in_stride, mode=l.mode, chunks_per_block=l.chunks_per_block, nparts=l.nparts)
+                      for l in lv[:nl.value]]
+
+
 def allan_var_host(ctx, series, fs):
     """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (avar, tau)."""
     a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))

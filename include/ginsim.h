@@ -719,6 +719,21 @@ int ginsim_free_integration(ginsim_ctx* ctx, int32_t algo, int32_t ref_frame, do
 int ginsim_allan(ginsim_ctx* ctx, const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs,
                  double* tau, double* avar, int32_t* ntau, int32_t cap);
 
+/* Which kernel form ginsim_allan runs at every decade level of such a call, from the planning code the call itself launches
+ * from.  Host arithmetic only: no context, no device, nothing launched, x never followed (only its value modulo 16 counts).
+ * Level k holds n / 10^k entries per series.  mode: 0 register-staged allan_level_kernel, 1 wave-pair LDS-DMA allan_pair_kernel,
+ * 2 allan_fused_kernel as its first level, 3 as its second, 4 allan_tail_kernel (levels of at most one 2520-entry chunk).
+ * chunks_per_block and nparts: chunks a wavefront (mode 0) or workgroup (1, 2, 3) folds, and partial records per series.
+ * *ntau as ginsim_allan reports it, *nlevels = levels of the call (0 when ntau is 0); GINSIM_ERR_RANGE when cap is smaller.
+ * A call whose chunked levels (modes 0-3) have more series than the device's maxGridSize[1] is refused by ginsim_allan with
+ * GINSIM_ERR_RANGE before any launch: split the batch.  Added without a change of GINSIM_ABI_VERSION: nothing existing moved. */
+typedef struct {
+    int64_t n_in, in_stride;
+    int32_t mode, chunks_per_block, nparts, reserved;
+} ginsim_allan_level;
+int ginsim_allan_plan(const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t* ntau,
+                      int32_t* nlevels, ginsim_allan_level* levels /*[cap]*/, int32_t cap);
+
 /* Device-to-device re-layout of a Monte-Carlo series [ncomp][n][runs] (run fastest, what ginsim_mc_run writes) into
  * per-run contiguous series [runs][ncomp][n] -- the input layout of ginsim_allan, so that the Allan plugin
  * (demo_algorithms/allan_analysis.py:33-49) works on the generated sensors without a host round trip. */

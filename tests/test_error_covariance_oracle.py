@@ -29,9 +29,9 @@ def test_header_declares_and_library_exports_and_binds_the_new_entry_points():
         assert getattr(ginsim.lib, name).argtypes is not None
     assert ginsim.lib.ginsim_abi_version() == 9
     assert 'GINSIM_COV_RECORD 10' in hdr
-    assert len(declared) == 85
+    assert len(declared) == 86
     readme = open(os.path.join(REPO, 'README.md')).read()
-    assert '85 entry points' in readme
+    assert '86 entry points' in readme
     assert callable(ginsim.track_frame) and callable(ginsim.error_ellipse)
     for f in ('pack', 'unpack', 'merge', 'zero', 'cov'):
         assert hasattr(ginsim.CovResult, f)
