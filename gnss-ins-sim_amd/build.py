@@ -73,6 +73,7 @@ SOURCES = [
     # no spills)
     ('error_cov.hip', ['--offload-arch=' + ARCH, '-mllvm', '-disable-machine-licm']),
     ('allan.hip', ['--offload-arch=' + ARCH]),
+    ('oallan.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),
     ('vib_psd.hip', ['--offload-arch=' + ARCH]),
     ('selftest.hip', ['--offload-arch=' + ARCH]),
@@ -99,6 +100,7 @@ def build(force=False, verbose=False, tag=None, defines=(), xflags=()):
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hpp', '.h'))]
     deps.append(os.path.join(REPO, 'include', 'ginsim.h'))
+    deps.append(os.path.join(REPO, 'include', 'ginsim_oallan.h'))
     deps.append(os.path.abspath(__file__))
     objs = []
     for src, extra in SOURCES:

@@ -11,7 +11,9 @@
 #include <vector>
 
 #include "ginsim.h"
+#include "ginsim_oallan.h"
 #include "allan.hpp"
+#include "oallan.hpp"
 #include "comm.hpp"
 #include "launch.hpp"
 #include "placed.hpp"
@@ -135,13 +137,11 @@ struct AllanPlan {
     std::vector<int32_t> mode, chunks_per_block, nparts;       // per level, as ginsim_allan_level reports them
 };
 
-static int allan_plan(const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, AllanPlan& P) {
-    REQUIRE(n >= 1 && nseries >= 1 && series_stride >= n && fs > 0, "allan: bad sizes");
-    // averaging factors exactly as allan.py:29-43
+// The averaging factors exactly as allan.py:29-43 (none: the series is shorter than 9 s); returns the number of decades.
+static int allan_factors(int64_t n, double fs, std::vector<int64_t>& mult, int64_t* mmax_out) {
     const double ts = 1.0 / fs;
-    const int64_t mmax = (int64_t)floor((double)n / 9.0);
-    if ((double)mmax * ts < 1.0) return GINSIM_OK;
-    std::vector<int64_t>& mult = P.mult;
+    const int64_t mmax = *mmax_out = (int64_t)floor((double)n / 9.0);
+    if ((double)mmax * ts < 1.0) return 0;
     const int decades = (int)ceil(log10((double)mmax));
     double scale = 0.1;
     for (int i = 0; i < decades; ++i) {
@@ -152,6 +152,14 @@ static int allan_plan(const double* x, int64_t n, int32_t nseries, int64_t serie
             mult.push_back(m);
         }
     }
+    return decades;
+}
+
+static int allan_plan(const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, AllanPlan& P) {
+    REQUIRE(n >= 1 && nseries >= 1 && series_stride >= n && fs > 0, "allan: bad sizes");
+    int64_t mmax = 0;
+    const int decades = allan_factors(n, fs, P.mult, &mmax);
+    if ((double)mmax * (1.0 / fs) < 1.0) return GINSIM_OK;
     const int levels = P.levels = decades;
     // levels of more than one chunk: per-wavefront / per-workgroup partial sums; ONE launch at the end folds them and runs
     // the levels of at most one chunk (the last three or four).  Where the level's rows are 16-byte aligned the
@@ -236,6 +244,50 @@ static int allan_plan(const double* x, int64_t n, int32_t nseries, int64_t serie
         fold.nlevels = k;
     }
     REQUIRE(levels - fold.nlevels <= 4, "allan: internal level plan");
+    return GINSIM_OK;
+}
+
+// What one overlapping-Allan call runs: the same factors, the first `tile` of them in the tile form (2m <= H, ascending m), the
+// others in the stream form, and the scratch it takes.  ginsim_oallan launches from it and ginsim_oallan_plan reports it.
+struct OallanPlan {
+    OallanFactors F;
+    int tile = 0;
+    int64_t theta_stride = 0;
+    size_t b_records = 0, b_theta = 0, b_sums = 0;
+};
+
+static int oallan_plan(int64_t n, int32_t nseries, int64_t series_stride, double fs, OallanPlan& P) {
+    REQUIRE(n >= 1 && nseries >= 1 && series_stride >= n && fs > 0 && std::isfinite(fs), "oallan: bad sizes");
+    OallanFactors& F = P.F;
+    memset(&F, 0, sizeof(F));
+    std::vector<int64_t> mult;
+    int64_t mmax = 0;
+    allan_factors(n, fs, mult, &mmax);
+    if (mult.empty()) return GINSIM_OK;
+    REQUIRE((int)mult.size() <= kOallanMaxFactors && n < ((int64_t)1 << 31), "oallan: series too long");
+    const char* e = getenv("GINSIM_OALLAN_TILE");           // read per call: 0 sends every factor through the stream form
+    const bool tiles = !(e && e[0] == '0' && e[1] == 0);
+    const int64_t C = oallan_tile_payload(), H = oallan_tile_halo(), W = oallan_stream_item();
+    F.count = (int32_t)mult.size();
+    int64_t records = 0;
+    for (int i = 0; i < F.count; ++i) {
+        const int64_t m = mult[i], terms = n - 2 * m + 1;   // n / m >= 9: terms > 0
+        const bool tile = tiles && 2 * m <= H && i == P.tile && P.tile < kOallanTileFactors;
+        if (tile) ++P.tile;
+        const int64_t per = tile ? C : W;
+        F.m[i] = (int32_t)m;
+        F.nparts[i] = (int32_t)((terms + per - 1) / per);
+        F.offset[i] = (int32_t)records;
+        records += F.nparts[i];
+    }
+    F.records = (int32_t)records;
+    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    P.b_records = pad(sizeof(double) * (size_t)records * (size_t)nseries);
+    if (F.count > P.tile) {
+        P.theta_stride = (n + 2) & ~(int64_t)1;             // theta[0 .. n], rows 16-byte aligned
+        P.b_theta = pad(sizeof(double) * (size_t)P.theta_stride * (size_t)nseries);
+        P.b_sums = pad(sizeof(double) * (size_t)(n / oallan_scan_chunk() + 1) * (size_t)nseries);
+    }
     return GINSIM_OK;
 }
 
@@ -1502,6 +1554,77 @@ int ginsim_allan(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, int
             avar[(size_t)s * cap + i] = 0.5 / (double)(nb - 1) * sum / ((double)m * (double)m);
         }
     }
+    *ntau = nt;
+    return GINSIM_OK;
+}
+
+// ---- overlapping Allan variance (include/ginsim_oallan.h, csrc/oallan.hip)
+int ginsim_oallan_plan(const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t* ntau,
+                       ginsim_oallan_factor* f, int32_t cap, ginsim_oallan_geometry* g) {
+    (void)x;
+    REQUIRE(ntau && g && (f || cap == 0) && cap >= 0, "oallan_plan: bad arguments");
+    OallanPlan P;
+    const int rc = oallan_plan(n, nseries, series_stride, fs, P);
+    if (rc) return rc;
+    const int nt = P.F.count;
+    *ntau = nt;
+    g->tile_payload = oallan_tile_payload();
+    g->tile_halo = oallan_tile_halo();
+    g->scratch_bytes = (int64_t)(P.b_records + P.b_theta + P.b_sums);
+    g->tile_factors = P.tile;
+    g->stream_factors = nt - P.tile;
+    if (nt > cap) { set_error("oallan_plan: %d averaging factors but capacity %d", nt, cap); return GINSIM_ERR_RANGE; }
+    for (int i = 0; i < nt; ++i) {
+        f[i].m = P.F.m[i];
+        f[i].terms = n - 2 * (int64_t)P.F.m[i] + 1;
+        f[i].form = i < P.tile ? 0 : 1;
+        f[i].nparts = P.F.nparts[i];
+    }
+    return GINSIM_OK;
+}
+
+int ginsim_oallan(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, double* tau,
+                  double* oavar, int32_t* ntau, int32_t cap) {
+    REQUIRE(c && x && tau && oavar && ntau, "oallan: NULL argument");
+    *ntau = 0;
+    OallanPlan P;
+    const int rc = oallan_plan(n, nseries, series_stride, fs, P);
+    if (rc) return rc;
+    const OallanFactors& F = P.F;
+    const int nt = F.count;
+    if (nt == 0) return GINSIM_OK;
+    // the tile, chunk-sum, apply and stream launches have the series on the grid's y dimension (the scan of the chunk sums and
+    // the finishing launch on x)
+    if (nseries > c->max_grid_y) {
+        set_error("oallan: %d series on the grid's y dimension but the device takes %d: split the batch into calls of at most %d series",
+                  (int)nseries, c->max_grid_y, c->max_grid_y);
+        return GINSIM_ERR_RANGE;
+    }
+    if (nt > cap) { set_error("oallan: %d averaging factors but capacity %d", nt, cap); return GINSIM_ERR_RANGE; }
+    HIP_TRY(hipSetDevice(c->device));
+    void* region = nullptr;
+    HIP_TRY(scratch(c, 1, P.b_records + P.b_theta + P.b_sums, &region));
+    double* records = reinterpret_cast<double*>(region);
+    double* theta = reinterpret_cast<double*>(reinterpret_cast<char*>(region) + P.b_records);
+    double* sums = reinterpret_cast<double*>(reinterpret_cast<char*>(region) + P.b_records + P.b_theta);
+    if (P.tile > 0) HIP_TRY(launch_oallan_tile(x, n, series_stride, nseries, F, 0, P.tile, records, c->stream));
+    if (nt > P.tile) {
+        HIP_TRY(launch_oallan_theta(x, n, series_stride, nseries, sums, theta, P.theta_stride, c->stream));
+        HIP_TRY(launch_oallan_stream(theta, n, P.theta_stride, nseries, F, P.tile, nt - P.tile, records, c->stream));
+    }
+    // tau and the variances go straight into the pinned host memory ginsim_allan's sums go to: no copy, one synchronisation
+    const size_t nout = (size_t)nt * ((size_t)nseries + 1);
+    if (c->allan_host_doubles < nout) {
+        if (c->allan_host) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipHostFree(c->allan_host)); c->allan_host = nullptr; c->allan_host_doubles = 0; }
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->allan_host), sizeof(double) * (nout + nout / 4 + 64), hipHostMallocDefault));
+        c->allan_host_doubles = nout + nout / 4 + 64;
+    }
+    HIP_TRY(launch_oallan_finish(records, n, nseries, 1.0 / fs, F, c->allan_host, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double* h = c->allan_host;
+    for (int i = 0; i < nt; ++i) tau[i] = h[i];
+    for (int s = 0; s < nseries; ++s)
+        for (int i = 0; i < nt; ++i) oavar[(size_t)s * cap + i] = h[(size_t)nt * (s + 1) + i];
     *ntau = nt;
     return GINSIM_OK;
 }

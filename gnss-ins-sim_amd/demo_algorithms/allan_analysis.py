@@ -6,7 +6,8 @@ import numpy as np
 
 
 class Allan(object):
-    def __init__(self):
+    def __init__(self, overlapping=False):
+        self.overlapping = overlapping      # the estimator over every window shift (ginsim_oallan) instead of the reference's bins
         self.input = ['fs', 'accel', 'gyro']
         self.output = ['algo_time', 'ad_accel', 'ad_gyro']
         self.batch = True
@@ -16,13 +17,14 @@ class Allan(object):
         import ginsim
         fs, accel, gyro = set_of_input[0], np.asarray(set_of_input[1]), np.asarray(set_of_input[2])
         series = np.concatenate([accel.T, gyro.T], axis=0)                   # (6, n)
-        avar, tau = ginsim.allan_var_host(ginsim.default_context(), series, fs)
+        var_host = ginsim.oallan_var_host if self.overlapping else ginsim.allan_var_host
+        avar, tau = var_host(ginsim.default_context(), series, fs)
         self.results = [tau, np.sqrt(avar[0:3].T), np.sqrt(avar[3:6].T)]     # allan_analysis.py:47-49
 
     def run_device(self, sensor_job, fs):
         """Device protocol of this package's Sim: all runs of `sensor_job` (a ginsim.MonteCarloJob that kept its sensor
         series) at once.  Returns one [tau, ad_accel, ad_gyro] list per run, in run order."""
-        tau, ad = sensor_job.allan(fs)
+        tau, ad = sensor_job.allan(fs, overlapping=self.overlapping)
         per_run = [[tau, ad['accel'][r], ad['gyro'][r]] for r in range(sensor_job.runs)]
         self.results = per_run[-1]
         return per_run

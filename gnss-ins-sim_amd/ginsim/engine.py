@@ -917,11 +917,12 @@ class MonteCarloJob(BatchJob):
                 p.out_traj[s] = self._bufs['traj_' + a].ptr
 
     # bytes the launch writes to HBM (the algorithmic traffic of SURVEY 8(d))
-    def allan(self, fs=None, names=('accel', 'gyro')):
+    def allan(self, fs=None, names=('accel', 'gyro'), overlapping=False):
         """Allan deviation of the kept sensor series on the device (allan_analysis.py:33-49 for every run at once):
         returns (tau (ntau,), {name: (runs, ntau, 3)}).  The series of all named sensors are laid out as
         [sensor][run][axis][n] (one run is already three contiguous series; more runs are re-laid out
-        [3][n][runs] -> [runs][3][n] on the device) and go through ONE ginsim_allan call."""
+        [3][n][runs] -> [runs][3][n] on the device) and go through ONE ginsim_allan call -- with ``overlapping`` through ONE
+        ginsim_oallan call (the estimator over every window shift, same tau)."""
         if not self.keep_sensors or self.precision != 'f64':
             raise ValueError('Allan analysis needs the fp64 sensor series (keep_sensors=True)')
         fs = float(self.params.fs if fs is None else fs)
@@ -945,7 +946,7 @@ class MonteCarloJob(BatchJob):
                 else:
                     check(lib.ginsim_runs_to_series(self.ctx.handle, self._bufs[nm].ptr, 3, self.n, self.runs, tmp.at(i * per)))
             ptr = tmp.ptr
-        avar, tau = allan_var(self.ctx, ptr, self.n, 3 * self.runs * len(names), self.n, fs)
+        avar, tau = (oallan_var if overlapping else allan_var)(self.ctx, ptr, self.n, 3 * self.runs * len(names), self.n, fs)
         ad = np.sqrt(avar).reshape(len(names), self.runs, 3, -1)
         return tau, {nm: ad[i].transpose(0, 2, 1).copy() for i, nm in enumerate(names)}
 
@@ -1221,3 +1222,43 @@ def allan_var_host(ctx, series, fs):
     finally:
         buf.free()
     return (avar[0], tau) if np.ndim(series) == 1 else (avar, tau)
+
+
+def oallan_var(ctx, x, n, nseries, series_stride, fs, cap=128):
+    """Overlapping Allan variance of `nseries` device-resident series (DeviceBuffer, DeviceView or raw pointer): the window of
+    ``allan_var`` at every shift of one sample, same averaging factors (include/ginsim_oallan.h).
+    Returns (oavar (nseries, ntau), tau (ntau,))."""
+    ptr = getattr(x, 'ptr', x)
+    tau = np.empty(cap)
+    oavar = np.empty((nseries, cap))
+    nt = C.c_int32(0)
+    check(ctx.retry_oom(lambda: lib.ginsim_oallan(ctx.handle, ptr, int(n), int(nseries), int(series_stride), float(fs), dptr(tau),
+                                                  dptr(oavar), C.byref(nt), cap)))
+    return np.ascontiguousarray(oavar[:, :nt.value]), tau[:nt.value].copy()
+
+
+OALLAN_FORMS = ('tile', 'stream')       # ginsim_oallan_factor.form 0..1
+
+
+def oallan_plan(x, n, nseries, series_stride, fs):
+    """What ``oallan_var`` with these arguments runs, from the library's own planning code (ginsim_oallan_plan: host only, no
+    context, nothing launched).  Returns (factors, geometry): one dict per averaging factor with m, terms, form (index into
+    OALLAN_FORMS) and nparts, and a dict with tile_payload, tile_halo, scratch_bytes, tile_factors and stream_factors."""
+    ptr = getattr(x, 'ptr', x)
+    f = (_lib.OallanFactor * 128)()
+    g = _lib.OallanGeometry()
+    nt = C.c_int32(0)
+    check(lib.ginsim_oallan_plan(ptr, int(n), int(nseries), int(series_stride), float(fs), C.byref(nt), f, 128, C.byref(g)))
+    return ([dict(m=e.m, terms=e.terms, form=e.form, nparts=e.nparts) for e in f[:nt.value]],
+            {k: getattr(g, k) for k, _ in _lib.OallanGeometry._fields_})
+
+
+def oallan_var_host(ctx, series, fs):
+    """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (oavar, tau)."""
+    a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
+    buf = ctx.upload(a)
+    try:
+        oavar, tau = oallan_var(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs)
+    finally:
+        buf.free()
+    return (oavar[0], tau) if np.ndim(series) == 1 else (oavar, tau)

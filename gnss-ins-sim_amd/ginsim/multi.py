@@ -230,9 +230,9 @@ class JobSet(_Parts):
     def trajectories(self, algo, run_ids, displacement=False):
         return self._route(run_ids, lambda j, ids: j.trajectories(algo, ids, displacement=displacement))
 
-    def allan(self, fs=None, names=('accel', 'gyro')):
+    def allan(self, fs=None, names=('accel', 'gyro'), overlapping=False):
         """MonteCarloJob.allan on every device at the same time: (tau, {name: (runs, ntau, 3)})."""
-        got = [g for g in self._each_part(lambda j: j.allan(fs, names)) if g is not None]
+        got = [g for g in self._each_part(lambda j: j.allan(fs, names, overlapping=overlapping)) if g is not None]
         return got[0][0], {nm: np.concatenate([g[1][nm] for g in got], axis=0) for nm in names}
 
     def buffer(self, name):
