@@ -65,10 +65,11 @@ SOURCES = [
     ('ins_loose_still.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
-    # error_curve.hip's flags: the keys are formed with its error expression (tests/test_error_quantiles_oracle.py reads the
-    # resource report: no scratch)
+    # error_curve.hip's flags: the keys are formed from the shared error expression (traj_error.hpp, quantity_error) and their sums
+    # are spelt as fused multiply-adds, so no flag decides their bits (tests/test_error_quantiles_oracle.py reads the resource
+    # report: no scratch)
     ('error_quantile.hip', ['--offload-arch=' + ARCH]),
-    # error_curve.hip's error expression; machine-LICM off as for mc_kernel.hip: hoisted out of the run loop, the constants of the
+    # the same error expression (traj_error.hpp); machine-LICM off as for mc_kernel.hip: hoisted out of the run loop, the constants of the
     # geodetic conversion (NED form) spill 16 SGPRs (tests/test_error_covariance_oracle.py reads the resource report: no scratch,
     # no spills)
     ('error_cov.hip', ['--offload-arch=' + ARCH, '-mllvm', '-disable-machine-licm']),

@@ -3,17 +3,12 @@
 // points; the cross moments do: rotated by the truth's yaw they are the along-track and cross-track variances, and their principal
 // axes are the horizontal error ellipse (both on the host, ginsim/engine.py).
 //
-// Inputs as radial_keys_kernel (error_quantile.hip): which = 0 position (planes 3..5), 1 velocity (planes 6..8), the error formed by
-// sample_error (moments.hpp), the fp32 form adds the origin table in fp64 as curve_partial_kernel does.  Only the three planes of
-// the selected quantity are read: 24 B (fp64) or 12 B (fp32) per sample*run.
-//
-// Shape as error_curve.hip: the unit of work is a WAVEFRONT, one sample and one slice of the run axis, lanes stride along the runs,
-// the truth row and the sample index are wave-uniform (scalar loads), `which` is a wave-uniform branch, every lane keeps one
-// Welford accumulator and the lanes are folded with a shuffle butterfly.  No LDS, no barrier, no atomics:
+// The unit of work, the error of the selected quantity (quantity_error: which = 0 position, 1 velocity) and the cut of the run
+// axis are traj_error.hpp's.  Only the three planes of the selected quantity are read: 24 B (fp64) or 12 B (fp32) per sample*run.
+// Every lane keeps one Welford accumulator and the lanes are folded with a shuffle butterfly:
 //   many samples, few runs   one wavefront per sample (parts = 1), the record is written directly
 //   few samples, many runs   the run axis is cut into `parts` slices so that the launch still fills the device; the slice
 //                            records are folded by cov_final_kernel in a fixed order
-// parts depends on (runs, m) alone: the same (n, runs, m) takes the same path and gives the same bytes at every launch.
 //
 // Conditioning: the lanes accumulate about a SHIFT, the error of the launch's first run at the sample (where finite, else 0), as
 // curve_partial_kernel does.  Welford alone is not enough when |mean| >> sigma: the mean of the fold carries a rounding error of
@@ -23,28 +18,13 @@
 // the number of runs that did.  The loop uses the same rule for the lanes past the end of the row: they hold NaN.
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
-#include "moments.hpp"
+#include "traj_error.hpp"
 #include "cov_record.hpp"
-#include "launch.hpp"
 
 namespace ginsim {
 
-constexpr int kCovBlock = 256;                      // four wavefronts, each with its own (sample, slice)
-constexpr int kCovWaves = kCovBlock / 64;
 constexpr int kCovMaxParts = 256;
-constexpr int64_t kCovTargetWaves = 8192;           // 256 CUs x 4 SIMDs x 8 wavefronts
 constexpr int kCovBatch = 2;                        // runs of a lane whose loads are in flight together
-
-typedef const int64_t __attribute__((address_space(4))) * uniform_idx;
-
-// the slices of the run axis for `m` samples of `runs` runs (a slice holds at least one step of a wavefront)
-static int cov_parts(int64_t runs, int64_t m) {
-    const int64_t most = (runs + 63) / 64;
-    int64_t want = (kCovTargetWaves + m - 1) / m;
-    if (want > most) want = most;
-    if (want > kCovMaxParts) want = kCovMaxParts;
-    return (int)(want < 1 ? 1 : want);
-}
 
 __device__ inline Cov shfl_xor(const Cov& a, int mask) {
     Cov o;
@@ -56,51 +36,25 @@ __device__ inline Cov shfl_xor(const Cov& a, int mask) {
     return o;
 }
 
-// the error of run r against the truth (t0, t1, t2) of the selected quantity, from its three plane values
-template <bool NED>
-__device__ __forceinline__ void run_error(double a0, double a1, double a2, double t0, double t1, double t2, int which,
-                                          const ProcOrigin& org, int64_t r, double (&e3)[3]) {
-    double x[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, t[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, e[9];
-    if (which) {                                    // wave-uniform
-        x[6] = a0; x[7] = a1; x[8] = a2;
-        t[6] = t0; t[7] = t1; t[8] = t2;
-        sample_error(x, t, 0, e);
-        e3[0] = e[6]; e3[1] = e[7]; e3[2] = e[8];
-    } else {
-        double o0 = 0.0, o1 = 0.0, o2 = 0.0;
-        if (org.table) {                            // the run's initial state, as in the MC kernels (moments.hpp, ProcOrigin)
-            const uint64_t call = org.ini_first + (uint64_t)r;
-            const double* o = org.table + 3 * (call < (uint64_t)org.n_ini ? call : 0);
-            o0 = o[0]; o1 = o[1]; o2 = o[2];
-        }
-        x[3] = a0 + o0; x[4] = a1 + o1; x[5] = a2 + o2;
-        t[3] = t0; t[4] = t1; t[5] = t2;
-        sample_error(x, t, NED ? 1 : 0, e);
-        e3[0] = e[3]; e3[1] = e[4]; e3[2] = e[5];
-    }
-}
-
 // out: [m] records when parts == 1, else [m][parts] slice records accumulated about `shift` ([m][3], written by slice 0 and added
 // by cov_final_kernel)
 template <typename T, bool NED>
-__global__ void __launch_bounds__(kCovBlock) cov_partial_kernel(const T* __restrict__ traj, const double* __restrict__ ref, int64_t n,
+__global__ void __launch_bounds__(kUnitBlock) cov_partial_kernel(const T* __restrict__ traj, const double* __restrict__ ref, int64_t n,
                                                                int64_t runs, const int64_t* __restrict__ samples, int64_t m, int parts,
                                                                int which, Cov* __restrict__ out, double* __restrict__ shift,
                                                                const ProcOrigin org) {
     const int lane = threadIdx.x & 63;
-    const int64_t unit = (int64_t)blockIdx.x * kCovWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (unit >= m * parts) return;                  // wave-uniform
-    const int64_t s = unit / parts;
-    const int part = (int)(unit - s * parts);
-    const int64_t j = samples ? ((uniform_idx)(uintptr_t)samples)[s] : s;
-    const int64_t plane = n * runs;
-    const int c0 = which ? 6 : 3;
-    const uniform_ref truth = (uniform_ref)(uintptr_t)ref;
+    const int64_t unit = wave_unit();
+    if (unit >= m * parts) return;
+    const WorkUnit w(unit, ref, n, runs, samples, parts);
+    const int64_t s = w.s, j = w.j, plane = w.plane;
+    const int part = (int)(unit - s * parts), c0 = which ? 6 : 3;
+    const uniform_ref truth = w.truth;
     const double t0 = truth[9 * j + c0], t1 = truth[9 * j + c0 + 1], t2 = truth[9 * j + c0 + 2];
     const T* row = traj + c0 * plane + j * runs;
     // the shift: the error of the launch's first run at this sample (every lane forms the same three numbers)
     double k3[3];
-    run_error<NED>((double)row[0], (double)row[plane], (double)row[2 * plane], t0, t1, t2, which, org, 0, k3);
+    quantity_error<NED>((double)row[0], (double)row[plane], (double)row[2 * plane], t0, t1, t2, which, org, 0, k3);
 #pragma unroll
     for (int c = 0; c < 3; ++c) k3[c] = __builtin_isfinite(k3[c]) ? k3[c] : 0.0;
     Cov a{0.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
@@ -120,7 +74,7 @@ __global__ void __launch_bounds__(kCovBlock) cov_partial_kernel(const T* __restr
         for (int k = 0; k < kCovBatch; ++k) {
             const int64_t r = r0 + k * step;
             double e[3];
-            run_error<NED>((double)v[k][0], (double)v[k][1], (double)v[k][2], t0, t1, t2, which, org, r < runs ? r : 0, e);
+            quantity_error<NED>((double)v[k][0], (double)v[k][1], (double)v[k][2], t0, t1, t2, which, org, r < runs ? r : 0, e);
             if (__builtin_isfinite(e[0]) && __builtin_isfinite(e[1]) && __builtin_isfinite(e[2])) {
                 a.n += 1.0;
                 const double icnt = rcp_nr(a.n);
@@ -163,37 +117,30 @@ __global__ void __launch_bounds__(64) cov_final_kernel(const Cov* __restrict__ p
 }
 
 // scratch: [m] records, then (parts > 1) [m][parts] slice records and [m][3] shifts
-size_t error_cov_scratch_bytes(int64_t runs, int64_t m) {
-    const int parts = cov_parts(runs, m);
-    size_t b = sizeof(Cov) * (size_t)m;
-    if (parts > 1) b += sizeof(Cov) * (size_t)m * parts + sizeof(double) * 3 * (size_t)m;
+size_t error_cov_scratch_bytes(const TrajView& v) {
+    const int parts = run_slices(v.runs, v.m, 64, kCovMaxParts);
+    size_t b = sizeof(Cov) * (size_t)v.m;
+    if (parts > 1) b += sizeof(Cov) * (size_t)v.m * parts + sizeof(double) * 3 * (size_t)v.m;
     return b;
 }
 
 template <typename T>
-static hipError_t launch_cov(const T* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m, int which,
-                             int pos_ned, void* scratch, const ProcOrigin org, hipStream_t st) {
-    const int parts = cov_parts(runs, m);
+static hipError_t launch_cov(const TrajView& v, int which, int pos_ned, void* scratch, hipStream_t st) {
+    const int64_t m = v.m;
+    const int parts = run_slices(v.runs, m, 64, kCovMaxParts);
     Cov* out = reinterpret_cast<Cov*>(scratch);
     Cov* partial = out + m;
     double* shift = reinterpret_cast<double*>(partial + m * parts);
-    const unsigned blocks = (unsigned)((m * parts + kCovWaves - 1) / kCovWaves);
     // the geodetic conversion only where the position is asked for in NED: the velocity takes the plain form
-    hipLaunchKernelGGL((pos_ned && !which ? cov_partial_kernel<T, true> : cov_partial_kernel<T, false>), dim3(blocks), dim3(kCovBlock), 0,
-                       st, traj, ref, n, runs, samples, m, parts, which, parts == 1 ? out : partial, shift, org);
+    hipLaunchKernelGGL((pos_ned && !which ? cov_partial_kernel<T, true> : cov_partial_kernel<T, false>), dim3(unit_blocks(m, parts)),
+                       dim3(kUnitBlock), 0, st, static_cast<const T*>(v.traj), v.ref, v.n, v.runs, v.samples, m, parts, which,
+                       parts == 1 ? out : partial, shift, v.org);
     if (parts > 1) hipLaunchKernelGGL(cov_final_kernel, dim3((unsigned)m), dim3(64), 0, st, partial, shift, parts, out);
     return hipGetLastError();
 }
 
-hipError_t launch_error_cov(const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                            int which, int pos_ned, void* scratch, hipStream_t st) {
-    return launch_cov<double>(traj, ref, n, runs, samples, m, which, pos_ned, scratch, ProcOrigin{nullptr, 0, 0}, st);
-}
-
-hipError_t launch_error_cov_f32(const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                                int which, int pos_ned, void* scratch, const double* origin, int64_t n_ini, uint64_t ini_first,
-                                hipStream_t st) {
-    return launch_cov<float>(traj, ref, n, runs, samples, m, which, pos_ned, scratch, ProcOrigin{origin, n_ini, ini_first}, st);
+hipError_t launch_error_cov(const TrajView& v, int which, int pos_ned, void* scratch, hipStream_t st) {
+    return v.f32 ? launch_cov<float>(v, which, pos_ned, scratch, st) : launch_cov<double>(v, which, pos_ned, scratch, st);
 }
 
 // host: the records of `nparts` sets of runs, each [m] records, folded record by record in the order given

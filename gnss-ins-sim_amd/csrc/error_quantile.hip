@@ -1,15 +1,14 @@
 // Error quantiles across the runs: the radius that holds a given share of the runs (CEP50, CEP95 / R95) and the same quantiles of
 // the vertical and the 3-D error, at every requested sample.  Two kernels, both over kept trajectory planes:
 //
-//   radial_keys_kernel    per (sample, run) the error of position or velocity against the truth (sample_error, moments.hpp, the
-//                         expression of error_curve.hip) and from it three non-negative KEYS: horizontal sqrt(e0^2 + e1^2),
+//   radial_keys_kernel    per (sample, run) the error of position or velocity against the truth (quantity_error,
+//                         traj_error.hpp) and from it three non-negative KEYS: horizontal sqrt(e0^2 + e1^2),
 //                         vertical |e2|, 3-D sqrt(e0^2 + e1^2 + e2^2), written to keys[(k * m + s) * row_stride + col0 + r].
 //                         row_stride and col0 let blocks of runs (and devices) fill one long row per (key, sample).
 //   quantile_rows_kernel  exact order statistics of every key row for up to 8 probabilities at once: nearest rank
 //                         (np.quantile(method='inverted_cdf')), the k-th smallest finite key, k = min(max(ceil(p N), 1), N).
 //
-// Keys: the unit of work is a WAVEFRONT, as in error_curve.hip: one sample and one slice of the run axis, lanes stride along the
-// runs (coalesced loads and stores), the truth row is wave-uniform (scalar loads), no LDS, no barrier.  Only the three planes of
+// Keys: the unit of work and the cut of the run axis are traj_error.hpp's (coalesced loads and stores).  Only the three planes of
 // the selected quantity are read: 24 B (fp64) per sample*run in, 24 B out.
 //
 // Select: one workgroup per row, MSB-first radix select with 8-bit digits.  A finite double x orders as the integer
@@ -23,97 +22,52 @@
 // it stays in L2).  Keys that are not finite are left out (-0.0 orders before +0.0).
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
-#include "moments.hpp"
-#include "launch.hpp"
+#include "traj_error.hpp"
 
 namespace ginsim {
 
-constexpr int kKeysBlock = 256;                     // four wavefronts, each with its own (sample, slice)
-constexpr int kKeysWaves = kKeysBlock / 64;
 constexpr int kKeysMaxParts = 1024;
-constexpr int64_t kKeysTargetWaves = 8192;          // 256 CUs x 4 SIMDs x 8 wavefronts
 
-typedef const int64_t __attribute__((address_space(4))) * uniform_idx;
-
-// the slices of the run axis for `m` samples of `runs` runs: one wavefront per sample when there are many samples, else enough
-// slices to fill the device (a slice holds at least one step of a wavefront)
-static int keys_parts(int64_t runs, int64_t m) {
-    const int64_t most = (runs + 63) / 64;
-    int64_t want = (kKeysTargetWaves + m - 1) / m;
-    if (want > most) want = most;
-    if (want > kKeysMaxParts) want = kKeysMaxParts;
-    return (int)(want < 1 ? 1 : want);
-}
-
-// which: 0 position (planes 3..5), 1 velocity (planes 6..8).  NED: the position error in local NED metres (lla_error_ned), a
-// template parameter as in curve_partial_kernel; it has no effect on the velocity.  org: the origin table of the fp32 displacement
-// series (T = float), added to the position in fp64 exactly as curve_partial_kernel adds it.
+// which, NED, org: see quantity_error (traj_error.hpp)
 template <typename T, bool NED>
-__global__ void __launch_bounds__(kKeysBlock) radial_keys_kernel(const T* __restrict__ traj, const double* __restrict__ ref, int64_t n,
+__global__ void __launch_bounds__(kUnitBlock) radial_keys_kernel(const T* __restrict__ traj, const double* __restrict__ ref, int64_t n,
                                                                 int64_t runs, const int64_t* __restrict__ samples, int64_t m, int parts,
                                                                 int which, double* __restrict__ keys, int64_t row_stride, int64_t col0,
                                                                 const ProcOrigin org) {
     const int lane = threadIdx.x & 63;
-    const int64_t unit = (int64_t)blockIdx.x * kKeysWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (unit >= m * parts) return;                  // wave-uniform
-    const int64_t s = unit / parts;
-    const int part = (int)(unit - s * parts);
-    const int64_t j = samples ? ((uniform_idx)(uintptr_t)samples)[s] : s;
-    const int64_t plane = n * runs;
+    const int64_t unit = wave_unit();
+    if (unit >= m * parts) return;
+    const WorkUnit w(unit, ref, n, runs, samples, parts);
+    const int64_t j = w.j, plane = w.plane;
     const int c0 = which ? 6 : 3;
-    const uniform_ref truth = (uniform_ref)(uintptr_t)ref;
-    const double t0 = truth[9 * j + c0], t1 = truth[9 * j + c0 + 1], t2 = truth[9 * j + c0 + 2];
+    const double t0 = w.truth[9 * j + c0], t1 = w.truth[9 * j + c0 + 1], t2 = w.truth[9 * j + c0 + 2];
     const T* row = traj + c0 * plane + j * runs;
-    double* out = keys + s * row_stride + col0;
+    double* out = keys + w.s * row_stride + col0;
     const int64_t kstep = m * row_stride;           // from one key's rows to the next key's
+    const int part = (int)(unit - w.s * parts);
     for (int64_t r = (int64_t)part * 64 + lane; r < runs; r += (int64_t)parts * 64) {
-        const double a0 = (double)row[r], a1 = (double)row[plane + r], a2 = (double)row[2 * plane + r];
-        double x[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, t[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, e[9];
-        double e0, e1, e2;
-        if (which) {                                // wave-uniform
-            x[6] = a0; x[7] = a1; x[8] = a2;
-            t[6] = t0; t[7] = t1; t[8] = t2;
-            sample_error(x, t, 0, e);
-            e0 = e[6]; e1 = e[7]; e2 = e[8];
-        } else {
-            double o0 = 0.0, o1 = 0.0, o2 = 0.0;
-            if (org.table) {                        // the run's initial state, as in the MC kernels (moments.hpp, ProcOrigin)
-                const uint64_t call = org.ini_first + (uint64_t)r;
-                const double* o = org.table + 3 * (call < (uint64_t)org.n_ini ? call : 0);
-                o0 = o[0]; o1 = o[1]; o2 = o[2];
-            }
-            x[3] = a0 + o0; x[4] = a1 + o1; x[5] = a2 + o2;
-            t[3] = t0; t[4] = t1; t[5] = t2;
-            sample_error(x, t, NED ? 1 : 0, e);
-            e0 = e[3]; e1 = e[4]; e2 = e[5];
-        }
-        const double h2 = e0 * e0 + e1 * e1;
+        double e[3];
+        quantity_error<NED>((double)row[r], (double)row[plane + r], (double)row[2 * plane + r], t0, t1, t2, which, org, r, e);
+        // the fused form is spelt out: left to the compiler's contraction, which product is fused, and so every key's rounding, is its choice
+        const double h2 = __builtin_fma(e[1], e[1], e[0] * e[0]);
         out[r] = sqrt(h2);
-        out[kstep + r] = fabs(e2);
-        out[2 * kstep + r] = sqrt(h2 + e2 * e2);
+        out[kstep + r] = fabs(e[2]);
+        out[2 * kstep + r] = sqrt(__builtin_fma(e[2], e[2], h2));
     }
 }
 
 template <typename T>
-static hipError_t launch_keys(const T* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m, int which,
-                              int pos_ned, double* keys, int64_t row_stride, int64_t col0, const ProcOrigin org, hipStream_t st) {
-    const int parts = keys_parts(runs, m);
-    const unsigned blocks = (unsigned)((m * parts + kKeysWaves - 1) / kKeysWaves);
-    hipLaunchKernelGGL((pos_ned ? radial_keys_kernel<T, true> : radial_keys_kernel<T, false>), dim3(blocks), dim3(kKeysBlock), 0, st, traj,
-                       ref, n, runs, samples, m, parts, which, keys, row_stride, col0, org);
+static hipError_t launch_keys(const TrajView& v, int which, int pos_ned, double* keys, int64_t row_stride, int64_t col0, hipStream_t st) {
+    const int parts = run_slices(v.runs, v.m, 64, kKeysMaxParts);
+    hipLaunchKernelGGL((pos_ned ? radial_keys_kernel<T, true> : radial_keys_kernel<T, false>), dim3(unit_blocks(v.m, parts)),
+                       dim3(kUnitBlock), 0, st, static_cast<const T*>(v.traj), v.ref, v.n, v.runs, v.samples, v.m, parts, which, keys,
+                       row_stride, col0, v.org);
     return hipGetLastError();
 }
 
-hipError_t launch_radial_keys(const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                              int which, int pos_ned, double* keys, int64_t row_stride, int64_t col0, hipStream_t st) {
-    return launch_keys<double>(traj, ref, n, runs, samples, m, which, pos_ned, keys, row_stride, col0, ProcOrigin{nullptr, 0, 0}, st);
-}
-
-hipError_t launch_radial_keys_f32(const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                                  int which, int pos_ned, double* keys, int64_t row_stride, int64_t col0, const double* origin,
-                                  int64_t n_ini, uint64_t ini_first, hipStream_t st) {
-    return launch_keys<float>(traj, ref, n, runs, samples, m, which, pos_ned, keys, row_stride, col0, ProcOrigin{origin, n_ini, ini_first},
-                              st);
+hipError_t launch_radial_keys(const TrajView& v, int which, int pos_ned, double* keys, int64_t row_stride, int64_t col0, hipStream_t st) {
+    return v.f32 ? launch_keys<float>(v, which, pos_ned, keys, row_stride, col0, st)
+                 : launch_keys<double>(v, which, pos_ned, keys, row_stride, col0, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the select

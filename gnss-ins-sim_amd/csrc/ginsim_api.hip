@@ -124,6 +124,25 @@ static int gather_run(const char* who, ginsim_ctx* c, const void* series, int32_
     return GINSIM_OK;
 }
 
+// One launch over kept trajectories at requested samples (curve_entry, keys_entry, cov_entry below), on checked input; v.samples
+// is still on the host.  Scratch: [body bytes: the family's records, then its slice records and shifts]
+// [m sample indices].  launch(view with the samples on the device, scratch); out_bytes from the front of the scratch to the host.
+template <class Launch>
+static int traj_run(ginsim_ctx* c, TrajView v, size_t body, double* host_out, size_t out_bytes, Launch launch) {
+    HIP_TRY(hipSetDevice(c->device));
+    void* ws = nullptr;
+    HIP_TRY(scratch(c, 2, body + sizeof(int64_t) * (size_t)v.m, &ws));
+    if (v.samples) {
+        int64_t* d_samples = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ws) + body);
+        HIP_TRY(hipMemcpyAsync(d_samples, v.samples, sizeof(int64_t) * (size_t)v.m, hipMemcpyHostToDevice, c->stream));
+        v.samples = d_samples;
+    }
+    HIP_TRY(launch(v, ws));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(host_out, ws, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
 // What one Allan call runs: the averaging factors of allan.py:29-43, the decade levels, and for every level the kernel form that
 // takes it.  Host arithmetic only; ginsim_allan launches from it and ginsim_allan_plan reports it, so the two cannot differ.
 struct AllanStep { int k; int mode; };     // mode 0: allan_level_kernel, 1: wave-pair LDS-DMA kernel, 2: levels k and k+1 fused
@@ -1139,22 +1158,15 @@ int ginsim_end_stats_all_finish(ginsim_ctx* c, int32_t slot, ginsim_stats* merge
 
 // The per-run statistics of kept trajectories (stats.hip's process kernel) in the context's scratch.  proc_out: the records of the
 // samples >= first_sample, [runs][3][9], to the host.  end_out (proc_out NULL): a one-sample window at n - 1, whose "mean" plane
-// [9][runs] IS the end-point error, reduced by ginsim_end_stats.  f32: traj is float, positions as displacement from origin.
-static int traj_stats_run(ginsim_ctx* c, const void* traj, int f32, const double* ref, int64_t n, int64_t runs, int64_t first_sample,
-                          int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* proc_out, ginsim_stats* end_out) {
+// [9][runs] IS the end-point error, reduced by ginsim_end_stats.
+static int traj_stats_run(ginsim_ctx* c, const TrajView& v, int64_t first_sample, int32_t pos_ned, double* proc_out, ginsim_stats* end_out) {
     HIP_TRY(hipSetDevice(c->device));
     void* ws = nullptr;
-    const size_t bytes = sizeof(double) * 27 * (size_t)runs;
+    const size_t bytes = sizeof(double) * 27 * (size_t)v.runs;
     HIP_TRY(scratch(c, 2, bytes, &ws));
     double* rec = reinterpret_cast<double*>(ws);
-    const int64_t j0 = proc_out ? first_sample : n - 1;
-    const int run_major = proc_out ? 1 : 0;
-    if (f32)
-        HIP_TRY(launch_process_stats_f32(reinterpret_cast<const float*>(traj), ref, n, runs, j0, pos_ned, run_major, rec, origin, n_ini,
-                                         ini_first, c->stream));
-    else
-        HIP_TRY(launch_process_stats(reinterpret_cast<const double*>(traj), ref, n, runs, j0, pos_ned, run_major, rec, c->stream));
-    if (!proc_out) return ginsim_end_stats(c, rec + (size_t)9 * runs, runs, end_out);
+    HIP_TRY(launch_process_stats(v, proc_out ? first_sample : v.n - 1, pos_ned, proc_out ? 1 : 0, rec, c->stream));
+    if (!proc_out) return ginsim_end_stats(c, rec + (size_t)9 * v.runs, v.runs, end_out);
     HIP_TRY(hipMemcpyAsync(proc_out, ws, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GINSIM_OK;
@@ -1164,78 +1176,71 @@ int ginsim_process_stats(ginsim_ctx* c, const double* traj, const double* ref, i
                          int32_t pos_ned, double* host_out) {
     REQUIRE(c && traj && ref && host_out, "process_stats: NULL argument");
     REQUIRE(n >= 1 && runs >= 1 && first_sample >= 0 && first_sample < n, "process_stats: bad sizes");
-    return traj_stats_run(c, traj, 0, ref, n, runs, first_sample, pos_ned, nullptr, 0, 0, host_out, nullptr);
+    return traj_stats_run(c, TrajView{traj, 0, ref, n, runs, nullptr, 0, {nullptr, 0, 0}}, first_sample, pos_ned, host_out, nullptr);
 }
 
 int ginsim_end_stats_from_traj(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, int32_t pos_ned,
                                ginsim_stats* host_out) {
     REQUIRE(c && traj && ref && host_out && n >= 1 && runs >= 1, "end_stats_from_traj: bad arguments");
-    return traj_stats_run(c, traj, 0, ref, n, runs, 0, pos_ned, nullptr, 0, 0, nullptr, host_out);
+    return traj_stats_run(c, TrajView{traj, 0, ref, n, runs, nullptr, 0, {nullptr, 0, 0}}, 0, pos_ned, nullptr, host_out);
 }
 
 int ginsim_process_stats_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, int64_t first_sample,
                              int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* host_out) {
     REQUIRE(c && traj && ref && origin && host_out, "process_stats_f32: NULL argument");
     REQUIRE(n >= 1 && runs >= 1 && first_sample >= 0 && first_sample < n && n_ini >= 1, "process_stats_f32: bad sizes");
-    return traj_stats_run(c, traj, 1, ref, n, runs, first_sample, pos_ned, origin, n_ini, ini_first, host_out, nullptr);
+    return traj_stats_run(c, TrajView{traj, 1, ref, n, runs, nullptr, 0, {origin, n_ini, ini_first}}, first_sample, pos_ned, host_out, nullptr);
 }
 
 int ginsim_end_stats_from_traj_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, int32_t pos_ned,
                                    const double* origin, int32_t n_ini, uint64_t ini_first, ginsim_stats* host_out) {
     REQUIRE(c && traj && ref && origin && host_out && n >= 1 && runs >= 1 && n_ini >= 1, "end_stats_from_traj_f32: bad arguments");
-    return traj_stats_run(c, traj, 1, ref, n, runs, 0, pos_ned, origin, n_ini, ini_first, nullptr, host_out);
+    return traj_stats_run(c, TrajView{traj, 1, ref, n, runs, nullptr, 0, {origin, n_ini, ini_first}}, 0, pos_ned, nullptr, host_out);
 }
 
-// ---- error-growth curves (csrc/error_curve.hip): the across-run record of every requested sample
-static int check_curve_args(const char* who, const void* c, const void* traj, const void* ref, int64_t n, int64_t runs,
-                            const int64_t* samples, int64_t m, const void* host_out) {
-    REQUIRE(c && traj && ref && host_out, "%s: NULL argument", who);
-    REQUIRE(n >= 1 && runs >= 1, "%s: n=%lld runs=%lld must be >= 1", who, (long long)n, (long long)runs);
+// ---- across-run statistics of kept trajectories at requested samples: error-growth curves (csrc/error_curve.hip), quantile keys
+// (csrc/error_quantile.hip) and error covariance (csrc/error_cov.hip).  The entry points describe their input as a TrajView whose
+// samples are still on the HOST; the checks below and traj_run (above) are the one path of the three families.
+static int check_curve_args(const char* who, const void* c, const TrajView& v, const void* host_out) {
+    const int64_t n = v.n, m = v.m;
+    REQUIRE(c && v.traj && v.ref && host_out, "%s: NULL argument", who);
+    REQUIRE(n >= 1 && v.runs >= 1, "%s: n=%lld runs=%lld must be >= 1", who, (long long)n, (long long)v.runs);
     REQUIRE(m >= 1, "%s: m=%lld samples (at least one is needed)", who, (long long)m);
-    REQUIRE(samples || m == n, "%s: samples == NULL means every sample, so m must be n (m=%lld, n=%lld)", who, (long long)m, (long long)n);
+    REQUIRE(v.samples || m == n, "%s: samples == NULL means every sample, so m must be n (m=%lld, n=%lld)", who, (long long)m, (long long)n);
     REQUIRE(m <= 0x7FFFFFFFll, "%s: too many samples for one call", who);
-    if (samples)
+    if (v.samples)
         for (int64_t i = 0; i < m; ++i)
-            REQUIRE(samples[i] >= 0 && samples[i] < n, "%s: sample %lld (entry %lld) is outside [0, %lld)", who, (long long)samples[i],
+            REQUIRE(v.samples[i] >= 0 && v.samples[i] < n, "%s: sample %lld (entry %lld) is outside [0, %lld)", who, (long long)v.samples[i],
                     (long long)i, (long long)n);
     return GINSIM_OK;
 }
 
-// the scratch region of a curve: [records and slice records of error_curve.hip][m sample indices]
-static int curve_run(ginsim_ctx* c, const void* traj, int f32, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
-                     int64_t m, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* host_out) {
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t body = error_curve_scratch_bytes(traj, runs, m);
-    void* ws = nullptr;
-    HIP_TRY(scratch(c, 2, body + sizeof(int64_t) * (size_t)m, &ws));
-    int64_t* d_samples = nullptr;
-    if (samples) {
-        d_samples = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ws) + body);
-        HIP_TRY(hipMemcpyAsync(d_samples, samples, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    }
-    if (f32)
-        HIP_TRY(launch_error_curve_f32(reinterpret_cast<const float*>(traj), ref, n, runs, d_samples, m, pos_ned, ws, origin, n_ini,
-                                       ini_first, c->stream));
-    else
-        HIP_TRY(launch_error_curve(reinterpret_cast<const double*>(traj), ref, n, runs, d_samples, m, pos_ned, ws, c->stream));
-    HIP_TRY(hipMemcpyAsync(host_out, ws, sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+static int check_which(const char* who, int32_t which) {
+    REQUIRE(which == 0 || which == 1, "%s: which=%d is neither 0 (position) nor 1 (velocity)", who, (int)which);
     return GINSIM_OK;
+}
+
+static int check_origin(const char* who, const TrajView& v) {
+    REQUIRE(!v.f32 || (v.org.table && v.org.n_ini >= 1), "%s: the origin table of the displacement series is missing", who);
+    return GINSIM_OK;
+}
+
+static int curve_entry(const char* who, ginsim_ctx* c, const TrajView& v, int32_t pos_ned, double* host_out) {
+    int rc = check_curve_args(who, c, v, host_out);
+    if (!rc) rc = check_origin(who, v);
+    if (rc) return rc;
+    return traj_run(c, v, error_curve_scratch_bytes(v), host_out, sizeof(double) * 36 * (size_t)v.m,
+                    [&](const TrajView& d, void* ws) { return launch_error_curve(d, pos_ned, ws, c->stream); });
 }
 
 int ginsim_error_curve(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
                        int32_t pos_ned, double* host_out) {
-    const int rc = check_curve_args("error_curve", c, traj, ref, n, runs, samples, m, host_out);
-    if (rc) return rc;
-    return curve_run(c, traj, 0, ref, n, runs, samples, m, pos_ned, nullptr, 0, 0, host_out);
+    return curve_entry("error_curve", c, TrajView{traj, 0, ref, n, runs, samples, m, {nullptr, 0, 0}}, pos_ned, host_out);
 }
 
 int ginsim_error_curve_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
                            int64_t m, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* host_out) {
-    const int rc = check_curve_args("error_curve_f32", c, traj, ref, n, runs, samples, m, host_out);
-    if (rc) return rc;
-    REQUIRE(origin && n_ini >= 1, "error_curve_f32: the origin table of the displacement series is missing");
-    return curve_run(c, traj, 1, ref, n, runs, samples, m, pos_ned, origin, n_ini, ini_first, host_out);
+    return curve_entry("error_curve_f32", c, TrajView{traj, 1, ref, n, runs, samples, m, {origin, n_ini, ini_first}}, pos_ned, host_out);
 }
 
 int ginsim_curve_merge(const double* parts, int32_t nparts, int64_t m, double* out) {
@@ -1244,55 +1249,35 @@ int ginsim_curve_merge(const double* parts, int32_t nparts, int64_t m, double* o
     return GINSIM_OK;
 }
 
-// ---- error quantiles across the runs (csrc/error_quantile.hip): the keys of every (sample, run), then the order statistics of key rows
-static int check_keys_args(const char* who, const void* c, const void* traj, const void* ref, int64_t n, int64_t runs,
-                           const int64_t* samples, int64_t m, int32_t which, const void* keys, int64_t row_stride, int64_t col0) {
-    const int rc = check_curve_args(who, c, traj, ref, n, runs, samples, m, keys);
+// the keys of every (sample, run) go to the caller's device rows: no records in the scratch, nothing to copy back
+static int keys_entry(const char* who, ginsim_ctx* c, const TrajView& v, int32_t which, int32_t pos_ned, double* keys, int64_t row_stride,
+                      int64_t col0) {
+    int rc = check_curve_args(who, c, v, keys);
+    if (!rc) rc = check_which(who, which);
     if (rc) return rc;
-    REQUIRE(which == 0 || which == 1, "%s: which=%d is neither 0 (position) nor 1 (velocity)", who, (int)which);
     REQUIRE(col0 >= 0, "%s: col0=%lld is negative", who, (long long)col0);
-    REQUIRE(row_stride >= col0 + runs, "%s: row_stride=%lld is shorter than col0 + runs = %lld + %lld", who, (long long)row_stride,
-            (long long)col0, (long long)runs);
-    return GINSIM_OK;
-}
-
-static int keys_run(ginsim_ctx* c, const void* traj, int f32, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
-                    int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first, double* keys,
-                    int64_t row_stride, int64_t col0) {
-    HIP_TRY(hipSetDevice(c->device));
-    int64_t* d_samples = nullptr;
-    if (samples) {
-        void* ws = nullptr;
-        HIP_TRY(scratch(c, 2, sizeof(int64_t) * (size_t)m, &ws));
-        d_samples = reinterpret_cast<int64_t*>(ws);
-        HIP_TRY(hipMemcpyAsync(d_samples, samples, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    }
-    if (f32)
-        HIP_TRY(launch_radial_keys_f32(reinterpret_cast<const float*>(traj), ref, n, runs, d_samples, m, which, pos_ned, keys, row_stride,
-                                       col0, origin, n_ini, ini_first, c->stream));
-    else
-        HIP_TRY(launch_radial_keys(reinterpret_cast<const double*>(traj), ref, n, runs, d_samples, m, which, pos_ned, keys, row_stride,
-                                   col0, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GINSIM_OK;
+    REQUIRE(row_stride >= col0 + v.runs, "%s: row_stride=%lld is shorter than col0 + runs = %lld + %lld", who, (long long)row_stride,
+            (long long)col0, (long long)v.runs);
+    rc = check_origin(who, v);
+    if (rc) return rc;
+    return traj_run(c, v, 0, nullptr, 0, [&](const TrajView& d, void*) {
+        return launch_radial_keys(d, which, pos_ned, keys, row_stride, col0, c->stream);
+    });
 }
 
 int ginsim_radial_keys(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
                        int32_t which, int32_t pos_ned, double* keys, int64_t row_stride, int64_t col0) {
-    const int rc = check_keys_args("radial_keys", c, traj, ref, n, runs, samples, m, which, keys, row_stride, col0);
-    if (rc) return rc;
-    return keys_run(c, traj, 0, ref, n, runs, samples, m, which, pos_ned, nullptr, 0, 0, keys, row_stride, col0);
+    return keys_entry("radial_keys", c, TrajView{traj, 0, ref, n, runs, samples, m, {nullptr, 0, 0}}, which, pos_ned, keys, row_stride, col0);
 }
 
 int ginsim_radial_keys_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
                            int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first,
                            double* keys, int64_t row_stride, int64_t col0) {
-    const int rc = check_keys_args("radial_keys_f32", c, traj, ref, n, runs, samples, m, which, keys, row_stride, col0);
-    if (rc) return rc;
-    REQUIRE(origin && n_ini >= 1, "radial_keys_f32: the origin table of the displacement series is missing");
-    return keys_run(c, traj, 1, ref, n, runs, samples, m, which, pos_ned, origin, n_ini, ini_first, keys, row_stride, col0);
+    return keys_entry("radial_keys_f32", c, TrajView{traj, 1, ref, n, runs, samples, m, {origin, n_ini, ini_first}}, which, pos_ned, keys,
+                      row_stride, col0);
 }
 
+// the order statistics of key rows (csrc/error_quantile.hip, the select)
 int ginsim_quantile_rows(ginsim_ctx* c, const double* keys, int64_t rows, int64_t len, int64_t row_stride, const double* probs,
                          int32_t q, double* host_out, double* host_count) {
     REQUIRE(c && keys && probs && host_out && host_count, "quantile_rows: NULL argument");
@@ -1320,46 +1305,24 @@ int ginsim_quantile_rows(ginsim_ctx* c, const double* keys, int64_t rows, int64_
     return GINSIM_OK;
 }
 
-// ---- error covariance across the runs (csrc/error_cov.hip): the record of every requested sample
-// the scratch region: [records and slice records of error_cov.hip][m sample indices]
-static int cov_run(ginsim_ctx* c, const void* traj, int f32, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
-                   int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first,
-                   double* host_out) {
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t body = error_cov_scratch_bytes(runs, m);
-    void* ws = nullptr;
-    HIP_TRY(scratch(c, 2, body + sizeof(int64_t) * (size_t)m, &ws));
-    int64_t* d_samples = nullptr;
-    if (samples) {
-        d_samples = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ws) + body);
-        HIP_TRY(hipMemcpyAsync(d_samples, samples, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    }
-    if (f32)
-        HIP_TRY(launch_error_cov_f32(reinterpret_cast<const float*>(traj), ref, n, runs, d_samples, m, which, pos_ned, ws, origin, n_ini,
-                                     ini_first, c->stream));
-    else
-        HIP_TRY(launch_error_cov(reinterpret_cast<const double*>(traj), ref, n, runs, d_samples, m, which, pos_ned, ws, c->stream));
-    HIP_TRY(hipMemcpyAsync(host_out, ws, sizeof(double) * GINSIM_COV_RECORD * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GINSIM_OK;
+static int cov_entry(const char* who, ginsim_ctx* c, const TrajView& v, int32_t which, int32_t pos_ned, double* host_out) {
+    int rc = check_curve_args(who, c, v, host_out);
+    if (!rc) rc = check_which(who, which);
+    if (!rc) rc = check_origin(who, v);
+    if (rc) return rc;
+    return traj_run(c, v, error_cov_scratch_bytes(v), host_out, sizeof(double) * GINSIM_COV_RECORD * (size_t)v.m,
+                    [&](const TrajView& d, void* ws) { return launch_error_cov(d, which, pos_ned, ws, c->stream); });
 }
 
 int ginsim_error_cov(ginsim_ctx* c, const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
                      int32_t which, int32_t pos_ned, double* host_out) {
-    const int rc = check_curve_args("error_cov", c, traj, ref, n, runs, samples, m, host_out);
-    if (rc) return rc;
-    REQUIRE(which == 0 || which == 1, "error_cov: which=%d is neither 0 (position) nor 1 (velocity)", (int)which);
-    return cov_run(c, traj, 0, ref, n, runs, samples, m, which, pos_ned, nullptr, 0, 0, host_out);
+    return cov_entry("error_cov", c, TrajView{traj, 0, ref, n, runs, samples, m, {nullptr, 0, 0}}, which, pos_ned, host_out);
 }
 
 int ginsim_error_cov_f32(ginsim_ctx* c, const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples,
                          int64_t m, int32_t which, int32_t pos_ned, const double* origin, int32_t n_ini, uint64_t ini_first,
                          double* host_out) {
-    const int rc = check_curve_args("error_cov_f32", c, traj, ref, n, runs, samples, m, host_out);
-    if (rc) return rc;
-    REQUIRE(which == 0 || which == 1, "error_cov_f32: which=%d is neither 0 (position) nor 1 (velocity)", (int)which);
-    REQUIRE(origin && n_ini >= 1, "error_cov_f32: the origin table of the displacement series is missing");
-    return cov_run(c, traj, 1, ref, n, runs, samples, m, which, pos_ned, origin, n_ini, ini_first, host_out);
+    return cov_entry("error_cov_f32", c, TrajView{traj, 1, ref, n, runs, samples, m, {origin, n_ini, ini_first}}, which, pos_ned, host_out);
 }
 
 int ginsim_cov_merge(const double* parts, int32_t nparts, int64_t m, double* out) {

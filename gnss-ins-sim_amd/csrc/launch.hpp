@@ -1,7 +1,7 @@
 // The host interface between the kernel files and the C ABI glue (ginsim_api.hip): every launcher and host helper that one
-// file defines and another calls, grouped by the file that defines it.  Every defining file includes it, and the library is
-// linked without undefined symbols, so a signature that drifts from its definition fails the build.  (allan.hpp, comm.hpp and
-// placed.hpp are the same thing for their files.)
+// file defines and another calls, grouped by the file that defines it, and the structs that describe a launch to them (LooseLaunch,
+// TrajView).  Every defining file includes it, and the library is linked without undefined symbols, so a signature that drifts
+// from its definition fails the build.  (allan.hpp, comm.hpp and placed.hpp are the same thing for their files.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -88,40 +88,47 @@ hipError_t launch_pattern_fill(void* p, uint64_t words, uint32_t tag, hipStream_
 hipError_t launch_pattern_check(const void* p, uint64_t words, uint32_t tag, unsigned long long* out, hipStream_t s);
 hipError_t launch_digest(const void* p, uint64_t words, unsigned long long* out, hipStream_t s);
 
+// The series of the fp32 kernel hold the DISPLACEMENT from the run's initial position in their position planes
+// (ginsim_mc_params.precision), so the position of a sample is origin[run's initial state] + displacement, formed in fp64;
+// everything after that (errors, moments) is the fp64 arithmetic of the double version.
+struct ProcOrigin {
+    const double* table;    // device [n_ini][3]: ECEF (ref_frame 1) or LLA (ref_frame 0) of every initial state, or nullptr (fp64 series)
+    int64_t n_ini;
+    uint64_t ini_first;     // the run's initial state is row (ini_first + run < n_ini ? ini_first + run : 0), as in the MC kernels
+};
+
+// Kept trajectories as the kernels that read them across the runs take them (stats.hip's process kernel, error_curve.hip,
+// error_quantile.hip, error_cov.hip): one launcher per family, which picks the kernel's precision from f32.
+struct TrajView {
+    const void* traj;           // device [9][n][runs], double or (f32) float
+    int f32;
+    const double* ref;          // device [n][9], the truth
+    int64_t n, runs;
+    const int64_t* samples;     // device: the m sample indices, or NULL: every sample (m == n)
+    int64_t m;
+    ProcOrigin org;             // f32: the origin table; else {nullptr, 0, 0}
+};
+
 // stats.hip
 size_t stats_scratch_bytes(int64_t runs);
 int stats_blocks(int64_t runs);
 hipError_t launch_end_stats(const double* end_err, int64_t runs, void* scratch, hipStream_t s);
 void stats_merge_host(const ginsim_stats* parts, int nparts, ginsim_stats* out);
-hipError_t launch_process_stats(const double* traj, const double* ref, int64_t n, int64_t runs, int64_t j0, int pos_ned,
-                                int run_major, double* out, hipStream_t s);
-hipError_t launch_process_stats_f32(const float* traj, const double* ref, int64_t n, int64_t runs, int64_t j0, int pos_ned,
-                                    int run_major, double* out, const double* origin, int64_t n_ini, uint64_t ini_first, hipStream_t s);
+hipError_t launch_process_stats(const TrajView& v, int64_t j0, int pos_ned, int run_major, double* out, hipStream_t s);     // v.samples, v.m unused
 
 // error_curve.hip
-size_t error_curve_scratch_bytes(const void* traj, int64_t runs, int64_t m);
-hipError_t launch_error_curve(const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                              int pos_ned, void* scratch, hipStream_t s);
-hipError_t launch_error_curve_f32(const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                                  int pos_ned, void* scratch, const double* origin, int64_t n_ini, uint64_t ini_first, hipStream_t s);
+size_t error_curve_scratch_bytes(const TrajView& v);
+hipError_t launch_error_curve(const TrajView& v, int pos_ned, void* scratch, hipStream_t s);
 void curve_merge_host(const double* parts, int nparts, int64_t m, double* out);
 
 // error_quantile.hip
-hipError_t launch_radial_keys(const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                              int which, int pos_ned, double* keys, int64_t row_stride, int64_t col0, hipStream_t s);
-hipError_t launch_radial_keys_f32(const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                                  int which, int pos_ned, double* keys, int64_t row_stride, int64_t col0, const double* origin,
-                                  int64_t n_ini, uint64_t ini_first, hipStream_t s);
+hipError_t launch_radial_keys(const TrajView& v, int which, int pos_ned, double* keys, int64_t row_stride, int64_t col0, hipStream_t s);
 hipError_t launch_quantile_rows(const double* keys, int64_t rows, int64_t len, int64_t row_stride, const double* probs, int q,
                                 double* out, double* count, hipStream_t s);
 
 // error_cov.hip
-size_t error_cov_scratch_bytes(int64_t runs, int64_t m);
-hipError_t launch_error_cov(const double* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                            int which, int pos_ned, void* scratch, hipStream_t s);
-hipError_t launch_error_cov_f32(const float* traj, const double* ref, int64_t n, int64_t runs, const int64_t* samples, int64_t m,
-                                int which, int pos_ned, void* scratch, const double* origin, int64_t n_ini, uint64_t ini_first,
-                                hipStream_t s);
+size_t error_cov_scratch_bytes(const TrajView& v);
+hipError_t launch_error_cov(const TrajView& v, int which, int pos_ned, void* scratch, hipStream_t s);
 void cov_merge_host(const double* parts, int nparts, int64_t m, double* out);
 
 // Predicates on a parameter block that the dispatch of several files asks.

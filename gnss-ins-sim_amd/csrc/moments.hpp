@@ -49,15 +49,6 @@ __device__ __forceinline__ double angle_range_pi_mul(double x) {
     return m > kPi ? m - kTwoPi : m;
 }
 
-// T = float: the series of the fp32 kernel -- the position planes hold the DISPLACEMENT from the run's initial position
-// (ginsim_mc_params.precision), so the position of a sample is origin[run's initial state] + displacement, formed in fp64;
-// everything after that (errors, moments) is the fp64 arithmetic of the double version.
-struct ProcOrigin {
-    const double* table;    // device [n_ini][3]: ECEF (ref_frame 1) or LLA (ref_frame 0) of every initial state, or nullptr (T = double)
-    int64_t n_ini;
-    uint64_t ini_first;     // the run's initial state is row (ini_first + run < n_ini ? ini_first + run : 0), as in the MC kernels
-};
-
 // the error of a sample against its truth row t: x = the nine values of the run (position: origin already added)
 __device__ __forceinline__ void sample_error(const double (&x)[9], const double (&t)[9], int pos_ned, double (&e)[9]) {
 #pragma unroll

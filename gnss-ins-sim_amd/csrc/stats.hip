@@ -8,8 +8,7 @@
 #include "ginsim.h"
 #include "fastmath.hpp"
 #include "ins_math.hpp"
-#include "moments.hpp"
-#include "launch.hpp"
+#include "traj_error.hpp"
 
 namespace ginsim {
 
@@ -96,11 +95,7 @@ __global__ void __launch_bounds__(64 * kSeg) process_stats_kernel(const T* __res
     for (int c = 0; c < 9; ++c) { mean[c] = 0.0; m2[c] = 0.0; mx[c] = 0.0; }
     double cnt = 0.0;
     double o3[3] = {0.0, 0.0, 0.0};
-    if (org.table && active) {
-        const uint64_t call = org.ini_first + (uint64_t)r;
-        const double* row = org.table + 3 * (call < (uint64_t)org.n_ini ? call : 0);
-        o3[0] = row[0]; o3[1] = row[1]; o3[2] = row[2];
-    }
+    if (org.table && active) run_origin(org, r, o3);
     // the error of sample j against the truth
     auto error = [&](int64_t j, double (&e)[9]) {
         double x[9], t[9];
@@ -166,18 +161,15 @@ __global__ void __launch_bounds__(64 * kSeg) process_stats_kernel(const T* __res
     }
 }
 
-hipError_t launch_process_stats(const double* traj, const double* ref, int64_t n, int64_t runs, int64_t j0, int pos_ned,
-                                int run_major, double* out, hipStream_t s) {
-    hipLaunchKernelGGL((process_stats_kernel<double>), dim3((unsigned)((runs + 63) / 64)), dim3(64 * kSeg), 0, s, traj, ref, n, runs, j0,
-                       pos_ned, run_major, out, ProcOrigin{nullptr, 0, 0});
+template <typename T>
+static hipError_t launch_proc(const TrajView& v, int64_t j0, int pos_ned, int run_major, double* out, hipStream_t s) {
+    hipLaunchKernelGGL((process_stats_kernel<T>), dim3((unsigned)((v.runs + 63) / 64)), dim3(64 * kSeg), 0, s,
+                       static_cast<const T*>(v.traj), v.ref, v.n, v.runs, j0, pos_ned, run_major, out, v.org);
     return hipGetLastError();
 }
 
-hipError_t launch_process_stats_f32(const float* traj, const double* ref, int64_t n, int64_t runs, int64_t j0, int pos_ned,
-                                    int run_major, double* out, const double* origin, int64_t n_ini, uint64_t ini_first, hipStream_t s) {
-    hipLaunchKernelGGL((process_stats_kernel<float>), dim3((unsigned)((runs + 63) / 64)), dim3(64 * kSeg), 0, s, traj, ref, n, runs, j0,
-                       pos_ned, run_major, out, ProcOrigin{origin, n_ini, ini_first});
-    return hipGetLastError();
+hipError_t launch_process_stats(const TrajView& v, int64_t j0, int pos_ned, int run_major, double* out, hipStream_t s) {
+    return v.f32 ? launch_proc<float>(v, j0, pos_ned, run_major, out, s) : launch_proc<double>(v, j0, pos_ned, run_major, out, s);
 }
 
 int stats_blocks(int64_t runs) {
