@@ -83,7 +83,9 @@ def test_run_ids_beyond_32_bits(ctx, turn):
 
 @pytest.mark.parametrize('rf', [0, 1])
 def test_multi_column_initial_states_and_run_times(ctx, turn, rf):
-    """free_integration.py:42-61, 85-87: run r uses column r while r < k, else column 0; run_times keeps counting."""
+    """free_integration.py:42-61, 85-87: run r uses column r while r < k, else column 0; run_times keeps counting.  The columns
+    differ in speed, yaw and POSITION (200 m of altitude and 1e-5 rad of latitude, 64 m, per column): all nine end errors against
+    the C oracle, the attitude and the position at the tolerances of test_vibration_models_against_the_oracles."""
     import ginsim
     from ginsim import workloads
     from oracle import c_oracle
@@ -93,6 +95,8 @@ def test_multi_column_initial_states_and_run_times(ctx, turn, rf):
     table = np.repeat(ini[:, None], k, axis=1)
     table[3, :] += np.arange(k) * 0.5           # different initial forward speed per column
     table[6, :] += np.arange(k) * 1e-3          # and yaw
+    table[2, :] += np.arange(k) * 200.0         # and altitude
+    table[0, :] += np.arange(k) * 1e-5          # and latitude
     g = np.full((1, k), 9.79)
     table10 = np.vstack([table, g])
     for tab in (table, table10):
@@ -100,6 +104,11 @@ def test_multi_column_initial_states_and_run_times(ctx, turn, rf):
         end, _, _ = c_oracle.mc_run(4, 0, 9, 100.0, rf, truth, acc, gyr, tab, ini_first=2)
         np.testing.assert_allclose(dev[:, 6:9], end[:, 6:9], rtol=0, atol=1e-9)
         assert np.abs(dev[0, 6:9] - dev[5, 6:9]).max() > 1e-3      # column 2 vs column 0
+        np.testing.assert_allclose(dev[:, 3:6], end[:, 3:6], rtol=0, atol=2e-8)
+        assert np.max(np.abs(np.mod(dev[:, :3] - end[:, :3] + np.pi, 2 * np.pi) - np.pi)) < 1e-9
+        # runs 0, 1, 2 start on columns 2, 3, 4, every later run on column 0: the end position says which
+        up = dev[:, 5] if rf == 0 else np.linalg.norm(dev[:, 3:6], axis=1)
+        assert np.all(np.abs(up[:3] - up[3:].mean()) > 100.0) and np.abs(up[1] - up[0]) > 100.0 and np.abs(up[2] - up[1]) > 100.0
 
 
 def test_sim_second_run_keeps_counting_columns(ctx, turn):

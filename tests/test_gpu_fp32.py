@@ -150,6 +150,140 @@ def test_fp32_short_series_every_tile_boundary(ctx, name):
             job.release()
 
 
+@pytest.mark.parametrize('rf', [0, 1])
+def test_fp32_multi_column_initial_states_through_the_readers(ctx, rf):
+    """The fp32 twin of tests/test_gpu_edge_cases.py's multi-column test: five columns that differ in speed, yaw and POSITION (200 m
+    of altitude and 1e-5 rad of latitude per column), nine runs, ini_first = 2, so runs 0, 1, 2 start on columns 2, 3, 4 and every
+    later run on column 0.  The float series (position: displacement from the run's OWN column) equal the float oracle bit for bit,
+    and everything that reads them back with the origin table -- error_curve, error_cov, error_quantiles, process_stats,
+    stats_from_traj -- equals its restatement on job.trajectories (origin + displacement formed on the host).  A reader that took
+    another row of the table for a run would be 200 m or more off."""
+    import ginsim
+    from ginsim import workloads
+    from oracle import c_oracle
+    import error_curve_ref
+    import error_covariance_ref
+    import error_quantiles_ref
+    from test_gpu_error_curve import _assert_curve
+    ini, truth, _ = workloads.truth_from_profile('turn_90deg', 100.0, rf)
+    acc, gyr = workloads.imu_grade('mid-accuracy')
+    k, R, seed = 5, 9, 4
+    table = np.repeat(np.asarray(ini, dtype=np.float64)[:, None], k, axis=1)
+    table[3, :] += np.arange(k) * 0.5
+    table[6, :] += np.arange(k) * 1e-3
+    table[2, :] += np.arange(k) * 200.0
+    table[0, :] += np.arange(k) * 1e-5
+    job = ginsim.MonteCarloJob(ctx, 100.0, rf, truth, acc, gyr, table, runs=R, seed=seed, ini_first=2, keep_traj=True, precision='f32').run()
+    ids = np.arange(R)
+    end, traj, _, _ = c_oracle.mc_run_f32(seed, 0, R, 100.0, rf, truth, acc, gyr, table, ini_first=2, keep=R)
+    att, dpos, vel = job.trajectories('free', ids, displacement=True)
+    _bits_equal(att, traj[:, :, 0:3], 'multi-column att')
+    _bits_equal(dpos, traj[:, :, 3:6], 'multi-column displacement')
+    _bits_equal(vel, traj[:, :, 6:9], 'multi-column vel')
+    att, pos, vel = job.trajectories('free', ids)
+    # the host copy starts every run on its own column: 400, 600, 800 m above column 0
+    from gnss_ins_sim.geoparams import geoparams
+    start = table[0:3, [2, 3, 4, 0, 0, 0, 0, 0, 0]].T
+    np.testing.assert_allclose(pos[:, 0], geoparams.lla2ecef(start) if rf == 1 else start, rtol=0, atol=1e-9)
+    series = np.concatenate([att, pos, vel], axis=2)
+    ref_nav = np.ascontiguousarray(np.concatenate([truth['ref_att'], truth['ref_pos'], truth['ref_vel']], axis=1))
+    n = job.n
+    rows = np.array([0, 1, 500, n - 1])
+    for ned in ([False, True] if rf == 0 else [False]):
+        what = 'multi-column rf%d ned=%d' % (rf, ned)
+        e = error_curve_ref.errors(series, ref_nav, None, ned)
+        want = error_curve_ref.curve(series, ref_nav, None, ned)
+        _assert_curve(job.error_curve('free', None, pos_ned=ned), want, None, ned, what=what + ' curve')
+        _assert_curve(job.error_curve('free', rows, pos_ned=ned), want, rows, ned, what=what + ' curve rows')
+        st = job.stats_from_traj('free', pos_ned=ned)
+        rec = np.empty((1, 9, 4))
+        rec[0, :, 0], rec[0, :, 1], rec[0, :, 2], rec[0, :, 3] = st.count, st.mean, st.m2, st.maxabs
+        _assert_curve(ginsim.CurveResult(rec), want, [n - 1], ned, what=what + ' end statistics')
+        for which in (0, 1):
+            e3 = error_covariance_ref.errors3(series, ref_nav, None, which, ned)
+            b = error_covariance_ref.bounded(e3)
+            slack = error_covariance_ref.input_slack(b['rec'], error_covariance_ref.component_tolerance(e3, which, ned)) if ned and not which else None
+            error_covariance_ref.assert_record(job.error_cov('free', None, which, pos_ned=ned).pack(), b, what + ' cov which %d' % which, slack)
+        for first in (0, 700):
+            stats = error_curve_ref.array_stats(np.moveaxis(e[:, first:], 1, 0))
+            got = job.process_stats('free', first, pos_ned=ned)
+            for i, key in enumerate(('max', 'avg', 'std')):      # the tolerance of test_fp32_process_and_ned_statistics_over_float_trajectories
+                np.testing.assert_allclose(got[:, i], stats[key], rtol=1e-9, atol=2e-8 if ned else 1e-12, err_msg='%s process %s' % (what, key))
+    # the quantiles: ref_frame 0 always in NED metres; the select is exact, the keys carry the key tolerance
+    ned = rf == 0
+    for which in (0, 1):
+        keys = error_quantiles_ref.keys(series, ref_nav, rows, which, ned)
+        want, count = error_quantiles_ref.quantile_rows(keys.reshape(-1, R), (0.5, 0.95))
+        got = job.error_quantiles('free', rows, which, probs=(0.5, 0.95))
+        assert np.all(got.count == R) and np.all(count == R)
+        tol = error_quantiles_ref.key_tolerance(want.reshape(3, rows.size, 2), which, ned)
+        assert np.all(np.abs(got.values - want.reshape(3, rows.size, 2)) <= tol), 'multi-column quantiles which %d' % which
+    # the position error at the first sample is the column's offset: the curve's max there says that run 2 took column 4
+    if rf == 0:
+        assert abs(job.error_curve('free', [0]).maxabs[0, 5] - 800.0) < 1.0
+    job.release()
+
+
+@pytest.mark.parametrize('rf', [1, 0])
+def test_blocked_fp32_sim_with_a_multi_column_table_equals_the_kept_sim(rf):
+    """A statistics-only fp32 Sim whose plugin holds FOUR initial states with distinct positions, 4096 runs integrated again in
+    four blocks of 1024: block b reads its float series back with ini_first = 1024 b, so blocks 1 to 3 are past the end of the
+    table (every run on column 0) while runs 1, 2, 3 of block 0 have columns of their own.  error_curve, error_covariance and
+    error_quantiles against the fp32 Sim that keeps all trajectories, under the rules of the blocked tests of
+    tests/test_gpu_error_curve.py (to rounding), test_gpu_error_covariance.py (both against the restatement on the kept
+    trajectories) and test_gpu_error_quantiles.py (the same bytes)."""
+    import sys
+    from conftest import PKG
+    import error_covariance_cases as cc
+    import error_covariance_ref as ref
+    from test_gpu_error_curve import _assert_same_curve
+    sys.path[:0] = [PKG] if PKG not in sys.path else []
+    from gnss_ins_sim.sim import imu_model, ins_sim
+    from demo_algorithms import free_integration
+    from ginsim import workloads
+    ini = np.asarray(workloads.parse_motion(cc.SHORT_TURN)[0], dtype=np.float64)
+    table = np.repeat(ini[:, None], 4, axis=1)
+    table[2, :] += np.arange(4) * 200.0
+    table[0, :] += np.arange(4) * 1e-5
+    runs, rows = 4096, np.array([1, 20, 63, 40])
+
+    def make(**kw):
+        imu = imu_model.IMU(accuracy='mid-accuracy', axis=6, gps=False)
+        sim = ins_sim.Sim([cc.FS, 0.0, 0.0], cc.SHORT_TURN, ref_frame=rf, imu=imu, algorithm=free_integration.FreeIntegration(table.copy()),
+                          seed=99, precision='f32', **kw)
+        sim.run(runs)
+        return sim
+
+    kept = make(keep_trajectories=True)
+    sim = make(keep_trajectories=False, max_device_bytes=1024 * 9 * 4 * cc.CUT)
+    job = kept.mc.jobs[0]
+    assert job.precision == 'f32' and job.keep_traj and job.n == cc.CUT and job._ini_table.shape[0] == 4
+    assert sim.mc.jobs[0].precision == 'f32' and sim.mc.jobs[0].keep_traj is False and sim.mc._block_runs == 1024
+    ned, opt = rf == 0, ('ned' if rf == 0 else '')
+    # the kept runs really start on four positions
+    att, pos, vel = job.trajectories('free', np.arange(6))
+    up = pos[:, 0, 2] if rf == 0 else np.linalg.norm(pos[:, 0] - pos[5, 0], axis=1)
+    assert np.all(np.abs(np.abs(up - up[5])[:4] - np.array([0.0, 200.0, 400.0, 600.0])) < 70.0) and abs(up[4] - up[5]) < 1e-6
+    _assert_same_curve(sim.error_curve(extra_opt=opt), kept.error_curve(extra_opt=opt), 'multi-column fp32 blocked rf%d' % rf)
+    att, pos, vel = job.trajectories('free', np.arange(runs))
+    series = np.concatenate([att, pos, vel], axis=2)
+    name = kept.mc.nav_names[0]
+    for which in (0, 1):
+        e = ref.errors3(series, job._ref_nav, rows, which, ned)
+        b = ref.bounded(e)
+        slack = ref.input_slack(b['rec'], ref.component_tolerance(e, which, ned))
+        for what, s in (('kept', kept), ('blocked', sim)):
+            got = s.mc.error_covariance(name, rows, cc.CUT, which, ned=ned).pack()
+            ref.assert_record(got, b, 'multi-column fp32 %s rf%d which %d' % (what, rf, which), slack)
+    whole = kept.error_quantiles(('pos', 'vel'), (0.5, 0.95, 0.999), samples=rows)
+    got = sim.error_quantiles(('pos', 'vel'), (0.5, 0.95, 0.999), samples=rows)
+    for nm in ('pos', 'vel'):
+        assert np.all(got[nm]['count'][name] == runs)
+        for part in ('horizontal', 'vertical', '3d'):
+            assert got[nm][part][name].tobytes() == whole[nm][part][name].tobytes(), (nm, part)
+    job.release()
+
+
 @pytest.mark.parametrize('name', ['bosch', 'nxp', 'tumble'])
 def test_fp32_given_data_fixtures(ctx, name):
     """The plugin boundary in fp32: logged fp64 IMU series on the device, rounded to float as the kernel reads them."""
