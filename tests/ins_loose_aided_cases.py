@@ -59,3 +59,8 @@ def aid(mask, every=1, odo_err=ODO_ERR, nhc_std=NHC_STD, **kw):
 def aid_options(mask, every=1, nhc_std=NHC_STD, **kw):
     """The same as the `aid` dict InsLooseJob takes."""
     return dict({'odo': bool(mask & 1), 'nhc': bool(mask & 6), 'every': every, 'nhc_std': nhc_std}, **kw)
+
+
+def aid_kw(mask, every=1, **kw):
+    """The keywords of an InsLooseJob aided by the rows of `mask`, under kw; mask 0: kw alone, no aiding argument at all."""
+    return dict(dict(odo_err=ODO_ERR, aid=aid_options(mask, every)), **kw) if mask else kw

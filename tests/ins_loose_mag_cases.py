@@ -59,6 +59,11 @@ def model(mag_err, ref_frame, every=1, geo=GEO, **kw):
     return mag_model(mag_err, geo, ref_frame, dict({'every': every}, **kw))
 
 
+def mag_kw(mag_err, geo=GEO, every=1, **kw):
+    """The keywords of an InsLooseJob aided by the magnetometer mag_err in the field geo, under kw."""
+    return dict(dict(mag_err=mag_err, geo_mag_n=geo, mag={'every': every}), **kw)
+
+
 # ------------------------------------------------------------------------------------------------- consistency by profile and frame
 # profile name -> (motion CSV, geomagnetic field, magnetometer model): the level outage profile as the tests above use it, and the
 # tilted southern profile with a general calibration

@@ -17,63 +17,17 @@ import pytest
 
 import ins_loose_aided_cases as ac
 import ins_loose_cases as cs
+import ins_loose_dump
 import ins_loose_ref as ref
+from ins_loose_dump import ctx, held, planes, result, same_bits
 
 pytestmark = pytest.mark.gpu
 
-FS, FS_GPS = 20.0, 2.0
 
-
-@pytest.fixture(scope='module')
-def ctx():
-    import ginsim
-    c = ginsim.Context(0)
-    yield c
-    c.close()
-
-
-class Dump(object):
-    """The device's own accel, gyro, odometer (ginsim_mc_run) and fixes (ginsim_aux_sensors) of `runs` runs, on the device and on
-    the host.  vbx0: the initial forward speed the FILTER starts from (None: the profile's)."""
-
-    def __init__(self, ctx, rf, n, runs, seed=77, run_offset=0, fs=FS, fs_gps=FS_GPS, gps=True, vbx0=None, profile=cs.OUTAGE_CSV):
-        import ginsim
-        self.rf, self.fs, self.runs, self.seed, self.run_offset = rf, fs, runs, seed, run_offset
-        self.ini, truth, self.stamps = ac.outage_truth(fs, rf, fs_gps, n, profile)
-        if vbx0 is not None:
-            self.ini = np.array(self.ini, dtype=np.float64)
-            self.ini[3] = vbx0
-        self.truth_gps = truth
-        if not gps:
-            truth = dict(truth, ref_gps=np.zeros((0, 6)), gps_time=np.zeros(0), gps_visibility=np.zeros(0))
-            self.stamps = self.stamps[:0]
-        self.truth = truth
-        self.n = truth['ref_accel'].shape[0]
-        self.acc_e, self.gyr_e = cs.imu_errors()
-        self.mc = ginsim.MonteCarloJob(ctx, fs, rf, truth, self.acc_e, self.gyr_e, self.ini, runs=runs, algos=('free',), odo_err=ac.ODO_ERR,
-                                       seed=seed, run_offset=run_offset, keep_sensors=True).run()
-        ids = np.arange(runs)
-        self.accel, self.gyro, self.odo = self.mc.sensors('accel', ids), self.mc.sensors('gyro', ids), self.mc.sensors('odo', ids)
-        self.given = {'accel': self.mc.buffer('accel'), 'gyro': self.mc.buffer('gyro'), 'odo': self.mc.buffer('odo')}
-        self.aux, self.gps = None, None
-        if gps:
-            self.aux = ginsim.AuxSensorJob(ctx, runs, seed=seed, run_offset=run_offset, ref_gps=truth['ref_gps'], gps_err=cs.GPS_ERR,
-                                           ref_frame=rf).run()
-            self.gps = self.aux.series('gps', ids)
-            self.given['gps'] = self.aux._bufs['gps']
-        self.model = ginsim.filter_model(fs, self.acc_e, self.gyr_e, cs.GPS_ERR)
-
+class Dump(ins_loose_dump.Dump):
     def job(self, ctx, mask, every=1, given=False, **kw):
         """mask 0: the unaided job (no aiding argument at all)."""
-        import ginsim
-        kw = dict(dict(seed=self.seed, run_offset=self.run_offset, keep_traj=True), **kw)
-        if mask:
-            kw = dict(dict(odo_err=ac.ODO_ERR, aid=ac.aid_options(mask, every)), **kw)
-        return ginsim.InsLooseJob(ctx, self.fs, self.rf, self.truth, self.acc_e, self.gyr_e, cs.GPS_ERR, self.ini, self.runs,
-                                  given=(given if isinstance(given, dict) else self.given) if given else None, **kw)
-
-    def _args(self):
-        return (self.rf, self.fs, self.gyro, self.accel, self.ini, self.model, self.gps, self.stamps, self.truth['gps_visibility'])
+        return super().job(ctx, given, **ac.aid_kw(mask, every, **kw))
 
     def restate(self, mask, every=1):
         return ref.run(*self._args(), odo=self.odo, aid=ac.aid(mask, every))
@@ -82,44 +36,13 @@ class Dump(object):
         """16 x the aided restatement's own float64 error on this case (its first 8 runs)."""
         return cs.parity_bound(*self._args(), odo=self.odo, aid=ac.aid(mask, every))
 
-    def release(self):
-        self.mc.release()
-        if self.aux is not None:
-            self.aux.release()
-
-
-def result(job):
-    ids = np.arange(job.runs)
-    out = {k: job.series(k, ids) for k in ('att', 'pos', 'vel', 'wb', 'ab')}
-    out['pdiag_end'] = job.final_pdiag()
-    return out
-
-
-def planes(job):
-    """Every output of a job as raw arrays (bit comparisons)."""
-    R, n = job.runs, job.n
-    out = {'traj': job.ctx.download(job.buffer('traj_loose'), (9, n, R)), 'wb': job.ctx.download(job.buffer('wb'), (3, n, R)),
-           'ab': job.ctx.download(job.buffer('ab'), (3, n, R)), 'end': job.end_errors().T.copy(), 'pdiag': job.final_pdiag()}
-    out['bias'] = np.concatenate(job.final_biases(), axis=1)
-    return out
-
-
-def same_bits(a, b, runs_a=None, runs_b=None):
-    for k in a:
-        x = a[k] if runs_a is None else (a[k][..., runs_a] if k in ('traj', 'wb', 'ab', 'end') else a[k][runs_a])
-        y = b[k] if runs_b is None else (b[k][..., runs_b] if k in ('traj', 'wb', 'ab', 'end') else b[k][runs_b])
-        assert np.array_equal(x.view(np.uint64), y.view(np.uint64)), k
-
 
 def held_to_the_restatement(ctx, d, mask, every, what):
     job = d.job(ctx, mask, every, given=True).run()
     assert job.kernel_name() == 'ginsim::loose_aided_kernel<%d, true, false, false>' % d.rf
     dev = result(job)
     job.release()
-    got, bound = cs.deviation(dev, d.restate(mask, every)), d.bound(mask, every)
-    print('%s rf%d mask %d every %d: ' % (what, d.rf, mask, every) + ', '.join('%s %.2e (bound %.2e)' % (k, got[k], bound[k]) for k in got))
-    for k in got:
-        assert got[k] <= bound[k], (k, got[k], bound[k])
+    held('%s rf%d mask %d every %d' % (what, d.rf, mask, every), cs.deviation(dev, d.restate(mask, every)), d.bound(mask, every))
     return dev
 
 
@@ -233,7 +156,7 @@ def test_run_list_in_shuffled_order(ctx, big):
     for k in ('traj', 'wb', 'ab'):
         assert np.array_equal(got[k][..., ids].view(np.uint64), whole[k][..., ids].view(np.uint64)), k
         assert not got[k][..., rest].any(), k               # the other runs' columns were not touched
-    assert np.array_equal(got['pdiag'][ids].view(np.uint64), whole['pdiag'][ids].view(np.uint64))
+    assert np.array_equal(got['pdiag'][..., ids].view(np.uint64), whole['pdiag'][..., ids].view(np.uint64))
     part.release()
 
 
@@ -253,7 +176,7 @@ def test_a_non_finite_odometer_sample_stays_in_its_run(ctx, dump, value):
     keep = np.setdiff1d(np.arange(65), [33])
     same_bits(got, want, runs_a=keep, runs_b=keep)
     assert not np.any(np.isfinite(got['traj'][3:9, -1, 33]))                   # position and velocity of the last row
-    assert not np.all(np.isfinite(got['end'][:, 33])) and not np.all(np.isfinite(got['pdiag'][33]))
+    assert not np.all(np.isfinite(got['end'][:, 33])) and not np.all(np.isfinite(got['pdiag'][:, 33]))
     assert np.array_equal(got['traj'][:, :100, 33], want['traj'][:, :100, 33])  # rows before the block of sample 100
 
 
@@ -357,10 +280,7 @@ def test_sim_runs_the_aided_and_the_unaided_filter_on_one_realisation(ctx):
     got = {k: np.stack([np.asarray(src.data['%s_%d' % (aided, r)]) for r in runs])
            for k, src in (('att', d.att_euler), ('pos', d.pos), ('vel', d.vel), ('wb', d.wb), ('ab', d.ab))}
     got['pdiag_end'] = job1.final_pdiag()[runs]
-    dev = cs.deviation(got, exp)
-    print('Sim pairing: ' + ', '.join('%s %.2e (bound %.2e)' % (k, dev[k], bound[k]) for k in dev))
-    for k in dev:
-        assert dev[k] <= bound[k], (k, dev[k], bound[k])
+    held('Sim pairing', cs.deviation(got, exp), bound)
     # the curve, and the benefit at the outage's last sample
     samples = np.array(ac.outage_samples({'gps_visibility': vis, 'ref_accel': accel[0]}, stamps, fs, fs_gps))
     curve = sim.error_curve(('pos',), samples=samples)

@@ -13,51 +13,11 @@ import pytest
 import ins_loose_aided_cases as ac
 import ins_loose_cases as cs
 import ins_loose_cons_ref as cref
-from test_gpu_ins_loose_aided import Dump, planes, same_bits
-from test_ins_loose_cons_oracle import in_bands
+from ins_loose_cons_cases import in_bands
+from ins_loose_cons_dump import cons_held, record
+from ins_loose_dump import Dump, ctx, planes, same_bits
 
 pytestmark = pytest.mark.gpu
-
-COLUMNS = ['count'] + ['P_' + s for s in cref.STATES] + ['e2_' + s for s in cref.STATES[:9]] + ['nes_' + s for s in cref.STATES[:9]] \
-    + ['nees_r', 'nees_v', 'nees_psi']
-
-
-@pytest.fixture(scope='module')
-def ctx():
-    import ginsim
-    c = ginsim.Context(0)
-    yield c
-    c.close()
-
-
-def nav_of(truth):
-    return np.concatenate([truth['ref_att'], truth['ref_pos'], truth['ref_vel']], axis=1)
-
-
-def restated(d, mask, every, samples, runs=None, accel=None, dtype=np.float64):
-    """The restatement's record of Dump d over `runs` (None: all) at `samples`."""
-    r = np.arange(d.runs) if runs is None else np.asarray(runs)
-    acc = d.accel if accel is None else accel
-    return cref.run(d.rf, d.fs, d.gyro[r], acc[r], d.ini, d.model, nav_of(d.truth), samples, None if d.gps is None else d.gps[r], d.stamps,
-                    d.truth['gps_visibility'], dtype=dtype, odo=d.odo[r], aid=ac.aid(mask, every) if mask else None)
-
-
-def held(what, dev, d, mask, every, samples, **kw):
-    """Assert the device record dev (m, 43) against the restatement within 16 x the restatement's own float64 error; print both."""
-    lo, hi = restated(d, mask, every, samples, **kw), restated(d, mask, every, samples, dtype=np.longdouble, **kw)
-    bound = cs.PARITY_MARGIN * cref.deviation(lo, hi)
-    got = cref.deviation(dev, lo)
-    worst = int(np.argmax(got / np.maximum(bound, 1e-300)))
-    print('%s rf%d mask %d: largest deviation %.2e, smallest bound %.2e; tightest column %s %.2e (bound %.2e)'
-          % (what, d.rf, mask, got.max(), bound[1:].min(), COLUMNS[worst], got[worst], bound[worst]))
-    assert not dev[:, 37:].any()
-    for k in range(37):
-        assert got[k] <= bound[k], (what, COLUMNS[k], got[k], bound[k])
-    return lo
-
-
-def record(job):
-    return job.consistency().pack()
 
 
 @pytest.fixture(scope='module', params=[0, 1], ids=['rf0', 'rf1'])
@@ -74,20 +34,20 @@ SAMPLES = [0, 1, 10, 333, 698, 699]                         # the first two and 
 @pytest.mark.parametrize('mask,every', [(0, 1), (7, 7)])
 def test_parity_with_the_restatement(ctx, dump, mask, every):
     assert 10 in dump.stamps
-    job = dump.job(ctx, mask, every, given=True, cons_samples=SAMPLES, keep_traj=False).run()
+    job = dump.job(ctx, given=True, cons_samples=SAMPLES, keep_traj=False, **ac.aid_kw(mask, every)).run()
     assert job.kernel_name() == 'ginsim::loose_cons_kernel<%d, true, false, %s>' % (dump.rf, 'true' if mask else 'false')
     dev = record(job)
     res = job.consistency()
     job.release()
-    lo = held('parity', dev, dump, mask, every, SAMPLES)
+    lo = cons_held('parity', dev, dump, mask, every, SAMPLES)
     assert np.all(res.count == 65) and res.ratio.shape == (6, 9) and np.all(res.nees[2:] > 0)
     np.testing.assert_allclose(res.sigma, np.sqrt(lo[:, 1:16] / 65), rtol=1e-9)
 
 
 @pytest.mark.parametrize('mask,every', [(0, 1), (7, 7)])
 def test_generated_form_equals_given_form_bit_for_bit(ctx, dump, mask, every):
-    gen = dump.job(ctx, mask, every, cons_samples=SAMPLES, keep_traj=False).run()
-    giv = dump.job(ctx, mask, every, given=True, cons_samples=SAMPLES, keep_traj=False).run()
+    gen = dump.job(ctx, cons_samples=SAMPLES, keep_traj=False, **ac.aid_kw(mask, every)).run()
+    giv = dump.job(ctx, given=True, cons_samples=SAMPLES, keep_traj=False, **ac.aid_kw(mask, every)).run()
     assert gen.kernel_name() == 'ginsim::loose_cons_kernel<%d, false, false, %s>' % (dump.rf, 'true' if mask else 'false')
     a, b = record(gen), record(giv)
     gen.release()
@@ -102,15 +62,15 @@ TAIL_SAMPLES = [0, 150, 299]
 @pytest.mark.parametrize('runs', [1, 63, 64, 65, 129])
 def test_run_counts_around_a_wavefront(ctx, runs):
     d = Dump(ctx, 1, 300, runs, seed=21)
-    job = d.job(ctx, 7, 1, given=True, cons_samples=TAIL_SAMPLES, keep_traj=False).run()
+    job = d.job(ctx, given=True, cons_samples=TAIL_SAMPLES, keep_traj=False, **ac.aid_kw(7, 1)).run()
     dev = record(job)
     assert np.all(dev[:, 0] == runs)
-    held('%d runs' % runs, dev, d, 7, 1, TAIL_SAMPLES)
+    cons_held('%d runs' % runs, dev, d, 7, 1, TAIL_SAMPLES)
     if runs == 129:                                         # 40 scattered runs of the 129: the record is over the listed runs
         ids = np.random.default_rng(3).permutation(129)[:40]
         part = record(job.run(ids))
         assert np.all(part[:, 0] == 40)
-        held('40 of 129 runs', part, d, 7, 1, TAIL_SAMPLES, runs=ids)
+        cons_held('40 of 129 runs', part, d, 7, 1, TAIL_SAMPLES, runs=ids)
     job.release()
     d.release()
 
@@ -119,18 +79,18 @@ def test_run_counts_around_a_wavefront(ctx, runs):
 def test_the_checkpoint_perturbs_nothing_and_the_record_repeats(ctx):
     n = 300
     d = Dump(ctx, 0, n, 65, seed=31)
-    plain = d.job(ctx, 7, 3).run()
+    plain = d.job(ctx, **ac.aid_kw(7, 3)).run()
     want = planes(plain)
     pdiag = plain.final_pdiag()
     plain.release()
-    every = d.job(ctx, 7, 3, cons_samples=range(n)).run()
+    every = d.job(ctx, cons_samples=range(n), **ac.aid_kw(7, 3)).run()
     same_bits(planes(every), want)                          # trajectory, wb, ab, end record, pdiag_end, final biases
     dense = record(every)
     again = record(every.run())
     assert np.array_equal(dense.view(np.uint64), again.view(np.uint64))        # two launches of one job: identical bits
     every.release()
     sparse_at = [0, 7, 64, 150, 298, 299]
-    sparse = d.job(ctx, 7, 3, cons_samples=sparse_at, keep_traj=False).run()
+    sparse = d.job(ctx, cons_samples=sparse_at, keep_traj=False, **ac.aid_kw(7, 3)).run()
     got = record(sparse)
     sparse.release()
     assert np.array_equal(got.view(np.uint64), dense[sparse_at].view(np.uint64))
@@ -147,7 +107,7 @@ def test_a_non_finite_run_is_left_out_of_every_sum(ctx):
     acc = ctx.download(d.mc.buffer('accel'), (3, n, 65))
     acc[1, 100:, bad_run] = np.nan                          # enters the state with the step from sample 100 to 101
     bad = ctx.upload(acc)
-    job = d.job(ctx, 0, given=True, cons_samples=samples, keep_traj=False)
+    job = d.job(ctx, given=True, cons_samples=samples, keep_traj=False, **ac.aid_kw(0))
     job.mc.in_accel = bad.ptr
     dev = record(job.run())
     job.release()
@@ -155,9 +115,9 @@ def test_a_non_finite_run_is_left_out_of_every_sum(ctx):
     assert list(dev[:, 0]) == [65, 65, 64, 64, 64] and np.all(np.isfinite(dev))
     host = d.accel.copy()
     host[bad_run, 100:, 1] = np.nan
-    held('non-finite run, all runs', dev, d, 0, 1, samples, accel=host)        # the restatement leaves it out by the same rule
+    cons_held('non-finite run, all runs', dev, d, 0, 1, samples, accel=host)        # the restatement leaves it out by the same rule
     keep = np.setdiff1d(np.arange(65), [bad_run])
-    held('non-finite run, the others', dev[2:], d, 0, 1, samples[2:], runs=keep)
+    cons_held('non-finite run, the others', dev[2:], d, 0, 1, samples[2:], runs=keep)
     d.release()
 
 

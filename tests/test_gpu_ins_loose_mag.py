@@ -17,67 +17,29 @@ import pytest
 
 import ins_loose_aided_cases as ac
 import ins_loose_cases as cs
+import ins_loose_dump
 import ins_loose_mag_cases as mc
 import ins_loose_ref as ref
+from ins_loose_dump import ctx, held, planes, result, same_bits
 
 pytestmark = pytest.mark.gpu
 
-FS, FS_GPS = 20.0, 2.0
 
+class Dump(ins_loose_dump.Dump):
+    """With one magnetometer series per magnetometer model."""
 
-@pytest.fixture(scope='module')
-def ctx():
-    import ginsim
-    c = ginsim.Context(0)
-    yield c
-    c.close()
-
-
-class Dump(object):
-    """The device's own accel, gyro, odometer (ginsim_mc_run), fixes and magnetometer (ginsim_aux_sensors, one series per
-    magnetometer model) of `runs` runs, on the device and on the host."""
-
-    def __init__(self, ctx, rf, n, runs, seed=77, run_offset=0, fs=FS, fs_gps=FS_GPS, mag_errs=(('plain', mc.MAG_ERR), ('skew', mc.MAG_ERR_SKEW)),
+    def __init__(self, ctx, rf, n, runs, seed=77, run_offset=0, fs=20.0, fs_gps=2.0, mag_errs=(('plain', mc.MAG_ERR), ('skew', mc.MAG_ERR_SKEW)),
                  profile=cs.OUTAGE_CSV, geo=mc.GEO):
-        import ginsim
-        self.rf, self.fs, self.runs, self.seed, self.run_offset, self.geo = rf, fs, runs, seed, run_offset, geo
-        self.ini, self.truth, self.stamps = mc.outage_truth(fs, rf, fs_gps, n, profile, geo)
-        truth = self.truth
-        self.n = truth['ref_accel'].shape[0]
-        self.acc_e, self.gyr_e = cs.imu_errors()
-        self.mc = ginsim.MonteCarloJob(ctx, fs, rf, truth, self.acc_e, self.gyr_e, self.ini, runs=runs, algos=('free',), odo_err=ac.ODO_ERR,
-                                       seed=seed, run_offset=run_offset, keep_sensors=True).run()
-        ids = np.arange(runs)
-        self.accel, self.gyro, self.odo = self.mc.sensors('accel', ids), self.mc.sensors('gyro', ids), self.mc.sensors('odo', ids)
-        self.given = {'accel': self.mc.buffer('accel'), 'gyro': self.mc.buffer('gyro'), 'odo': self.mc.buffer('odo')}
-        self.mag_errs = dict(mag_errs)
-        self.aux, self.mag = {}, {}
-        for i, (name, err) in enumerate(mag_errs):                              # the fixes come with the first
-            self.aux[name] = ginsim.AuxSensorJob(ctx, runs, seed=seed, run_offset=run_offset, ref_gps=truth['ref_gps'] if i == 0 else None,
-                                                 gps_err=cs.GPS_ERR, ref_frame=rf, ref_mag=truth['ref_mag'], mag_err=err).run()
-            self.mag[name] = self.aux[name].series('mag', ids)
-            if i == 0:
-                self.gps = self.aux[name].series('gps', ids)
-                self.given['gps'] = self.aux[name]._bufs['gps']
-        self.model = ginsim.filter_model(fs, self.acc_e, self.gyr_e, cs.GPS_ERR)
+        super().__init__(ctx, rf, n, runs, seed, run_offset, fs, fs_gps, truth_fn=mc.outage_truth, profile=profile, geo=geo, mag_errs=mag_errs)
 
     def job(self, ctx, which, mask=0, every=1, given=False, runs=None, aid_every=1, **kw):
         """which: 'plain' | 'skew', the magnetometer model that generates and that the filter assumes; None: no magnetometer
         argument at all.  mask 0: no aiding argument at all."""
-        import ginsim
-        kw = dict(dict(seed=self.seed, run_offset=self.run_offset, keep_traj=True), **kw)
-        if mask:
-            kw = dict(dict(odo_err=ac.ODO_ERR, aid=ac.aid_options(mask, aid_every)), **kw)
+        kw = ac.aid_kw(mask, aid_every, **kw)
         if which is not None:
-            kw = dict(dict(mag_err=self.mag_errs[which], geo_mag_n=self.geo, mag={'every': every}), **kw)
-        src = None
-        if given:
-            src = dict(self.given) if which is None else dict(self.given, mag=self.aux[which]._bufs['mag'])
-        return ginsim.InsLooseJob(ctx, self.fs, self.rf, self.truth, self.acc_e, self.gyr_e, cs.GPS_ERR, self.ini, runs or self.runs,
-                                  given=src, **kw)
-
-    def _args(self):
-        return (self.rf, self.fs, self.gyro, self.accel, self.ini, self.model, self.gps, self.stamps, self.truth['gps_visibility'])
+            kw = mc.mag_kw(self.mag_errs[which], self.geo, every, **kw)
+            given = self.given_with_mag(which) if given else False
+        return super().job(ctx, given, runs=runs, **kw)
 
     def _kw(self, which, mask, every):
         return dict(odo=self.odo, mag=self.mag[which]), ac.aid(mask) if mask else None, mc.model(self.mag_errs[which], self.rf, every, self.geo)
@@ -89,34 +51,6 @@ class Dump(object):
     def bound(self, which, mask, every):
         series, aid, model = self._kw(which, mask, every)
         return cs.parity_bound(*self._args(), odo=series['odo'], aid=aid, mag=series['mag'], mag_model=model)
-
-    def release(self):
-        self.mc.release()
-        for a in self.aux.values():
-            a.release()
-
-
-def result(job):
-    ids = np.arange(job.runs)
-    out = {k: job.series(k, ids) for k in ('att', 'pos', 'vel', 'wb', 'ab')}
-    out['pdiag_end'] = job.final_pdiag()
-    return out
-
-
-def planes(job):
-    """Every output of a job as raw arrays (bit comparisons)."""
-    R, n = job.runs, job.n
-    out = {'traj': job.ctx.download(job.buffer('traj_loose'), (9, n, R)), 'wb': job.ctx.download(job.buffer('wb'), (3, n, R)),
-           'ab': job.ctx.download(job.buffer('ab'), (3, n, R)), 'end': job.end_errors().T.copy(), 'pdiag': job.final_pdiag()}
-    out['bias'] = np.concatenate(job.final_biases(), axis=1)
-    return out
-
-
-def same_bits(a, b, runs_a=None, runs_b=None):
-    for k in a:
-        x = a[k] if runs_a is None else (a[k][..., runs_a] if k in ('traj', 'wb', 'ab', 'end') else a[k][runs_a])
-        y = b[k] if runs_b is None else (b[k][..., runs_b] if k in ('traj', 'wb', 'ab', 'end') else b[k][runs_b])
-        assert np.array_equal(x.view(np.uint64), y.view(np.uint64)), k
 
 
 @pytest.fixture(scope='module', params=[0, 1], ids=['rf0', 'rf1'])
@@ -135,11 +69,8 @@ def test_parity_with_the_restatement(ctx, dump, which, mask, every):
     assert job.kernel_name() == 'ginsim::loose_mag_kernel<%d, true, false, false>' % dump.rf
     dev = result(job)
     job.release()
-    got, bound = cs.deviation(dev, dump.restate(which, mask, every)), dump.bound(which, mask, every)
-    print('parity rf%d %s mask %d every %d: ' % (dump.rf, which, mask, every) +
-          ', '.join('%s %.2e (bound %.2e)' % (k, got[k], bound[k]) for k in got))
-    for k in got:
-        assert got[k] <= bound[k], (k, got[k], bound[k])
+    held('parity rf%d %s mask %d every %d' % (dump.rf, which, mask, every), cs.deviation(dev, dump.restate(which, mask, every)),
+         dump.bound(which, mask, every))
     plain = dump.job(ctx, None, mask, given=True).run()
     assert not np.array_equal(result(plain)['att'], dev['att'])                # the block did something
     plain.release()
@@ -215,7 +146,7 @@ def test_run_list_in_shuffled_order(ctx, big):
     for k in ('traj', 'wb', 'ab'):
         assert np.array_equal(got[k][..., ids].view(np.uint64), whole[k][..., ids].view(np.uint64)), k
         assert not got[k][..., rest].any(), k               # the other runs' columns were not touched
-    assert np.array_equal(got['pdiag'][ids].view(np.uint64), whole['pdiag'][ids].view(np.uint64))
+    assert np.array_equal(got['pdiag'][..., ids].view(np.uint64), whole['pdiag'][..., ids].view(np.uint64))
     part.release()
 
 
@@ -338,10 +269,7 @@ def test_sim_runs_the_magnetometer_aided_and_the_unaided_filter_on_one_realisati
     got = {k: np.stack([np.asarray(src.data['%s_%d' % (aided, r)]) for r in runs])
            for k, src in (('att', d.att_euler), ('pos', d.pos), ('vel', d.vel), ('wb', d.wb), ('ab', d.ab))}
     got['pdiag_end'] = job1.final_pdiag()[runs]
-    dev = cs.deviation(got, exp)
-    print('Sim pairing: ' + ', '.join('%s %.2e (bound %.2e)' % (k, dev[k], bound[k]) for k in dev))
-    for k in dev:
-        assert dev[k] <= bound[k], (k, dev[k], bound[k])
+    held('Sim pairing', cs.deviation(got, exp), bound)
     # the benefit: yaw at the end, and the curve along the outage
     samples = np.array(ac.outage_samples({'gps_visibility': vis, 'ref_accel': accel[0]}, stamps, fs, fs_gps))
     curve = sim.error_curve(('att_euler', 'pos'), samples=samples)

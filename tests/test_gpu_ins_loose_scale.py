@@ -19,9 +19,11 @@ import pytest
 
 import ins_loose_aided_cases as ac
 import ins_loose_cases as cs
+import ins_loose_dump
 import ins_loose_ref as ref
 import ins_loose_scale_cases as sc
 import ins_loose_scale_ref as sref
+from ins_loose_dump import ctx, held, planes, result, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -29,49 +31,19 @@ FS, FS_GPS, N, RUNS = 20.0, 2.0, 1200, 257
 ODO_ERR = {'scale': 0.985, 'stdv': sc.ODO_STDV}        # what the odometer of the dumps reads; the filter starts from 1.0
 
 
-@pytest.fixture(scope='module')
-def ctx():
-    import ginsim
-    c = ginsim.Context(0)
-    yield c
-    c.close()
+class Dump(ins_loose_dump.Dump):
+    """The odometer of the dump reads ODO_ERR's scale."""
 
-
-class Dump(object):
-    """The device's own accel, gyro, odometer (ginsim_mc_run) and fixes (ginsim_aux_sensors) of `runs` runs of the outage profile,
-    on the device and on the host."""
-
-    def __init__(self, ctx, rf, runs=RUNS, seed=77, n=N, vib=None):
-        import ginsim
-        self.rf, self.fs, self.runs, self.seed, self.vib = rf, FS, runs, seed, vib
-        self.ini, self.truth, self.stamps = ac.outage_truth(FS, rf, FS_GPS, n)
-        self.n = self.truth['ref_accel'].shape[0]
-        self.acc_e, self.gyr_e = cs.imu_errors()
-        kw = {} if vib is None else {'vib_accel': vib}
-        self.mc = ginsim.MonteCarloJob(ctx, FS, rf, self.truth, self.acc_e, self.gyr_e, self.ini, runs=runs, algos=('free',), odo_err=ODO_ERR,
-                                       seed=seed, keep_sensors=True, **kw).run()
-        ids = np.arange(runs)
-        self.accel, self.gyro, self.odo = self.mc.sensors('accel', ids), self.mc.sensors('gyro', ids), self.mc.sensors('odo', ids)
-        self.aux = ginsim.AuxSensorJob(ctx, runs, seed=seed, ref_gps=self.truth['ref_gps'], gps_err=cs.GPS_ERR, ref_frame=rf).run()
-        self.gps = self.aux.series('gps', ids)
-        self.given = {'accel': self.mc.buffer('accel'), 'gyro': self.mc.buffer('gyro'), 'odo': self.mc.buffer('odo'),
-                      'gps': self.aux._bufs['gps']}
-        self.model = ginsim.filter_model(FS, self.acc_e, self.gyr_e, cs.GPS_ERR)
+    def __init__(self, ctx, rf, n, runs, seed=77, vib=None):
+        super().__init__(ctx, rf, n, runs, seed, fs=FS, fs_gps=FS_GPS, odo_err=ODO_ERR, vib=vib)
         self._restated = {}
 
     def job(self, ctx, mask, every=1, given=False, state=None, runs=None, **kw):
         """state: the options of the scale-factor state ({}: the defaults); None: the 15-state aided job."""
-        import ginsim
-        kw = dict(dict(seed=self.seed, keep_traj=True, odo_err=ODO_ERR, aid=ac.aid_options(mask, every)), **kw)
+        kw = dict(dict(keep_traj=True, odo_err=ODO_ERR, aid=ac.aid_options(mask, every)), **kw)
         if state is not None:
             kw = dict(dict(odo_scale_state=state, keep_scale=kw['keep_traj']), **kw)
-        if self.vib is not None and not given:
-            kw['vib_accel'] = self.vib
-        return ginsim.InsLooseJob(ctx, self.fs, self.rf, self.truth, self.acc_e, self.gyr_e, cs.GPS_ERR, self.ini, runs or self.runs,
-                                  given=self.given if given else None, **kw)
-
-    def _args(self):
-        return (self.rf, self.fs, self.gyro, self.accel, self.ini, self.model, self.gps, self.stamps, self.truth['gps_visibility'])
+        return super().job(ctx, given, runs=runs, **kw)
 
     def restate(self, mask, every=1, scale0=sc.SCALE0, p0=sc.P0_SCALE):
         """The restatement of all runs and 16 x its own float64 error on the first 8, once per case."""
@@ -85,48 +57,6 @@ class Dump(object):
             self._restated[key] = (out, bound)
         return self._restated[key]
 
-    def release(self):
-        self.mc.release()
-        self.aux.release()
-
-
-def result(job):
-    ids = np.arange(job.runs)
-    out = {k: job.series(k, ids) for k in ('att', 'pos', 'vel', 'wb', 'ab')}
-    out['pdiag_end'] = job.final_pdiag()
-    if job.scalep is not None:
-        k_end, sigma = job.final_scale()
-        out['k_est'], out['pcross_end'] = job.series('odo_scale', ids), job.final_pcross()
-        out['scale_end'] = job.ctx.download(job.scalep.out_scale_end, (2, job.runs)).T.copy()
-        assert np.array_equal(out['scale_end'][:, 0], k_end) and np.array_equal(np.sqrt(out['scale_end'][:, 1]), sigma)
-        assert np.array_equal(job.final_sigmas(), np.sqrt(np.concatenate([out['pdiag_end'], out['scale_end'][:, 1:2]], axis=1)))
-    return out
-
-
-def planes(job):
-    """Every output of a job as raw arrays (bit comparisons); run is the last axis of every one."""
-    R, n = job.runs, job.n
-    out = {'traj': job.ctx.download(job.buffer('traj_loose'), (9, n, R)), 'wb': job.ctx.download(job.buffer('wb'), (3, n, R)),
-           'ab': job.ctx.download(job.buffer('ab'), (3, n, R)), 'end': job.end_errors().T.copy(), 'pdiag': job.final_pdiag().T.copy(),
-           'bias': np.concatenate(job.final_biases(), axis=1).T.copy()}
-    if job.scalep is not None:
-        out['scale'] = job.ctx.download(job.scalep.out_scale, (n, R))
-        out['scale_end'] = job.ctx.download(job.scalep.out_scale_end, (2, R))
-        out['pcross'] = job.ctx.download(job.scalep.out_pcross_end, (15, R))
-    return out
-
-
-def same_bits(a, b, runs=None, keys=None):
-    for k in keys or a:
-        x, y = (a[k], b[k]) if runs is None else (a[k][..., runs], b[k][..., runs])
-        assert np.array_equal(np.ascontiguousarray(x).view(np.uint64), np.ascontiguousarray(y).view(np.uint64)), k
-
-
-def held(what, got, bound):
-    print(what + ': ' + ', '.join('%s %.2e (bound %.2e)' % (k, got[k], bound[k]) for k in got))
-    for k in got:
-        assert got[k] <= bound[k], (k, got[k], bound[k])
-
 
 @pytest.fixture(scope='module')
 def dumps(ctx):
@@ -134,7 +64,7 @@ def dumps(ctx):
 
     def get(rf):
         if rf not in made:
-            made[rf] = Dump(ctx, rf)
+            made[rf] = Dump(ctx, rf, N, RUNS)
         return made[rf]
     yield get
     for d in made.values():
@@ -225,7 +155,7 @@ def test_run_list_subset(ctx, dumps):
     got = planes(part)
     part.release()
     rest = np.setdiff1d(np.arange(d.runs), ids)
-    same_bits(got, whole, runs=ids, keys=('traj', 'wb', 'ab', 'pdiag', 'scale', 'scale_end', 'pcross'))
+    same_bits(got, whole, ids, ids, keys=('traj', 'wb', 'ab', 'pdiag', 'scale', 'scale_end', 'pcross'))
     for k in ('traj', 'wb', 'ab', 'scale', 'scale_end', 'pcross'):
         assert not got[k][..., rest].any(), k               # the other runs keep what they held
 
@@ -247,12 +177,12 @@ def test_online_process_statistics_equal_those_of_the_kept_planes(ctx, dumps, rf
 # ------------------------------------------------------------------------------------------------- 6. vibration
 def test_vibration_variant_given_equals_generated(ctx):
     vib = {'type': 'random', 'x': 0.05, 'y': 0.05, 'z': 0.05}
-    d = Dump(ctx, 1, runs=65, seed=41, n=400, vib=vib)
+    d = Dump(ctx, 1, 400, 65, seed=41, vib=vib)
     gen, giv = d.job(ctx, 7, 1, state={}).run(), d.job(ctx, 7, 1, given=True, state={}).run()
     assert gen.kernel_name() == 'ginsim::loose_scale_kernel<1, false, true, false>'
     assert giv.kernel_name() == 'ginsim::loose_scale_kernel<1, true, false, false>'
     same_bits(planes(gen), planes(giv))
-    calm = Dump(ctx, 1, runs=65, seed=41, n=400)
+    calm = Dump(ctx, 1, 400, 65, seed=41)
     assert not np.array_equal(calm.accel, d.accel)                             # the vibration term is in the samples
     for x in (gen, giv, calm, d):
         x.release()

@@ -16,8 +16,10 @@ import pytest
 
 import ins_loose_aided_cases as ac
 import ins_loose_cases as cs
+import ins_loose_dump
 import ins_loose_ref as ref
 import ins_loose_still_cases as sc
+from ins_loose_dump import ctx, held, planes, result, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -25,53 +27,20 @@ FS, FS_GPS = 20.0, 2.0
 VIB = {'type': 'random', 'x': 0.05, 'y': 0.05, 'z': 0.05}
 
 
-@pytest.fixture(scope='module')
-def ctx():
-    import ginsim
-    c = ginsim.Context(0)
-    yield c
-    c.close()
-
-
-class Dump(object):
-    """The device's own accel, gyro, odometer (ginsim_mc_run) and fixes (ginsim_aux_sensors) of `runs` runs of the stops profile, on
-    the device and on the host."""
+class Dump(ins_loose_dump.Dump):
+    """The stops profile, with the standstill signal of its truth in .flags."""
 
     def __init__(self, ctx, rf, n, runs, seed=77, run_offset=0, vib=None):
-        import ginsim
-        self.rf, self.fs, self.runs, self.seed, self.run_offset = rf, FS, runs, seed, run_offset
-        self.vib = {} if vib is None else {'vib_accel': vib}
-        self.ini, self.truth, self.stamps = sc.stops_truth(FS, rf, FS_GPS, n)
-        truth = self.truth
-        self.n = truth['ref_accel'].shape[0]
-        self.flags = sc.flags_of(truth)
-        self.acc_e, self.gyr_e = cs.imu_errors()
-        self.mc = ginsim.MonteCarloJob(ctx, FS, rf, truth, self.acc_e, self.gyr_e, self.ini, runs=runs, algos=('free',), odo_err=ac.ODO_ERR,
-                                       seed=seed, run_offset=run_offset, keep_sensors=True, **self.vib).run()
-        ids = np.arange(runs)
-        self.accel, self.gyro, self.odo = self.mc.sensors('accel', ids), self.mc.sensors('gyro', ids), self.mc.sensors('odo', ids)
-        self.aux = ginsim.AuxSensorJob(ctx, runs, seed=seed, run_offset=run_offset, ref_gps=truth['ref_gps'], gps_err=cs.GPS_ERR, ref_frame=rf).run()
-        self.gps = self.aux.series('gps', ids)
-        self.given = {'accel': self.mc.buffer('accel'), 'gyro': self.mc.buffer('gyro'), 'odo': self.mc.buffer('odo'), 'gps': self.aux._bufs['gps']}
-        self.model = ginsim.filter_model(FS, self.acc_e, self.gyr_e, cs.GPS_ERR)
+        super().__init__(ctx, rf, n, runs, seed, run_offset, FS, FS_GPS, truth_fn=sc.stops_truth, vib=vib, flags=sc.flags_of)
 
     def job(self, ctx, smask, mask=0, every=1, given=False, runs=None, flags=None, **kw):
         """smask: the standstill rows (1 ZUPT, 2 ZARU, 3 both); 0: still={zupt: False, zaru: False}; None: no still argument at all.
         mask 0: no aiding argument at all.  flags None: the job derives the signal from the truth."""
-        import ginsim
-        kw = dict(dict(seed=self.seed, run_offset=self.run_offset, keep_traj=True), **kw)
-        if mask:
-            kw = dict(dict(odo_err=ac.ODO_ERR, aid=ac.aid_options(mask)), **kw)
+        kw = ac.aid_kw(mask, **kw)
         if smask is not None:
             still = sc.options(smask, every) if smask else {'zupt': False, 'zaru': False, 'every': every}
             kw = dict(dict(still=dict(still, flags=flags)), **kw)
-        if not given:
-            kw = dict(self.vib, **kw)
-        return ginsim.InsLooseJob(ctx, self.fs, self.rf, self.truth, self.acc_e, self.gyr_e, cs.GPS_ERR, self.ini, runs or self.runs,
-                                  given=dict(self.given) if given else None, **kw)
-
-    def _args(self):
-        return (self.rf, self.fs, self.gyro, self.accel, self.ini, self.model, self.gps, self.stamps, self.truth['gps_visibility'])
+        return super().job(ctx, given, runs=runs, **kw)
 
     def _kw(self, smask, mask, every, flags):
         return dict(odo=self.odo, aid=ac.aid(mask) if mask else None, still=sc.model(self.model, self.fs, smask, every),
@@ -83,40 +52,6 @@ class Dump(object):
     def bound(self, smask, mask=0, every=1, flags=None):
         kw = self._kw(smask, mask, every, flags)
         return cs.parity_bound(*self._args(), odo=kw['odo'], aid=kw['aid'], still=kw['still'], flags=kw['flags'])
-
-    def release(self):
-        self.mc.release()
-        self.aux.release()
-
-
-def result(job):
-    ids = np.arange(job.runs)
-    out = {k: job.series(k, ids) for k in ('att', 'pos', 'vel', 'wb', 'ab')}
-    out['pdiag_end'] = job.final_pdiag()
-    return out
-
-
-def planes(job):
-    """Every output of a job as raw arrays (bit comparisons)."""
-    R, n = job.runs, job.n
-    out = {'traj': job.ctx.download(job.buffer('traj_loose'), (9, n, R)), 'wb': job.ctx.download(job.buffer('wb'), (3, n, R)),
-           'ab': job.ctx.download(job.buffer('ab'), (3, n, R)), 'end': job.end_errors().T.copy(), 'pdiag': job.final_pdiag()}
-    out['bias'] = np.concatenate(job.final_biases(), axis=1)
-    return out
-
-
-def same_bits(a, b, runs_a=None, runs_b=None):
-    for k in a:
-        x = a[k] if runs_a is None else (a[k][..., runs_a] if k in ('traj', 'wb', 'ab', 'end') else a[k][runs_a])
-        y = b[k] if runs_b is None else (b[k][..., runs_b] if k in ('traj', 'wb', 'ab', 'end') else b[k][runs_b])
-        assert np.array_equal(x.view(np.uint64), y.view(np.uint64)), k
-
-
-def assert_parity(tag, dev, exp, bound):
-    got = cs.deviation(dev, exp)
-    print('parity %s: ' % tag + ', '.join('%s %.2e (bound %.2e)' % (k, got[k], bound[k]) for k in got))
-    for k in got:
-        assert got[k] <= bound[k], (k, got[k], bound[k])
 
 
 @pytest.fixture(scope='module', params=[0, 1], ids=['rf0', 'rf1'])
@@ -146,7 +81,7 @@ def test_parity_with_the_restatement(ctx, dump, name, smask, mask, every):
     assert job.kernel_name() == 'ginsim::loose_still_kernel<%d, false, false, false>' % dump.rf
     dev = result(job)
     job.release()
-    assert_parity('rf%d %s' % (dump.rf, name), dev, dump.restate(smask, mask, every), dump.bound(smask, mask, every))
+    held('parity rf%d %s' % (dump.rf, name), cs.deviation(dev, dump.restate(smask, mask, every)), dump.bound(smask, mask, every))
     plain = dump.job(ctx, None, mask).run()
     other = result(plain)
     assert not np.array_equal(other['vel' if smask & 1 else 'wb'], dev['vel' if smask & 1 else 'wb'])      # the block did something
@@ -164,7 +99,7 @@ def test_parity_with_a_vibration_term(ctx, rf):
     assert job.kernel_name() == 'ginsim::loose_still_kernel<%d, false, true, false>' % rf
     dev = result(job)
     job.release()
-    assert_parity('rf%d both with vibration' % rf, dev, d.restate(3), d.bound(3))
+    held('parity rf%d both with vibration' % rf, cs.deviation(dev, d.restate(3)), d.bound(3))
     d.release()
 
 
@@ -176,7 +111,7 @@ def test_a_flag_on_the_last_sample(ctx, short):
     flags[n - 1] = 1
     job = short.job(ctx, 3, flags=flags).run()
     dev = result(job)
-    assert_parity('rf%d a flag at n - 1' % short.rf, dev, short.restate(3, flags=flags), short.bound(3, flags=flags))
+    held('parity rf%d a flag at n - 1' % short.rf, cs.deviation(dev, short.restate(3, flags=flags)), short.bound(3, flags=flags))
     flags[n - 1] = 0
     without = short.job(ctx, 3, flags=flags).run()
     w = result(without)
@@ -270,7 +205,7 @@ def test_run_counts_around_a_wavefront_with_a_shuffled_run_list(ctx, big, runs):
     for k in ('traj', 'wb', 'ab'):
         assert np.array_equal(got[k][..., ids].view(np.uint64), whole[k][..., ids].view(np.uint64)), k
         assert not got[k][..., rest].any(), k               # the other runs' columns were not touched
-    assert np.array_equal(got['pdiag'][ids].view(np.uint64), whole['pdiag'][ids].view(np.uint64))
+    assert np.array_equal(got['pdiag'][..., ids].view(np.uint64), whole['pdiag'][..., ids].view(np.uint64))
     part.release()
 
 
@@ -370,7 +305,7 @@ def test_sim_runs_the_standstill_aided_and_the_unaided_filter_on_one_realisation
     got = {k: np.stack([np.asarray(src.data['%s_%d' % (aided, r)]) for r in runs])
            for k, src in (('att', d.att_euler), ('pos', d.pos), ('vel', d.vel), ('wb', d.wb), ('ab', d.ab))}
     got['pdiag_end'] = job1.final_pdiag()[runs]
-    assert_parity('Sim pairing', got, exp, bound)
+    held('parity Sim pairing', cs.deviation(got, exp), bound)
     with pytest.raises(NotImplementedError, match='zupt'):
         sim.consistency_curve(every=5.0)
     # statistics only: the same numbers in results()
