@@ -1,5 +1,5 @@
 """Shared inputs of the tests of InsLoose's scale-factor state (tests/test_ins_loose_scale_oracle.py on the CPU,
-tests/test_gpu_ins_loose_scale.py on the device): the options, the draws, the metrics of the parity bound (deviation),
+tests/test_gpu_ins_loose_scale.py and tests/test_gpu_ins_loose_tilted_aids.py on the device): the options, the draws, the metrics of the parity bound (deviation),
 and every number the CPU test measures and records."""
 import numpy as np
 
@@ -18,6 +18,15 @@ READS = 0.99                                    # the odometer of the payoff tab
 CONSISTENCY_BAND = (0.8, 1.25)
 CONSISTENCY_RATIOS = (1.001, 0.982, 0.925, 1.059, 0.974, 0.939, 0.950, 0.974, 1.007, 1.014, 1.015, 0.998, 0.999, 0.972, 0.980, 0.999)
 # at the end of those runs: RMS of k_est - k 0.00040, sqrt(mean P[15][15]) 0.00040 (from the initial 0.02)
+# CONSISTENCY_RATIOS is the LEVEL outage profile's.  By profile: 'tilted' is the same draw (draws(1024, CONSISTENCY_SEED, profile=
+# ins_loose_cases.TILTED_CSV)) and the same filter on tests/golden/ins_loose/motion_def_tilted.csv; measured by
+# tests/test_ins_loose_scale_oracle.py::test_restatement_consistency_on_the_tilted_profile, inside the same band.
+# tests/test_gpu_ins_loose_tilted_aids.py holds the device to them within x/: 1.25.
+CONSISTENCY_BY_PROFILE = {
+    'level': CONSISTENCY_RATIOS,
+    'tilted': (0.999, 1.015, 0.915, 1.014, 0.989, 0.990, 0.955, 0.982, 1.023, 1.030, 1.043, 1.023, 0.966, 0.957, 0.954, 1.008),
+    # at the end of those runs: RMS of k_est - k 0.00048, sqrt(mean P[15][15]) 0.00047
+}
 # The defect the state removes: on the same runs (the same noise, every odometer reading 0.99) the 15-state filter that assumes 1.0.
 # The largest of its position and velocity ratios (it must exceed 3) and the state it belongs to.
 # All 15: 4.089, 28.037, 5.093, 7.317, 1.371, 5.607, 2.961, 1.317, 1.015, 1.012, 2.299, 1.003, 0.999, 0.973, 1.041.
@@ -79,14 +88,14 @@ def deviation(a, b):
     return out
 
 
-def draws(runs, seed, ref_frame=1, fs=cs.CONSISTENCY_FS, fs_gps=cs.CONSISTENCY_FS_GPS, scales=None):
-    """One set of runs drawn from the filter's own model on the outage profile: accel, gyro and GPS as
+def draws(runs, seed, ref_frame=1, fs=cs.CONSISTENCY_FS, fs_gps=cs.CONSISTENCY_FS_GPS, scales=None, profile=cs.OUTAGE_CSV):
+    """One set of runs drawn from the filter's own model on the outage profile (or `profile`): accel, gyro and GPS as
     tests/test_ins_loose_aided_oracle.py draws them, then the true scale of every run (scales None: ~ N(1, P0_SCALE^2); a number:
     that scale in every run, nothing drawn) and the odometer's noise.  Returns a dict: ini, truth, stamps, acc_e, gyr_e, accel, gyro,
     tba, tbg, gps, scales (R,), noise (R, n) [the odometer's, stdv z] and model."""
     import ins_loose_ref as ref
     from ginsim.ins_loose import filter_model
-    ini, truth, stamps = ac.outage_truth(fs, ref_frame, fs_gps)
+    ini, truth, stamps = ac.outage_truth(fs, ref_frame, fs_gps, None, profile)
     acc_e, gyr_e = cs.imu_errors()
     rng = np.random.default_rng(seed)
     accel, gyro, tba, tbg = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, runs)

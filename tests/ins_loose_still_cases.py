@@ -1,5 +1,5 @@
 """Shared inputs of the standstill-aided InsLoose tests (tests/test_ins_loose_still_oracle.py on the CPU,
-tests/test_gpu_ins_loose_still.py on the device): the stops profile's truth and its standstill windows, the block's numbers,
+tests/test_gpu_ins_loose_still.py and tests/test_gpu_ins_loose_tilted_aids.py on the device): the stops profiles' truth and its standstill windows, the block's numbers,
 and the constants the CPU test measures and the device test is held to."""
 import functools
 import os
@@ -11,6 +11,10 @@ import ins_loose_cases as cs
 
 # cruise at 5 m/s, brake to a stop (GPS visible), drive on, turn, an 18 s GPS outage (27-45 s) with a second stop inside it, turn back
 STOPS_CSV = os.path.join(cs.REPO, 'tests', 'golden', 'ins_loose', 'motion_def_stops.csv')
+# 41 S 150 W, 300 m: the same shape on a slope.  Yaw 170, pitch 12, roll -10 deg, braking from 6 m/s to a stop of 8 s (GPS visible), a
+# turn of 30 deg through +-180 deg that also takes the pitch to -8 and the roll to 5 deg, a second stop inside a 16 s GPS outage (24-40 s),
+# the turn back: 48 s.  vb = (vx, 0, 0) throughout, so the vehicle climbs and descends while it moves
+TILTED_STOPS_CSV = os.path.join(cs.REPO, 'tests', 'golden', 'ins_loose', 'motion_def_tilted_stops.csv')
 
 FILTERS = {'gps': 0, 'zupt': 1, 'zaru': 2, 'still': 3}                      # name -> still_mask
 
@@ -27,6 +31,16 @@ CONSISTENCY_RATIOS = {
             'end': (1.011, 1.006, 0.911, 0.929, 1.006, 0.965, 1.001, 0.966, 1.015, 0.985, 1.000, 0.992, 1.012, 0.957, 1.023)},
     'still': {'stop': (0.769, 0.734, 0.512, 0.498, 0.497, 0.692, 0.794, 0.812, 0.991, 1.008, 0.998, 0.976, 0.979, 0.935, 0.951),
               'end': (0.884, 0.912, 0.535, 0.927, 0.997, 0.873, 1.012, 0.972, 0.913, 1.056, 1.061, 1.008, 1.012, 0.957, 1.017)},
+}
+# CONSISTENCY_RATIOS is the LEVEL stops profile's.  By profile: 'tilted' is tests/golden/ins_loose/motion_def_tilted_stops.csv, the filter
+# with both rows on consistency_draw(1, 20 Hz, 1024 runs, profile=TILTED_STOPS_CSV), at the last sample of its first stop (sample 301)
+# and at its end; measured by tests/test_ins_loose_still_oracle.py::test_restatement_consistency_on_the_tilted_stops_profile, which
+# asserts of them what the level test asserts of the filter with both rows.  tests/test_gpu_ins_loose_tilted_aids.py holds the device
+# to them within x/: 1.25.
+CONSISTENCY_BY_PROFILE = {
+    'level': CONSISTENCY_RATIOS,
+    'tilted': {'still': {'stop': (0.788, 0.625, 0.493, 0.504, 0.499, 0.686, 0.812, 0.828, 1.004, 1.050, 0.993, 0.972, 0.973, 0.943, 0.925),
+                         'end': (0.890, 0.872, 0.517, 0.913, 0.918, 0.858, 0.939, 0.969, 0.925, 1.028, 1.071, 0.972, 0.999, 0.965, 0.966)}},
 }
 
 
@@ -60,12 +74,12 @@ def model(filter_numbers, fs, mask, every=1, **kw):
     return still_model(filter_numbers, fs, options(mask, every, **kw))
 
 
-def consistency_draw(rf, fs, runs, n=None):
+def consistency_draw(rf, fs, runs, n=None, profile=STOPS_CSV):
     """One draw for all FILTERS: accel, gyro, fixes in that order from np.random.default_rng(ins_loose_cases.CONSISTENCY_SEED), 2 Hz
-    GPS, 'mid-accuracy' IMU, the stops profile cut to its first n samples."""
+    GPS, 'mid-accuracy' IMU, the stops profile (or `profile`) cut to its first n samples."""
     import ins_loose_ref as ref
     from ginsim.ins_loose import filter_model
-    ini, truth, stamps = stops_truth(fs, rf, cs.CONSISTENCY_FS_GPS, n)
+    ini, truth, stamps = stops_truth(fs, rf, cs.CONSISTENCY_FS_GPS, n, profile)
     acc_e, gyr_e = cs.imu_errors()
     c = {'rf': rf, 'fs': fs, 'ini': ini, 'truth': truth, 'stamps': stamps, 'acc_e': acc_e, 'gyr_e': gyr_e, 'runs': runs,
          'model': filter_model(fs, acc_e, gyr_e, cs.GPS_ERR)}

@@ -1,4 +1,5 @@
-"""CPU: the InsLoose restatements (tests/ins_loose_ref.py with its aiding and magnetometer blocks, tests/ins_loose_cons_ref.py) against
+"""CPU: the InsLoose restatements (tests/ins_loose_ref.py with its aiding, magnetometer and standstill blocks,
+tests/ins_loose_scale_ref.py, tests/ins_loose_cons_ref.py) against
 the nonlinear model they linearise, at 200 random attitudes (yaw over +-pi, pitch over +-80 deg, roll over +-pi) with fully
 three-dimensional velocities, specific forces and fields, in np.longdouble where the platform has it.  The rotation the tests hold
 the restatements to (rot_nb: Rx(roll) Ry(pitch) Rz(yaw) from elementary rotations, Rodrigues' formula for the error rotation) is
@@ -16,6 +17,20 @@ whose residual stays within the allowance there -- what level attitudes cannot s
     magnetometer block (B2)  none
     transition blocks (B3)   none
     checkpoint (B4)          none
+    rest rate (B5')          dcm_sp, dcm_sr (the residual is exactly the original's)
+    odometer row, 16 states (B6')  dcm_sp, cross_order (a level vehicle moves along D[0,:]: v x D[0,:], the row's whole psi part, is zero)
+    all rows, 16 states (B6')      dcm_sp, dcm_sr
+B5'-B7' are the blocks of the two newest kernel families (the ZARU rest rate of ins_loose_ref.LooseFilter.still, the rows of
+ins_loose_scale_ref.ScaleFilter.aid; the primes keep them apart from the consistency tests B5, B6 at the end of this file):
+    B5'  rest_rate() in ref_frame 0 against rot_nb(att) (W cos lat, 0, -W sin lat): no linearisation, the allowance is rounding,
+         8 eps W_IE (measured 0: both sides round alike); zero in ref_frame 1 and without earth_rot.
+    B6'  the rows read back from what one block does to P = I, against central differences of the nonlinear innovation
+         (D_est (v + dv))[0] - odo / (k + dk): measured 3.3e-9, B2's truncation.  The odometer's row reads D[0,:] only, so dcm_sr
+         cannot move it (asserted); it is held to the 100 x on all three rows of the block.
+    B7'  zero, +W sin lat, D^T for D, pitch and roll ignored as the rest rate move the restatement's wb on
+         tests/golden/ins_loose/motion_def_tilted_stops.csv (4 runs, ref_frame 0, ZUPT and ZARU) by 5.5e7-1.0e9 x the parity bound
+         tests/test_gpu_ins_loose_tilted_aids.py allows the device there (>= 100 x asserted); on the level stops profile 'pitch and roll
+         ignored' moves it by 6e4 x only (printed).
 B1, B3 and B4 see dcm_sp and dcm_sr on level attitudes only because their psi is general: the mutant then shows at 2 |psi| = 2e-4 rad,
 not at 1 rad as on the random attitudes.  The level PROFILE has no such reference at all -- its tests compare kernel and restatement
 with each other, and in a term that sp or sr multiplies both may carry the same mistake; that, and the rows above, is the gap.
@@ -47,19 +62,23 @@ import pytest
 import ins_loose_cases as cs
 import ins_loose_cons_ref as cref
 import ins_loose_mag_cases as mc
-import ins_loose_ref                # noqa: F401  (family() copies the two restatements from sys.modules)
+import ins_loose_ref                # noqa: F401  (family() copies the restatements from sys.modules)
+import ins_loose_scale_ref          # noqa: F401
+import ins_loose_still_cases as stc
 from oracle import ins_np
 
 LD = np.longdouble
 N_ATT, PSI_NORM = 200, 1e-4
-ORDER = ['ins_loose_ref', 'ins_loose_cons_ref']
+ORDER = ['ins_loose_ref', 'ins_loose_cons_ref', 'ins_loose_scale_ref']
 TRANSPOSE = ('C = np.swapaxes(self.D, 1, 2)', 'C = self.D')
+REST_RATE = "w_ie[:, 2] = -ins_np.W_IE * sl\n            w = np.einsum('rij,rj->ri', self.D, w_ie)"       # the two lines of rest_rate()
 # name -> {module: [(expression, replacement), ...]}; every expression must occur in its module
 MUTATIONS = {
     'dcm_sp': {'ins_loose_ref': [('m[..., 0, 2] = -sp', 'm[..., 0, 2] = sp')]},
     'dcm_sr': {'ins_loose_ref': [('m[..., 1, 2] = cp * sr', 'm[..., 1, 2] = -cp * sr')]},
     'transpose_C': {'ins_loose_ref': [TRANSPOSE, ('D, v = self.D, self.vel', 'D, v = np.swapaxes(self.D, 1, 2), self.vel'),
-                                      ('        D = self.D\n', '        D = np.swapaxes(self.D, 1, 2)\n')],
+                                      ('        D = self.D\n', '        D = np.swapaxes(self.D, 1, 2)\n'),
+                                      (REST_RATE, REST_RATE.replace('rij,rj->ri', 'rji,rj->ri'))],
                     'ins_loose_cons_ref': [('Ce = np.swapaxes(ref.dcm_zyx(f.att), 1, 2)', 'Ce = ref.dcm_zyx(f.att)'),
                                            ('Ct = ref.dcm_zyx(t[None, 0:3])[0].T', 'Ct = ref.dcm_zyx(t[None, 0:3])[0]')]},
     'negate_skew': {'ins_loose_ref': [('return np.stack([np.stack([z, -v[:, 2], v[:, 1]], 1)', 'return -np.stack([np.stack([z, -v[:, 2], v[:, 1]], 1)')]},
@@ -68,11 +87,15 @@ MUTATIONS = {
                                       ('np.cross(np.broadcast_to(m_n, D.shape), D)', 'np.cross(D, np.broadcast_to(m_n, D.shape))')],
                     'ins_loose_cons_ref': [('e[:, 6] = (M[:, 1, 2] - M[:, 2, 1]) / 2', 'e[:, 6] = (M[:, 2, 1] - M[:, 1, 2]) / 2')]},
     'cal_si_T': {'ins_loose_ref': [("np.einsum('ik,rk->ri', cal_si.reshape(3, 3)", "np.einsum('ki,rk->ri', cal_si.reshape(3, 3)")]},
+    'rest_hemisphere': {'ins_loose_ref': [(REST_RATE, REST_RATE.replace('-ins_np.W_IE * sl', 'ins_np.W_IE * sl'))]},
+    'scale_entry_sign': {'ins_loose_scale_ref': [('return vb0 - odo_j / self.k_est, vb0 / self.k_est', 'return vb0 - odo_j / self.k_est, -vb0 / self.k_est')]},
 }
 # measured residuals of the unmodified restatement (module docstring); the allowance is 10 x
 BASE = {'feedback': 2.6e-8, 'feedback_reverse': 2.6e-8, 'aid_rows': 3.3e-9, 'mag_rows': 1.7e-9, 'mag_block': 2.5e-9,
-        'phi': {0: 7.0e-6, 1: 1.7e-4}, 'cons_psi': 1.7e-13}
-LEVEL_BLIND = {'feedback': [], 'rows': ['dcm_sp', 'dcm_sr'], 'phi': [], 'cons': []}
+        'phi': {0: 7.0e-6, 1: 1.7e-4}, 'cons_psi': 1.7e-13, 'scale_row': 3.3e-9, 'scale_rows': 3.3e-9,
+        # not measured: rounding of a three-term dot product of entries not above 1 (the allowance, 10 x, is 8 eps W_IE)
+        'rest': 0.8 * float(np.finfo(LD).eps) * ins_np.W_IE}
+LEVEL_BLIND = {'feedback': [], 'rows': ['dcm_sp', 'dcm_sr'], 'phi': [], 'cons': [], 'rest': ['dcm_sp', 'dcm_sr'], 'scale_row': ['dcm_sp', 'cross_order'], 'scale_rows': ['dcm_sp', 'dcm_sr']}
 
 
 def family(name=None):
@@ -189,6 +212,7 @@ def draw(kind):
     d['psi'] = psi / np.linalg.norm(psi, axis=1, keepdims=True) * PSI_NORM
     d['gyro'], d['accel'] = rng.normal(0, 0.5, (n, 3)), rng.normal(0, 3, (n, 3))
     d['dr'], d['dv'] = rng.normal(0, 3, (n, 3)), rng.normal(0, 0.3, (n, 3))
+    d['k'] = u(0.95, 1.05)                                                        # the odometer's scale factor (B6); drawn last
     _DRAWN[kind] = d = {k: v.astype(LD) for k, v in d.items()}
     return d
 
@@ -199,12 +223,18 @@ def model(fs):
     return filter_model(fs, acc_e, gyr_e, cs.GPS_ERR)
 
 
-def make_filter(fam, rf, d, att=None, fs=20.0):
-    """A filter of N_ATT runs, one per case, at the case's position and navigation-frame velocity with the attitude att."""
+def make_filter(fam, rf, d, att=None, fs=20.0, scale=False):
+    """A filter of N_ATT runs, one per case, at the case's position and navigation-frame velocity with the attitude att.
+    scale: the 16-state filter (ins_loose_scale_ref.ScaleFilter) whose estimate of the scale factor is the case's k."""
     att = d['att'] if att is None else att
     vel_b = np.einsum('rij,rj->ri', rot_nb(att), d['vel'])
     ini = np.concatenate([d['lla'], vel_b, att], axis=1).T
-    f = fam['ins_loose_ref'].LooseFilter(rf, fs, np.asarray(ini, dtype=np.float64), N_ATT, model(fs), dtype=LD)
+    if scale:
+        f = fam['ins_loose_scale_ref'].ScaleFilter(rf, fs, np.asarray(ini, dtype=np.float64), N_ATT, model(fs),
+                                                   {'scale0': 1.0, 'p0_scale': 1.0, 'q_k': 0.0}, dtype=LD)
+        f.k_est = d['k'].copy()
+    else:
+        f = fam['ins_loose_ref'].LooseFilter(rf, fs, np.asarray(ini, dtype=np.float64), N_ATT, model(fs), dtype=LD)
     # the constructor takes float64: put the long double values in, through the module's own dcm_zyx
     f.att, f.D = att.copy(), fam['ins_loose_ref'].dcm_zyx(att)
     f.vel = d['vel'].copy()
@@ -349,6 +379,136 @@ def test_measurement_rows_are_the_jacobian_of_the_nonlinear_measurement(families
     assert blind == LEVEL_BLIND['rows'] and blind_m == LEVEL_BLIND['rows']
     check('B2 magnetometer block', mag_block_residual, families, ['dcm_sp', 'dcm_sr', 'transpose_C', 'cross_order', 'cal_si_T'],
           BASE['mag_block'])
+
+
+# ------------------------------------------------------------------------------------------------- B5' the rest rate (standstill block)
+def rest_residual(fam, kind):
+    """LooseFilter.rest_rate() in ref_frame 0 against rot_nb(att) (W cos lat, 0, -W sin lat): the largest entry's deviation [rad/s]."""
+    d = draw(kind)
+    f = make_filter(fam, 0, d)
+    lat = d['lla'][:, 0]
+    w_n = LD(ins_np.W_IE) * np.stack([np.cos(lat), np.zeros_like(lat), -np.sin(lat)], axis=1)
+    want = np.einsum('rij,rj->ri', rot_nb(d['att']), w_n)
+    got = f.rest_rate()
+    assert got.dtype == LD
+    return float(np.max(np.abs(got - want)))
+
+
+def test_rest_rate_is_the_earth_rate_in_the_body_axes(families):
+    """No linearisation: the allowance is rounding, 8 eps W_IE (check() takes 10 x BASE['rest'] = 0.8 eps W_IE)."""
+    blind = check("B5' rest rate", rest_residual, families, ['dcm_sp', 'dcm_sr', 'transpose_C', 'rest_hemisphere'], BASE['rest'])
+    assert blind == LEVEL_BLIND['rest']
+    for kind in ('tilted', 'level'):
+        d = draw(kind)
+        assert not make_filter(families[None], 1, d).rest_rate().any()
+        f = make_filter(families[None], 0, d)
+        assert f.rest_rate().any()
+        f.earth_rot = False
+        assert not f.rest_rate().any()
+
+
+# ------------------------------------------------------------------------------------------------- B6' the odometer row of the 16 states
+DK_STEP = LD(1e-6)
+SCALE_STATES = [3, 4, 5, 6, 7, 8, 15]
+
+
+def scale_row_residual(fam, kind, rows=(0,)):
+    """ScaleFilter.aid's rows, read back one at a time from what one block (mask 1 << i, P = I, R = 1) does to P:
+    I - P' = h h^T / (|h|^2 + 1) on the states 3-8 and 15.  Compared, as h h^T / |h|^2, with central differences of the nonlinear
+    innovation: the odometer's z_0(dv, psi, dk) = (D_est (v + dv))[0] - odo / (k + dk) at odo = k v_b[0], the constraints'
+    z_i = (D_est (v + dv))[i], which do not depend on dk.  Exact in dv, a step of 1e-4 rad in psi through the exact rotation, a step
+    of 1e-6 in dk (truncation step^2 / k^2 = 1e-12 of the entry).  The largest deviation over `rows`."""
+    d = draw(kind)
+    C = np.swapaxes(rot_nb(d['att']), 1, 2)
+    k = d['k']
+    odo = k * np.einsum('rj,rj->r', C[:, :, 0], d['vel'])
+    J = np.zeros((N_ATT, 3, 7), dtype=LD)
+    J[:, :, 0:6] = measurement_jacobian(C, d['vel'], True)
+    J[:, 0, 6] = (-odo / (k + DK_STEP) + odo / (k - DK_STEP)) / (2 * DK_STEP)
+    pick = np.ix_(np.arange(N_ATT), SCALE_STATES, SCALE_STATES)
+    worst = 0.0
+    for i in rows:
+        f = make_filter(fam, 1, d, scale=True)
+        f.P = np.zeros((N_ATT, 15, 15), dtype=LD)
+        f.P[:] = np.eye(15, dtype=LD)
+        f.c, f.pkk = np.zeros((N_ATT, 15), dtype=LD), np.ones(N_ATT, dtype=LD)
+        f.aid(odo, 1 << i, 1.0, 1.0, 1.0)
+        M = np.eye(16, dtype=LD) - f.full_p()
+        outside = M.copy()
+        outside[pick] = 0
+        assert np.max(np.abs(outside)) < 1e-15                                    # the rows touch dv, psi and dk only
+        M = M[pick]
+        hh = M / (1 - np.trace(M, axis1=1, axis2=2))[:, None, None]
+        want = J[:, i, :, None] * J[:, i, None, :]
+        worst = max(worst, float(np.max(np.abs(hh - want) / np.trace(want, axis1=1, axis2=2)[:, None, None])))
+    return worst
+
+
+def test_scale_row_is_the_jacobian_of_the_nonlinear_odometer_innovation(families):
+    """The odometer's row reads D[0, :] = (cp cy, cp sy, -sp) and nothing else of D, so the mutant dcm_sr (the sign of D[1, 2]) cannot
+    move it: that is asserted, and dcm_sr is held to the 100 x with the two constraint rows of the same block next to the odometer's
+    (their entry on state 15 is zero), where every one of the five mutants shows."""
+    blind = check("B6' odometer row, 16 states", scale_row_residual, families, ['dcm_sp', 'transpose_C', 'cross_order', 'scale_entry_sign'],
+                  BASE['scale_row'])
+    assert blind == LEVEL_BLIND['scale_row']
+    assert scale_row_residual(families['dcm_sr'], 'tilted') == scale_row_residual(families[None], 'tilted')
+    blind = check("B6' all three rows, 16 states", lambda fam, kind: scale_row_residual(fam, kind, (0, 1, 2)), families,
+                  ['dcm_sp', 'dcm_sr', 'transpose_C', 'cross_order', 'scale_entry_sign'], BASE['scale_rows'])
+    assert blind == LEVEL_BLIND['scale_rows']
+
+
+# ------------------------------------------------------------------------------------------------- B7' the parity bound sees the rest rate
+def _rest_zero(f):
+    return np.zeros((f.R, 3), dtype=f.dtype)
+
+
+def _rest_with(f, hemisphere=1.0, transposed=False, level=False):
+    _, _, _, sl, cl = ins_np.geo_param(f.pos[:, 0], f.pos[:, 2])
+    w_ie = np.zeros((f.R, 3), dtype=f.dtype)
+    w_ie[:, 0], w_ie[:, 2] = ins_np.W_IE * cl, -hemisphere * ins_np.W_IE * sl
+    D = ins_loose_ref.dcm_zyx(f.att * np.array([1.0, 0.0, 0.0], dtype=f.dtype)) if level else f.D
+    return np.einsum('rji,rj->ri' if transposed else 'rij,rj->ri', D, w_ie)
+
+
+WRONG_REST_RATES = {'zero': _rest_zero, '+W sin lat': lambda f: _rest_with(f, hemisphere=-1.0), 'D^T for D': lambda f: _rest_with(f, transposed=True),
+                    'pitch and roll ignored': lambda f: _rest_with(f, level=True)}
+
+
+def rest_rate_ratios(profile, runs=4):
+    """{wrong version: deviation of the restatement with it from the unmodified one in wb, over the parity bound of the case}: 4 runs
+    drawn from the model on `profile`, ref_frame 0, ZUPT and ZARU at every flagged sample."""
+    rf, fs = 0, 20.0
+    ini, truth, stamps = stc.stops_truth(fs, rf, 2.0, None, profile)
+    acc_e, gyr_e = cs.imu_errors()
+    rng = np.random.default_rng(20260118)
+    accel, gyro, _, _ = ins_loose_ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, runs)
+    gps = cs.sample_gps(rng, truth, rf, runs)
+    m = model(fs)
+    args = (rf, fs, gyro, accel, ini, m, gps, stamps, truth['gps_visibility'])
+    kw = dict(still=stc.model(m, fs, 3), flags=stc.flags_of(truth))
+    assert _rest_with(ins_loose_ref.LooseFilter(rf, fs, ini, runs, m)).tobytes() == ins_loose_ref.LooseFilter(rf, fs, ini, runs, m).rest_rate().tobytes()
+    good = ins_loose_ref.run(*args, **kw)
+    bound = cs.parity_bound(*args, **kw)
+    out = {}
+    for name, fn in WRONG_REST_RATES.items():
+        wrong = type('WrongRestRate', (ins_loose_ref.LooseFilter,), {'rest_rate': fn})
+        o = ins_loose_ref.run(*args, filt=wrong(rf, fs, ini, runs, m), **kw)
+        dev = cs.deviation(o, good)
+        out[name] = {k: dev[k] / bound[k] for k in dev}
+    return out
+
+
+def test_the_parity_bound_sees_a_wrong_rest_rate_on_the_tilted_stops_profile():
+    """What tests/test_gpu_ins_loose_tilted_aids.py would do to a kernel whose w_rest is wrong: each of four wrong rest rates moves the
+    restatement's wb on the tilted stops profile by at least 100 x the parity bound the device is allowed there.  The level stops
+    profile's ratios are printed for information."""
+    for label, profile in (('tilted stops', stc.TILTED_STOPS_CSV), ('level stops', stc.STOPS_CSV)):
+        ratios = rest_rate_ratios(profile)
+        for name, r in ratios.items():
+            print("B7' %s, rest rate '%s': deviation over the parity bound: " % (label, name) + ', '.join('%s %.1e' % kv for kv in r.items()))
+        if profile == stc.TILTED_STOPS_CSV:
+            for name, r in ratios.items():
+                assert r['wb'] >= 100.0, (name, r)
 
 
 # ------------------------------------------------------------------------------------------------- B3 transition blocks

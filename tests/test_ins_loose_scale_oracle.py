@@ -255,6 +255,23 @@ def test_restatement_consistency(consistency):
     assert np.sqrt(np.mean(o16['scale_end'][:, 1])) < 0.25 * sc.P0_SCALE        # the state was learnt, not only carried
 
 
+def test_restatement_consistency_on_the_tilted_profile():
+    """The same filter and draw on tests/golden/ins_loose/motion_def_tilted.csv (41 S, yaw through +-180 deg twice, pitch and roll away
+    from level, climbing and descending): all 16 ratios inside the same band and as recorded in
+    ins_loose_scale_cases.CONSISTENCY_BY_PROFILE['tilted'], which tests/test_gpu_ins_loose_tilted_aids.py holds the device to."""
+    d = sc.draws(cs.CONSISTENCY_RUNS, cs.CONSISTENCY_SEED, profile=cs.TILTED_CSV)
+    assert d['gyro'].shape[1] == 800
+    o16 = sref.run(*_args(d), odo=sc.odometer(d), aid=sc.aid(1), scale=sc.scale())
+    r16 = sc.ratios16(d, o16, d['scales'])
+    print('tilted profile, consistency ratios, 16 states:', np.array2string(r16, precision=3, separator=', '))
+    print('k_est - k at the end: rms %.5f, mean sigma %.5f' % (np.sqrt(np.mean((o16['scale_end'][:, 0] - d['scales']) ** 2)),
+                                                                np.sqrt(np.mean(o16['scale_end'][:, 1]))))
+    lo, hi = sc.CONSISTENCY_BAND
+    assert r16.shape == (16,) and np.all(r16 >= lo) and np.all(r16 <= hi), r16
+    np.testing.assert_allclose(r16, sc.CONSISTENCY_BY_PROFILE['tilted'], rtol=0, atol=2e-3)
+    assert np.sqrt(np.mean(o16['scale_end'][:, 1])) < 0.25 * sc.P0_SCALE        # the state was learnt, not only carried
+
+
 def test_the_wrong_scale_is_the_defect_the_state_removes(consistency):
     """The same 15-state filter assuming 1.0 for an odometer that reads 0.99, on the same runs: a position or velocity ratio above 3."""
     _, _, r15, _ = consistency

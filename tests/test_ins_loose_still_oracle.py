@@ -299,6 +299,30 @@ def test_the_stops_profile_has_two_standstill_windows_one_inside_the_outage(rf):
         assert d[0][1] / fs < hidden.min()                                      # the first one has GPS
 
 
+@pytest.mark.parametrize('rf', [0, 1])
+def test_the_tilted_stops_profile_parks_twice_on_a_slope_once_inside_the_outage(rf):
+    """tests/golden/ins_loose/motion_def_tilted_stops.csv, what tests/test_gpu_ins_loose_tilted_aids.py and the B7' test of
+    tests/test_ins_loose_attitude_oracle.py rely on: 48 s at 20 Hz with 2 Hz fixes; the default flags give the windows 180-301 and
+    600-721; the vehicle stands at (170, 12, -10) deg and at (-160, -8, 5) deg, 41 S; the yaw wraps after samples 422 and 875; the
+    fixes 48-79 are hidden and the second stop lies inside that outage."""
+    fs = 20.0
+    ini, truth, stamps = sc.stops_truth(fs, rf, 2.0, None, sc.TILTED_STOPS_CSV)
+    n = truth['ref_accel'].shape[0]
+    assert n == 960 and stamps.size == 96 and np.array_equal(stamps, np.arange(96) * 10)
+    w = sc.windows(sc.flags_of(truth))
+    assert w == [(180, 301), (600, 721)]
+    att = np.rad2deg(truth['ref_att'])
+    for (a, b), want in zip(w, ((170.0, 12.0, -10.0), (-160.0, -8.0, 5.0))):
+        np.testing.assert_allclose(att[a:b + 1], np.tile(want, (b + 1 - a, 1)), rtol=0, atol=1e-3)
+        assert np.max(np.linalg.norm(truth['ref_vel'][a:b + 1], axis=1)) <= 0.01
+    assert np.nonzero(np.abs(np.diff(truth['ref_att'][:, 0])) > np.pi)[0].tolist() == [422, 875]
+    assert np.rad2deg(ini[0]) == pytest.approx(-41.0)                             # the southern hemisphere
+    hidden = np.nonzero(np.asarray(truth['gps_visibility']) == 0)[0]
+    assert hidden.tolist() == list(range(48, 80))
+    assert stamps[hidden[0]] < w[1][0] and w[1][1] < stamps[hidden[-1]]           # the second stop lies inside the outage
+    assert w[0][1] < stamps[hidden[0]]                                            # the first one has GPS
+
+
 # ------------------------------------------------------------------------------------------------- the restatement
 @pytest.fixture(scope='module', params=[(1, 0), (0, 7)], ids=['rf1', 'rf0-aided'])
 def small(request):
@@ -433,6 +457,25 @@ def test_restatement_consistency(consistency):
         assert np.all(s[6:15] >= lo), (tag, s)
         np.testing.assert_allclose(g, sc.CONSISTENCY_RATIOS['gps'][tag], rtol=0, atol=2e-3)
         np.testing.assert_allclose(s, sc.CONSISTENCY_RATIOS['still'][tag], rtol=0, atol=2e-3)
+
+
+def test_restatement_consistency_on_the_tilted_stops_profile():
+    """The same on tests/golden/ins_loose/motion_def_tilted_stops.csv (ref_frame 1, 1024 runs, both rows): what the level test asserts
+    of the filter with both rows -- every state <= 1.4 at both instants, psi, dbg and dba >= 0.7 -- and the ratios recorded in
+    ins_loose_still_cases.CONSISTENCY_BY_PROFILE['tilted'], which tests/test_gpu_ins_loose_tilted_aids.py holds the device to.
+    Measured: dr and dv lie low as on the level profile and for the same reason (dr_y 0.63, dr_z 0.49, dv 0.50-0.69 at the end of
+    the stop, dr_z 0.52 at the end); psi, dbg and dba stay in 0.81-1.07."""
+    c = sc.consistency_draw(1, cs.CONSISTENCY_FS, cs.CONSISTENCY_RUNS, profile=sc.TILTED_STOPS_CSV)
+    j = sc.windows(c['flags'])[0][1]
+    o = sc.restate_filter(c, 'still', keep_pdiag=True)
+    got = {'stop': sc.ratios(sc.error_at(c, o, j), o['pdiag'][:, j]), 'end': sc.ratios(sc.error_at(c, o, -1), o['pdiag'][:, -1])}
+    for tag in ('stop', 'end'):
+        print('tilted stops, still %s:' % tag, np.array2string(got[tag], precision=3, separator=', '))
+    lo, hi = sc.BAND
+    for tag in ('stop', 'end'):
+        assert np.all(got[tag] <= hi), (tag, got[tag])
+        assert np.all(got[tag][6:15] >= lo), (tag, got[tag])
+        np.testing.assert_allclose(got[tag], sc.CONSISTENCY_BY_PROFILE['tilted']['still'][tag], rtol=0, atol=2e-3)
 
 
 # ------------------------------------------------------------------------------------------------- Python surface
