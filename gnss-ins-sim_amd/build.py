@@ -75,6 +75,8 @@ SOURCES = [
     ('error_cov.hip', ['--offload-arch=' + ARCH, '-mllvm', '-disable-machine-licm']),
     ('allan.hip', ['--offload-arch=' + ARCH]),
     ('oallan.hip', ['--offload-arch=' + ARCH]),
+    # one instantiation per segment length, 8 .. 8192 (tests/test_psd_oracle.py reads the resource report: no scratch)
+    ('psd.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),
     ('vib_psd.hip', ['--offload-arch=' + ARCH]),
     ('selftest.hip', ['--offload-arch=' + ARCH]),
@@ -102,6 +104,7 @@ def build(force=False, verbose=False, tag=None, defines=(), xflags=()):
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hpp', '.h'))]
     deps.append(os.path.join(REPO, 'include', 'ginsim.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_oallan.h'))
+    deps.append(os.path.join(REPO, 'include', 'ginsim_psd.h'))
     deps.append(os.path.abspath(__file__))
     objs = []
     for src, extra in SOURCES:

@@ -12,8 +12,10 @@
 
 #include "ginsim.h"
 #include "ginsim_oallan.h"
+#include "ginsim_psd.h"
 #include "allan.hpp"
 #include "oallan.hpp"
+#include "psd.hpp"
 #include "comm.hpp"
 #include "launch.hpp"
 #include "placed.hpp"
@@ -307,6 +309,26 @@ static int oallan_plan(int64_t n, int32_t nseries, int64_t series_stride, double
         P.b_theta = pad(sizeof(double) * (size_t)P.theta_stride * (size_t)nseries);
         P.b_sums = pad(sizeof(double) * (size_t)(n / oallan_scan_chunk() + 1) * (size_t)nseries);
     }
+    return GINSIM_OK;
+}
+
+// What one Welch call runs (psd.hpp): the refusals that ginsim_psd_welch and ginsim_psd_plan share, in the order
+// include/ginsim_psd.h states and under the caller's prefix -- the arguments first (the call checks its window and detrend between
+// the two), then the series against one segment.
+static int psd_check(const char* who, int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t nperseg, int32_t step) {
+    REQUIRE(n >= 1 && nseries >= 1 && series_stride >= n && fs > 0 && std::isfinite(fs), "%s: bad sizes", who);
+    REQUIRE(nperseg >= (1 << kPsdMinLog2) && nperseg <= (1 << kPsdMaxLog2) && (nperseg & (nperseg - 1)) == 0,
+            "%s: nperseg %d is not a power of two in [%d, %d]", who, (int)nperseg, 1 << kPsdMinLog2, 1 << kPsdMaxLog2);
+    REQUIRE(step >= 1 && step <= nperseg, "%s: step %d outside [1, %d]", who, (int)step, (int)nperseg);
+    return GINSIM_OK;
+}
+
+static int psd_plan(const char* who, int64_t n, int32_t nseries, int32_t nperseg, int32_t step, PsdShape& S) {
+    if (n < nperseg) {
+        set_error("%s: a series of n = %lld samples is shorter than one segment of nperseg = %d", who, (long long)n, (int)nperseg);
+        return GINSIM_ERR_RANGE;
+    }
+    S = psd_plan_shape(n, nseries, nperseg, step);
     return GINSIM_OK;
 }
 
@@ -1589,6 +1611,65 @@ int ginsim_oallan(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, in
     for (int s = 0; s < nseries; ++s)
         for (int i = 0; i < nt; ++i) oavar[(size_t)s * cap + i] = h[(size_t)nt * (s + 1) + i];
     *ntau = nt;
+    return GINSIM_OK;
+}
+
+// ---- Welch power spectral density (include/ginsim_psd.h, csrc/psd.hip)
+int ginsim_psd_plan(int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t nperseg, int32_t step,
+                    ginsim_psd_geometry* g) {
+    REQUIRE(g, "psd_plan: NULL argument");
+    int rc = psd_check("psd_plan", n, nseries, series_stride, fs, nperseg, step);
+    if (rc) return rc;
+    PsdShape S;
+    rc = psd_plan("psd_plan", n, nseries, nperseg, step, S);
+    if (rc) return rc;
+    g->segments = S.segments;
+    g->scratch_bytes = (int64_t)S.record_bytes;
+    g->segs_per_part = S.segs_per_part;
+    g->nparts = S.nparts;
+    g->lds_bytes = psd_lds_bytes(nperseg);
+    g->threads = psd_threads(nperseg);
+    return GINSIM_OK;
+}
+
+int ginsim_psd_welch(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t nperseg,
+                     int32_t step, int32_t window, int32_t detrend, double* freq, double* psd, int32_t* nfreq, int32_t cap) {
+    REQUIRE(c && x && freq && psd && nfreq, "psd: NULL argument");
+    *nfreq = 0;
+    int rc = psd_check("psd", n, nseries, series_stride, fs, nperseg, step);
+    if (rc) return rc;
+    REQUIRE((window == GINSIM_PSD_BOXCAR || window == GINSIM_PSD_HANN) && (detrend == 0 || detrend == 1),
+            "psd: window %d (0 boxcar, 1 hann) or detrend %d (0, 1) out of range", (int)window, (int)detrend);
+    PsdShape S;
+    rc = psd_plan("psd", n, nseries, nperseg, step, S);
+    if (rc) return rc;
+    // both launches have the series on the grid's y dimension
+    if (nseries > c->max_grid_y) {
+        set_error("psd: %d series on the grid's y dimension but the device takes %d: split the batch into calls of at most %d series",
+                  (int)nseries, c->max_grid_y, c->max_grid_y);
+        return GINSIM_ERR_RANGE;
+    }
+    const int nb = S.nbins;
+    *nfreq = nb;
+    if (nb > cap) { set_error("psd: %d frequencies but capacity %d", nb, (int)cap); return GINSIM_ERR_RANGE; }
+    HIP_TRY(hipSetDevice(c->device));
+    void* region = nullptr;
+    HIP_TRY(scratch(c, 1, S.record_bytes, &region));
+    double* records = reinterpret_cast<double*>(region);
+    HIP_TRY(launch_psd_parts(x, series_stride, nseries, step, window, detrend, S, records, c->stream));
+    // the densities go straight into the pinned host memory the Allan results go to: no copy, one synchronisation
+    const size_t nout = (size_t)nb * (size_t)nseries;
+    if (c->allan_host_doubles < nout) {
+        if (c->allan_host) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipHostFree(c->allan_host)); c->allan_host = nullptr; c->allan_host_doubles = 0; }
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->allan_host), sizeof(double) * (nout + nout / 4 + 64), hipHostMallocDefault));
+        c->allan_host_doubles = nout + nout / 4 + 64;
+    }
+    const double U = window == GINSIM_PSD_HANN ? 0.375 * (double)nperseg : (double)nperseg;
+    HIP_TRY(launch_psd_finish(records, nseries, S, 1.0 / ((double)S.segments * fs * U), c->allan_host, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double* h = c->allan_host;
+    for (int k = 0; k < nb; ++k) freq[k] = (double)k * fs / (double)nperseg;
+    for (int s = 0; s < nseries; ++s) memcpy(psd + (size_t)s * cap, h + (size_t)s * nb, sizeof(double) * nb);
     return GINSIM_OK;
 }
 

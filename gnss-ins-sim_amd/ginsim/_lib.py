@@ -167,6 +167,12 @@ class OallanGeometry(C.Structure):
                 ('tile_factors', C.c_int32), ('stream_factors', C.c_int32)]
 
 
+class PsdGeometry(C.Structure):
+    """ginsim_psd_geometry (include/ginsim_psd.h): the segments of a Welch call, their partition into parts and what a workgroup takes."""
+    _fields_ = [('segments', C.c_int64), ('scratch_bytes', C.c_int64), ('segs_per_part', C.c_int32), ('nparts', C.c_int32),
+                ('lds_bytes', C.c_int32), ('threads', C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [('count', C.c_double), ('mean', C.c_double * 9), ('m2', C.c_double * 9),
                 ('maxabs', C.c_double * 9)]
@@ -292,6 +298,12 @@ _SIGS_OALLAN = {
     'ginsim_oallan_plan': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, C.POINTER(C.c_int32),
                                      C.POINTER(OallanFactor), C.c_int32, C.POINTER(OallanGeometry)]),
 }
+# include/ginsim_psd.h: the third header, the third table (ginsim.PSD_EXPORTS)
+_SIGS_PSD = {
+    'ginsim_psd_welch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_int32, _PD, _PD, C.POINTER(C.c_int32), C.c_int32]),
+    'ginsim_psd_plan': (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.POINTER(PsdGeometry)]),
+}
 _OPTIONAL = {}
 
 
@@ -300,7 +312,7 @@ def _load():
         raise ImportError('libginsim.so not built: run `python gnss-ins-sim_amd/build.py` '
                           '(or __graft_entry__.build()); expected %s' % LIB_PATH)
     lib = C.cdll.LoadLibrary(LIB_PATH)
-    for sigs in (_SIGS, _SIGS_OALLAN):
+    for sigs in (_SIGS, _SIGS_OALLAN, _SIGS_PSD):
         for name, (res, args) in sigs.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -314,6 +326,7 @@ def _load():
 lib = _load()
 EXPORTS = tuple(_SIGS)
 OALLAN_EXPORTS = tuple(_SIGS_OALLAN)
+PSD_EXPORTS = tuple(_SIGS_PSD)
 
 
 def check(rc):

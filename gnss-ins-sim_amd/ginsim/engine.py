@@ -916,6 +916,28 @@ class MonteCarloJob(BatchJob):
                 self._bufs['traj_' + a] = ctx.malloc(9 * plane, placed=use_placed)
                 p.out_traj[s] = self._bufs['traj_' + a].ptr
 
+    def _sensor_series(self, names):
+        """Device address of the kept series of the named sensors as [sensor][run][axis][n], 3 * runs * len(names) series of n
+        samples: the job's own buffer where it already has that order, otherwise a re-laid-out copy that lives with the job."""
+        per = 3 * self.n * self.runs * 8
+        contiguous = (self.runs == 1 or self.sensor_layout == 'series') and \
+            all(self._bufs[names[i + 1]].ptr == self._bufs[names[i]].ptr + per for i in range(len(names) - 1))
+        if contiguous:              # already [sensor][run][axis][n]: the Allan kernels read the job's own buffer
+            return self._bufs[names[0]].ptr
+        # the re-laid-out copy lives with the job (released with it): a 2 GB hipMalloc + hipFree per call cost 0.4 ms,
+        # as much as the Allan kernels themselves
+        tmp = self._bufs.get('_allan_layout')
+        if tmp is None or tmp.nbytes < per * len(names):
+            if tmp is not None:
+                tmp.free()
+            tmp = self._bufs['_allan_layout'] = self.ctx.malloc(per * len(names))
+        for i, nm in enumerate(names):      # one run: C = 3, R = 1 makes the re-layout a plain copy
+            if self.sensor_layout == 'series':
+                check(lib.ginsim_runs_to_series(self.ctx.handle, self._bufs[nm].ptr, 1, 3 * self.n * self.runs, 1, tmp.at(i * per)))
+            else:
+                check(lib.ginsim_runs_to_series(self.ctx.handle, self._bufs[nm].ptr, 3, self.n, self.runs, tmp.at(i * per)))
+        return tmp.ptr
+
     # bytes the launch writes to HBM (the algorithmic traffic of SURVEY 8(d))
     def allan(self, fs=None, names=('accel', 'gyro'), overlapping=False):
         """Allan deviation of the kept sensor series on the device (allan_analysis.py:33-49 for every run at once):
@@ -927,28 +949,23 @@ class MonteCarloJob(BatchJob):
             raise ValueError('Allan analysis needs the fp64 sensor series (keep_sensors=True)')
         fs = float(self.params.fs if fs is None else fs)
         names = tuple(names)
-        per = 3 * self.n * self.runs * 8
-        contiguous = (self.runs == 1 or self.sensor_layout == 'series') and \
-            all(self._bufs[names[i + 1]].ptr == self._bufs[names[i]].ptr + per for i in range(len(names) - 1))
-        if contiguous:              # already [sensor][run][axis][n]: the Allan kernels read the job's own buffer
-            ptr = self._bufs[names[0]].ptr
-        else:
-            # the re-laid-out copy lives with the job (released with it): a 2 GB hipMalloc + hipFree per call cost 0.4 ms,
-            # as much as the Allan kernels themselves
-            tmp = self._bufs.get('_allan_layout')
-            if tmp is None or tmp.nbytes < per * len(names):
-                if tmp is not None:
-                    tmp.free()
-                tmp = self._bufs['_allan_layout'] = self.ctx.malloc(per * len(names))
-            for i, nm in enumerate(names):      # one run: C = 3, R = 1 makes the re-layout a plain copy
-                if self.sensor_layout == 'series':
-                    check(lib.ginsim_runs_to_series(self.ctx.handle, self._bufs[nm].ptr, 1, 3 * self.n * self.runs, 1, tmp.at(i * per)))
-                else:
-                    check(lib.ginsim_runs_to_series(self.ctx.handle, self._bufs[nm].ptr, 3, self.n, self.runs, tmp.at(i * per)))
-            ptr = tmp.ptr
+        ptr = self._sensor_series(names)
         avar, tau = (oallan_var if overlapping else allan_var)(self.ctx, ptr, self.n, 3 * self.runs * len(names), self.n, fs)
         ad = np.sqrt(avar).reshape(len(names), self.runs, 3, -1)
         return tau, {nm: ad[i].transpose(0, 2, 1).copy() for i, nm in enumerate(names)}
+
+    def psd(self, fs=None, names=('accel', 'gyro'), nperseg=1024, step=None, window='hann', detrend=True):
+        """Welch power spectral density of the kept sensor series on the device, every run at once: returns
+        (freq (nfreq,), {name: (runs, nfreq, 3)}), single-sided densities in unit^2 / Hz.  The series go through ONE
+        ginsim_psd_welch call from the [sensor][run][axis][n] buffer that ``allan`` reads."""
+        if not self.keep_sensors or self.precision != 'f64':
+            raise ValueError('the spectral density needs the fp64 sensor series (keep_sensors=True)')
+        fs = float(self.params.fs if fs is None else fs)
+        names = tuple(names)
+        ptr = self._sensor_series(names)
+        p, freq = welch_psd(self.ctx, ptr, self.n, 3 * self.runs * len(names), self.n, fs, nperseg, step, window, detrend)
+        p = p.reshape(len(names), self.runs, 3, -1)
+        return freq, {nm: p[i].transpose(0, 2, 1).copy() for i, nm in enumerate(names)}
 
     def bytes_written(self):
         per_sample = 0
@@ -1262,3 +1279,48 @@ def oallan_var_host(ctx, series, fs):
     finally:
         buf.free()
     return (oavar[0], tau) if np.ndim(series) == 1 else (oavar, tau)
+
+
+PSD_WINDOWS = ('boxcar', 'hann')        # ginsim_psd_welch's window 0..1
+
+
+def _psd_args(nperseg, step, window, detrend):
+    if window not in PSD_WINDOWS:
+        raise ValueError('window: one of %s' % (PSD_WINDOWS,))
+    return int(nperseg), int(nperseg) // 2 if step is None else int(step), PSD_WINDOWS.index(window), int(bool(detrend))
+
+
+def welch_psd(ctx, x, n, nseries, series_stride, fs, nperseg, step=None, window='hann', detrend=True):
+    """Welch's power spectral density of `nseries` device-resident series (DeviceBuffer, DeviceView or raw pointer): segments of
+    `nperseg` samples (a power of two, 8 .. 8192) every `step` samples (default nperseg // 2), window 'hann' or 'boxcar', each
+    segment's mean removed with `detrend` -- scipy.signal.welch(x, fs, window, nperseg, nperseg - step, detrend='constant' or
+    False, scaling='density') (include/ginsim_psd.h).  Returns (psd (nseries, nperseg // 2 + 1), freq)."""
+    ptr = getattr(x, 'ptr', x)
+    L, D, w, d = _psd_args(nperseg, step, window, detrend)
+    cap = max(L // 2 + 1, 1)
+    freq = np.empty(cap)
+    psd = np.empty((nseries, cap))
+    nf = C.c_int32(0)
+    check(ctx.retry_oom(lambda: lib.ginsim_psd_welch(ctx.handle, ptr, int(n), int(nseries), int(series_stride), float(fs), L, D, w, d,
+                                                     dptr(freq), dptr(psd), C.byref(nf), cap)))
+    return np.ascontiguousarray(psd[:, :nf.value]), freq[:nf.value].copy()
+
+
+def welch_plan(n, nseries, series_stride, fs, nperseg, step=None):
+    """What ``welch_psd`` with these arguments runs, from the library's own planning code (ginsim_psd_plan: host only, no context,
+    nothing launched): a dict with segments, segs_per_part, nparts, threads, lds_bytes and scratch_bytes."""
+    L, D, _, _ = _psd_args(nperseg, step, 'hann', True)
+    g = _lib.PsdGeometry()
+    check(lib.ginsim_psd_plan(int(n), int(nseries), int(series_stride), float(fs), L, D, C.byref(g)))
+    return {k: getattr(g, k) for k, _ in _lib.PsdGeometry._fields_}
+
+
+def welch_psd_host(ctx, series, fs, nperseg, step=None, window='hann', detrend=True):
+    """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (psd, freq)."""
+    a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
+    buf = ctx.upload(a)
+    try:
+        psd, freq = welch_psd(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs, nperseg, step, window, detrend)
+    finally:
+        buf.free()
+    return (psd[0], freq) if np.ndim(series) == 1 else (psd, freq)

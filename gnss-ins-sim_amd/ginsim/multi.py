@@ -235,6 +235,11 @@ class JobSet(_Parts):
         got = [g for g in self._each_part(lambda j: j.allan(fs, names, overlapping=overlapping)) if g is not None]
         return got[0][0], {nm: np.concatenate([g[1][nm] for g in got], axis=0) for nm in names}
 
+    def psd(self, fs=None, names=('accel', 'gyro'), nperseg=1024, step=None, window='hann', detrend=True):
+        """MonteCarloJob.psd on every device at the same time: (freq, {name: (runs, nfreq, 3)})."""
+        got = [g for g in self._each_part(lambda j: j.psd(fs, names, nperseg, step, window, detrend)) if g is not None]
+        return got[0][0], {nm: np.concatenate([g[1][nm] for g in got], axis=0) for nm in names}
+
     def buffer(self, name):
         raise ValueError('a JobSet spans several devices: take the buffer from one of its parts')
 

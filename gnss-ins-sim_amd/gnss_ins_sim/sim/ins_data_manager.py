@@ -62,6 +62,12 @@ _REGISTRY = [
     ('odo_scale', 'odometer scale factor estimation', [''], None, ['odo_scale'], {}),
     ('ad_gyro', 'Allan deviation of gyro', _RATE, _RATE_OUT, ['AD_wx', 'AD_wy', 'AD_wz'], {'logx': True, 'logy': True}),
     ('ad_accel', 'Allan deviation of accel', _ACC, None, ['AD_ax', 'AD_ay', 'AD_az'], {'logx': True, 'logy': True}),
+    # Welch spectra (demo_algorithms.psd_analysis): densities, so no rad -> deg conversion on output
+    ('psd_freq', 'frequencies of the power spectral densities', ['Hz'], None, ['psd_freq'], {'logx': True}),
+    ('psd_gyro', 'power spectral density of gyro', ['(rad/s)^2/Hz'] * 3, None, ['PSD_wx', 'PSD_wy', 'PSD_wz'],
+     {'logx': True, 'logy': True}),
+    ('psd_accel', 'power spectral density of accel', ['(m/s^2)^2/Hz'] * 3, None, ['PSD_ax', 'PSD_ay', 'PSD_az'],
+     {'logx': True, 'logy': True}),
 ]
 
 # which slice of the 9-component end-point record each error quantity occupies
