@@ -314,7 +314,8 @@ static int oallan_plan(int64_t n, int32_t nseries, int64_t series_stride, double
 
 // What one Welch call runs (psd.hpp): the refusals that ginsim_psd_welch and ginsim_psd_plan share, in the order
 // include/ginsim_psd.h states and under the caller's prefix -- the arguments first (the call checks its window and detrend between
-// the two), then the series against one segment.
+// the two), then the series against one segment, then the shape against what a launch and the geometry can state (psd.hpp keeps
+// nparts in 64 bits until here).
 static int psd_check(const char* who, int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t nperseg, int32_t step) {
     REQUIRE(n >= 1 && nseries >= 1 && series_stride >= n && fs > 0 && std::isfinite(fs), "%s: bad sizes", who);
     REQUIRE(nperseg >= (1 << kPsdMinLog2) && nperseg <= (1 << kPsdMaxLog2) && (nperseg & (nperseg - 1)) == 0,
@@ -328,7 +329,19 @@ static int psd_plan(const char* who, int64_t n, int32_t nseries, int32_t nperseg
         set_error("%s: a series of n = %lld samples is shorter than one segment of nperseg = %d", who, (long long)n, (int)nperseg);
         return GINSIM_ERR_RANGE;
     }
-    S = psd_plan_shape(n, nseries, nperseg, step);
+    // a local: the caller's shape, and behind it ginsim_psd_plan's *g, stays as it was when the call is refused
+    PsdShape s = psd_plan_shape(n, nperseg, step);
+    if (s.nparts > kPsdMaxParts) {
+        set_error("%s: %lld segments in parts of %d are %lld parts per series, more than the %lld a call can have: analyse the series in pieces",
+                  who, (long long)s.segments, (int)s.segs_per_part, (long long)s.nparts, (long long)kPsdMaxParts);
+        return GINSIM_ERR_RANGE;
+    }
+    if (!psd_record_bytes(s, nseries)) {
+        set_error("%s: the records of %lld parts per series and %d series, %d sums each, pass 2^63 bytes: split the batch or the series",
+                  who, (long long)s.nparts, (int)nseries, (int)s.nbins);
+        return GINSIM_ERR_RANGE;
+    }
+    S = s;
     return GINSIM_OK;
 }
 
@@ -1626,7 +1639,7 @@ int ginsim_psd_plan(int64_t n, int32_t nseries, int64_t series_stride, double fs
     g->segments = S.segments;
     g->scratch_bytes = (int64_t)S.record_bytes;
     g->segs_per_part = S.segs_per_part;
-    g->nparts = S.nparts;
+    g->nparts = (int32_t)S.nparts;
     g->lds_bytes = psd_lds_bytes(nperseg);
     g->threads = psd_threads(nperseg);
     return GINSIM_OK;

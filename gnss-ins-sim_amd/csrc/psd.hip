@@ -203,8 +203,9 @@ template <int L>
 hipError_t launch_parts(const double* x, int64_t series_stride, int32_t nseries, int32_t D, int32_t window, int32_t detrend,
                         const PsdShape& s, double* records, hipStream_t st) {
     static_assert(psd_lds_bytes(L) <= 160 * 1024, "the workgroup's LDS");
-    hipLaunchKernelGGL(psd_part_kernel<L>, dim3(s.nparts, nseries), dim3(PsdGeom<L>::T), 0, st, x, series_stride, D, window, detrend,
-                       s.segments, s.segs_per_part, s.nparts, records);
+    const int32_t nparts = (int32_t)s.nparts;                   // at most kPsdMaxParts: the glue has refused the rest
+    hipLaunchKernelGGL(psd_part_kernel<L>, dim3(nparts, nseries), dim3(PsdGeom<L>::T), 0, st, x, series_stride, D, window, detrend,
+                       s.segments, s.segs_per_part, nparts, records);
     return hipGetLastError();
 }
 
@@ -222,7 +223,7 @@ hipError_t launch_psd_parts(const double* x, int64_t series_stride, int32_t nser
 }
 
 hipError_t launch_psd_finish(const double* records, int32_t nseries, const PsdShape& s, double scale, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(psd_finish_kernel, dim3((s.nbins + 255) / 256, nseries), dim3(256), 0, st, records, s.nparts, s.nbins, scale, out);
+    hipLaunchKernelGGL(psd_finish_kernel, dim3((s.nbins + 255) / 256, nseries), dim3(256), 0, st, records, (int32_t)s.nparts, s.nbins, scale, out);
     return hipGetLastError();
 }
 

@@ -28,12 +28,15 @@ constexpr int psd_lds_bytes(int L) { return 8 * (2 * L + psd_table_doubles(L) + 
 // bytes: nparts (L/2 + 1) <= K L / (2 segs_per_part) + .. <= n / 8 with segs_per_part >= 4 L / D.
 struct PsdShape {
     int64_t segments;           // K = (n - L) / D + 1
+    int64_t nparts;             // ceil(K / segs_per_part): 64 bits until the glue has held it to kPsdMaxParts
     int32_t segs_per_part;
-    int32_t nparts;             // ceil(K / segs_per_part)
     int32_t nbins;              // L/2 + 1
     int32_t log2L;
-    size_t record_bytes;        // [nseries][nparts][nbins] doubles, padded to 256
+    size_t record_bytes;        // [nseries][nparts][nbins] doubles, padded to 256; 0 until psd_record_bytes has set it
 };
+
+// the parts of a series are a launch's grid x dimension and an int32_t of ginsim_psd_geometry
+constexpr int64_t kPsdMaxParts = 0x7FFFFFFF;
 
 inline int64_t psd_segs_per_part(int64_t L, int64_t D) {
     int64_t pairs = 8192 / D;
@@ -42,17 +45,27 @@ inline int64_t psd_segs_per_part(int64_t L, int64_t D) {
     return 2 * pairs;
 }
 
-// on checked arguments: L a power of two in range, 1 <= D <= L <= n
-inline PsdShape psd_plan_shape(int64_t n, int32_t nseries, int32_t L, int32_t D) {
+// on checked arguments: L a power of two in range, 1 <= D <= L <= n.  Nothing is narrowed here: any such n has an answer in 64 bits
+// (K <= n, and K - 1 + segs_per_part is never formed), and the caller refuses what a launch or the geometry cannot state
+inline PsdShape psd_plan_shape(int64_t n, int32_t L, int32_t D) {
     PsdShape s;
     s.segments = (n - L) / D + 1;
     s.segs_per_part = (int32_t)psd_segs_per_part(L, D);
-    s.nparts = (int32_t)((s.segments + s.segs_per_part - 1) / s.segs_per_part);
+    s.nparts = (s.segments - 1) / s.segs_per_part + 1;
     s.nbins = L / 2 + 1;
     s.log2L = 0;
     while ((1 << s.log2L) < L) ++s.log2L;
-    s.record_bytes = (sizeof(double) * (size_t)nseries * (size_t)s.nparts * (size_t)s.nbins + 255) & ~(size_t)255;
+    s.record_bytes = 0;
     return s;
+}
+
+// the records of a shape whose nparts is at most kPsdMaxParts: false, and nothing set, when their padded bytes pass INT64_MAX
+// (nseries nparts < 2^62 is exact; the bytes are compared by division, never formed past 64 bits)
+inline bool psd_record_bytes(PsdShape& s, int32_t nseries) {
+    const int64_t records = (int64_t)nseries * s.nparts;
+    if (records > (INT64_MAX - 255) / (int64_t)(sizeof(double) * (size_t)s.nbins)) return false;
+    s.record_bytes = (sizeof(double) * (size_t)records * (size_t)s.nbins + 255) & ~(size_t)255;
+    return true;
 }
 
 // one workgroup per (part, series): records[series][part][0 .. L/2] = sum over the part's segments of |X_s[k]|^2, NaN at every

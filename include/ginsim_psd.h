@@ -35,7 +35,9 @@ extern "C" {
  * do not depend on nseries or on its neighbours, and no atomics are used: every launch gives the same bits.
  * Refusals, before any launch and in this order: a NULL argument; n, nseries, series_stride < n or fs not positive and finite;
  * nperseg not a power of two in [8, 8192]; step outside [1, nperseg]; window or detrend outside their values (GINSIM_ERR_ARG);
- * n < nperseg; more series than the device's maxGridSize[1]; cap below *nfreq, which is still reported (GINSIM_ERR_RANGE). */
+ * n < nperseg; a series of more than 2^31 - 1 parts (ginsim_psd_plan's nparts), or records of nseries * nparts * (nperseg/2 + 1)
+ * doubles that pass 2^63 bytes -- the message names the number of parts; more series than the device's maxGridSize[1]; cap below
+ * *nfreq, which is still reported (GINSIM_ERR_RANGE). */
 int ginsim_psd_welch(ginsim_ctx* ctx, const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs,
                      int32_t nperseg, int32_t step, int32_t window, int32_t detrend,
                      double* freq, double* psd, int32_t* nfreq, int32_t cap);
@@ -44,7 +46,9 @@ int ginsim_psd_welch(ginsim_ctx* ctx, const double* x, int64_t n, int32_t nserie
  * context, no device, nothing launched.  A workgroup of `threads` owns one series and one part, segs_per_part consecutive segments
  * (a function of nperseg and step alone; the last part has the rest), and leaves one partial record of nperseg/2 + 1 sums; a
  * finishing launch adds a series' nparts records in ascending order.  lds_bytes: the workgroup's LDS; scratch_bytes: what the call
- * takes from the context's scratch.  The same refusals as the call's, as far as its arguments go, with the prefix psd_plan:. */
+ * takes from the context's scratch.  The same refusals as the call's, as far as its arguments go, with the prefix psd_plan:; any n
+ * is a legal question, and one whose nparts or scratch_bytes this structure cannot state is refused (GINSIM_ERR_RANGE), never
+ * answered with a narrowed number.  A refused plan leaves *g as it was. */
 typedef struct {
     int64_t segments, scratch_bytes;
     int32_t segs_per_part, nparts, lds_bytes, threads;

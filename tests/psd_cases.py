@@ -1,5 +1,6 @@
-"""The shapes of the Welch PSD tests, shared by test_psd_oracle.py (the plan of every shape, without a device) and test_gpu_psd.py
-(parity with psd_exact under its tolerance), and the margin of the test that takes a requested vibration spectrum back out.
+"""The shapes of the Welch PSD tests, shared by test_psd_oracle.py (the plan and the float64 restatement of every shape, without a
+device), test_gpu_psd.py (parity with psd_exact under its tolerance) and test_gpu_psd_edges.py (which also takes the helper that
+runs a batch on the device from here), and the margin of the test that takes a requested vibration spectrum back out.
 
 A case: id, L, D, K, tail, kinds, pad, window, detrend, where.
   n = (K - 1) D + L + tail samples per series (tail < D: samples the call must not read), series_stride = n + pad,
@@ -37,6 +38,20 @@ CASES = [
     ('L4096_quarter_step_boxcar_raw',         4096, 1024, 9,  500, ('white', 'offset', 'tone'), 0,  'boxcar', False, None),
     ('L8192_K1_n_equals_L',                   8192, 4096, 1,  0,   ('white', 'offset', 'walk'), 0,  'hann',   True,  None),
     ('L8192_half_overlap_K_part_plus_1_tail', 8192, 4096, 9,  1000, KINDS5,                     0,  'hann',   True,  (1, 1)),
+    # appended (the ids and positions above stay): the three segment lengths no case above launches -- 16 and 32, smaller than a
+    # wavefront and a single row of the planes, 2048, the first with 512 threads -- and part boundaries crossed at small and odd
+    # steps, with last parts of 1, 2 and 3 segments and a series of three full parts
+    ('L16_K5_odd_tail',                       16,   5,    5,  4,   ('white', 'offset', 'tone'), 0,  'hann',   True,  None),
+    ('L32_D7_boxcar_raw_stride',              32,   7,    12, 0,   KINDS5,                      3,  'boxcar', False, None),
+    ('L2048_half_overlap_part_plus_3',        2048, 1024, 19, 700, KINDS5,                      0,  'hann',   True,  (1, 3)),
+    ('L2048_no_overlap_boxcar_raw',           2048, 2048, 9,  0,   ('white', 'offset', 'walk'), 8,  'boxcar', False, (1, 1)),
+    ('L8_D1_two_parts_plus_1',                8,    1,    32769, 0, ('white', 'walk', 'offset'), 0, 'hann',   True,  (2, 1)),
+    ('L64_D3_part_plus_2',                    64,   3,    5462, 2, ('white', 'walk', 'tone'),   1,  'hann',   True,  (1, 2)),
+    ('L128_no_overlap_part_plus_1',           128,  128,  129, 0,  ('white', 'offset', 'constant'), 0, 'boxcar', True, (1, 1)),
+    ('L256_D129_three_full_parts',            256,  129,  378, 100, KINDS5,                     0,  'hann',   True,  (3, 0)),
+    ('L512_D511_part_plus_3',                 512,  511,  35, 0,   ('white', 'walk', 'tone'),   5,  'boxcar', True,  (1, 3)),
+    ('L4096_D64_dense_overlap_part_plus_1',   4096, 64,   257, 63, ('white', 'offset', 'walk'), 0,  'hann',   True,  (1, 1)),
+    ('L8192_no_overlap_two_parts_plus_1',     8192, 8192, 9,  0,   ('white', 'tone', 'walk'),   0,  'hann',   False, (2, 1)),
 ]
 IDS = [c[0] for c in CASES]
 
@@ -57,6 +72,16 @@ def rows(case, seed=11):
     for s, kind in enumerate(case[5]):
         a[s, :n] = px.series(kind, n, seed + 17 * s)
     return a
+
+
+def device_psd(ctx, a, n, L, D, win, det, fs=100.0):
+    """ginsim.welch_psd on the rows of `a` (S, stride), of which n samples each are the series: (psd, freq)."""
+    import ginsim
+    buf = ctx.upload(np.ascontiguousarray(a))
+    try:
+        return ginsim.welch_psd(ctx, buf, n, a.shape[0], a.shape[1], fs, L, D, win, det)
+    finally:
+        buf.free()
 
 
 # the requested vibration spectrum: four points up to fs / 2 = 50 Hz, NOT the series' own grid, zero at fs / 2 (the generator

@@ -26,14 +26,7 @@ def ctx():
     c.close()
 
 
-def device_psd(ctx, a, n, L, D, win, det, fs=FS):
-    """ginsim.welch_psd on the rows of `a` (S, stride), of which n samples each are the series."""
-    import ginsim
-    buf = ctx.upload(np.ascontiguousarray(a))
-    try:
-        return ginsim.welch_psd(ctx, buf, n, a.shape[0], a.shape[1], fs, L, D, win, det)
-    finally:
-        buf.free()
+device_psd = pc.device_psd          # shared with test_gpu_psd_edges.py; fs defaults to FS
 
 
 # ---- parity with the exact values
@@ -150,7 +143,35 @@ def test_device_refusals_and_their_order(ctx):
         buf.free()
 
 
-# ---- through the job
+def test_device_refuses_what_the_plan_cannot_state(ctx):
+    """The call's half of tests/test_psd_oracle.py::test_plan_refuses_what_it_cannot_state: more than 2^31 - 1 parts, or records
+    past 2^63 bytes, are refused under 'psd:' after "n < nperseg" and before the grid's y limit; nothing is launched, so the
+    256 samples behind the pointer are never read at those lengths."""
+    from ginsim import _lib
+    err = lambda: _lib.lib.ginsim_last_error().decode()     # noqa: E731
+    freq, p, nf = np.full(8, -3.0), np.full(8, -3.0), C.c_int32(-7)
+    buf = ctx.upload(np.zeros(256))
+    n_last = (2 ** 31 - 1) * 16384 + 7                  # L = 8, D = 1: 2^31 - 1 full parts of 16384 segments
+
+    def call(n, S=1, L=8, D=1, cap=5):
+        return _lib.lib.ginsim_psd_welch(ctx.handle, buf.ptr, n, S, n, 1.0, L, D, 1, 1, _lib.dptr(freq), _lib.dptr(p), C.byref(nf), cap)
+    try:
+        for n in (n_last + 1, 2 ** 62):
+            for S in (1, 2 ** 31 - 1):                   # the parts before the grid's y limit
+                assert call(n, S) == _lib.ERR_RANGE
+                msg = err()
+                assert msg.startswith('psd: ') and '%d parts' % (-(-(n - 7) // 16384)) in msg, msg
+                assert nf.value == 0
+        assert call(n_last, 2 ** 31 - 1) == _lib.ERR_RANGE                                              # the bytes before it too
+        msg = err()
+        assert msg.startswith('psd: ') and '%d parts' % (2 ** 31 - 1) in msg and '2^63 bytes' in msg, msg
+        assert call(7, 2 ** 31 - 1) == _lib.ERR_RANGE and 'shorter than one segment' in err()           # n < nperseg before both
+        assert call(n_last + 1, cap=0) == _lib.ERR_RANGE and 'parts' in err()                           # and the capacity after
+        assert np.all(freq == -3.0) and np.all(p == -3.0)
+        assert call(256) == _lib.OK and nf.value == 5 and np.all(p[:5] == 0.0)                          # the context still works
+    finally:
+        buf.free()
+    print('psd unstatable shapes on the device: refused in order')
 def _static_truth(n, fs=FS):
     import ginsim
     from ginsim import workloads

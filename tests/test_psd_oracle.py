@@ -4,7 +4,8 @@ build's resource report.
 
 Measured here (CPU, long double of 64 mantissa bits): the float64 restatement reaches 0.35 of ``tol`` at worst over this file's
 cases (L = 8192, D = L, boxcar, no detrend, the offset of 1e6); with the first form of the tolerance (sqrt(L) at every bin, see
-psd_exact's text) the same cases reached 5.6 at bin 0 (L = 4096, D = L/2, boxcar, detrend, the offset of 1e6)."""
+psd_exact's text) the same cases reached 5.6 at bin 0 (L = 4096, D = L/2, boxcar, detrend, the offset of 1e6).  On the 25 shapes of tests/psd_cases.py, the ones the device is held
+to, it reaches 0.184 (L1024_K2_quarter_step_raw), 0.115 on the eleven appended last (L8192_no_overlap_two_parts_plus_1)."""
 import ctypes as C
 import math
 import os
@@ -36,6 +37,25 @@ def test_float64_restatement_stays_within_the_tolerance(L):
                     r = px.ratio(px.restated(x, FS, L, D, win, det), e, px.tol(x, FS, L, D, win, det, e))
                     worst = max(worst, (r, (D, kind, win, det)))
     print('psd restatement L %d: error / tol %.3g at %s' % (L, worst[0], worst[1]))
+    assert worst[0] <= 1.0
+
+
+def test_float64_restatement_on_every_gpu_shape():
+    """The reference's own margin on every shape the device is held to (tests/psd_cases.py): the float64 restatement against the
+    exact values, under the tolerance and the bound of test_gpu_psd.py::test_parity_with_exact."""
+    worst = (0.0, None)
+    for case in pc.CASES:
+        name, L, D, K, tail, kinds, pad, win, det, _ = case
+        n, S, stride = pc.shape(case)
+        a = pc.rows(case)
+        here = 0.0
+        for s in range(S):
+            x = a[s, :n]
+            e, _ = px.exact(x, FS, L, D, win, det)
+            here = max(here, px.ratio(px.restated(x, FS, L, D, win, det), e, px.tol(x, FS, L, D, win, det, e)))
+        assert here <= 1.0, (name, here)
+        worst = max(worst, (here, name))
+    print('psd restatement on the %d device shapes: error / tol %.3g at %s' % (len(pc.CASES), worst[0], worst[1]))
     assert worst[0] <= 1.0
 
 
@@ -139,6 +159,78 @@ def test_plan_refusals_and_their_order():
     assert call(n=64, D=1) == _lib.OK and call(n=64, D=64) == _lib.OK
     for L in (8, 8192):
         assert call(n=8192, L=L, D=L) == _lib.OK
+
+
+# L = 8, D = 1: parts of 16384 segments; N_LAST is the longest series of 2^31 - 1 parts, all of them full
+MAX_PARTS = 2 ** 31 - 1
+N_LAST = MAX_PARTS * 16384 + 7
+
+
+def _plan_raw(n, S, g, L=8, D=1):
+    from ginsim import _lib
+    return _lib.lib.ginsim_psd_plan(n, S, n, 1.0, L, D, C.byref(g))
+
+
+def test_plan_states_the_last_length_it_can():
+    from ginsim import _lib
+    assert pc.segs_per_part(8, 1) == 16384
+    g = _lib.PsdGeometry()
+    assert _plan_raw(N_LAST, 1, g) == _lib.OK
+    assert g.segments == MAX_PARTS * 16384 == N_LAST - 8 + 1
+    assert (g.segs_per_part, g.nparts) == (16384, MAX_PARTS)
+    assert g.scratch_bytes == (8 * MAX_PARTS * 5 + 255) // 256 * 256
+    assert _plan_raw(N_LAST - 16384, 1, g) == _lib.OK and g.nparts == MAX_PARTS - 1
+    assert _plan_raw(N_LAST - 16384 + 1, 1, g) == _lib.OK and g.nparts == MAX_PARTS      # a last part of one segment
+    # the largest batch of that length whose records stay below 2^63 bytes
+    S = (2 ** 63 - 256) // (40 * MAX_PARTS)
+    assert _plan_raw(N_LAST, S, g) == _lib.OK and g.scratch_bytes == (40 * MAX_PARTS * S + 255) // 256 * 256 < 2 ** 63
+    # another shape at its own edge: L = 8192, D = 8192, parts of 4 segments
+    n = MAX_PARTS * 4 * 8192
+    assert _plan_raw(n, 1, g, 8192, 8192) == _lib.OK and (g.segments, g.segs_per_part, g.nparts) == (MAX_PARTS * 4, 4, MAX_PARTS)
+    assert g.scratch_bytes == (8 * MAX_PARTS * 4097 + 255) // 256 * 256
+
+
+def test_plan_refuses_what_it_cannot_state():
+    """Any n is a legal question (host arithmetic only); an answer that does not fit the geometry is refused, not narrowed: the
+    parent of this test answered n = 2^62 with GINSIM_OK and nparts == 0."""
+    from ginsim import _lib
+    fields = [k for k, _ in _lib.PsdGeometry._fields_]
+
+    def refused(n, S, parts, L=8, D=1, words=()):
+        g = _lib.PsdGeometry(-11, -12, -13, -14, -15, -16)
+        before = [getattr(g, k) for k in fields]
+        assert _plan_raw(n, S, g, L, D) == _lib.ERR_RANGE, (n, S, g.nparts)
+        msg = _err()
+        assert msg.startswith('psd_plan: ') and '%d parts' % parts in msg and all(w in msg for w in words), msg
+        assert [getattr(g, k) for k in fields] == before
+    refused(N_LAST + 1, 1, 2 ** 31)                                  # one segment past the last full part
+    refused(N_LAST + 1, 2 ** 31 - 1, 2 ** 31)
+    refused(2 ** 62, 1, 2 ** 48)
+    refused(2 ** 63 - 1, 1, 2 ** 49)                                 # the longest series there is
+    refused(N_LAST, 2 ** 31 - 1, MAX_PARTS, words=('2^63 bytes',))   # the parts fit, the records' bytes do not
+    S = (2 ** 63 - 256) // (40 * MAX_PARTS)
+    refused(N_LAST, S + 1, MAX_PARTS, words=('2^63 bytes',))
+    refused(MAX_PARTS * 4 * 8192 + 8192, 1, 2 ** 31, L=8192, D=8192)
+    import ginsim
+    with pytest.raises(ValueError, match='psd_plan: .* 281474976710656 parts'):
+        ginsim.welch_plan(2 ** 62, 1, 2 ** 62, 1.0, 8, 1)
+
+
+def test_plan_refusal_sits_behind_the_arguments_and_the_short_series():
+    """The new refusal's place in the order of include/ginsim_psd.h: after the arguments and after "n < nperseg".  (Before the
+    grid's y limit: tests/test_gpu_psd.py::test_device_refuses_what_the_plan_cannot_state, which needs the context.)"""
+    from ginsim import _lib
+    g = _lib.PsdGeometry()
+    big = 2 ** 62
+    for kw, msg in ((dict(S=0), 'psd_plan: bad sizes'), (dict(L=12), 'psd_plan: nperseg 12 is not a power of two in [8, 8192]'),
+                    (dict(D=9), 'psd_plan: step 9 outside [1, 8]')):
+        L, D = kw.get('L', 8), kw.get('D', 1)
+        assert _lib.lib.ginsim_psd_plan(big, kw.get('S', 1), big, 1.0, L, D, C.byref(g)) == _lib.ERR_ARG and _err() == msg
+    assert _lib.lib.ginsim_psd_plan(7, 2 ** 31 - 1, big, 1.0, 8, 1, C.byref(g)) == _lib.ERR_RANGE
+    assert _err() == 'psd_plan: a series of n = 7 samples is shorter than one segment of nperseg = 8'
+    hdr = open(os.path.join(REPO, 'include', 'ginsim_psd.h')).read()
+    order = [hdr.index(w) for w in ('n < nperseg;', '2^31 - 1 parts', "device's maxGridSize[1]", 'cap below')]
+    assert order == sorted(order)
 
 
 def test_call_refusals_with_a_null_context_and_their_order():
