@@ -77,6 +77,9 @@ SOURCES = [
     ('oallan.hip', ['--offload-arch=' + ARCH]),
     # one instantiation per segment length, 8 .. 8192 (tests/test_psd_oracle.py reads the resource report: no scratch)
     ('psd.hip', ['--offload-arch=' + ARCH]),
+    # the half-band decimation of the octave cascade; its sums are spelt as fused multiply-adds, so no flag decides their bits
+    # (tests/test_lpsd_oracle.py reads the resource report: no scratch)
+    ('lpsd.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),
     ('vib_psd.hip', ['--offload-arch=' + ARCH]),
     ('selftest.hip', ['--offload-arch=' + ARCH]),
@@ -101,10 +104,11 @@ def build(force=False, verbose=False, tag=None, defines=(), xflags=()):
         LIB = os.path.join(HERE, 'lib', 'libginsim_%s.so' % tag)
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hpp', '.h'))]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hpp', '.h', '.inc'))]
     deps.append(os.path.join(REPO, 'include', 'ginsim.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_oallan.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_psd.h'))
+    deps.append(os.path.join(REPO, 'include', 'ginsim_lpsd.h'))
     deps.append(os.path.abspath(__file__))
     objs = []
     for src, extra in SOURCES:

@@ -13,9 +13,11 @@
 #include "ginsim.h"
 #include "ginsim_oallan.h"
 #include "ginsim_psd.h"
+#include "ginsim_lpsd.h"
 #include "allan.hpp"
 #include "oallan.hpp"
 #include "psd.hpp"
+#include "lpsd.hpp"
 #include "comm.hpp"
 #include "launch.hpp"
 #include "placed.hpp"
@@ -342,6 +344,49 @@ static int psd_plan(const char* who, int64_t n, int32_t nseries, int32_t nperseg
         return GINSIM_ERR_RANGE;
     }
     S = s;
+    return GINSIM_OK;
+}
+
+// What one cascade call runs (lpsd.hpp) and the scratch it takes: the refusals that ginsim_lpsd and ginsim_lpsd_plan share behind
+// psd_check and psd_plan of level 0, in the order include/ginsim_lpsd.h states.  S0 is level 0's checked shape (its records hold
+// every other level's: fewer parts of the same size).
+struct LpsdPlan {
+    LpsdLevels lv;
+    size_t b_level[2] = {0, 0}, b_records = 0, b_out = 0;
+    size_t bytes() const { return b_level[0] + b_level[1] + b_records + b_out; }
+};
+
+static int lpsd_plan(const char* who, int64_t n, int32_t nseries, int32_t nperseg, int32_t step, int32_t min_segments,
+                     const PsdShape& S0, LpsdPlan& P) {
+    REQUIRE(min_segments >= 1, "%s: min_segments %d must be at least 1", who, (int)min_segments);
+    if (S0.segments < min_segments) {
+        set_error("%s: %lld segments at level 0 are fewer than min_segments = %d", who, (long long)S0.segments, (int)min_segments);
+        return GINSIM_ERR_RANGE;
+    }
+    LpsdPlan p;
+    p.lv = lpsd_plan_levels(n, nperseg, step, min_segments);
+    p.lv.S[0] = S0;
+    if (p.lv.levels > 1 && decimate2_tiles(p.lv.n[1]) > kDecMaxTiles) {
+        set_error("%s: level 1 of %lld samples is %lld tiles of %d, more than the %lld a launch can have: analyse the series in pieces",
+                  who, (long long)p.lv.n[1], (long long)decimate2_tiles(p.lv.n[1]), kDecTile, (long long)kDecMaxTiles);
+        return GINSIM_ERR_RANGE;
+    }
+    p.b_records = S0.record_bytes;
+    p.b_out = (sizeof(double) * (size_t)nseries * (size_t)S0.nbins + 255) & ~(size_t)255;
+    for (int j = 1; j <= 2 && j < p.lv.levels; ++j) {
+        // nseries n_j doubles, compared by division and never formed past 64 bits; a quarter of the range each leaves the sum exact
+        if (p.lv.n[j] > (INT64_MAX / 4 - 255) / (int64_t)sizeof(double) / nseries) {
+            set_error("%s: the level buffers of %d series and %lld samples at level %d pass 2^63 bytes: split the batch or the series",
+                      who, (int)nseries, (long long)p.lv.n[j], j);
+            return GINSIM_ERR_RANGE;
+        }
+        p.b_level[j - 1] = (sizeof(double) * (size_t)nseries * (size_t)p.lv.n[j] + 255) & ~(size_t)255;
+    }
+    if (p.b_records > (size_t)INT64_MAX / 4 || p.b_out > (size_t)INT64_MAX / 8) {
+        set_error("%s: the scratch of %d series passes 2^63 bytes: split the batch or the series", who, (int)nseries);
+        return GINSIM_ERR_RANGE;
+    }
+    P = p;
     return GINSIM_OK;
 }
 
@@ -1682,6 +1727,130 @@ int ginsim_psd_welch(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries,
     HIP_TRY(hipStreamSynchronize(c->stream));
     const double* h = c->allan_host;
     for (int k = 0; k < nb; ++k) freq[k] = (double)k * fs / (double)nperseg;
+    for (int s = 0; s < nseries; ++s) memcpy(psd + (size_t)s * cap, h + (size_t)s * nb, sizeof(double) * nb);
+    return GINSIM_OK;
+}
+
+// ---- multi-resolution PSD: Welch's estimate on a decimating octave cascade (include/ginsim_lpsd.h, csrc/lpsd.hip)
+int ginsim_decimate2(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, int64_t series_stride, double* y, int64_t y_stride,
+                     int64_t* n_out) {
+    REQUIRE(c && x && y && n_out, "decimate2: NULL argument");
+    *n_out = 0;
+    REQUIRE(nseries >= 1 && n >= kHalfbandTaps && series_stride >= n,
+            "decimate2: bad sizes (n = %lld must be at least %d, series_stride at least n)", (long long)n, kHalfbandTaps);
+    const int64_t no = decimate2_outputs(n);
+    *n_out = no;
+    if (y_stride < no) { set_error("decimate2: y_stride %lld is below the %lld outputs of a series", (long long)y_stride, (long long)no); return GINSIM_ERR_RANGE; }
+    // the ranges x[0 .. (nseries-1) series_stride + n) and y[0 .. (nseries-1) y_stride + n_out), in bytes; a product past 64 bits
+    // cannot be an allocation
+    const __int128 xb = ((__int128)(nseries - 1) * series_stride + n) * 8, yb = ((__int128)(nseries - 1) * y_stride + no) * 8;
+    const __int128 xa = (__int128)(uintptr_t)x, ya = (__int128)(uintptr_t)y;
+    if (xa < ya + yb && ya < xa + xb) { set_error("decimate2: the ranges of x and y overlap"); return GINSIM_ERR_RANGE; }
+    if (decimate2_tiles(no) > kDecMaxTiles) {
+        set_error("decimate2: %lld outputs are %lld tiles of %d, more than the %lld a launch can have", (long long)no,
+                  (long long)decimate2_tiles(no), kDecTile, (long long)kDecMaxTiles);
+        return GINSIM_ERR_RANGE;
+    }
+    if (nseries > c->max_grid_y) {
+        set_error("decimate2: %d series on the grid's y dimension but the device takes %d: split the batch into calls of at most %d series",
+                  (int)nseries, c->max_grid_y, c->max_grid_y);
+        return GINSIM_ERR_RANGE;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_decimate2(x, n, series_stride, nseries, y, y_stride, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GINSIM_OK;
+}
+
+int ginsim_lpsd_plan(int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t nperseg, int32_t step,
+                     int32_t min_segments, ginsim_lpsd_geometry* g) {
+    REQUIRE(g, "lpsd_plan: NULL argument");
+    int rc = psd_check("lpsd_plan", n, nseries, series_stride, fs, nperseg, step);
+    if (rc) return rc;
+    PsdShape S0;
+    rc = psd_plan("lpsd_plan", n, nseries, nperseg, step, S0);
+    if (rc) return rc;
+    LpsdPlan P;
+    rc = lpsd_plan("lpsd_plan", n, nseries, nperseg, step, min_segments, S0, P);
+    if (rc) return rc;
+    memset(g, 0, sizeof(*g));
+    g->scratch_bytes = (int64_t)P.bytes();
+    g->levels = P.lv.levels;
+    g->nbins = P.lv.nbins;
+    for (int j = 0; j < P.lv.levels; ++j) {
+        g->level[j].n = P.lv.n[j];
+        g->level[j].segments = P.lv.S[j].segments;
+        g->level[j].first_bin = P.lv.first_bin[j];
+        g->level[j].bins = P.lv.bins[j];
+        g->level[j].nparts = (int32_t)P.lv.S[j].nparts;
+    }
+    return GINSIM_OK;
+}
+
+int ginsim_lpsd(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t nperseg,
+                int32_t step, int32_t window, int32_t detrend, int32_t min_segments, double* freq, double* psd, int32_t* level,
+                int32_t* nbins, int32_t cap) {
+    REQUIRE(c && x && freq && psd && level && nbins, "lpsd: NULL argument");
+    *nbins = 0;
+    int rc = psd_check("lpsd", n, nseries, series_stride, fs, nperseg, step);
+    if (rc) return rc;
+    REQUIRE((window == GINSIM_PSD_BOXCAR || window == GINSIM_PSD_HANN) && (detrend == 0 || detrend == 1),
+            "lpsd: window %d (0 boxcar, 1 hann) or detrend %d (0, 1) out of range", (int)window, (int)detrend);
+    PsdShape S0;
+    rc = psd_plan("lpsd", n, nseries, nperseg, step, S0);
+    if (rc) return rc;
+    // every launch has the series on the grid's y dimension
+    if (nseries > c->max_grid_y) {
+        set_error("lpsd: %d series on the grid's y dimension but the device takes %d: split the batch into calls of at most %d series",
+                  (int)nseries, c->max_grid_y, c->max_grid_y);
+        return GINSIM_ERR_RANGE;
+    }
+    LpsdPlan P;
+    rc = lpsd_plan("lpsd", n, nseries, nperseg, step, min_segments, S0, P);
+    if (rc) return rc;
+    const LpsdLevels& lv = P.lv;
+    const int nb = lv.nbins, full = S0.nbins;
+    *nbins = nb;
+    if (nb > cap) { set_error("lpsd: %d bins but capacity %d", nb, (int)cap); return GINSIM_ERR_RANGE; }
+    HIP_TRY(hipSetDevice(c->device));
+    void* region = nullptr;
+    HIP_TRY(scratch(c, 1, P.bytes(), &region));
+    char* base = reinterpret_cast<char*>(region);
+    double* buf[2] = {reinterpret_cast<double*>(base), reinterpret_cast<double*>(base + P.b_level[0])};
+    double* records = reinterpret_cast<double*>(base + P.b_level[0] + P.b_level[1]);
+    double* dens = reinterpret_cast<double*>(base + P.b_level[0] + P.b_level[1] + P.b_records);
+    // the reported bins go to the pinned host memory the Allan results go to, [nseries][nb]: one synchronisation at the end
+    const size_t nout = (size_t)nb * (size_t)nseries;
+    if (c->allan_host_doubles < nout) {
+        if (c->allan_host) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipHostFree(c->allan_host)); c->allan_host = nullptr; c->allan_host_doubles = 0; }
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->allan_host), sizeof(double) * (nout + nout / 4 + 64), hipHostMallocDefault));
+        c->allan_host_doubles = nout + nout / 4 + 64;
+    }
+    const double U = window == GINSIM_PSD_HANN ? 0.375 * (double)nperseg : (double)nperseg;
+    const double* xj = x;                   // level j's series and their stride: the caller's, then the level buffers in turn
+    int64_t stride_j = series_stride;
+    double fs_j = fs;
+    int col = nb;                           // level 0 is the last block of columns of the output
+    for (int j = 0; j < lv.levels; ++j) {
+        const PsdShape& S = lv.S[j];
+        HIP_TRY(launch_psd_parts(xj, stride_j, nseries, step, window, detrend, S, records, c->stream));
+        HIP_TRY(launch_psd_finish(records, nseries, S, 1.0 / ((double)S.segments * fs_j * U), dens, c->stream));
+        col -= lv.bins[j];
+        HIP_TRY(launch_lpsd_report(dens, nseries, full, lv.first_bin[j], lv.bins[j], c->allan_host + col, nb, c->stream));
+        for (int k = 0; k < lv.bins[j]; ++k) {
+            freq[col + k] = (double)(lv.first_bin[j] + k) * fs_j / (double)nperseg;
+            level[col + k] = j;
+        }
+        if (j + 1 < lv.levels) {
+            double* out = buf[j & 1];       // level j + 1: odd levels in the first buffer, even ones in the second
+            HIP_TRY(launch_decimate2(xj, lv.n[j], stride_j, nseries, out, lv.n[j + 1], c->stream));
+            xj = out;
+            stride_j = lv.n[j + 1];
+            fs_j *= 0.5;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double* h = c->allan_host;
     for (int s = 0; s < nseries; ++s) memcpy(psd + (size_t)s * cap, h + (size_t)s * nb, sizeof(double) * nb);
     return GINSIM_OK;
 }

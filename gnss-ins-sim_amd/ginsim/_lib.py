@@ -173,6 +173,20 @@ class PsdGeometry(C.Structure):
                 ('lds_bytes', C.c_int32), ('threads', C.c_int32)]
 
 
+class LpsdLevel(C.Structure):
+    """ginsim_lpsd_level (include/ginsim_lpsd.h): one level of the octave cascade and the bins it reports."""
+    _fields_ = [('n', C.c_int64), ('segments', C.c_int64), ('first_bin', C.c_int32), ('bins', C.c_int32), ('nparts', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+LPSD_MAX_LEVELS = 32
+
+
+class LpsdGeometry(C.Structure):
+    """ginsim_lpsd_geometry: the levels of a cascade call, all its reported bins and the scratch it takes."""
+    _fields_ = [('scratch_bytes', C.c_int64), ('levels', C.c_int32), ('nbins', C.c_int32), ('level', LpsdLevel * LPSD_MAX_LEVELS)]
+
+
 class Stats(C.Structure):
     _fields_ = [('count', C.c_double), ('mean', C.c_double * 9), ('m2', C.c_double * 9),
                 ('maxabs', C.c_double * 9)]
@@ -304,6 +318,15 @@ _SIGS_PSD = {
                                    C.c_int32, C.c_int32, _PD, _PD, C.POINTER(C.c_int32), C.c_int32]),
     'ginsim_psd_plan': (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.POINTER(PsdGeometry)]),
 }
+# include/ginsim_lpsd.h: the fourth header, the fourth table (ginsim.LPSD_EXPORTS)
+_SIGS_LPSD = {
+    'ginsim_decimate2': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64,
+                                   C.POINTER(C.c_int64)]),
+    'ginsim_lpsd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                              C.c_int32, C.c_int32, _PD, _PD, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]),
+    'ginsim_lpsd_plan': (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(LpsdGeometry)]),
+}
 _OPTIONAL = {}
 
 
@@ -312,7 +335,7 @@ def _load():
         raise ImportError('libginsim.so not built: run `python gnss-ins-sim_amd/build.py` '
                           '(or __graft_entry__.build()); expected %s' % LIB_PATH)
     lib = C.cdll.LoadLibrary(LIB_PATH)
-    for sigs in (_SIGS, _SIGS_OALLAN, _SIGS_PSD):
+    for sigs in (_SIGS, _SIGS_OALLAN, _SIGS_PSD, _SIGS_LPSD):
         for name, (res, args) in sigs.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -327,6 +350,7 @@ lib = _load()
 EXPORTS = tuple(_SIGS)
 OALLAN_EXPORTS = tuple(_SIGS_OALLAN)
 PSD_EXPORTS = tuple(_SIGS_PSD)
+LPSD_EXPORTS = tuple(_SIGS_LPSD)
 
 
 def check(rc):

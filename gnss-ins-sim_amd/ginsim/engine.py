@@ -423,6 +423,21 @@ def sensor_model(err, rw_key, fs):
     return m
 
 
+def model_psd(err, rw_key, fs, freq):
+    """The single-sided density (unit^2 / Hz) of the error that ``sensor_model`` generates, at the frequencies `freq`, as
+    (nfreq, 3): the white noise, 2 sigma^2 / fs with sigma the per-sample deviation, plus the drift.  The drift of a finite
+    correlation time is the discrete first-order process d[j+1] = a d[j] + b z[j] (pathgen.bias_drift), whose spectrum is
+    2 b^2 / fs / (1 - 2 a cos(2 pi f / fs) + a^2) once its start from zero has died away; of an infinite one it is white,
+    2 b^2 / fs.  The constant bias is a line at f = 0 and is not part of it."""
+    m = sensor_model(err, rw_key, fs)
+    f = np.asarray(freq, dtype=np.float64)
+    out = np.empty(f.shape + (3,))
+    for i in range(3):
+        a, b = m.gm_a[i], m.gm_b[i]
+        out[..., i] = 2.0 * m.white[i] ** 2 / fs + 2.0 * b * b / fs / (1.0 - 2.0 * a * np.cos(2 * np.pi * f / fs) + a * a)
+    return out
+
+
 VIB_TYPES = {'random': 1, 'sinusoidal': 2}
 
 
@@ -967,6 +982,19 @@ class MonteCarloJob(BatchJob):
         p = p.reshape(len(names), self.runs, 3, -1)
         return freq, {nm: p[i].transpose(0, 2, 1).copy() for i, nm in enumerate(names)}
 
+    def lpsd(self, fs=None, names=('accel', 'gyro'), nperseg=1024, step=None, window='hann', detrend=True, min_segments=1):
+        """Multi-resolution spectral density of the kept sensor series on the device, every run at once: Welch's estimate of
+        ``psd`` on a decimating octave cascade (``lpsd``).  Returns (freq (nbins,), {name: (runs, nbins, 3)}, level (nbins,)), the
+        frequencies ascending and the level each bin came from.  ONE ginsim_lpsd call from the buffer that ``allan`` reads."""
+        if not self.keep_sensors or self.precision != 'f64':
+            raise ValueError('the spectral density needs the fp64 sensor series (keep_sensors=True)')
+        fs = float(self.params.fs if fs is None else fs)
+        names = tuple(names)
+        ptr = self._sensor_series(names)
+        p, freq, level = lpsd(self.ctx, ptr, self.n, 3 * self.runs * len(names), self.n, fs, nperseg, step, window, detrend, min_segments)
+        p = p.reshape(len(names), self.runs, 3, -1)
+        return freq, {nm: p[i].transpose(0, 2, 1).copy() for i, nm in enumerate(names)}, level
+
     def bytes_written(self):
         per_sample = 0
         if self.keep_sensors:
@@ -1324,3 +1352,58 @@ def welch_psd_host(ctx, series, fs, nperseg, step=None, window='hann', detrend=T
     finally:
         buf.free()
     return (psd[0], freq) if np.ndim(series) == 1 else (psd, freq)
+
+
+def decimate2(ctx, x, n, nseries, series_stride, y, y_stride):
+    """One level of the cascade, device to device (ginsim_decimate2): the half-band low-pass of 27 taps with a stride of two on
+    `nseries` series of n samples; `y` (DeviceBuffer, DeviceView or raw pointer) takes (n - 27) // 2 + 1 outputs per series,
+    y_stride apart.  Returns that count."""
+    n_out = C.c_int64(0)
+    check(lib.ginsim_decimate2(ctx.handle, getattr(x, 'ptr', x), int(n), int(nseries), int(series_stride), getattr(y, 'ptr', y),
+                               int(y_stride), C.byref(n_out)))
+    return n_out.value
+
+
+def lpsd_plan(n, nseries, series_stride, fs, nperseg, step=None, min_segments=1):
+    """What ``lpsd`` with these arguments runs, from the library's own planning code (ginsim_lpsd_plan: host only, no context,
+    nothing launched): a dict with nbins, scratch_bytes and levels, one dict per level with n, segments, first_bin, bins, nparts."""
+    L, D, _, _ = _psd_args(nperseg, step, 'hann', True)
+    g = _lib.LpsdGeometry()
+    check(lib.ginsim_lpsd_plan(int(n), int(nseries), int(series_stride), float(fs), L, D, int(min_segments), C.byref(g)))
+    return dict(nbins=g.nbins, scratch_bytes=g.scratch_bytes,
+                levels=[dict(n=l.n, segments=l.segments, first_bin=l.first_bin, bins=l.bins, nparts=l.nparts) for l in g.level[:g.levels]])
+
+
+def lpsd(ctx, x, n, nseries, series_stride, fs, nperseg, step=None, window='hann', detrend=True, min_segments=1):
+    """Multi-resolution power spectral density of `nseries` device-resident series: ``welch_psd`` with these arguments on the
+    series, on the series low-passed and halved (``decimate2``) at fs / 2, and so on while `min_segments` segments still fit;
+    every level reports the octave it resolves best (include/ginsim_lpsd.h).  Returns (psd (nseries, nbins), freq, level), the
+    frequencies ascending and level[i] the level bin i came from."""
+    ptr = getattr(x, 'ptr', x)
+    L, D, w, d = _psd_args(nperseg, step, window, detrend)
+    nb = C.c_int32(0)
+
+    def call(freq, psd, level, cap):
+        return lib.ginsim_lpsd(ctx.handle, ptr, int(n), int(nseries), int(series_stride), float(fs), L, D, w, d, int(min_segments),
+                               dptr(freq), dptr(psd), level.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nb), cap)
+    # asked with no capacity, a call that has nothing else against it is refused last of all and reports its bins: the arrays
+    # are then exactly as large as the result (the worst case, 32 levels, is 16 times nperseg per series)
+    none = np.empty(1), np.empty((max(int(nseries), 1), 1)), np.empty(1, dtype=np.int32)
+    rc = call(none[0], none[1], none[2], 0)
+    if nb.value <= 0:
+        check(rc)
+    cap = nb.value
+    freq, psd, level = np.empty(cap), np.empty((nseries, cap)), np.empty(cap, dtype=np.int32)
+    check(ctx.retry_oom(lambda: call(freq, psd, level, cap)))
+    return psd, freq, level
+
+
+def lpsd_host(ctx, series, fs, nperseg, step=None, window='hann', detrend=True, min_segments=1):
+    """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (psd, freq, level)."""
+    a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
+    buf = ctx.upload(a)
+    try:
+        psd, freq, level = lpsd(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs, nperseg, step, window, detrend, min_segments)
+    finally:
+        buf.free()
+    return (psd[0], freq, level) if np.ndim(series) == 1 else (psd, freq, level)

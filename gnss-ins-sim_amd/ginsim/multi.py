@@ -240,6 +240,11 @@ class JobSet(_Parts):
         got = [g for g in self._each_part(lambda j: j.psd(fs, names, nperseg, step, window, detrend)) if g is not None]
         return got[0][0], {nm: np.concatenate([g[1][nm] for g in got], axis=0) for nm in names}
 
+    def lpsd(self, fs=None, names=('accel', 'gyro'), nperseg=1024, step=None, window='hann', detrend=True, min_segments=1):
+        """MonteCarloJob.lpsd on every device at the same time: (freq, {name: (runs, nbins, 3)}, level)."""
+        got = [g for g in self._each_part(lambda j: j.lpsd(fs, names, nperseg, step, window, detrend, min_segments)) if g is not None]
+        return got[0][0], {nm: np.concatenate([g[1][nm] for g in got], axis=0) for nm in names}, got[0][2]
+
     def buffer(self, name):
         raise ValueError('a JobSet spans several devices: take the buffer from one of its parts')
 
