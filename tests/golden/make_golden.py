@@ -8,6 +8,7 @@ Run in the build container only (needs /root/reference, which does not exist on 
 What is produced (all from reference code, nothing hand-typed):
   t1_fixture_{bosch,nxp}.npz   FreeIntegration.run on the reference's logged-IMU fixtures
                                (recipe of demo_free_integration_openimu.py:31-53).
+  t1_fixture_tumble[_odo].npz  both plugins on synthetic rates that fold the pitch and wrap yaw and roll.
   t2_turn_rf{0,1}.npz          noise-free closed loop on the 90-degree turn: path_gen truth +
                                FreeIntegration / odo-FreeIntegration outputs (decimated).
   t2_long_drive_rf0.npz        path_gen truth of long_drive @200 Hz with GPS@10 Hz + odo, and the
@@ -150,10 +151,9 @@ def t1_rates():
     save('t1_rates', count=3, **out)
 
 
-def t1_tumble():
+def tumble_inputs():
     """Synthetic body rates that drive the pitch through +-90 deg (the fold of attitude.euler_update_zyx,
-    attitude.py:700-712) and yaw / roll through +-180 deg (the single 2 pi wrap, :713-720) several times.
-    Every sample is kept: the branches are what is being pinned."""
+    attitude.py:700-712) and yaw / roll through +-180 deg (the single 2 pi wrap, :713-720) several times."""
     n = 900
     t = np.arange(n) / 100.0
     ini = np.array([32.0 * D2R, 120.0 * D2R, 0.0, 5.0, 0.0, 0.0, 170.0 * D2R, 78.0 * D2R, 0.0, 9.794])
@@ -164,12 +164,32 @@ def t1_tumble():
                      late * (70.0 * D2R + 10.0 * D2R * np.sin(2 * np.pi * t / 2.9))], axis=1)
     accel = np.stack([0.3 * np.sin(2 * np.pi * t / 3.0), 0.2 * np.cos(2 * np.pi * t / 1.7),
                       -9.794 + 0.1 * np.sin(2 * np.pi * t / 0.9)], axis=1)
+    return ini, gyro, accel
+
+
+def t1_tumble():
+    """Every sample is kept: the branches are what is being pinned."""
+    ini, gyro, accel = tumble_inputs()
     att = t1_run('tumble', ini, gyro, accel, 1)
     pit = att[:, 1]
     dy, dr = np.abs(np.diff(att[:, 0])), np.abs(np.diff(att[:, 2]))
     print('   tumble: min |cos(pitch)| = %.2e, %d folds, %d wraps, %d steps > 0.25 rad' % (
         np.min(np.abs(np.cos(pit))), int(np.sum((dy > 2) & (dy < 4) & (dr > 2) & (dr < 4))), int(np.sum(dy > 5) + np.sum(dr > 5)),
         int(np.sum(np.maximum(dy, dr) > 0.25))))
+
+
+def t1_tumble_odo():
+    """The odometer plugin (free_integration_odo.py:63-160) on the tumble rates with a constant forward speed, both frames, every
+    sample, called as t1_rates calls it: the fold and the wraps through the algorithm that takes its velocity from the attitude."""
+    ini, gyro, _ = tumble_inputs()
+    odo = np.full(gyro.shape[0], 5.0)
+    out = {}
+    for tag, rf, use_g, erot in (('extg', 0, True, False), ('wgs', 0, False, True), ('rf1', 1, False, True)):
+        algo = free_integration_odo.FreeIntegration(ini.copy() if use_g else ini[0:9].copy(), earth_rot=erot)
+        algo.run([rf, 100.0, gyro.copy(), odo.copy()])
+        att, pos, vel = algo.get_results()
+        out.update({'att_' + tag: att, 'pos_' + tag: pos, 'vel_' + tag: vel})
+    save('t1_fixture_tumble_odo', ini=ini, gyro=gyro, odo=odo, fs=100.0, **out)
 
 
 # ------------------------------------------------------------------ T2: noise-free closed loop
@@ -641,6 +661,7 @@ def t3_mag9(rf):
 CASES = [
     ('profiles', 'emit_profiles()', ['motion_profiles/turn_90deg.csv', 'motion_profiles/long_drive.csv', 'motion_profiles/static_1800s.csv']),
     ('t1_tumble', 't1_tumble()', ['t1_fixture_tumble.npz']),
+    ('t1_tumble_odo', 't1_tumble_odo()', ['t1_fixture_tumble_odo.npz']),
     ('t1_rates', 't1_rates()', ['t1_rates.npz']),
     ('t1_bosch', "t1_fixture('bosch')", ['t1_fixture_bosch.npz']),
     ('t1_nxp', "t1_fixture('nxp')", ['t1_fixture_nxp.npz']),
