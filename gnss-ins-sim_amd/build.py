@@ -80,6 +80,9 @@ SOURCES = [
     # the half-band decimation of the octave cascade; its sums are spelt as fused multiply-adds, so no flag decides their bits
     # (tests/test_lpsd_oracle.py reads the resource report: no scratch)
     ('lpsd.hip', ['--offload-arch=' + ARCH]),
+    # one instantiation per segment length, 8 .. 4096, four accumulators per bin in registers (tests/test_csd_oracle.py reads the
+    # resource report: no scratch)
+    ('csd.hip', ['--offload-arch=' + ARCH]),
     ('placed.hip', ['--offload-arch=' + ARCH]),
     ('vib_psd.hip', ['--offload-arch=' + ARCH]),
     ('selftest.hip', ['--offload-arch=' + ARCH]),
@@ -109,6 +112,7 @@ def build(force=False, verbose=False, tag=None, defines=(), xflags=()):
     deps.append(os.path.join(REPO, 'include', 'ginsim_oallan.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_psd.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_lpsd.h'))
+    deps.append(os.path.join(REPO, 'include', 'ginsim_csd.h'))
     deps.append(os.path.abspath(__file__))
     objs = []
     for src, extra in SOURCES:

@@ -14,10 +14,12 @@
 #include "ginsim_oallan.h"
 #include "ginsim_psd.h"
 #include "ginsim_lpsd.h"
+#include "ginsim_csd.h"
 #include "allan.hpp"
 #include "oallan.hpp"
 #include "psd.hpp"
 #include "lpsd.hpp"
+#include "csd.hpp"
 #include "comm.hpp"
 #include "launch.hpp"
 #include "placed.hpp"
@@ -1728,6 +1730,114 @@ int ginsim_psd_welch(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries,
     const double* h = c->allan_host;
     for (int k = 0; k < nb; ++k) freq[k] = (double)k * fs / (double)nperseg;
     for (int s = 0; s < nseries; ++s) memcpy(psd + (size_t)s * cap, h + (size_t)s * nb, sizeof(double) * nb);
+    return GINSIM_OK;
+}
+
+// ---- Welch cross-spectral density between pairs of series (include/ginsim_csd.h, csrc/csd.hip)
+// The refusals that ginsim_csd_welch and ginsim_csd_plan share, in the order include/ginsim_csd.h states and under the caller's
+// prefix: the sizes, the pair count, the segment length and step (the call checks window, detrend and the pair table after this).
+static int csd_check(const char* who, int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t npairs, int32_t nperseg,
+                     int32_t step) {
+    REQUIRE(n >= 1 && nseries >= 1 && series_stride >= n && fs > 0 && std::isfinite(fs), "%s: bad sizes", who);
+    REQUIRE(npairs >= 1, "%s: npairs %d: a call needs at least one pair", who, (int)npairs);
+    REQUIRE(nperseg != (1 << kPsdMaxLog2),
+            "%s: nperseg %d is not taken: a workgroup keeps four sums per bin in registers and at %d the PSD kernel, with one, already "
+            "holds 254 of 256; the largest segment is %d", who, (int)nperseg, (int)nperseg, 1 << kCsdMaxLog2);
+    REQUIRE(nperseg >= (1 << kCsdMinLog2) && nperseg <= (1 << kCsdMaxLog2) && (nperseg & (nperseg - 1)) == 0,
+            "%s: nperseg %d is not a power of two in [%d, %d]", who, (int)nperseg, 1 << kCsdMinLog2, 1 << kCsdMaxLog2);
+    REQUIRE(step >= 1 && step <= nperseg, "%s: step %d outside [1, %d]", who, (int)step, (int)nperseg);
+    return GINSIM_OK;
+}
+
+// the shape (psd.hpp's partition of one series) and the scratch of a call: records, then the pair table
+static int csd_plan(const char* who, int64_t n, int32_t npairs, int32_t nperseg, int32_t step, PsdShape& S, size_t& table_bytes) {
+    if (n < nperseg) {
+        set_error("%s: a series of n = %lld samples is shorter than one segment of nperseg = %d", who, (long long)n, (int)nperseg);
+        return GINSIM_ERR_RANGE;
+    }
+    PsdShape s = psd_plan_shape(n, nperseg, step);     // a local: a refused plan leaves the caller's as it was
+    if (s.nparts > kPsdMaxParts) {
+        set_error("%s: %lld segments in parts of %d are %lld parts per pair, more than the %lld a call can have: analyse the series in pieces",
+                  who, (long long)s.segments, (int)s.segs_per_part, (long long)s.nparts, (long long)kPsdMaxParts);
+        return GINSIM_ERR_RANGE;
+    }
+    size_t tb = 0;
+    if (!csd_scratch_bytes(s, npairs, tb)) {
+        set_error("%s: the records of %lld parts per pair and %d pairs, %d sums each, pass 2^63 bytes: split the table or the series",
+                  who, (long long)s.nparts, (int)npairs, kCsdPlanes * (int)s.nbins);
+        return GINSIM_ERR_RANGE;
+    }
+    S = s;
+    table_bytes = tb;
+    return GINSIM_OK;
+}
+
+int ginsim_csd_plan(int64_t n, int32_t nseries, int64_t series_stride, double fs, int32_t npairs, int32_t nperseg, int32_t step,
+                    ginsim_csd_geometry* g) {
+    REQUIRE(g, "csd_plan: NULL argument");
+    int rc = csd_check("csd_plan", n, nseries, series_stride, fs, npairs, nperseg, step);
+    if (rc) return rc;
+    PsdShape S;
+    size_t tb = 0;
+    rc = csd_plan("csd_plan", n, npairs, nperseg, step, S, tb);
+    if (rc) return rc;
+    g->segments = S.segments;
+    g->scratch_bytes = (int64_t)(S.record_bytes + tb);
+    g->segs_per_part = S.segs_per_part;
+    g->nparts = (int32_t)S.nparts;
+    g->lds_bytes = csd_lds_bytes(nperseg);
+    g->threads = csd_threads(nperseg);
+    return GINSIM_OK;
+}
+
+int ginsim_csd_welch(ginsim_ctx* c, const double* x, int64_t n, int32_t nseries, int64_t series_stride, double fs,
+                     const int32_t* pairs, int32_t npairs, int32_t nperseg, int32_t step, int32_t window, int32_t detrend,
+                     double* freq, double* pxx, double* pyy, double* pxy_re, double* pxy_im, int32_t* nfreq, int32_t cap) {
+    REQUIRE(c && x && pairs && freq && pxx && pyy && pxy_re && pxy_im && nfreq, "csd: NULL argument");
+    *nfreq = 0;
+    int rc = csd_check("csd", n, nseries, series_stride, fs, npairs, nperseg, step);
+    if (rc) return rc;
+    REQUIRE((window == GINSIM_PSD_BOXCAR || window == GINSIM_PSD_HANN) && (detrend == 0 || detrend == 1),
+            "csd: window %d (0 boxcar, 1 hann) or detrend %d (0, 1) out of range", (int)window, (int)detrend);
+    for (int32_t p = 0; p < npairs; ++p)
+        REQUIRE(pairs[2 * p] >= 0 && pairs[2 * p] < nseries && pairs[2 * p + 1] >= 0 && pairs[2 * p + 1] < nseries,
+                "csd: pair %d is (%d, %d) but the series are 0 .. %d", (int)p, (int)pairs[2 * p], (int)pairs[2 * p + 1], (int)nseries - 1);
+    PsdShape S;
+    size_t tb = 0;
+    rc = csd_plan("csd", n, npairs, nperseg, step, S, tb);
+    if (rc) return rc;
+    // both launches have the pairs on the grid's y dimension
+    if (npairs > c->max_grid_y) {
+        set_error("csd: %d pairs on the grid's y dimension but the device takes %d: split the table into calls of at most %d pairs",
+                  (int)npairs, c->max_grid_y, c->max_grid_y);
+        return GINSIM_ERR_RANGE;
+    }
+    const int nb = S.nbins;
+    *nfreq = nb;
+    if (nb > cap) { set_error("csd: %d frequencies but capacity %d", nb, (int)cap); return GINSIM_ERR_RANGE; }
+    HIP_TRY(hipSetDevice(c->device));
+    void* region = nullptr;
+    HIP_TRY(scratch(c, 1, S.record_bytes + tb, &region));
+    double* records = reinterpret_cast<double*>(region);
+    int32_t* d_pairs = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(region) + S.record_bytes);
+    // the table once per call; the copy has read the caller's (pageable) array when it returns
+    HIP_TRY(hipMemcpyAsync(d_pairs, pairs, sizeof(int32_t) * 2 * (size_t)npairs, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_csd_parts(x, series_stride, d_pairs, npairs, step, window, detrend, S, records, c->stream));
+    // the four planes go straight into the pinned host memory the Allan and PSD results go to: no copy, one synchronisation
+    const size_t plane = (size_t)nb * (size_t)npairs, nout = kCsdPlanes * plane;
+    if (c->allan_host_doubles < nout) {
+        if (c->allan_host) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipHostFree(c->allan_host)); c->allan_host = nullptr; c->allan_host_doubles = 0; }
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->allan_host), sizeof(double) * (nout + nout / 4 + 64), hipHostMallocDefault));
+        c->allan_host_doubles = nout + nout / 4 + 64;
+    }
+    const double U = window == GINSIM_PSD_HANN ? 0.375 * (double)nperseg : (double)nperseg;
+    HIP_TRY(launch_csd_finish(records, npairs, S, 1.0 / ((double)S.segments * fs * U), c->allan_host, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double* h = c->allan_host;
+    double* const outs[kCsdPlanes] = {pxx, pyy, pxy_re, pxy_im};
+    for (int k = 0; k < nb; ++k) freq[k] = (double)k * fs / (double)nperseg;
+    for (int q = 0; q < kCsdPlanes; ++q)
+        for (int p = 0; p < npairs; ++p) memcpy(outs[q] + (size_t)p * cap, h + q * plane + (size_t)p * nb, sizeof(double) * nb);
     return GINSIM_OK;
 }
 

@@ -173,6 +173,12 @@ class PsdGeometry(C.Structure):
                 ('lds_bytes', C.c_int32), ('threads', C.c_int32)]
 
 
+class CsdGeometry(C.Structure):
+    """ginsim_csd_geometry (include/ginsim_csd.h): the segments of a cross-spectral call, the parts of a pair and what a workgroup takes."""
+    _fields_ = [('segments', C.c_int64), ('scratch_bytes', C.c_int64), ('segs_per_part', C.c_int32), ('nparts', C.c_int32),
+                ('lds_bytes', C.c_int32), ('threads', C.c_int32)]
+
+
 class LpsdLevel(C.Structure):
     """ginsim_lpsd_level (include/ginsim_lpsd.h): one level of the octave cascade and the bins it reports."""
     _fields_ = [('n', C.c_int64), ('segments', C.c_int64), ('first_bin', C.c_int32), ('bins', C.c_int32), ('nparts', C.c_int32),
@@ -327,6 +333,13 @@ _SIGS_LPSD = {
     'ginsim_lpsd_plan': (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_int32,
                                    C.POINTER(LpsdGeometry)]),
 }
+# include/ginsim_csd.h: the fifth header, the fifth table (ginsim.CSD_EXPORTS)
+_SIGS_CSD = {
+    'ginsim_csd_welch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double, C.POINTER(C.c_int32), C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, C.POINTER(C.c_int32), C.c_int32]),
+    'ginsim_csd_plan': (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                  C.POINTER(CsdGeometry)]),
+}
 _OPTIONAL = {}
 
 
@@ -335,7 +348,7 @@ def _load():
         raise ImportError('libginsim.so not built: run `python gnss-ins-sim_amd/build.py` '
                           '(or __graft_entry__.build()); expected %s' % LIB_PATH)
     lib = C.cdll.LoadLibrary(LIB_PATH)
-    for sigs in (_SIGS, _SIGS_OALLAN, _SIGS_PSD, _SIGS_LPSD):
+    for sigs in (_SIGS, _SIGS_OALLAN, _SIGS_PSD, _SIGS_LPSD, _SIGS_CSD):
         for name, (res, args) in sigs.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -351,6 +364,7 @@ EXPORTS = tuple(_SIGS)
 OALLAN_EXPORTS = tuple(_SIGS_OALLAN)
 PSD_EXPORTS = tuple(_SIGS_PSD)
 LPSD_EXPORTS = tuple(_SIGS_LPSD)
+CSD_EXPORTS = tuple(_SIGS_CSD)
 
 
 def check(rc):

@@ -995,6 +995,45 @@ class MonteCarloJob(BatchJob):
         p = p.reshape(len(names), self.runs, 3, -1)
         return freq, {nm: p[i].transpose(0, 2, 1).copy() for i, nm in enumerate(names)}, level
 
+    def series_buffer(self, names=('accel', 'gyro')):
+        """(device address, nseries): the kept fp64 series of the named sensors as [sensor][run][axis][n], the buffer that ``psd``
+        and ``csd`` read -- series (s * runs + run) * 3 + axis, n samples each, n apart -- for calls of one's own (``welch_csd``
+        between runs, say).  It lives with the job."""
+        if not self.keep_sensors or self.precision != 'f64':
+            raise ValueError('the series buffer needs the fp64 sensor series (keep_sensors=True)')
+        names = tuple(names)
+        return self._sensor_series(names), 3 * self.runs * len(names)
+
+    def csd(self, fs=None, pairs=None, names=('accel', 'gyro'), nperseg=1024, step=None, window='hann', detrend=True):
+        """Welch cross-spectral density between axes of the kept sensor series on the device, the same pairs in every run.
+        `pairs` is a sequence of ((name, axis), (name, axis)), x-series and y-series; by default every distinct pair of the named
+        sensors' axes (15 for two sensors).  Returns (freq (nfreq,), dict) with 'pairs' (the table as given), 'pxx', 'pyy',
+        'coherence', 'phase' (runs, npairs, nfreq) and 'pxy' complex of the same shape.  ONE ginsim_csd_welch call for all runs
+        from the [sensor][run][axis][n] buffer that ``psd`` reads."""
+        if not self.keep_sensors or self.precision != 'f64':
+            raise ValueError('the spectral density needs the fp64 sensor series (keep_sensors=True)')
+        fs = float(self.params.fs if fs is None else fs)
+        names = tuple(names)
+        if pairs is None:
+            ends = [(nm, a) for nm in names for a in range(3)]
+            pairs = [(ends[i], ends[j]) for i in range(len(ends)) for j in range(i + 1, len(ends))]
+        pairs = [((str(a[0]), int(a[1])), (str(b[0]), int(b[1]))) for a, b in pairs]
+        for end in (e for p in pairs for e in p):
+            if end[0] not in names or not 0 <= end[1] < 3:
+                raise ValueError('pairs: %r is not an axis 0..2 of %s' % (end, names))
+        if not pairs:
+            raise ValueError('pairs: at least one pair')
+
+        def series(run, end):
+            return (names.index(end[0]) * self.runs + run) * 3 + end[1]
+        table = [(series(r, a), series(r, b)) for r in range(self.runs) for a, b in pairs]
+        ptr = self._sensor_series(names)
+        res = welch_csd(self.ctx, ptr, self.n, 3 * self.runs * len(names), self.n, fs, table, nperseg, step, window, detrend)
+        shape = (self.runs, len(pairs), -1)
+        out = {k: getattr(res, k).reshape(shape) for k in ('pxx', 'pyy', 'pxy', 'coherence', 'phase')}
+        out['pairs'] = pairs
+        return res.freq, out
+
     def bytes_written(self):
         per_sample = 0
         if self.keep_sensors:
@@ -1407,3 +1446,84 @@ def lpsd_host(ctx, series, fs, nperseg, step=None, window='hann', detrend=True, 
     finally:
         buf.free()
     return (psd[0], freq, level) if np.ndim(series) == 1 else (psd, freq, level)
+
+
+class CsdResult:
+    """Welch's cross-spectral estimate of `npairs` pairs of series (include/ginsim_csd.h): ``freq`` (nfreq,), ``pairs`` (npairs, 2)
+    series indices (x, y), ``pxx`` and ``pyy`` (npairs, nfreq) single-sided densities, ``pxy`` complex (npairs, nfreq), the mean
+    of conj(X) Y.  The derived quantities are properties, formed from these arrays when they are asked for."""
+
+    def __init__(self, freq, pairs, pxx, pyy, pxy):
+        self.freq, self.pairs, self.pxx, self.pyy, self.pxy = freq, pairs, pxx, pyy, pxy
+
+    @property
+    def coherence(self):
+        """Magnitude-squared coherence |pxy|^2 / (pxx pyy); NaN where the denominator is 0."""
+        den = self.pxx * self.pyy
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(den == 0, np.nan, np.abs(self.pxy) ** 2 / den)
+
+    @property
+    def phase(self):
+        """angle(pxy): the phase of y against x, radians."""
+        return np.angle(self.pxy)
+
+    @property
+    def transfer(self):
+        """pxy / pxx: the H1 estimate of the response of y over x."""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return self.pxy / self.pxx
+
+    @property
+    def gain(self):
+        """|transfer|."""
+        return np.abs(self.transfer)
+
+
+def _csd_pairs(pairs):
+    p = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64))
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError('pairs: a sequence of (i, j) series indices')
+    if p.size and (p.min() < -2 ** 31 or p.max() >= 2 ** 31):
+        raise ValueError('pairs: a series index does not fit 32 bits')
+    return np.ascontiguousarray(p.astype(np.int32))
+
+
+def welch_csd(ctx, x, n, nseries, series_stride, fs, pairs, nperseg, step=None, window='hann', detrend=True):
+    """Welch's cross-spectral density between pairs of `nseries` device-resident series (DeviceBuffer, DeviceView or raw pointer):
+    `pairs` is a sequence of (i, j) series indices, x-series and y-series; segments, window and detrend as ``welch_psd`` with
+    nperseg 8 .. 4096 -- scipy.signal.csd(x_i, x_j, fs, window, nperseg, nperseg - step, detrend='constant' or False,
+    scaling='density') (include/ginsim_csd.h).  Returns a ``CsdResult``."""
+    ptr = getattr(x, 'ptr', x)
+    L, D, w, d = _psd_args(nperseg, step, window, detrend)
+    tab = _csd_pairs(pairs)
+    npairs = tab.shape[0]
+    cap = max(L // 2 + 1, 1)
+    freq = np.empty(cap)
+    out = np.empty((4, max(npairs, 1), cap))
+    nf = C.c_int32(0)
+    check(ctx.retry_oom(lambda: lib.ginsim_csd_welch(ctx.handle, ptr, int(n), int(nseries), int(series_stride), float(fs),
+                                                     tab.ctypes.data_as(C.POINTER(C.c_int32)), npairs, L, D, w, d, dptr(freq),
+                                                     dptr(out[0]), dptr(out[1]), dptr(out[2]), dptr(out[3]), C.byref(nf), cap)))
+    k = nf.value
+    return CsdResult(freq[:k].copy(), tab.copy(), np.ascontiguousarray(out[0, :, :k]), np.ascontiguousarray(out[1, :, :k]),
+                     out[2, :, :k] + 1j * out[3, :, :k])
+
+
+def csd_plan(n, nseries, series_stride, fs, npairs, nperseg, step=None):
+    """What ``welch_csd`` with these arguments runs, from the library's own planning code (ginsim_csd_plan: host only, no context,
+    nothing launched): a dict with segments, segs_per_part, nparts, threads, lds_bytes and scratch_bytes."""
+    L, D, _, _ = _psd_args(nperseg, step, 'hann', True)
+    g = _lib.CsdGeometry()
+    check(lib.ginsim_csd_plan(int(n), int(nseries), int(series_stride), float(fs), int(npairs), L, D, C.byref(g)))
+    return {k: getattr(g, k) for k, _ in _lib.CsdGeometry._fields_}
+
+
+def welch_csd_host(ctx, series, fs, pairs, nperseg, step=None, window='hann', detrend=True):
+    """Host arrays in: series (S, n).  Uploads, runs the device kernels, returns the ``CsdResult`` of `pairs`."""
+    a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
+    buf = ctx.upload(a)
+    try:
+        return welch_csd(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs, pairs, nperseg, step, window, detrend)
+    finally:
+        buf.free()

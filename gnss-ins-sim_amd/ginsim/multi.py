@@ -245,6 +245,13 @@ class JobSet(_Parts):
         got = [g for g in self._each_part(lambda j: j.lpsd(fs, names, nperseg, step, window, detrend, min_segments)) if g is not None]
         return got[0][0], {nm: np.concatenate([g[1][nm] for g in got], axis=0) for nm in names}, got[0][2]
 
+    def csd(self, fs=None, pairs=None, names=('accel', 'gyro'), nperseg=1024, step=None, window='hann', detrend=True):
+        """MonteCarloJob.csd on every device at the same time: (freq, dict of (runs, npairs, nfreq) and 'pairs')."""
+        got = [g for g in self._each_part(lambda j: j.csd(fs, pairs, names, nperseg, step, window, detrend)) if g is not None]
+        out = {k: np.concatenate([g[1][k] for g in got], axis=0) for k in got[0][1] if k != 'pairs'}
+        out['pairs'] = got[0][1]['pairs']
+        return got[0][0], out
+
     def buffer(self, name):
         raise ValueError('a JobSet spans several devices: take the buffer from one of its parts')
 

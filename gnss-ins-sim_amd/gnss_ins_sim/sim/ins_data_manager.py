@@ -68,6 +68,10 @@ _REGISTRY = [
      {'logx': True, 'logy': True}),
     ('psd_accel', 'power spectral density of accel', ['(m/s^2)^2/Hz'] * 3, None, ['PSD_ax', 'PSD_ay', 'PSD_az'],
      {'logx': True, 'logy': True}),
+    # Welch cross spectra (demo_algorithms.csd_analysis): one column per pair of axes
+    ('csd_freq', 'frequencies of the cross spectral densities', ['Hz'], None, ['csd_freq'], {'logx': True}),
+    ('coherence', 'magnitude-squared coherence between sensor axes', None, None, None, {'logx': True}),
+    ('csd_phase', 'phase of the cross spectral density between sensor axes', ['rad'], None, None, {'logx': True}),
 ]
 
 # which slice of the 9-component end-point record each error quantity occupies
