@@ -63,6 +63,11 @@ SOURCES = [
     # the aided lane with the standstill block, ZUPT and ZARU (ins_loose.hpp, STILL): the same flags, its own resource report
     # (tests/test_ins_loose_still_oracle.py reads it)
     ('ins_loose_still.hip', MC_FLAGS),
+    # the aided lane with the magnetometer block, the standstill block and (ins_loose_all16.hip) the 16th state together
+    # (ins_loose.hpp, Tail::ALL), twelve instantiations per file: the same flags, their own resource reports
+    # (tests/test_ins_loose_all_oracle.py reads them)
+    ('ins_loose_all.hip', MC_FLAGS),
+    ('ins_loose_all16.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
     # error_curve.hip's flags: the keys are formed from the shared error expression (traj_error.hpp, quantity_error) and their sums
@@ -113,6 +118,7 @@ def build(force=False, verbose=False, tag=None, defines=(), xflags=()):
     deps.append(os.path.join(REPO, 'include', 'ginsim_psd.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_lpsd.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_csd.h'))
+    deps.append(os.path.join(REPO, 'include', 'ginsim_loose_all.h'))
     deps.append(os.path.abspath(__file__))
     objs = []
     for src, extra in SOURCES:

@@ -15,6 +15,7 @@
 #include "ginsim_psd.h"
 #include "ginsim_lpsd.h"
 #include "ginsim_csd.h"
+#include "ginsim_loose_all.h"
 #include "allan.hpp"
 #include "oallan.hpp"
 #include "psd.hpp"
@@ -928,9 +929,11 @@ static int check_loose_still(const ginsim_mc_params* m, const ginsim_loose_still
     return GINSIM_OK;
 }
 
-// The family of a launch of the filter, in one order: checkpoints, magnetometer, scale-factor state, standstill, aiding, plain.
+// The family of a launch of the filter, in one order: the combined family (two or three of the magnetometer, scale-factor and
+// standstill blocks), checkpoints, magnetometer, scale-factor state, standstill, aiding, plain.
 static hipError_t launch_loose(const LooseLaunch& L) {
     if (L.b->n_list <= 0 && !L.name) return hipSuccess;
+    if (L.all) return launch_loose_all(L);
     if (L.cons) return launch_loose_cons(L);
     if (L.mag) return launch_loose_mag(L);
     if (L.scale) return launch_loose_scale(L);
@@ -943,7 +946,10 @@ static hipError_t launch_loose(const LooseLaunch& L) {
 // degenerate block (cons_m == 0, mag_every == 0, still_mask == 0) is then no block.  L.name != NULL (c is not read): the kernel's name.  Otherwise
 // the stamps, the visibility flags (padded to 8 bytes) and the checkpoint samples are copied next to each other into the context's
 // scratch and the family is launched.
-enum LooseFamily { LOOSE_PLAIN, LOOSE_CONS, LOOSE_MAG, LOOSE_SCALE, LOOSE_STILL };
+// LOOSE_ALL (ginsim_loose_all.h): any of the magnetometer, scale-factor and standstill blocks, each NULL or checked as its own family
+// checks it, in that order; with two or three left after the degenerate ones the launch is the combined family's, with one or none
+// the launch that block's own entry point makes.
+enum LooseFamily { LOOSE_PLAIN, LOOSE_CONS, LOOSE_MAG, LOOSE_SCALE, LOOSE_STILL, LOOSE_ALL };
 
 static int loose_entry(LooseFamily who, ginsim_ctx* c, LooseLaunch L) {
     int rc = check_loose_params(L.mc, L.b);
@@ -951,9 +957,15 @@ static int loose_entry(LooseFamily who, ginsim_ctx* c, LooseLaunch L) {
     rc = who == LOOSE_CONS ? check_loose_cons(L.mc, L.b, L.cons) : who == LOOSE_MAG ? check_loose_mag(L.mc, L.mag)
        : who == LOOSE_SCALE ? check_loose_scale(L.b, L.scale) : who == LOOSE_STILL ? check_loose_still(L.mc, L.still) : GINSIM_OK;
     if (rc) return rc;
+    if (who == LOOSE_ALL) {
+        if (L.mag && (rc = check_loose_mag(L.mc, L.mag))) return rc;
+        if (L.scale && (rc = check_loose_scale(L.b, L.scale))) return rc;
+        if (L.still && (rc = check_loose_still(L.mc, L.still))) return rc;
+    }
     if (L.cons && L.cons->cons_m == 0) L.cons = nullptr;
     if (L.mag && L.mag->mag_every == 0) L.mag = nullptr;
     if (L.still && L.still->still_mask == 0) L.still = nullptr;
+    L.all = who == LOOSE_ALL && (L.mag != nullptr) + (L.scale != nullptr) + (L.still != nullptr) >= 2;
     if (L.name) {
         L.name[0] = 0;
         (void)launch_loose(L);
@@ -1039,6 +1051,18 @@ int ginsim_loose_still_kernel_name(const ginsim_mc_params* mc, const ginsim_loos
 int ginsim_loose_still_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_still_params* still) {
     REQUIRE(c, "loose_still_run: NULL argument");
     return loose_entry(LOOSE_STILL, c, LooseLaunch{mc, p, nullptr, nullptr, nullptr, still});
+}
+
+int ginsim_loose_all_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
+                                 const ginsim_loose_scale_params* scale, const ginsim_loose_still_params* still, char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_all_kernel_name: bad arguments");
+    return loose_entry(LOOSE_ALL, nullptr, LooseLaunch{mc, p, nullptr, mag, scale, still, buf, cap});
+}
+
+int ginsim_loose_all_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
+                         const ginsim_loose_scale_params* scale, const ginsim_loose_still_params* still) {
+    REQUIRE(c, "loose_all_run: NULL argument");
+    return loose_entry(LOOSE_ALL, c, LooseLaunch{mc, p, nullptr, mag, scale, still});
 }
 
 int ginsim_aux_sensors(ginsim_ctx* c, const ginsim_aux_params* p) {

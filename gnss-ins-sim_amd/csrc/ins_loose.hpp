@@ -9,9 +9,12 @@
 // error; what it adds is behind `NS == kLooseStates + 1` and compiles to nothing for NS = 15.
 // For ins_loose_still.hip's loose_still_kernel: the standstill block (loose_still) behind the flag STILL; its equations are in that
 // file's header.
+// For ins_loose_all.hip's loose_all_kernel: the three blocks above in one lane, each gated at run time; what it adds is behind
+// `TL == Tail::ALL` (the layout of the kernel's fifth argument) and compiles to nothing for the six files above.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
+#include "ginsim_loose_all.h"
 #include "ins_math.hpp"
 #include "philox.hpp"
 #include "sensor_synth.hpp"
@@ -215,23 +218,43 @@ __device__ __forceinline__ loose_ptr loose_params() {
     return (loose_ptr)(p + sizeof(ginsim_mc_params));
 }
 
+// What the kernel's fifth argument is.  ONE: the block of one family (loose_mag_kernel, loose_scale_kernel, loose_still_kernel): every
+// accessor below reads at the tail's start, and a lane has at most one of the three blocks.  ALL: a ginsim_loose_all_params
+// (loose_all_kernel): the three blocks one after the other, each accessor at its member's offset.
+enum class Tail { ONE, ALL };
+constexpr size_t kLooseTailOffset = sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*);
+static_assert(offsetof(ginsim_loose_all_params, mag) == 0 && offsetof(ginsim_loose_all_params, scale) == sizeof(ginsim_loose_mag_params) &&
+              offsetof(ginsim_loose_all_params, still) == sizeof(ginsim_loose_mag_params) + sizeof(ginsim_loose_scale_params) &&
+              sizeof(ginsim_loose_all_params) == sizeof(ginsim_loose_mag_params) + sizeof(ginsim_loose_scale_params) + sizeof(ginsim_loose_still_params),
+              "ginsim_loose_all_params: the three blocks one after the other, no padding");
+static_assert(kLooseTailOffset + sizeof(ginsim_loose_all_params) <= 4096, "the kernarg segment of loose_all_kernel: HIP's limit of 4 KB");
+
 // The fifth argument of loose_mag_kernel, loose_scale_kernel and loose_still_kernel, the family's block T by value: it follows the
-// two parameter blocks and the two pointers (stamp, visible) in the kernarg segment
-template <class T>
+// two parameter blocks and the two pointers (stamp, visible) in the kernarg segment.  OFFSET: where T lies inside the argument
+template <class T, size_t OFFSET = 0>
 __device__ __forceinline__ const T __attribute__((address_space(4))) * loose_tail_params() {
-    static_assert(sizeof(ginsim_mc_params) % 8 == 0 && sizeof(ginsim_loose_params) % 8 == 0 && alignof(T) == 8,
+    static_assert(sizeof(ginsim_mc_params) % 8 == 0 && sizeof(ginsim_loose_params) % 8 == 0 && alignof(T) == 8 && OFFSET % 8 == 0,
                   "the kernarg offsets of loose_params() / loose_tail_params()");
     typedef const char __attribute__((address_space(4))) * bytes_ptr;
     bytes_ptr p = (bytes_ptr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
-    return (const T __attribute__((address_space(4))) *)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*));
+    return (const T __attribute__((address_space(4))) *)(p + sizeof(ginsim_mc_params) + sizeof(ginsim_loose_params) + 2 * sizeof(void*) + OFFSET);
 }
 typedef const ginsim_loose_mag_params __attribute__((address_space(4))) * loose_mag_ptr;
 typedef const ginsim_loose_scale_params __attribute__((address_space(4))) * loose_scale_ptr;
 typedef const ginsim_loose_still_params __attribute__((address_space(4))) * loose_still_ptr;
-__device__ __forceinline__ loose_mag_ptr loose_mag_params() { return loose_tail_params<ginsim_loose_mag_params>(); }
-__device__ __forceinline__ loose_scale_ptr loose_scale_params() { return loose_tail_params<ginsim_loose_scale_params>(); }
-__device__ __forceinline__ loose_still_ptr loose_still_params() { return loose_tail_params<ginsim_loose_still_params>(); }
+template <Tail TL = Tail::ONE>
+__device__ __forceinline__ loose_mag_ptr loose_mag_params() {
+    return loose_tail_params<ginsim_loose_mag_params, TL == Tail::ALL ? offsetof(ginsim_loose_all_params, mag) : 0>();
+}
+template <Tail TL = Tail::ONE>
+__device__ __forceinline__ loose_scale_ptr loose_scale_params() {
+    return loose_tail_params<ginsim_loose_scale_params, TL == Tail::ALL ? offsetof(ginsim_loose_all_params, scale) : 0>();
+}
+template <Tail TL = Tail::ONE>
+__device__ __forceinline__ loose_still_ptr loose_still_params() {
+    return loose_tail_params<ginsim_loose_still_params, TL == Tail::ALL ? offsetof(ginsim_loose_all_params, still) : 0>();
+}
 
 // the standstill signal of sample j (wave-uniform: a scalar load, as visible[kf])
 __device__ __forceinline__ bool still_flag(const int32_t* flags, int64_t j) {
@@ -241,7 +264,7 @@ __device__ __forceinline__ bool still_flag(const int32_t* flags, int64_t j) {
 
 // P <- Phi P Phi^T + Qd for the step from the attitude with body -> navigation matrix C and bias-corrected specific force f^n
 // (NS = 16: Phi is the identity on state 15, whose row takes part in every congruence as a column; P[15][15] += q_k)
-template <int NS>
+template <Tail TL = Tail::ONE, int NS>
 __device__ __forceinline__ void loose_propagate(CovT<NS>& P, const double (&C)[3][3], double fx, double fy, double fz, double dt) {
     const double A[3][3] = {{0.0, -fz * dt, fy * dt}, {fz * dt, 0.0, -fx * dt}, {-fy * dt, fx * dt, 0.0}};      // [f^n x] dt
     double Cp[3][3], Cm[3][3];
@@ -263,7 +286,7 @@ __device__ __forceinline__ void loose_propagate(CovT<NS>& P, const double (&C)[3
     P.template add_rotated<6>(C, qp); phase_fence();
 #pragma unroll
     for (int a = 0; a < 3; ++a) { P.at(9 + a, 9 + a) += lp->q_bg[a]; P.at(12 + a, 12 + a) += lp->q_ba[a]; }
-    if (NS == kLooseScaleStates) P.at(kLooseStates, kLooseStates) += loose_scale_params()->q_k;
+    if (NS == kLooseScaleStates) P.at(kLooseStates, kLooseStates) += loose_scale_params<TL>()->q_k;
 }
 
 // The feedback of the error state x into the mechanisation and the bias estimates (truth = estimate - error).  mlat, mlon:
@@ -376,9 +399,10 @@ __device__ __forceinline__ void loose_aid(CovT<NS>& P, Nav& s, Vec3& bg, Vec3& b
 
 // One magnetometer block (ins_loose_mag.hip's header): the three rows in ascending order from x = 0; then the feedback.
 // D = C^T, z and every row are formed from the state before the first row.  mag: the raw sample of this lane.
-template <int RF>
-__device__ __forceinline__ void loose_mag(Cov& P, Nav& s, Vec3& bg, Vec3& ba, const double (&mag)[3]) {
-    const loose_mag_ptr mp = loose_mag_params();
+// NS = 16: the rows have h[15] = 0 (update_row_psi over 16 states) and the block ends with kest -= x[15], as loose_aid.
+template <int RF, Tail TL = Tail::ONE, int NS>
+__device__ __forceinline__ void loose_mag(CovT<NS>& P, Nav& s, Vec3& bg, Vec3& ba, const double (&mag)[3], double& kest) {
+    const loose_mag_ptr mp = loose_mag_params<TL>();
     double C[3][3];
     body_to_nav(s.att, C);
     const double m[3] = {mp->mag_n[0], mp->mag_n[1], mp->mag_n[2]};
@@ -398,21 +422,23 @@ __device__ __forceinline__ void loose_mag(Cov& P, Nav& s, Vec3& bg, Vec3& ba, co
         mlat = e.rm + s.pos.z;
         mlon = (e.rn + s.pos.z) * e.cl;
     }
-    double x[kLooseStates];
+    double x[NS];
 #pragma unroll
-    for (int k = 0; k < kLooseStates; ++k) x[k] = 0.0;
+    for (int k = 0; k < NS; ++k) x[k] = 0.0;
     phase_fence();
-    P.update_row_psi(h[0], z[0], loose_mag_params()->r_mag[0], x); phase_fence();
-    P.update_row_psi(h[1], z[1], loose_mag_params()->r_mag[1], x); phase_fence();
-    P.update_row_psi(h[2], z[2], loose_mag_params()->r_mag[2], x); phase_fence();
+    P.update_row_psi(h[0], z[0], loose_mag_params<TL>()->r_mag[0], x); phase_fence();
+    P.update_row_psi(h[1], z[1], loose_mag_params<TL>()->r_mag[1], x); phase_fence();
+    P.update_row_psi(h[2], z[2], loose_mag_params<TL>()->r_mag[2], x); phase_fence();
     loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
+    if (NS == kLooseScaleStates) kest -= x[NS - 1];
 }
 
 // One standstill block (ins_loose_still.hip's header): the rows `mask` selects (bit 0: dv, states 3-5; bit 1: dbg, states 9-11) in
 // ascending state order from x = 0; then the feedback.  Every z is formed from the state before the first row.  gyro_prev: the raw
 // gyro sample the lane integrated last (j - 1), before the bias was subtracted.  mask is wave-uniform.
-template <int RF>
-__device__ __forceinline__ void loose_still(Cov& P, Nav& s, Vec3& bg, Vec3& ba, const Vec3& gyro_prev, int mask) {
+// NS = 16: every row observes one of the first 15 states (h[15] = 0) and the block ends with kest -= x[15], as loose_aid.
+template <int RF, Tail TL = Tail::ONE, int NS>
+__device__ __forceinline__ void loose_still(CovT<NS>& P, Nav& s, Vec3& bg, Vec3& ba, const Vec3& gyro_prev, int mask, double& kest) {
     // the rate the mechanisation assumes of a body at rest (nav_step with v = 0): earth rate in the body axes of the estimate
     Vec3 wr{0.0, 0.0, 0.0};
     if (RF == 0) {
@@ -426,21 +452,22 @@ __device__ __forceinline__ void loose_still(Cov& P, Nav& s, Vec3& bg, Vec3& ba, 
         mlat = e.rm + s.pos.z;
         mlon = (e.rn + s.pos.z) * e.cl;
     }
-    double x[kLooseStates];
+    double x[NS];
 #pragma unroll
-    for (int k = 0; k < kLooseStates; ++k) x[k] = 0.0;
+    for (int k = 0; k < NS; ++k) x[k] = 0.0;
     phase_fence();
     if (mask & 1) {
-        P.template update<3>(zv[0], loose_still_params()->r_zupt, x); phase_fence();
-        P.template update<4>(zv[1], loose_still_params()->r_zupt, x); phase_fence();
-        P.template update<5>(zv[2], loose_still_params()->r_zupt, x); phase_fence();
+        P.template update<3>(zv[0], loose_still_params<TL>()->r_zupt, x); phase_fence();
+        P.template update<4>(zv[1], loose_still_params<TL>()->r_zupt, x); phase_fence();
+        P.template update<5>(zv[2], loose_still_params<TL>()->r_zupt, x); phase_fence();
     }
     if (mask & 2) {
-        P.template update<9>(zg[0], loose_still_params()->r_zaru[0], x); phase_fence();
-        P.template update<10>(zg[1], loose_still_params()->r_zaru[1], x); phase_fence();
-        P.template update<11>(zg[2], loose_still_params()->r_zaru[2], x); phase_fence();
+        P.template update<9>(zg[0], loose_still_params<TL>()->r_zaru[0], x); phase_fence();
+        P.template update<10>(zg[1], loose_still_params<TL>()->r_zaru[1], x); phase_fence();
+        P.template update<11>(zg[2], loose_still_params<TL>()->r_zaru[2], x); phase_fence();
     }
     loose_feedback<RF>(s, bg, ba, x, mlat, mlon);
+    if (NS == kLooseScaleStates) kest -= x[NS - 1];
 }
 
 // ---- consistency checkpoints (ins_loose_cons.hip)
@@ -564,11 +591,18 @@ __device__ __forceinline__ void put3(double* base, int64_t plane, int64_t off, c
 // aiding block of the same sample, before the row is stored (the magnetometer block's place; with AID, without CONS and MAG, NS = 15);
 // its numbers are the kernel's fifth argument (loose_still_params).  The lane carries the raw gyro sample it integrated last.  With
 // STILL an aid_mask of 0 fires no aiding block at all.  STILL = false is the lane as it was.
-template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false, bool MAG = false, int NS = kLooseStates, bool STILL = false>
+// TL: the layout of the kernel's fifth argument (Tail).  ALL (loose_all_kernel, with AID, MAG and STILL, NS 15 or 16): the lane may have
+// the three blocks together, each gated at run time: a magnetometer block with mag_every == 0 and a standstill block with
+// still_mask == 0 never fire and none of their pointers is read.  TL = Tail::ONE is the lane as it was.
+template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false, bool MAG = false, int NS = kLooseStates, bool STILL = false,
+          Tail TL = Tail::ONE>
 __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const ginsim_loose_params& b, const int64_t* __restrict__ stamp,
                                            const int32_t* __restrict__ visible, uint32_t* ntab, const ConsArgs& cq = ConsArgs{}) {
-    static_assert(NS == kLooseStates || (NS == kLooseScaleStates && AID && !CONS && !MAG), "16 states: the aided lane only");
-    static_assert(!STILL || (AID && !CONS && !MAG && NS == kLooseStates), "the standstill block: the aided lane with 15 states only");
+    static_assert(NS == kLooseStates || (NS == kLooseScaleStates && AID && !CONS), "16 states: the aided lane without checkpoints only");
+    static_assert(!STILL || (AID && !CONS), "the standstill block: the aided lane without checkpoints only");
+    static_assert(!CONS || (!MAG && !STILL && NS == kLooseStates && TL == Tail::ONE), "checkpoints: no other block");
+    static_assert(TL == Tail::ALL || int(MAG) + int(STILL) + int(NS == kLooseScaleStates) <= 1,
+                  "one family's block as the fifth argument: the lane has at most one of the three");
     NormalTables tab{};
     if (!GIVEN) {
         tab = fill_normal_tables(ntab, threadIdx.x, blockDim.x);
@@ -584,7 +618,11 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
         return;
     }
     const int64_t r = b.run_list ? b.run_list[lane] : lane;
-    const int64_t n = a.n, runs = a.runs, plane = n * runs, m = b.m;
+    // Tail::ALL: n and runs through kernarg_params(), a load of their own.  Read from `a` they are part of one eight-dword scalar load
+    // of the block's head that lives across the loop; in loose_all_kernel<0, false, true, false, NS> the allocator gave that octet a
+    // spill slot before it chose to load it again instead, and the slot, never written, stayed as 36 bytes of scratch per lane
+    const int64_t n = TL == Tail::ALL ? kernarg_params()->n : a.n, runs = TL == Tail::ALL ? kernarg_params()->runs : a.runs;
+    const int64_t plane = n * runs, m = b.m;
     const double dt = 1.0 / a.fs;
 
     const uint64_t call = a.ini_first + (uint64_t)r;
@@ -610,7 +648,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
     }
     double kest = 0.0;      // the scale-factor estimate (NS = 16 only)
     if (NS == kLooseScaleStates) {
-        const loose_scale_ptr sp = loose_scale_params();
+        const loose_scale_ptr sp = loose_scale_params<TL>();
         kest = sp->scale0;
         P.at(kLooseStates, kLooseStates) = sp->p0_scale * sp->p0_scale;
     }
@@ -624,11 +662,13 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
     int64_t ja = every;
     // the next magnetometer block (wave-uniform), a counter of its own; a period of n or more never fires
     // (the period is read again from the kernarg segment at every block: one wave-uniform counter is all the loop holds)
-    int64_t jm = MAG ? (loose_mag_params()->mag_every < n ? loose_mag_params()->mag_every : n) : 0;
+    int64_t jm = MAG ? (loose_mag_params<TL>()->mag_every < n ? loose_mag_params<TL>()->mag_every : n) : 0;
+    if constexpr (MAG && TL == Tail::ALL) jm = jm < 1 ? n : jm;     // an absent block (mag_every == 0)
     int64_t kc = 0;         // the next checkpoint (wave-uniform)
     // the next sample at which a standstill block can fire (wave-uniform), a counter of its own as jm; and the raw gyro sample the
     // lane integrated last (STILL only: nothing reads it otherwise)
-    int64_t js = STILL ? (loose_still_params()->still_every < n ? loose_still_params()->still_every : n) : 0;
+    int64_t js = STILL ? (loose_still_params<TL>()->still_every < n ? loose_still_params<TL>()->still_every : n) : 0;
+    if constexpr (STILL && TL == Tail::ALL) js = loose_still_params<TL>()->still_mask == 0 ? n : js;        // an absent block
     Vec3 gyro_prev{0.0, 0.0, 0.0};
 
     for (int64_t j = 0; j < n; ++j) {
@@ -672,7 +712,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
         }
         if constexpr (MAG) {
             if (j == jm) {
-                const loose_mag_ptr mp = loose_mag_params();
+                const loose_mag_ptr mp = loose_mag_params<TL>();
                 jm += mp->mag_every < n ? mp->mag_every : n;
                 double mag[3];
                 if (GIVEN) {
@@ -687,17 +727,17 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
                     for (int c = 0; c < 3; ++c) mag[c] = mag_axis(mp->mag_si + 3 * c, v, mp->mag_std[c], z[c]);
                 }
                 phase_fence();
-                loose_mag<RF>(P, s, bg, ba, mag);
+                loose_mag<RF, TL>(P, s, bg, ba, mag, kest);
                 phase_fence();
             }
         }
         if constexpr (STILL) {
             if (j == js) {
-                const loose_still_ptr sp = loose_still_params();
+                const loose_still_ptr sp = loose_still_params<TL>();
                 js += sp->still_every < n ? sp->still_every : n;
                 if (still_flag(sp->still_flags, j)) {
                     phase_fence();
-                    loose_still<RF>(P, s, bg, ba, gyro_prev, sp->still_mask);
+                    loose_still<RF, TL>(P, s, bg, ba, gyro_prev, sp->still_mask, kest);
                     phase_fence();
                 }
             }
@@ -714,7 +754,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
         put3(lb->out_wb, plane, off, bg);
         put3(lb->out_ab, plane, off, ba);
         if (NS == kLooseScaleStates) {
-            double* const ks = loose_scale_params()->out_scale;
+            double* const ks = loose_scale_params<TL>()->out_scale;
             if (ks) ks[off] = kest;
         }
         if (PS) {
@@ -763,7 +803,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
         phase_fence();
         const bool resync = ((j + 1) & (kTrigResync - 1)) == 0;
         nav_step<RF, false>(s, gyr, acc, 0.0, dt, ka->earth_rot, resync, mk);
-        loose_propagate(P, C, fx, fy, fz, dt);
+        loose_propagate<TL>(P, C, fx, fy, fz, dt);
     }
     if (b.out_end) store_end(b.out_end, runs, r, s);
     if (RF == 0 && b.out_end_ned) store_end_ned(b.out_end_ned, runs, r, s);
@@ -777,7 +817,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
         for (int k = 0; k < kLooseStates; ++k) b.out_pdiag_end[k * runs + r] = P.get(k, k);
     }
     if (NS == kLooseScaleStates) {
-        const loose_scale_ptr sp = loose_scale_params();
+        const loose_scale_ptr sp = loose_scale_params<TL>();
         double* const se = sp->out_scale_end;
         double* const pc = sp->out_pcross_end;
         if (se) { se[r] = kest; se[runs + r] = P.get(kLooseStates, kLooseStates); }

@@ -45,6 +45,7 @@ struct LooseLaunch {
     const int32_t* visible;
     const int64_t* samples;
     hipStream_t stream;
+    bool all;                                   // two or three of mag, scale and still are left: the combined family (ins_loose_all.hip)
 };
 
 // ins_loose.hip, ins_loose_aided.hip (b->aid_mask != 0), ins_loose_cons.hip (cons), ins_loose_mag.hip (mag), ins_loose_scale.hip
@@ -55,6 +56,10 @@ hipError_t launch_loose_cons(const LooseLaunch& L);
 hipError_t launch_loose_mag(const LooseLaunch& L);
 hipError_t launch_loose_scale(const LooseLaunch& L);
 hipError_t launch_loose_still(const LooseLaunch& L);
+// ins_loose_all.hip (L.all; 15 states) and ins_loose_all16.hip (with L.scale; 16 states): the three blocks L has, an absent one all
+// zero, as the one ginsim_loose_all_params the kernel takes; b->aid_mask has bit 0 where L.scale is set
+hipError_t launch_loose_all(const LooseLaunch& L);
+hipError_t launch_loose_all16(const LooseLaunch& L);
 int loose_variant(const ginsim_mc_params& p);
 
 // aux_sensors.hip

@@ -12,7 +12,7 @@ The checkout's own stub (demo_algorithms.ins_loose) stays hosted.  fp64 only.
              mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None,
              odo_scale_state=False, odo_scale0=1.0, odo_scale_p0=0.02, odo_scale_q=0.0,
              zupt=False, zaru=False, still_every=1, still_speed=0.01, still_rate=2e-4, zupt_std=0.02, zaru_std=None,
-             standstill=None)
+             standstill=None, combined=False)
 
 ini_pos_vel_att: the initial states FreeIntegration takes ((9|10,) or (9|10, k)); None under a Sim: the motion definition's.
 imu: the IMU model the filter is tuned to (its accel_err, gyro_err, gps_err); None under a Sim: the Sim's own.  ref_frame is the
@@ -36,7 +36,7 @@ The odometer's scale factor as a state (csrc/ins_loose_scale.hip, DESIGN 4.11e; 
 odo_scale_state=True (needs odo=True) makes the scale factor the filter's 16th state instead of a number the user must know: the
 estimate starts at odo_scale0 with the 1 sigma odo_scale_p0, is learnt while GPS is visible and used through an outage;
 odo_scale_q [1/sqrt(s)] lets it wander (default 0: a constant).  ``output`` gains a trailing 'odo_scale', the estimate at every
-sample.  odo_scale= belongs to the filter without the state and is an error with it; not together with mag=True.
+sample.  odo_scale= belongs to the filter without the state and is an error with it; together with mag=True through combined=True (below).
 
 Standstill (csrc/ins_loose_still.hip; as NumPy in tests/ins_loose_ref.py): zupt=True tells the filter that
 the velocity is zero, zaru=True that the gyroscope reads its own bias (plus the earth rate the mechanisation assumes), at every
@@ -44,7 +44,13 @@ still_every-th IMU sample that the standstill signal marks.  The signal is stand
 own signal), or, under a Sim, the Sim's truth: |velocity| <= still_speed [m/s] and |angular rate| <= still_rate [rad/s].  ``run`` on
 a logged series has no truth and needs standstill=.  zupt_std [m/s], zaru_std [rad/s, per axis or one number]: the 1 sigma of the
 two pseudo-measurements (zaru_std default: the per-sample gyro noise of the filter's own model).  ``input`` and ``output`` are
-unchanged.  Not together with mag=True or odo_scale_state=True.
+unchanged.  Together with mag=True or odo_scale_state=True through combined=True (below).
+
+All of them together (csrc/ins_loose_all.hip; as NumPy in tests/ins_loose_all_ref.py): combined=True lifts the three
+"not together" rules above.  A plugin with two or three of mag=True, odo_scale_state=True and zupt / zaru then runs one kernel
+with every block, in the order GPS fix, odometer / constraints, magnetometer, standstill at a sample; ``input`` and ``output`` are
+the union of what the options add ('odo', 'mag'; 'odo_scale').  With one of them or none, combined=True changes nothing.
+odo_scale_state=True still needs odo=True; Sim.consistency_curve does not take such a plugin.
 """
 import numpy as np
 
@@ -61,16 +67,18 @@ class InsLoose(object):
                  odo=False, nhc=False, odo_every=1, odo_std=None, nhc_std=0.05, odo_scale=None,
                  mag=False, mag_every=1, mag_std=None, mag_si=None, mag_hi=None, geo_mag_n=None,
                  odo_scale_state=False, odo_scale0=1.0, odo_scale_p0=0.02, odo_scale_q=0.0,
-                 zupt=False, zaru=False, still_every=1, still_speed=0.01, still_rate=2e-4, zupt_std=0.02, zaru_std=None, standstill=None):
+                 zupt=False, zaru=False, still_every=1, still_speed=0.01, still_rate=2e-4, zupt_std=0.02, zaru_std=None, standstill=None,
+                 combined=False):
+        self.combined = bool(combined)
         self.odo, self.nhc, self.mag = bool(odo), bool(nhc), bool(mag)
         self.zupt, self.zaru = bool(zupt), bool(zaru)
         self.still = {'zupt': self.zupt, 'zaru': self.zaru, 'every': still_every, 'speed': still_speed, 'rate': still_rate,
                       'zupt_std': zupt_std, 'zaru_std': zaru_std}
         self.standstill = None if standstill is None else np.ascontiguousarray(np.asarray(standstill).reshape(-1) != 0, dtype=np.int32)
         if self.zupt or self.zaru:
-            if self.mag:
+            if self.mag and not self.combined:
                 raise ValueError('zupt / zaru together with mag=True is not built')
-            if odo_scale_state:
+            if odo_scale_state and not self.combined:
                 raise ValueError('zupt / zaru together with odo_scale_state=True is not built')
             from ginsim.ins_loose import still_model
             still_model({'q_psi': np.ones(3)}, 1.0, self.still)         # the errors of the numbers
@@ -81,7 +89,7 @@ class InsLoose(object):
             if odo_scale is not None:
                 raise ValueError('odo_scale= is the scale factor the filter WITHOUT the state assumes; with odo_scale_state=True the '
                                  'filter estimates it: give the starting value as odo_scale0=')
-            if self.mag:
+            if self.mag and not self.combined:
                 raise ValueError('odo_scale_state=True together with mag=True is not built')
             from ginsim.ins_loose import scale_model
             scale_model(None, {'scale0': odo_scale0, 'p0': odo_scale_p0, 'q': odo_scale_q}, 1.0)        # the errors of the three numbers
@@ -216,7 +224,8 @@ class InsLoose(object):
             job = InsLooseJob(ctx, fs, self.ref_frame, truth, self.imu.accel_err, self.imu.gyro_err, self.imu.gps_err, self.ini, 1,
                               ini_first=self.run_times, earth_rot=self.earth_rot, given=bufs, q_scale=self.q_scale, p0=self.p0,
                               keep_traj=True, odo_err=getattr(self.imu, 'odo_err', None), aid=self.aid(),
-                              **self._mag_arguments(), **self._scale_arguments(), **self._still_arguments()).run()
+                              **self._mag_arguments(), **self._scale_arguments(), **self._still_arguments(),
+                              **self.combined_arguments()).run()
             self.finish(*[job.series(k, [0])[0] for k in ('pos', 'vel', 'att', 'wb', 'ab') + (('odo_scale',) if self.odo_scale_state else ())])
         finally:
             if job is not None:
@@ -224,6 +233,11 @@ class InsLoose(object):
             for b in bufs.values():
                 b.free()
         self.run_times += 1
+
+    def combined_arguments(self):
+        """The keyword of ginsim.InsLooseJob that lets it hold several of the magnetometer block, the scale-factor state and the
+        standstill block; nothing for a plugin made without combined=True."""
+        return {'combined': True} if self.combined else {}
 
     def _mag_arguments(self):
         return {} if not self.mag else {'mag_err': getattr(self.imu, 'mag_err', None), 'geo_mag_n': self.geo_mag_n, 'mag': self.mag_options()}

@@ -12,6 +12,8 @@ a 16th state that the filter estimates (csrc/ins_loose_scale.hip, scale_model; r
 With still=... the filter also uses what it may assume while the vehicle stands still, the zero-velocity and the zero-angular-rate
 update (csrc/ins_loose_still.hip, still_model, standstill_flags; restated by tests/ins_loose_ref.py).
 What one launch does not combine is stated once (refuse_combinations); the job records the family it launches once (FAMILIES).
+With combined=True the magnetometer block, the scale-factor state and the standstill block go together in one launch
+(csrc/ins_loose_all.hip, COMBINED; restated by tests/ins_loose_all_ref.py, which composes the two restatements above).
 """
 import ctypes as C
 
@@ -264,22 +266,31 @@ def standstill_flags(truth, speed=0.01, rate=2e-4):
 
 # the family blocks a job can hold, in the order the C glue picks among them: (the job's attribute, the entry points' suffix)
 FAMILIES = (('cons', '_cons'), ('magp', '_mag'), ('scalep', '_scale'), ('stillp', '_still'))
+# the combined family, looked at before FAMILIES: a job made with combined=True that holds two or three of COMBINED_BLOCKS launches
+# through the entry points with this suffix, which take the three blocks (None: NULL) and not one
+COMBINED = ('allp', '_all')
+COMBINED_BLOCKS = ('magp', 'scalep', 'stillp')
 
 
-def refuse_combinations(scale, keep_scale, odo, mag, cons, proc, still=False):
+def refuse_combinations(scale, keep_scale, odo, mag, cons, proc, still=False, combined=False):
     """The options of InsLooseJob that one launch does not combine, stated once: (applies, message), the first row that applies is
     raised.  Arguments: is the option given (scale: odo_scale_state, odo: aid['odo'], cons: cons_samples, proc: proc_first,
-    still: still)."""
+    still: still).  combined: the job was made with combined=True: the three rows that name two of the magnetometer block, the
+    scale-factor state and the standstill block do not apply; what the combined family refuses comes first and says so."""
+    pair = not combined
+    more = sum(map(bool, (scale, mag, still))) >= 2
     rows = (
+        (combined and more and cons, 'combined: consistency checkpoints (cons_samples=...) of the combined family are not built'),
+        (combined and more and scale and not odo,"combined: a scale-factor state without the odometer (aid['odo']) is refused by the combined family too"),
         (keep_scale and not scale, 'keep_scale: the scale-factor series exists with odo_scale_state=... only'),
-        (scale and mag, 'odo_scale_state: the scale-factor state together with the magnetometer block (mag=...) is not built'),
+        (pair and scale and mag, 'odo_scale_state: the scale-factor state together with the magnetometer block (mag=...) is not built'),
         (scale and cons, 'odo_scale_state: consistency checkpoints (cons_samples=...) of the filter with the scale-factor state are not built'),
         (scale and not odo, "odo_scale_state: a scale-factor state without the odometer (aid['odo']) is refused"),
         (mag and cons, 'cons_samples: consistency checkpoints of the magnetometer-aided filter are not built (mag=...)'),
         (cons and proc, 'cons_samples: online process statistics (proc_first) and checkpoints in one launch are refused'),
-        (still and mag, 'still: the standstill block together with the magnetometer block (mag=...) is not built'),
+        (pair and still and mag, 'still: the standstill block together with the magnetometer block (mag=...) is not built'),
         (still and cons, 'still: consistency checkpoints (cons_samples=...) of the filter with the standstill block are not built'),
-        (still and scale, 'still: the standstill block together with the scale-factor state (odo_scale_state=...) is not built'),
+        (pair and still and scale, 'still: the standstill block together with the scale-factor state (odo_scale_state=...) is not built'),
     )
     for applies, text in rows:
         if applies:
@@ -310,12 +321,16 @@ class InsLooseJob(BatchJob):
     the same seed and run ids.  The given form reads given['mag'] [3][n][runs].  Not together with cons_samples.
     odo_scale_state: None, or the options of scale_model() ({} takes every default): the odometer's scale factor is the filter's
     16th state (csrc/ins_loose_scale.hip).  Needs aid['odo']; aid['scale'] is then not read (the filter starts from 'scale0'), and
-    r_odo defaults to (odo_err['stdv'] / scale0)^2.  Not together with mag, cons_samples or fp32.  keep_scale: materialise the
+    r_odo defaults to (odo_err['stdv'] / scale0)^2.  Together with mag and still through combined=True; not with cons_samples or fp32.  keep_scale: materialise the
     k_est series ([n][runs]; series('odo_scale', ...)).
     still: None, or the options of still_model() ({} takes every default): the zero-velocity and the zero-angular-rate update at the
     samples the standstill signal marks (csrc/ins_loose_still.hip).  The signal is still['flags'] (n,), or standstill_flags() of the
     truth with still['speed'] and still['rate']; it is the job's own device array in the generated and in the given form (nothing
-    is read from `given`).  Not together with mag, cons_samples or odo_scale_state.
+    is read from `given`).  Together with mag and odo_scale_state through combined=True; not with cons_samples.
+    combined: True lifts the three "not together" rules among mag, odo_scale_state and still: a job that holds two or three of them
+    launches the combined family (csrc/ins_loose_all.hip), one kernel that runs every block in the order fix, odometer /
+    constraints, magnetometer, standstill.  With one of them or none the job launches exactly what it launches without the keyword.
+    Still refused: cons_samples, fp32 (the C glue's check), odo_scale_state without aid['odo'].
     """
 
     algos = ('loose',)
@@ -323,8 +338,10 @@ class InsLooseJob(BatchJob):
     def __init__(self, ctx, fs, ref_frame, truth, accel_err, gyro_err, gps_err, ini, runs, seed=0, run_offset=0, ini_first=0,
                  earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
                  end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None,
-                 cons_samples=None, mag_err=None, geo_mag_n=None, mag=None, odo_scale_state=None, keep_scale=False, still=None):
+                 cons_samples=None, mag_err=None, geo_mag_n=None, mag=None, odo_scale_state=None, keep_scale=False, still=None,
+                 combined=False):
         self.ctx, self._bufs = ctx, {}
+        self.combined = bool(combined)
         self.keep_traj, self.keep_scale = bool(keep_traj), bool(keep_scale)
         self.proc_first, self.proc_ned, self.end_ned = proc_first, bool(proc_ned), bool(end_ned)
         table, ref_gps = self._sizes_and_stamps(fs, ref_frame, truth, ini, runs, seed, run_offset, ini_first, earth_rot, end_pos_ned,
@@ -333,7 +350,8 @@ class InsLooseJob(BatchJob):
         self.scale = scale_model(odo_err, odo_scale_state, fs)
         self.still = still_model(self.model, fs, still)
         refuse_combinations(scale=self.scale is not None, keep_scale=self.keep_scale, odo=bool(aid and aid.get('odo')),
-                            mag=mag is not None, cons=cons_samples is not None, proc=proc_first is not None, still=self.still is not None)
+                            mag=mag is not None, cons=cons_samples is not None, proc=proc_first is not None, still=self.still is not None,
+                            combined=self.combined)
         for k in ('r_diag', 'p0', 'q_v', 'q_psi', 'q_bg', 'q_ba', 'decay_g', 'decay_a'):     # the filter numbers
             getattr(self.params, k)[:] = [float(x) for x in np.asarray(self.model[k], dtype=np.float64).reshape(-1)]
         self._family_blocks(ref_frame, odo_err, aid, mag_err, geo_mag_n, mag)
@@ -343,6 +361,11 @@ class InsLooseJob(BatchJob):
         self._checkpoints(cons_samples)
         # the family the job launches, once: the first block of FAMILIES that the job has (the order of the C glue), else the plain entry
         self._family = next(((suffix, getattr(self, attr)) for attr, suffix in FAMILIES if getattr(self, attr) is not None), ('', None))
+        # the combined family first: two or three of its blocks in a job that opted in
+        held = tuple(getattr(self, attr) for attr in COMBINED_BLOCKS)
+        self.allp = held if self.combined and sum(b is not None for b in held) >= 2 else None
+        if self.allp is not None:
+            self._family = (COMBINED[1], self.allp)
 
     # ------------------------------------------------------------------ the constructor's steps
     def _sizes_and_stamps(self, fs, ref_frame, truth, ini, runs, seed, run_offset, ini_first, earth_rot, end_pos_ned, gps_stamps):
@@ -518,10 +541,11 @@ class InsLooseJob(BatchJob):
 
     # ------------------------------------------------------------------ launches
     def _entry(self, what, *head):
-        """The family's entry point ginsim_loose[_cons | _mag | _scale | _still]_<what> and its arguments: head, the two base blocks, the
-        family's block."""
+        """The family's entry point ginsim_loose[_cons | _mag | _scale | _still | _all]_<what> and its arguments: head, the two base
+        blocks, the family's block (the combined family's three, None for one the job does not hold)."""
         suffix, block = self._family
-        args = head + (C.byref(self.mc), C.byref(self.params)) + (() if block is None else (C.byref(block),))
+        blocks = () if block is None else block if isinstance(block, tuple) else (block,)
+        args = head + (C.byref(self.mc), C.byref(self.params)) + tuple(None if b is None else C.byref(b) for b in blocks)
         return getattr(lib, 'ginsim_loose%s_%s' % (suffix, what)), args
 
     def kernel_name(self):

@@ -519,7 +519,8 @@ class _Jobs(object):
                            seed=self.seed, run_offset=self.first + off, ini_first=kw.pop('ini_first', algo.run_times + self.first + off),
                            earth_rot=algo.earth_rot, keep_traj=keep, placed=sim.placed,
                            model=filter_model(sim.fs[0], tuned.accel_err, tuned.gyro_err, tuned.gps_err, algo.q_scale, algo.p0),
-                           **self._aiding(algo), **self._mag_aiding(algo, truth), **self._scale_state(algo, keep), **self._standstill(algo), **self.vib, **kw)
+                           **self._aiding(algo), **self._mag_aiding(algo, truth), **self._scale_state(algo, keep), **self._standstill(algo),
+                           **(algo.combined_arguments() if hasattr(algo, 'combined_arguments') else {}), **self.vib, **kw)
 
     def _aiding(self, algo):
         """The aiding arguments of an InsLooseJob: none for a plugin without aiding.  The odometer SAMPLES are the Sim's
@@ -1481,6 +1482,10 @@ class Sim(object):
             samples = np.arange(n, dtype=np.int64)
         out = {'time': t[samples], 'states': ['%s_%s' % (b, a) for b in ('dr', 'dv', 'psi', 'dbg', 'dba') for a in 'xyz']}
         for a, (_, job, _) in zip(names, getattr(self, 'loose_jobs', ())):
+            if getattr(job, 'allp', None) is not None:
+                raise NotImplementedError('consistency_curve: %s runs several of the magnetometer block, the scale-factor state and the '
+                                          'standstill block in one launch (InsLoose(combined=True)), and the consistency checkpoints of '
+                                          'that filter are not built' % a)
             if getattr(job, 'mag', None) is not None:
                 raise NotImplementedError('consistency_curve: %s is aided by the magnetometer (InsLoose(mag=True)), and the consistency '
                                           'checkpoints of that filter are not built' % a)

@@ -1,0 +1,113 @@
+"""Shared inputs of the tests of InsLoose with all its aids in one launch (tests/test_ins_loose_all_oracle.py on the CPU,
+tests/test_gpu_ins_loose_all.py on the device): the stops profiles' truth with the magnetometer's, every block's numbers, the draw of
+the consistency test and the ratios it measures and records."""
+import functools
+
+import numpy as np
+
+import ins_loose_aided_cases as ac
+import ins_loose_cases as cs
+import ins_loose_mag_cases as mc
+import ins_loose_scale_cases as kc
+import ins_loose_still_cases as sc
+
+READS = 0.985                                       # what the odometer of the device dumps reads; the filter starts from 1.0
+ODO_ERR = {'scale': READS, 'stdv': kc.ODO_STDV}
+MASK = 7                                            # odometer and both constraints next to the other blocks
+
+# Measured by tests/test_ins_loose_all_oracle.py::test_restatement_consistency: 1024 runs drawn from the filter's own model with
+# np.random.default_rng(ins_loose_cases.CONSISTENCY_SEED) (accel, gyro, GPS as the unaided case draws them, then the true scales
+# ~ N(1, 0.02^2), the odometer's noise and the magnetometer as ref_mag + 0.01 N), the stops profile at 20 Hz with 2 Hz GPS,
+# 'mid-accuracy' IMU, ref_frame 1; the odometer row alone (mask 1, as ins_loose_scale_cases: the constraint rows are pessimistic by
+# construction), the scale-factor state (scale0 1, p0 0.02, q 0), the magnetometer (MAG_ERR, GEO) and both standstill rows, every
+# block at every sample.  RMS error over sqrt(mean P_kk) of the 16 states, the 16th k_est - k, at the LAST SAMPLE OF THE FIRST STOP
+# ('stop': the profile truncated there) and at the profile's end ('end').  The cap is DESIGN 4.11g's: every ratio below CAP.
+CAP = 1.4
+CONSISTENCY_MASK = 1
+CONSISTENCY_RATIOS = {
+    'stop': (0.618, 0.667, 0.513, 0.706, 0.539, 0.695, 0.855, 0.977, 0.846, 1.028, 1.025, 1.000, 0.980, 0.935, 0.951, 0.974),
+    'end': (0.594, 0.871, 0.536, 0.904, 0.960, 0.871, 0.982, 1.028, 1.002, 1.055, 1.044, 1.077, 1.016, 0.953, 1.019, 0.947),
+}
+# at the end of the stop: RMS of k_est - k 0.00178, sqrt(mean P[15][15]) 0.00183; at the profile's end 0.00095 and 0.00101 (from 0.02).
+# The largest ratio is dbg_z at the profile's end, 1.077 (the standstill filter alone: 1.061, ins_loose_still_cases): the known
+# correlation of the ZARU sample's noise with q_psi, on the optimistic side and small.  The low ratios are dr and dv, as for the
+# standstill rows alone (r_zupt is a cautious pseudo-noise).  With the constraint rows too (mask 7) the end ratios are 0.572, 0.651,
+# 0.402, 0.900, 0.677, 0.792, 0.923, 1.027, 0.940, 1.054, 1.045, 1.069, 1.016, 0.953, 1.015, 0.934: lower in dr and dv, as mask 7 always is.
+
+
+@functools.lru_cache(maxsize=None)
+def stops_truth(fs, ref_frame, fs_gps, n=None, profile=sc.STOPS_CSV, geo=mc.GEO):
+    """(ini_pva, truth with 'ref_odo' and 'ref_mag', gps stamps) of a stops profile, cut to the first n samples."""
+    return mc.outage_truth(fs, ref_frame, fs_gps, n, profile, geo)
+
+
+def blocks(model, fs, rf, mask=MASK, mag=None, scale=False, smask=0, every=1, geo=mc.GEO, flags=None, scale0=kc.SCALE0, p0=kc.P0_SCALE):
+    """The keyword arguments of ins_loose_all_ref.run that describe the blocks (without the per-run series odo and mag): aid, and
+    mag_model (mag: the magnetometer's error dict), scale (scale: True), still and flags (smask: the standstill rows) where given.
+    every: the period of every block."""
+    kw = {'aid': (kc.aid(mask, every, scale0) if scale else ac.aid(mask, every, odo_err=ODO_ERR)) if mask else None}
+    if mag is not None:
+        kw['mag_model'] = mc.model(mag, rf, every, geo)
+    if scale:
+        kw['scale'] = kc.scale(scale0, p0)
+    if smask:
+        kw['still'], kw['flags'] = sc.model(model, fs, smask, every), flags
+    return kw
+
+
+def job_kw(mask=MASK, mag=None, scale=False, smask=0, every=1, geo=mc.GEO, flags=None, scale0=kc.SCALE0, p0=kc.P0_SCALE, keep=True):
+    """The same case as the keywords of an InsLooseJob (over odo_err=ODO_ERR)."""
+    kw = {'odo_err': ODO_ERR}
+    if mask:
+        kw['aid'] = ac.aid_options(mask, every)
+    if mag is not None:
+        kw = mc.mag_kw(mag, geo, every, **kw)
+    if scale:
+        kw.update(odo_scale_state={'scale0': scale0, 'p0': p0}, keep_scale=keep)
+    if smask:
+        kw['still'] = sc.options(smask, every, flags=flags)
+    return kw
+
+
+def deviation(a, b):
+    """ins_loose_scale_cases.deviation where the case has the 16th state, ins_loose_cases.deviation where not."""
+    return kc.deviation(a, b) if 'scale_end' in b else cs.deviation(a, b)
+
+
+def consistency_draw(rf, fs, runs, n=None):
+    """One draw for every subset of the blocks: accel, gyro, fixes, the true scales, the odometer's noise, the magnetometer, in that
+    order from np.random.default_rng(ins_loose_cases.CONSISTENCY_SEED); 2 Hz GPS, 'mid-accuracy' IMU, the stops profile cut to n."""
+    import ins_loose_ref as ref
+    from ginsim.ins_loose import filter_model
+    ini, truth, stamps = stops_truth(fs, rf, cs.CONSISTENCY_FS_GPS, n)
+    acc_e, gyr_e = cs.imu_errors()
+    c = {'rf': rf, 'fs': fs, 'ini': ini, 'truth': truth, 'stamps': stamps, 'acc_e': acc_e, 'gyr_e': gyr_e, 'runs': runs,
+         'model': filter_model(fs, acc_e, gyr_e, cs.GPS_ERR), 'flags': sc.flags_of(truth)}
+    rng = np.random.default_rng(cs.CONSISTENCY_SEED)
+    c['accel'], c['gyro'], c['tba'], c['tbg'] = ref.sample_sensors(rng, fs, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, runs)
+    c['gps'] = cs.sample_gps(rng, truth, rf, runs)
+    c['scales'] = 1.0 + kc.P0_SCALE * rng.standard_normal(runs)
+    c['odo'] = c['scales'][:, None] * np.asarray(truth['ref_odo'])[None] + kc.ODO_STDV * rng.standard_normal((runs, truth['ref_odo'].shape[0]))
+    c['mag'] = ref.sample_mag(rng, truth['ref_mag'], mc.MAG_ERR, runs)
+    return c
+
+
+def restate(c, mask, mag, scale, smask, n=None, keep_pdiag=False):
+    """ins_loose_all_ref.run on (the first n samples of) a consistency_draw with the named blocks."""
+    import ins_loose_all_ref as aref
+    n = c['truth']['ref_accel'].shape[0] if n is None else n
+    m = int(np.searchsorted(c['stamps'], n))
+    kw = blocks(c['model'], c['fs'], c['rf'], mask, mc.MAG_ERR if mag else None, scale, smask, flags=c['flags'][:n])
+    if kw['aid'] is not None and not scale:            # the 15-state filter is told the mean of the true scales
+        kw['aid'] = ac.aid(mask, 1, odo_err={'scale': 1.0, 'stdv': kc.ODO_STDV})
+    return aref.run(c['rf'], c['fs'], c['gyro'][:, :n], c['accel'][:, :n], c['ini'], c['model'], c['gps'][:, :m], c['stamps'][:m],
+                    c['truth']['gps_visibility'][:m], odo=c['odo'][:, :n], mag=c['mag'][:, :n] if mag else None, keep_pdiag=keep_pdiag, **kw)
+
+
+def ratios16(c, o, j):
+    """RMS error over sqrt(mean P_kk) of the 16 states at sample j = the last of a result o whose run ended there."""
+    e = sc.error_at(c, o, j)
+    se = np.asarray(o['scale_end'], dtype=np.float64)
+    e = np.concatenate([e, (se[:, 0] - c['scales'])[:, None]], axis=1)
+    p = np.concatenate([np.asarray(o['pdiag_end'], dtype=np.float64), se[:, 1:2]], axis=1)
+    return np.sqrt(np.mean(e * e, axis=0)) / np.sqrt(np.mean(p, axis=0))

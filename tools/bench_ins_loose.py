@@ -8,6 +8,7 @@
     python tools/bench_ins_loose.py --mag [--reps 20] [--out profiles/ins_loose_mag_timing.json]
     python tools/bench_ins_loose.py --odo-scale [--reps 20] [--out profiles/ins_loose_scale_timing.json]
     python tools/bench_ins_loose.py --still [--reps 20] [--out profiles/ins_loose_still_timing.json]
+    python tools/bench_ins_loose.py --combined [--reps 20] [--out profiles/ins_loose_all_timing.json]
 
 Workload: 65 536 runs x the 1000 samples of the 90-degree turn at 100 Hz (BASELINE config C2's shape) with GPS at 10 Hz, ref_frame 1,
 'mid-accuracy' IMU; statistics only (nothing but the per-run end records is written) and with everything kept (trajectory, wb, ab).
@@ -43,7 +44,13 @@ warm-up each.  The price is the 16-state time over the 15-state time of the same
 --still: the standstill block of csrc/ins_loose_still.hip, statistics only, on two profiles at 100 Hz with GPS at 10 Hz:
 the 90-degree turn (no sample is flagged: the price of the compiled-in test alone) and the stops profile
 (tests/golden/ins_loose/motion_def_stops.csv, 5500 samples).  On each: the unaided launch and the launch with both rows; on the stops
-profile also each row alone; launched in turn --reps times after one warm-up each."""
+profile also each row alone; launched in turn --reps times after one warm-up each.
+
+--combined: every aid in one launch (csrc/ins_loose_all.hip), statistics only, on the same two profiles: the unaided
+launch, each single family (aid_mask 7; the magnetometer; aid_mask 7 with the scale-factor state; both standstill rows) and the
+combined launch with 15 states (aid_mask 7, magnetometer, standstill) and with 16 (and the scale-factor state), every block at every
+sample, launched in turn --reps times after one warm-up each.  Printed beside the ratios over the unaided launch: the combined
+launch's excess over the unaided launch against the sum of the excesses of the single families it replaces."""
 import argparse
 import json
 import os
@@ -303,6 +310,63 @@ def time_still(runs, reps):
     return out
 
 
+def time_combined(runs, reps):
+    """{profile: {leg: {'kernel', 'ms_median', 'ms_min', 'ms_max', 'ms_all', 'over_unaided'}}} of the unaided launch, the four single
+    families and the two combined launches on the 90-degree turn and on the stops profile, interleaved per profile; per combined leg
+    also 'excess_over_sum': (its time - unaided) over the sum of (time - unaided) of the single families whose blocks it holds."""
+    import numpy as np
+    import ginsim
+    from ginsim import workloads
+    fs, fs_gps, rf, geo = 100.0, 10.0, 1, (30.0, -3.0, 40.0)
+    acc, gyr = workloads.imu_grade('mid-accuracy')
+    gps_err = {'stdp': np.array([5.0, 5.0, 7.0]), 'stdv': np.array([0.05, 0.05, 0.05])}
+    odo_err = {'scale': 0.99, 'stdv': 0.1}
+    mag_err = {'si': np.eye(3), 'hi': np.zeros(3), 'std': np.array([0.01, 0.01, 0.01])}
+    ctx = ginsim.Context(0)
+    out = {'device': ctx.name(), 'runs': runs, 'library': os.path.basename(ginsim.LIB_PATH)}
+
+    def truth_of(path):
+        ini, seg = workloads.parse_motion(path)
+        raw = ginsim.pathgen(ini, seg, fs, fs_gps, workloads.HIGH_MOBILITY, rf, gps=True, geo_mag_n=geo)
+        n = raw['imu'].shape[0]
+        return ini, {'ref_accel': np.ascontiguousarray(raw['imu'][:, 1:4]), 'ref_gyro': np.ascontiguousarray(raw['imu'][:, 4:7]),
+                     'ref_pos': np.ascontiguousarray(raw['nav'][:, 1:4]), 'ref_vel': np.ascontiguousarray(raw['nav'][:, 4:7]),
+                     'ref_att': np.ascontiguousarray(raw['nav'][:, 7:10]), 'ref_gps': np.ascontiguousarray(raw['gps'][:, 1:7]),
+                     'gps_time': raw['gps'][:, 0] / fs, 'gps_visibility': raw['gps'][:, 7].copy(),
+                     'ref_odo': np.ascontiguousarray(raw['odo'][:n, 2]), 'ref_mag': np.ascontiguousarray(raw['mag'][:n, 1:4])}
+    aid = {'odo_err': odo_err, 'aid': {'odo': True, 'nhc': True, 'every': 1}}
+    mag = {'mag_err': mag_err, 'geo_mag_n': geo, 'mag': {'every': 1}}
+    legs = [('unaided', {}), ('aided_mask7', aid), ('mag', mag), ('scale_mask7', dict(aid, odo_scale_state={})), ('still', {'still': {}}),
+            ('combined_15', dict(aid, still={}, combined=True, **mag)), ('combined_16', dict(aid, odo_scale_state={}, still={}, combined=True, **mag))]
+    replaced = {'combined_15': ('aided_mask7', 'mag', 'still'), 'combined_16': ('scale_mask7', 'mag', 'still')}
+    for profile, path in (('turn_90deg', workloads.profile_path('turn_90deg')),
+                          ('stops', os.path.join(REPO, 'tests', 'golden', 'ins_loose', 'motion_def_stops.csv'))):
+        ini, truth = truth_of(path)
+        res = out[profile] = {'samples': int(truth['ref_accel'].shape[0]), 'fixes': int(truth['ref_gps'].shape[0])}
+        jobs = [(label, ginsim.InsLooseJob(ctx, fs, rf, truth, acc, gyr, gps_err, ini, runs, seed=1, keep_traj=False, **kw)) for label, kw in legs]
+        res['flagged_samples'] = int(np.count_nonzero(dict(jobs)['still'].still_flags))
+        ms = {label: [] for label, _ in jobs}
+        for _, job in jobs:
+            job.run()                                       # warm-up: code object, LDS attribute
+        for _ in range(reps):
+            for label, job in jobs:
+                ctx.timer_begin()
+                job.launch()
+                ms[label].append(ctx.timer_end())
+        for label, job in jobs:
+            t = ms[label]
+            res[label] = {'kernel': job.kernel_name(), 'ms_median': float(np.median(t)), 'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)),
+                          'ms_all': [float(x) for x in t]}
+            job.release()
+        base = res['unaided']['ms_median']
+        for label, _ in jobs[1:]:
+            res[label]['over_unaided'] = res[label]['ms_median'] / base
+        for label, singles in replaced.items():
+            res[label]['excess_over_sum'] = (res[label]['ms_median'] - base) / sum(res[k]['ms_median'] - base for k in singles)
+    ctx.close()
+    return out
+
+
 def time_cons(runs, reps):
     """{leg: {'kernel', 'checkpoints', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the unaided launch without checkpoints, with one
     every 100 samples and with one at every sample, interleaved; and what one checkpoint costs, in steps."""
@@ -349,6 +413,7 @@ def main():
     ap.add_argument('--mag', action='store_true', help='the magnetometer leg: unaided, mag_every 1 and 10, aid_mask 7 with the magnetometer')
     ap.add_argument('--odo-scale', action='store_true', help='the scale-factor leg: aid_mask 7 with 15 and with 16 states, aid_every 1 and 10')
     ap.add_argument('--still', action='store_true', help='the standstill leg: unaided and ZUPT / ZARU on the 90-degree turn and on the stops profile')
+    ap.add_argument('--combined', action='store_true', help='every aid in one launch, with 15 and with 16 states, beside the unaided launch and each single family, on the 90-degree turn and on the stops profile')
     ap.add_argument('--runs', type=int, default=65536)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ops', type=int, default=0, help='fp64 instructions per step, instead of the count from the ISA')
@@ -358,8 +423,8 @@ def main():
         for k, (n, f, span) in sorted(isa_counts().items()):
             print('%s: %d fp64 VALU instructions (%d fused multiply-adds) in a time loop of %d lines' % (k, n, f, span))
         return
-    if a.aided or a.cons or a.mag or a.odo_scale or a.still:
-        res = time_still(a.runs, a.reps) if a.still else time_scale(a.runs, a.reps) if a.odo_scale else time_mag(a.runs, a.reps) if a.mag else time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
+    if a.aided or a.cons or a.mag or a.odo_scale or a.still or a.combined:
+        res = time_combined(a.runs, a.reps) if a.combined else time_still(a.runs, a.reps) if a.still else time_scale(a.runs, a.reps) if a.odo_scale else time_mag(a.runs, a.reps) if a.mag else time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
         print(json.dumps(res))
         if a.out:
             with open(a.out, 'w') as f:
