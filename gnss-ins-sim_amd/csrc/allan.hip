@@ -448,7 +448,8 @@ allan_pair_kernel(const double* __restrict__ in, double* __restrict__ out, doubl
     double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (c_begin < c_end && c_begin <= c_dma) dma_request_half(x + c_begin * kChunk, stage[0], wave, lane);
     if (c_begin + 1 < c_end && c_begin + 1 <= c_dma) dma_request_half(x + (c_begin + 1) * kChunk, stage[1], wave, lane);
-    int stores1 = 0, stores2 = 0;   // store instructions this wavefront is KNOWN to have issued in the last two iterations
+    // store instructions this wavefront is KNOWN to have issued in the last two iterations: a lower bound (too many waits too little)
+    int stores1 = 0, stores2 = 0;
 #pragma unroll 1
     for (int64_t c = c_begin; c < c_end; ++c) {
         double* w = stage[(c - c_begin) & 1];
@@ -479,7 +480,11 @@ allan_pair_kernel(const double* __restrict__ in, double* __restrict__ out, doubl
             compute_a<false, true>(e, lane, c, lv, shift, out_series, acc, piece);
             asm volatile("" ::: "memory");
             stores2 = stores1;
-            stores1 = out_series ? 4 : 0;
+            // the four sums of 10 are consecutive doubles, which the compiler writes as TWO 16-byte stores: the count must be the
+            // fewest instructions they can become, never the four of the source.  Counted as four, K was 18 where 14 operations
+            // were younger than the request, and the wait let the last four pieces of chunk c land after the barrier: a workgroup
+            // with two or more chunks could read a stage that still held the chunk before (seen as one wrong series in 1024)
+            stores1 = out_series ? 2 : 0;
         } else {
             double e[72];
             read_b_single(w, lane, e);

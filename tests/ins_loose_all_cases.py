@@ -1,6 +1,7 @@
 """Shared inputs of the tests of InsLoose with all its aids in one launch (tests/test_ins_loose_all_oracle.py on the CPU,
 tests/test_gpu_ins_loose_all.py on the device): the stops profiles' truth with the magnetometer's, every block's numbers, the draw of
-the consistency test and the ratios it measures and records."""
+the consistency test and the ratios it measures and records; and the schedule case of tests/test_ins_loose_all_schedule_oracle.py and
+tests/test_gpu_ins_loose_all_schedule.py: a period per block, the count of what fires on every sample, its standstill signal."""
 import functools
 
 import numpy as np
@@ -35,38 +36,96 @@ CONSISTENCY_RATIOS = {
 # 0.402, 0.900, 0.677, 0.792, 0.923, 1.027, 0.940, 1.054, 1.045, 1.069, 1.016, 0.953, 1.015, 0.934: lower in dr and dv, as mask 7 always is.
 
 
+# The schedule case (tests/test_ins_loose_all_schedule_oracle.py, tests/test_gpu_ins_loose_all_schedule.py): the first SCHEDULE_N samples
+# of the stops profile at 20 Hz with 2 Hz GPS (a fix every 10 samples; the outage begins at sample 540) and a period of its own for
+# every block, pairwise coprime.  ROTATED gives every block another block's period: a counter that borrows a period fails under one of
+# the two.  OUTAGE_FLAGS: see schedule_flags.
+SCHEDULE = {'aid': 4, 'mag': 3, 'still': 5}
+ROTATED = {'aid': 5, 'mag': 4, 'still': 3}
+SCHEDULE_N = 600
+OUTAGE_FLAGS = (540, 545, 560, 585)     # aid + mag + still, still alone, aid + still, mag + still: none with a fix applied
+FIX, AID, MAG, STILL = 1, 2, 4, 8       # the bits of schedule()
+# Measured by tests/test_ins_loose_all_schedule_oracle.py::test_the_random_walk_keeps_the_scale_state_open: 4 runs drawn from the model
+# (np.random.default_rng(11)), the schedule case with mask 1 and all three blocks.  The mean end sigma sqrt(P[15][15]) of the scale
+# state with q = 0 and with q = SCALE_Q [1/sqrt(s)], from the initial 0.02, by ref_frame.
+SCALE_Q = 1e-3
+SCALE_END_SIGMA = {0: (0.002544, 0.003827), 1: (0.002539, 0.003818)}
+
+
 @functools.lru_cache(maxsize=None)
 def stops_truth(fs, ref_frame, fs_gps, n=None, profile=sc.STOPS_CSV, geo=mc.GEO):
     """(ini_pva, truth with 'ref_odo' and 'ref_mag', gps stamps) of a stops profile, cut to the first n samples."""
     return mc.outage_truth(fs, ref_frame, fs_gps, n, profile, geo)
 
 
-def blocks(model, fs, rf, mask=MASK, mag=None, scale=False, smask=0, every=1, geo=mc.GEO, flags=None, scale0=kc.SCALE0, p0=kc.P0_SCALE):
+def periods(every):
+    """(aid, mag, still): the period of each block.  every: one int for all three, or {'aid': a, 'mag': m, 'still': s}."""
+    if isinstance(every, dict):
+        assert set(every) == {'aid', 'mag', 'still'}, every
+        return int(every['aid']), int(every['mag']), int(every['still'])
+    return every, every, every
+
+
+def blocks(model, fs, rf, mask=MASK, mag=None, scale=False, smask=0, every=1, geo=mc.GEO, flags=None, scale0=kc.SCALE0, p0=kc.P0_SCALE, q=0.0):
     """The keyword arguments of ins_loose_all_ref.run that describe the blocks (without the per-run series odo and mag): aid, and
     mag_model (mag: the magnetometer's error dict), scale (scale: True), still and flags (smask: the standstill rows) where given.
-    every: the period of every block."""
-    kw = {'aid': (kc.aid(mask, every, scale0) if scale else ac.aid(mask, every, odo_err=ODO_ERR)) if mask else None}
+    every: the period of every block, or one per block (periods).  q: the scale state's random walk [1/sqrt(s)]."""
+    ea, em, es = periods(every)
+    kw = {'aid': (kc.aid(mask, ea, scale0) if scale else ac.aid(mask, ea, odo_err=ODO_ERR)) if mask else None}
     if mag is not None:
-        kw['mag_model'] = mc.model(mag, rf, every, geo)
+        kw['mag_model'] = mc.model(mag, rf, em, geo)
     if scale:
-        kw['scale'] = kc.scale(scale0, p0)
+        kw['scale'] = kc.scale(scale0, p0, q, fs)
     if smask:
-        kw['still'], kw['flags'] = sc.model(model, fs, smask, every), flags
+        kw['still'], kw['flags'] = sc.model(model, fs, smask, es), flags
     return kw
 
 
-def job_kw(mask=MASK, mag=None, scale=False, smask=0, every=1, geo=mc.GEO, flags=None, scale0=kc.SCALE0, p0=kc.P0_SCALE, keep=True):
+def job_kw(mask=MASK, mag=None, scale=False, smask=0, every=1, geo=mc.GEO, flags=None, scale0=kc.SCALE0, p0=kc.P0_SCALE, keep=True, q=0.0):
     """The same case as the keywords of an InsLooseJob (over odo_err=ODO_ERR)."""
+    ea, em, es = periods(every)
     kw = {'odo_err': ODO_ERR}
     if mask:
-        kw['aid'] = ac.aid_options(mask, every)
+        kw['aid'] = ac.aid_options(mask, ea)
     if mag is not None:
-        kw = mc.mag_kw(mag, geo, every, **kw)
+        kw = mc.mag_kw(mag, geo, em, **kw)
     if scale:
-        kw.update(odo_scale_state={'scale0': scale0, 'p0': p0}, keep_scale=keep)
+        kw.update(odo_scale_state=dict({'scale0': scale0, 'p0': p0}, **({'q': q} if q else {})), keep_scale=keep)
     if smask:
-        kw['still'] = sc.options(smask, every, flags=flags)
+        kw['still'] = sc.options(smask, es, flags=flags)
     return kw
+
+
+def schedule(n, every, stamps, visible, flags, mask=MASK, mag=True, smask=3):
+    """(n,) int: which of {fix applied, aiding, magnetometer, standstill block} fires at every sample, as the bits FIX, AID, MAG, STILL;
+    counted from the periods, the stamps, the visibility and the flags alone (the kernel's and the restatement's rule: a block fires
+    at j > 0 with j % period == 0, the standstill block only where flags[j] != 0; a fix is applied where its visibility is not 0).
+    tests/test_ins_loose_all_schedule_oracle.py holds it to the block methods the restatement calls."""
+    ea, em, es = periods(every)
+    j = np.arange(n)
+    s = np.zeros(n, dtype=np.int64)
+    stamps, visible = np.asarray(stamps), np.asarray(visible)
+    s[stamps[(visible != 0) & (stamps < n)]] |= FIX
+    later = j > 0
+    if mask:
+        s[later & (j % ea == 0)] |= AID
+    if mag:
+        s[later & (j % em == 0)] |= MAG
+    if smask:
+        s[later & (j % es == 0) & (np.asarray(flags)[:n] != 0)] |= STILL
+    return s
+
+
+def schedule_flags(truth, stamps, n=SCHEDULE_N):
+    """The standstill signal of the schedule case: the truth's own over the first n samples and, constructed, the samples OUTAGE_FLAGS
+    inside the GPS outage, where the vehicle moves.  Parity does not need the signal to be physical; without them no standstill
+    block of these n samples falls into the outage, and an aiding and a standstill block (every 20 samples with SCHEDULE) always
+    meet a visible fix."""
+    flags = np.array(sc.flags_of(truth)[:n], dtype=np.int32)
+    hidden = np.asarray(stamps)[np.asarray(truth['gps_visibility']) == 0]
+    assert hidden.size and all(int(hidden[0]) <= j < n for j in OUTAGE_FLAGS)
+    flags[list(OUTAGE_FLAGS)] = 1
+    return flags
 
 
 def deviation(a, b):
