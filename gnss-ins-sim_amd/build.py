@@ -68,6 +68,10 @@ SOURCES = [
     # (tests/test_ins_loose_all_oracle.py reads them)
     ('ins_loose_all.hip', MC_FLAGS),
     ('ins_loose_all16.hip', MC_FLAGS),
+    # the combined lane once more with consistency checkpoints (ins_loose.hpp, CONS with Tail::ALL), six instantiations per file:
+    # the same flags, their own resource reports (tests/test_ins_loose_all_cons_oracle.py reads them)
+    ('ins_loose_all_cons.hip', MC_FLAGS),
+    ('ins_loose_all_cons16.hip', MC_FLAGS),
     ('stats.hip', ['--offload-arch=' + ARCH]),
     ('error_curve.hip', ['--offload-arch=' + ARCH]),
     # error_curve.hip's flags: the keys are formed from the shared error expression (traj_error.hpp, quantity_error) and their sums
@@ -119,6 +123,7 @@ def build(force=False, verbose=False, tag=None, defines=(), xflags=()):
     deps.append(os.path.join(REPO, 'include', 'ginsim_lpsd.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_csd.h'))
     deps.append(os.path.join(REPO, 'include', 'ginsim_loose_all.h'))
+    deps.append(os.path.join(REPO, 'include', 'ginsim_loose_all_cons.h'))
     deps.append(os.path.abspath(__file__))
     objs = []
     for src, extra in SOURCES:

@@ -16,6 +16,7 @@
 #include "ginsim_lpsd.h"
 #include "ginsim_csd.h"
 #include "ginsim_loose_all.h"
+#include "ginsim_loose_all_cons.h"
 #include "allan.hpp"
 #include "oallan.hpp"
 #include "psd.hpp"
@@ -930,9 +931,11 @@ static int check_loose_still(const ginsim_mc_params* m, const ginsim_loose_still
 }
 
 // The family of a launch of the filter, in one order: the combined family (two or three of the magnetometer, scale-factor and
-// standstill blocks), checkpoints, magnetometer, scale-factor state, standstill, aiding, plain.
+// standstill blocks), checkpoints, magnetometer, scale-factor state, standstill, aiding, plain.  Before them all: checkpoints through
+// ginsim_loose_all_cons.h, whatever blocks are left.
 static hipError_t launch_loose(const LooseLaunch& L) {
     if (L.b->n_list <= 0 && !L.name) return hipSuccess;
+    if (L.all_cons) return launch_loose_all_cons(L);
     if (L.all) return launch_loose_all(L);
     if (L.cons) return launch_loose_cons(L);
     if (L.mag) return launch_loose_mag(L);
@@ -949,7 +952,10 @@ static hipError_t launch_loose(const LooseLaunch& L) {
 // LOOSE_ALL (ginsim_loose_all.h): any of the magnetometer, scale-factor and standstill blocks, each NULL or checked as its own family
 // checks it, in that order; with two or three left after the degenerate ones the launch is the combined family's, with one or none
 // the launch that block's own entry point makes.
-enum LooseFamily { LOOSE_PLAIN, LOOSE_CONS, LOOSE_MAG, LOOSE_SCALE, LOOSE_STILL, LOOSE_ALL };
+// LOOSE_ALL_CONS (ginsim_loose_all_cons.h): LOOSE_ALL's blocks and checks, then the checkpoint block as LOOSE_CONS checks it, then
+// the truth of the scale factor (L.scale_truth, a device pointer); with cons_m == 0 it is LOOSE_ALL, otherwise the launch is
+// loose_all_cons_kernel whatever blocks are left.
+enum LooseFamily { LOOSE_PLAIN, LOOSE_CONS, LOOSE_MAG, LOOSE_SCALE, LOOSE_STILL, LOOSE_ALL, LOOSE_ALL_CONS };
 
 static int loose_entry(LooseFamily who, ginsim_ctx* c, LooseLaunch L) {
     int rc = check_loose_params(L.mc, L.b);
@@ -957,15 +963,20 @@ static int loose_entry(LooseFamily who, ginsim_ctx* c, LooseLaunch L) {
     rc = who == LOOSE_CONS ? check_loose_cons(L.mc, L.b, L.cons) : who == LOOSE_MAG ? check_loose_mag(L.mc, L.mag)
        : who == LOOSE_SCALE ? check_loose_scale(L.b, L.scale) : who == LOOSE_STILL ? check_loose_still(L.mc, L.still) : GINSIM_OK;
     if (rc) return rc;
-    if (who == LOOSE_ALL) {
+    if (who == LOOSE_ALL || who == LOOSE_ALL_CONS) {
         if (L.mag && (rc = check_loose_mag(L.mc, L.mag))) return rc;
         if (L.scale && (rc = check_loose_scale(L.b, L.scale))) return rc;
         if (L.still && (rc = check_loose_still(L.mc, L.still))) return rc;
     }
+    if (who == LOOSE_ALL_CONS) {
+        if ((rc = check_loose_cons(L.mc, L.b, L.cons))) return rc;
+        REQUIRE(!L.scale_truth || L.scale, "loose_all_cons_run: scale_truth without a scale block");
+    }
     if (L.cons && L.cons->cons_m == 0) L.cons = nullptr;
     if (L.mag && L.mag->mag_every == 0) L.mag = nullptr;
     if (L.still && L.still->still_mask == 0) L.still = nullptr;
-    L.all = who == LOOSE_ALL && (L.mag != nullptr) + (L.scale != nullptr) + (L.still != nullptr) >= 2;
+    L.all_cons = who == LOOSE_ALL_CONS && L.cons != nullptr;
+    L.all = (who == LOOSE_ALL || who == LOOSE_ALL_CONS) && (L.mag != nullptr) + (L.scale != nullptr) + (L.still != nullptr) >= 2;
     if (L.name) {
         L.name[0] = 0;
         (void)launch_loose(L);
@@ -1063,6 +1074,24 @@ int ginsim_loose_all_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim
                          const ginsim_loose_scale_params* scale, const ginsim_loose_still_params* still) {
     REQUIRE(c, "loose_all_run: NULL argument");
     return loose_entry(LOOSE_ALL, c, LooseLaunch{mc, p, nullptr, mag, scale, still});
+}
+
+int ginsim_loose_all_cons_kernel_name(const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
+                                      const ginsim_loose_scale_params* scale, const ginsim_loose_still_params* still,
+                                      const ginsim_loose_cons_params* cons, const double* scale_truth, char* buf, size_t cap) {
+    REQUIRE(buf && cap > 0, "loose_all_cons_kernel_name: bad arguments");
+    LooseLaunch L{mc, p, cons, mag, scale, still, buf, cap};
+    L.scale_truth = scale_truth;
+    return loose_entry(LOOSE_ALL_CONS, nullptr, L);
+}
+
+int ginsim_loose_all_cons_run(ginsim_ctx* c, const ginsim_mc_params* mc, const ginsim_loose_params* p, const ginsim_loose_mag_params* mag,
+                              const ginsim_loose_scale_params* scale, const ginsim_loose_still_params* still,
+                              const ginsim_loose_cons_params* cons, const double* scale_truth) {
+    REQUIRE(c, "loose_all_cons_run: NULL argument");
+    LooseLaunch L{mc, p, cons, mag, scale, still};
+    L.scale_truth = scale_truth;
+    return loose_entry(LOOSE_ALL_CONS, c, L);
 }
 
 int ginsim_aux_sensors(ginsim_ctx* c, const ginsim_aux_params* p) {

@@ -11,6 +11,8 @@
 // file's header.
 // For ins_loose_all.hip's loose_all_kernel: the three blocks above in one lane, each gated at run time; what it adds is behind
 // `TL == Tail::ALL` (the layout of the kernel's fifth argument) and compiles to nothing for the six files above.
+// For ins_loose_all_cons.hip's loose_all_cons_kernel: that lane with the checkpoint, and the checkpoint's three values of the
+// scale-factor state behind `NS == kLooseStates + 1`; CONS with Tail::ONE is loose_cons_kernel's lane as it was.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
@@ -488,8 +490,8 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 // e^T B^-1 e of the symmetric 3x3 block I of P by its adjugate and determinant; NaN unless the block is positive definite
 // (Sylvester: the three leading minors)
-template <int I>
-__device__ __forceinline__ double block_nees(const Cov& P, const double* e) {
+template <int I, int NS>
+__device__ __forceinline__ double block_nees(const CovT<NS>& P, const double* e) {
     const double a = P.get(I, I), b = P.get(I, I + 1), c = P.get(I, I + 2), d = P.get(I + 1, I + 1), f = P.get(I + 1, I + 2), g = P.get(I + 2, I + 2);
     const double a00 = d * g - f * f, a01 = c * f - b * g, a02 = b * f - c * d;
     const double a11 = a * g - c * c, a12 = b * c - a * f, a22 = a * d - b * b;
@@ -502,8 +504,12 @@ __device__ __forceinline__ double block_nees(const Cov& P, const double* e) {
 // (tests/ins_loose_ref.py, error_state), the record's values of this lane, their sums over the wavefront, and lane 0's store of
 // the partial record.  live: the lane carries a run of its own (a tail lane repeats the last run with weight 0).  Every lane of
 // the wavefront arrives here together (the checkpoints are wave-uniform).
-template <int RF>
-__device__ __forceinline__ void loose_checkpoint(const Cov& P, const Nav& s, uniform_ptr t, bool live, double* __restrict__ rec) {
+// NS = 16 (loose_all_cons_kernel): the record's slots 37-39 carry the scale state: P[15][15], and against the truth
+// ktrue[r] of run r the error kest - ktrue[r], squared and over P[15][15].  ktrue == NULL (wave-uniform): the two error sums are
+// written 0 and the scale error takes no part in a lane's inclusion.  NS = 15 is the checkpoint as it was.
+template <int RF, int NS>
+__device__ __forceinline__ void loose_checkpoint(const CovT<NS>& P, const Nav& s, uniform_ptr t, bool live, double* __restrict__ rec,
+                                                 double kest = 0.0, const double* __restrict__ ktrue = nullptr, int64_t r = 0) {
     double e[9];
     if (RF == 0) {
         const Geo g = geo_param(t[3], t[5]);
@@ -546,6 +552,16 @@ __device__ __forceinline__ void loose_checkpoint(const Cov& P, const Nav& s, uni
     }
 #pragma unroll
     for (int b = 0; b < 3; ++b) ok = ok && isfinite(nees[b]);
+    double ek2 = 0.0;       // (kest - ktrue[r])^2, 0 without a truth (NS = 16 only)
+    if constexpr (NS == kLooseScaleStates) {
+        const double pk = P.get(kLooseStates, kLooseStates);
+        ok = ok && pk > 0.0 && isfinite(pk);
+        if (ktrue) {
+            const double ek = kest - ktrue[r];
+            ek2 = ek * ek;
+            ok = ok && isfinite(ek2) && isfinite(ek2 / pk);
+        }
+    }
     phase_fence();
     // one value at a time: made again from e and the lane's column of P, summed, stored -- nothing of the record stays in registers
     const bool first = threadIdx.x == 0;
@@ -567,9 +583,14 @@ __device__ __forceinline__ void loose_checkpoint(const Cov& P, const Nav& s, uni
         const double v = wave_sum(ok ? nees[b] : 0.0);
         if (first) rec[34 + b] = v;
     }
+    if constexpr (NS == kLooseScaleStates) {
+        const double pk = P.get(kLooseStates, kLooseStates);
+        const double u = wave_sum(ok ? pk : 0.0), v = wave_sum(ok ? ek2 : 0.0), w = wave_sum(ok && ktrue ? ek2 / pk : 0.0);
+        if (first) { rec[37] = u; rec[38] = v; rec[39] = w; }
+    }
     if (first) {
 #pragma unroll
-        for (int k = 37; k < GINSIM_CONS_RECORD; ++k) rec[k] = 0.0;
+        for (int k = NS == kLooseScaleStates ? 40 : 37; k < GINSIM_CONS_RECORD; ++k) rec[k] = 0.0;
     }
 }
 
@@ -585,22 +606,27 @@ __device__ __forceinline__ void put3(double* base, int64_t plane, int64_t off, c
 // MAG: the magnetometer block (loose_mag) at every sample j > 0 with j % mag_every == 0, after a fix and an aiding block of the same
 // sample, before a checkpoint and before the row is stored; its numbers are the kernel's fifth argument (loose_mag_params).  With
 // MAG an aid_mask of 0 fires no aiding block at all.  MAG = false is the lane as it was.
-// NS: the number of states.  16 (with AID, without CONS and MAG): the odometer's scale factor is state 15 and its estimate kest a
+// NS: the number of states.  16 (with AID; without CONS and MAG unless TL is Tail::ALL): the odometer's scale factor is state 15 and its estimate kest a
 // value of the lane; its numbers and outputs are the kernel's fifth argument (loose_scale_params).  NS = 15 is the lane as it was.
 // STILL: the standstill block (loose_still) at every sample j > 0 with j % still_every == 0 and still_flags[j] != 0, after a fix and an
-// aiding block of the same sample, before the row is stored (the magnetometer block's place; with AID, without CONS and MAG, NS = 15);
+// aiding block of the same sample, before the row is stored (the magnetometer block's place; with AID, and unless TL is Tail::ALL without CONS and MAG, NS = 15);
 // its numbers are the kernel's fifth argument (loose_still_params).  The lane carries the raw gyro sample it integrated last.  With
 // STILL an aid_mask of 0 fires no aiding block at all.  STILL = false is the lane as it was.
 // TL: the layout of the kernel's fifth argument (Tail).  ALL (loose_all_kernel, with AID, MAG and STILL, NS 15 or 16): the lane may have
 // the three blocks together, each gated at run time: a magnetometer block with mag_every == 0 and a standstill block with
 // still_mask == 0 never fire and none of their pointers is read.  TL = Tail::ONE is the lane as it was.
+// CONS with Tail::ALL (loose_all_cons_kernel, ins_loose_all_cons.hpp): the checkpoint after the standstill block, on 15 or 16 states;
+// ktrue: the scale factor's truth per run for the record's slots 38 and 39, or NULL (loose_checkpoint).  Not read otherwise.
 template <int RF, bool GIVEN, bool VIB, bool PS, bool AID, bool CONS = false, bool MAG = false, int NS = kLooseStates, bool STILL = false,
           Tail TL = Tail::ONE>
 __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const ginsim_loose_params& b, const int64_t* __restrict__ stamp,
-                                           const int32_t* __restrict__ visible, uint32_t* ntab, const ConsArgs& cq = ConsArgs{}) {
-    static_assert(NS == kLooseStates || (NS == kLooseScaleStates && AID && !CONS), "16 states: the aided lane without checkpoints only");
-    static_assert(!STILL || (AID && !CONS), "the standstill block: the aided lane without checkpoints only");
-    static_assert(!CONS || (!MAG && !STILL && NS == kLooseStates && TL == Tail::ONE), "checkpoints: no other block");
+                                           const int32_t* __restrict__ visible, uint32_t* ntab, const ConsArgs& cq = ConsArgs{},
+                                           const double* __restrict__ ktrue = nullptr) {
+    static_assert(NS == kLooseStates || (NS == kLooseScaleStates && AID && (!CONS || TL == Tail::ALL)),
+                  "16 states: the aided lane, with checkpoints in the combined lane only");
+    static_assert(!STILL || (AID && (!CONS || TL == Tail::ALL)), "the standstill block: the aided lane, with checkpoints in the combined lane only");
+    static_assert(!CONS || (!MAG && !STILL && NS == kLooseStates && TL == Tail::ONE) || (AID && MAG && STILL && !PS && TL == Tail::ALL),
+                  "checkpoints: no other block, or the combined lane with all of them");
     static_assert(TL == Tail::ALL || int(MAG) + int(STILL) + int(NS == kLooseScaleStates) <= 1,
                   "one family's block as the fifth argument: the lane has at most one of the three");
     NormalTables tab{};
@@ -745,7 +771,7 @@ __device__ __forceinline__ void loose_body(const ginsim_mc_params& a, const gins
         if constexpr (CONS) {
             if (kc < cq.m && cq.sample[kc] == j) {
                 phase_fence();
-                loose_checkpoint<RF>(P, s, nav_truth + 9 * j, live, cq.work + ((int64_t)blockIdx.x * cq.m + kc) * GINSIM_CONS_RECORD);
+                loose_checkpoint<RF>(P, s, nav_truth + 9 * j, live, cq.work + ((int64_t)blockIdx.x * cq.m + kc) * GINSIM_CONS_RECORD, kest, ktrue, r);
                 phase_fence();
                 ++kc;
             }

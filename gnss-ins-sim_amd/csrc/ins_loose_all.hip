@@ -13,7 +13,8 @@
 // is read.  NS is a template argument: a launch without the scale block is the 15-state instantiation.
 // The kernel's fifth argument is one ginsim_loose_all_params by value, the three family blocks one after the other; the lane reads
 // each from the kernarg segment where it is used, at its member's offset (ins_loose.hpp, Tail::ALL), as the single families read
-// theirs at the argument's start.  No consistency checkpoints.  Every store is an ordinary per-lane store.
+// theirs at the argument's start.  No consistency checkpoints here: ins_loose_all_cons.hip has this lane with them.  Every store is
+// an ordinary per-lane store.
 //
 // This file: the 12 instantiations <RF, GIVEN, VIB, PS, 15>; P stays in LDS as [120][64].  ins_loose_all16.hip: <..., 16>, [136][64].
 // Built with ins_loose.hip's flags; the build's resource report (build/ins_loose_all.resources.txt, build/ins_loose_all16.resources.txt;

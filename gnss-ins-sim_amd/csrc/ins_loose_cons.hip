@@ -59,8 +59,12 @@ hipError_t launch_loose_cons(const LooseLaunch& L) {
     const ginsim_loose_cons_params& c = *L.cons;
     const hipError_t e = launch_loose_family<ConsFamily>(L, L.b->aid_mask != 0, ConsArgs{L.samples, c.cons_m, c.cons_work});
     if (L.name || e != hipSuccess) return e;
-    const int64_t waves = (L.b->n_list + kLooseBlock - 1) / kLooseBlock, len = c.cons_m * GINSIM_CONS_RECORD;
-    hipLaunchKernelGGL(cons_final_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, L.stream, c.cons_work, waves, len, c.out_cons);
+    return launch_cons_final(c, (L.b->n_list + kLooseBlock - 1) / kLooseBlock, L.stream);
+}
+
+hipError_t launch_cons_final(const ginsim_loose_cons_params& c, int64_t waves, hipStream_t stream) {
+    const int64_t len = c.cons_m * GINSIM_CONS_RECORD;
+    hipLaunchKernelGGL(cons_final_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, stream, c.cons_work, waves, len, c.out_cons);
     return hipGetLastError();
 }
 

@@ -46,6 +46,8 @@ struct LooseLaunch {
     const int64_t* samples;
     hipStream_t stream;
     bool all;                                   // two or three of mag, scale and still are left: the combined family (ins_loose_all.hip)
+    bool all_cons;                              // cons with any of mag, scale and still, or none: ins_loose_all_cons.hip (ginsim_loose_all_cons.h)
+    const double* scale_truth;                  // all_cons: the DEVICE truth of the scale factor per run, or NULL
 };
 
 // ins_loose.hip, ins_loose_aided.hip (b->aid_mask != 0), ins_loose_cons.hip (cons), ins_loose_mag.hip (mag), ins_loose_scale.hip
@@ -60,6 +62,12 @@ hipError_t launch_loose_still(const LooseLaunch& L);
 // zero, as the one ginsim_loose_all_params the kernel takes; b->aid_mask has bit 0 where L.scale is set
 hipError_t launch_loose_all(const LooseLaunch& L);
 hipError_t launch_loose_all16(const LooseLaunch& L);
+// ins_loose_all_cons.hip (L.all_cons; 15 states) and ins_loose_all_cons16.hip (with L.scale; 16 states): the combined lane with
+// checkpoints, then launch_cons_final
+hipError_t launch_loose_all_cons(const LooseLaunch& L);
+hipError_t launch_loose_all_cons16(const LooseLaunch& L);
+// ins_loose_cons.hip: cons_final_kernel, out_cons = the sum of the `waves` partial records of cons_work
+hipError_t launch_cons_final(const ginsim_loose_cons_params& c, int64_t waves, hipStream_t stream);
 int loose_variant(const ginsim_mc_params& p);
 
 // aux_sensors.hip

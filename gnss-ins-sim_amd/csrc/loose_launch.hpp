@@ -1,5 +1,5 @@
 // The host-side launch of the loose family (ins_loose.hip, ins_loose_aided.hip, ins_loose_cons.hip, ins_loose_mag.hip,
-// ins_loose_scale.hip, ins_loose_still.hip): each file defines its own __global__ wrapper of loose_body, describes it by a trait and hands a LooseLaunch
+// ins_loose_scale.hip, ins_loose_still.hip, ins_loose_all*.hip, ins_loose_all_cons*.hip): each file defines its own __global__ wrapper of loose_body, describes it by a trait and hands a LooseLaunch
 // (launch.hpp) to launch_loose_family, which chooses <RF, flag> and gives the three instantiations to launch_loose_trio.
 #pragma once
 #include <hip/hip_runtime.h>

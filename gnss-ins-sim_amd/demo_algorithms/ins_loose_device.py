@@ -50,7 +50,7 @@ All of them together (csrc/ins_loose_all.hip; as NumPy in tests/in
 "not together" rules above.  A plugin with two or three of mag=True, odo_scale_state=True and zupt / zaru then runs one kernel
 with every block, in the order GPS fix, odometer / constraints, magnetometer, standstill at a sample; ``input`` and ``output`` are
 the union of what the options add ('odo', 'mag'; 'odo_scale').  With one of them or none, combined=True changes nothing.
-odo_scale_state=True still needs odo=True; Sim.consistency_curve does not take such a plugin.
+odo_scale_state=True still needs odo=True; Sim.consistency_curve_any_family takes such a plugin.
 """
 import numpy as np
 

@@ -3,7 +3,7 @@
 Importing this package loads the HIP library through ctypes; it raises if the library has not been
 built.  There is no CPU implementation behind it.
 """
-from ._lib import lib, LIB_PATH, EXPORTS, OALLAN_EXPORTS, PSD_EXPORTS, LPSD_EXPORTS, CSD_EXPORTS, LOOSE_ALL_EXPORTS, GinsimError, GinsimOutOfMemory, PlacedUnavailable, ALGO_FREE, ALGO_ODO          # noqa: F401
+from ._lib import lib, LIB_PATH, EXPORTS, OALLAN_EXPORTS, PSD_EXPORTS, LPSD_EXPORTS, CSD_EXPORTS, LOOSE_ALL_EXPORTS, LOOSE_ALL_CONS_EXPORTS, GinsimError, GinsimOutOfMemory, PlacedUnavailable, ALGO_FREE, ALGO_ODO          # noqa: F401
 from .engine import (Context, DeviceBuffer, MonteCarloJob, AuxSensorJob, StatsResult, CurveResult, CovResult, track_frame, error_ellipse, QuantileResult, quantile_rows, ConsistencyResult, device_count, pathgen, pinned_empty, vibration, psd_amplitudes,  # noqa: F401
                      sensor_model, ini_table, free_integration_host, rng_normals, normal_transform, default_context, allan_var, allan_var_host, allan_plan, ALLAN_MODES,
                      oallan_var, oallan_var_host, oallan_plan, OALLAN_FORMS,

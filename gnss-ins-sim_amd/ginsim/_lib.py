@@ -353,6 +353,16 @@ _SIGS_LOOSE_ALL = {
     'ginsim_loose_all_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseMagParams),
                                                C.POINTER(LooseScaleParams), C.POINTER(LooseStillParams), C.c_char_p, C.c_size_t]),
 }
+# include/ginsim_loose_all_cons.h: the seventh header, the seventh table (ginsim.LOOSE_ALL_CONS_EXPORTS); scale_truth is a device
+# pointer
+_SIGS_LOOSE_ALL_CONS = {
+    'ginsim_loose_all_cons_run': (C.c_int, [C.c_void_p, C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseMagParams),
+                                            C.POINTER(LooseScaleParams), C.POINTER(LooseStillParams), C.POINTER(LooseConsParams),
+                                            C.c_void_p]),
+    'ginsim_loose_all_cons_kernel_name': (C.c_int, [C.POINTER(McParams), C.POINTER(LooseParams), C.POINTER(LooseMagParams),
+                                                    C.POINTER(LooseScaleParams), C.POINTER(LooseStillParams),
+                                                    C.POINTER(LooseConsParams), C.c_void_p, C.c_char_p, C.c_size_t]),
+}
 _OPTIONAL = {}
 
 
@@ -361,7 +371,7 @@ def _load():
         raise ImportError('libginsim.so not built: run `python gnss-ins-sim_amd/build.py` '
                           '(or __graft_entry__.build()); expected %s' % LIB_PATH)
     lib = C.cdll.LoadLibrary(LIB_PATH)
-    for sigs in (_SIGS, _SIGS_OALLAN, _SIGS_PSD, _SIGS_LPSD, _SIGS_CSD, _SIGS_LOOSE_ALL):
+    for sigs in (_SIGS, _SIGS_OALLAN, _SIGS_PSD, _SIGS_LPSD, _SIGS_CSD, _SIGS_LOOSE_ALL, _SIGS_LOOSE_ALL_CONS):
         for name, (res, args) in sigs.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -379,6 +389,7 @@ PSD_EXPORTS = tuple(_SIGS_PSD)
 LPSD_EXPORTS = tuple(_SIGS_LPSD)
 CSD_EXPORTS = tuple(_SIGS_CSD)
 LOOSE_ALL_EXPORTS = tuple(_SIGS_LOOSE_ALL)
+LOOSE_ALL_CONS_EXPORTS = tuple(_SIGS_LOOSE_ALL_CONS)
 
 
 def check(rc):

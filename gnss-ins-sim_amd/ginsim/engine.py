@@ -697,9 +697,12 @@ class ConsistencyResult(object):
     across the runs included, count (m,) and the MEANS pbar (m, 15) of P_kk, e2 (m, 9) of the squared navigation-state errors,
     nes (m, 9) of e_k^2 / P_kk and nees (m, 3) of the position / velocity / attitude block's e^T P_bb^-1 e (3 when consistent).
     States in the filter's order and units: dr [m], dv [m/s], psi [rad], dbg [rad/s], dba [m/s^2].  The records themselves are
-    sums, so the records of disjoint sets of runs over the same checkpoints merge by addition."""
+    sums, so the records of disjoint sets of runs over the same checkpoints merge by addition.
+    A filter with the scale-factor state (ginsim_loose_all_cons_run, columns 37-39) also has the means pbar_scale (m,) of P[15][15],
+    e2_scale (m,) of (k_est - k_true)^2 and nes_scale (m,) of that over P[15][15]; they are 0 for a filter without the state, and the
+    last two without a truth."""
 
-    WIDTH = 43          # GINSIM_CONS_RECORD: count, 15, 9, 9, 3 and six reserved zeros
+    WIDTH = 43          # GINSIM_CONS_RECORD: count, 15, 9, 9, 3, the scale state's 3 and three reserved zeros
 
     def __init__(self, records):
         self.records = np.array(records, dtype=np.float64).reshape(-1, self.WIDTH)
@@ -707,6 +710,7 @@ class ConsistencyResult(object):
         with np.errstate(divide='ignore', invalid='ignore'):
             mean = self.records / self.count[:, None]
         self.pbar, self.e2, self.nes, self.nees = mean[:, 1:16], mean[:, 16:25], mean[:, 25:34], mean[:, 34:37]
+        self.pbar_scale, self.e2_scale, self.nes_scale = mean[:, 37], mean[:, 38], mean[:, 39]
 
     @property
     def m(self):
@@ -728,6 +732,19 @@ class ConsistencyResult(object):
     @property
     def ratio(self):    # 1 for a consistent filter; above 1: overconfident
         return self.rms / self.sigma[:, :9]
+
+    @property
+    def sigma_scale(self):      # the filter's predicted 1 sigma of the scale-factor error
+        return np.sqrt(self.pbar_scale)
+
+    @property
+    def rms_scale(self):        # the across-run RMS error of the scale-factor estimate
+        return np.sqrt(self.e2_scale)
+
+    @property
+    def ratio_scale(self):
+        with np.errstate(divide='ignore', invalid='ignore'):        # 0 / 0 for a filter without the state
+            return self.rms_scale / self.sigma_scale
 
     def pack(self):
         """(m, 43) sums as the library lays them out."""

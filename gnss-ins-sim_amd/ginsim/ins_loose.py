@@ -14,6 +14,8 @@ update (csrc/ins_loose_still.hip, still_model, standstill_flags; restated by tes
 What one launch does not combine is stated once (refuse_combinations); the job records the family it launches once (FAMILIES).
 With combined=True the magnetometer block, the scale-factor state and the standstill block go together in one launch
 (csrc/ins_loose_all.hip, COMBINED; restated by tests/ins_loose_all_ref.py, which composes the two restatements above).
+With checkpoints=... any of these filters reduces the consistency record, the scale state's columns included
+(csrc/ins_loose_all_cons.hip, ALL_CONS; restated by tests/ins_loose_all_cons_ref.py).
 """
 import ctypes as C
 
@@ -270,6 +272,9 @@ FAMILIES = (('cons', '_cons'), ('magp', '_mag'), ('scalep', '_scale'), ('stillp'
 # through the entry points with this suffix, which take the three blocks (None: NULL) and not one
 COMBINED = ('allp', '_all')
 COMBINED_BLOCKS = ('magp', 'scalep', 'stillp')
+# checkpoints for every family (checkpoints=...), looked at before both: the entry points with this suffix take COMBINED_BLOCKS
+# (None: NULL), the checkpoint block and the device pointer of the scale factor's truth
+ALL_CONS = ('consp', '_all_cons')
 
 
 def refuse_combinations(scale, keep_scale, odo, mag, cons, proc, still=False, combined=False):
@@ -331,6 +336,14 @@ class InsLooseJob(BatchJob):
     launches the combined family (csrc/ins_loose_all.hip), one kernel that runs every block in the order fix, odometer /
     constraints, magnetometer, standstill.  With one of them or none the job launches exactly what it launches without the keyword.
     Still refused: cons_samples, fp32 (the C glue's check), odo_scale_state without aid['odo'].
+    checkpoints: None, or sample indices with cons_samples' rules (any order, repeats allowed): the consistency record
+    (consistency()) of a filter with any of mag, odo_scale_state and still -- with combined=True, with a single block or with
+    none -- through one kernel family that has every block and the checkpoints (csrc/ins_loose_all_cons.hip; restated
+    by tests/ins_loose_all_cons_ref.py).  cons_samples keeps its own kernel and every refusal it has.  Not together with
+    cons_samples or proc_first.
+    scale_truth: with checkpoints and odo_scale_state, the true scale factor the record's scale columns compare k_est with: a scalar
+    or (runs,), indexed by the run id.  None: odo_err['scale'] in the generated form (what the lane makes its odometer with); no
+    truth in the given form (e2_scale and nes_scale are then 0).
     """
 
     algos = ('loose',)
@@ -339,9 +352,17 @@ class InsLooseJob(BatchJob):
                  earth_rot=True, given=None, model=None, q_scale=1.0, p0=None, keep_traj=False, proc_first=None, proc_ned=False,
                  end_pos_ned=False, end_ned=False, vib_accel=None, vib_gyro=None, placed=None, gps_stamps=None, odo_err=None, aid=None,
                  cons_samples=None, mag_err=None, geo_mag_n=None, mag=None, odo_scale_state=None, keep_scale=False, still=None,
-                 combined=False):
+                 combined=False, checkpoints=None, scale_truth=None):
         self.ctx, self._bufs = ctx, {}
         self.combined = bool(combined)
+        if checkpoints is not None and cons_samples is not None:
+            raise ValueError('checkpoints: not together with cons_samples (one list of checkpoints per launch)')
+        if checkpoints is not None and proc_first is not None:
+            raise ValueError('checkpoints: online process statistics (proc_first) and checkpoints in one launch are refused')
+        if scale_truth is not None and (odo_scale_state is None or odo_scale_state is False):
+            raise ValueError('checkpoints: scale_truth without the scale-factor state (odo_scale_state=...)')
+        if scale_truth is not None and checkpoints is None:
+            raise ValueError('checkpoints: scale_truth is read at checkpoints (checkpoints=...) only')
         self.keep_traj, self.keep_scale = bool(keep_traj), bool(keep_scale)
         self.proc_first, self.proc_ned, self.end_ned = proc_first, bool(proc_ned), bool(end_ned)
         table, ref_gps = self._sizes_and_stamps(fs, ref_frame, truth, ini, runs, seed, run_offset, ini_first, earth_rot, end_pos_ned,
@@ -366,6 +387,15 @@ class InsLooseJob(BatchJob):
         self.allp = held if self.combined and sum(b is not None for b in held) >= 2 else None
         if self.allp is not None:
             self._family = (COMBINED[1], self.allp)
+        # checkpoints=: whatever blocks the job holds (none to three) go through the one entry point that has checkpoints for all
+        # of them (csrc/ins_loose_all_cons.hip); cons_samples= above keeps its own
+        self.consp = None
+        if checkpoints is not None:
+            self._checkpoints(checkpoints, 'checkpoints')
+            self.consp, self.cons = self.cons, None
+            self._scale_truth(scale_truth, given, odo_err)
+            truth_ptr = None if 'scale_truth' not in self._bufs else C.c_void_p(self._bufs['scale_truth'].ptr)
+            self._family = (ALL_CONS[1], held + (self.consp, truth_ptr))
 
     # ------------------------------------------------------------------ the constructor's steps
     def _sizes_and_stamps(self, fs, ref_frame, truth, ini, runs, seed, run_offset, ini_first, earth_rot, end_pos_ned, gps_stamps):
@@ -521,14 +551,31 @@ class InsLooseJob(BatchJob):
             if self.keep_scale:
                 g.out_scale = self._bufs['scale'].at(17 * R * 8)
 
-    def _checkpoints(self, cons_samples):
+    def _scale_truth(self, scale_truth, given, odo_err):
+        """The device copy [runs] of the scale factor's truth that the checkpoints of a filter with the scale-factor state compare
+        k_est with: a scalar or (runs,); None: what the lane itself generates the odometer with (odo_err['scale']) in the generated
+        form, no truth in the given form."""
+        if self.scalep is None:
+            return
+        if scale_truth is None:
+            if given is not None or odo_err is None:
+                return
+            scale_truth = float(odo_err['scale'])
+        v = np.asarray(scale_truth, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.full(self.runs, float(v))
+        if v.shape != (self.runs,):
+            raise ValueError('checkpoints: scale_truth must be a scalar or (runs,) = (%d,), one true scale factor per run' % self.runs)
+        self._bufs['scale_truth'] = self.ctx.upload(np.ascontiguousarray(v))
+
+    def _checkpoints(self, cons_samples, who='cons_samples'):
         """The checkpoint block (cons) and its record and work buffers."""
         self.cons = None
         if cons_samples is None:
             return
         asked = np.asarray(cons_samples, dtype=np.int64).reshape(-1)
         if asked.size == 0 or asked.min() < 0 or asked.max() >= self.n:
-            raise ValueError('cons_samples must be sample indices in [0, %d), at least one' % self.n)
+            raise ValueError('%s must be sample indices in [0, %d), at least one' % (who, self.n))
         # the kernel walks a strictly increasing list; _cons_back maps its records to the caller's order
         self._cons_samples, self._cons_back = np.unique(asked, return_inverse=True)
         self._cons_samples = np.ascontiguousarray(self._cons_samples, dtype=np.int64)
@@ -545,7 +592,8 @@ class InsLooseJob(BatchJob):
         blocks, the family's block (the combined family's three, None for one the job does not hold)."""
         suffix, block = self._family
         blocks = () if block is None else block if isinstance(block, tuple) else (block,)
-        args = head + (C.byref(self.mc), C.byref(self.params)) + tuple(None if b is None else C.byref(b) for b in blocks)
+        args = head + (C.byref(self.mc), C.byref(self.params)) + \
+            tuple(C.byref(b) if isinstance(b, C.Structure) else b for b in blocks)       # None: NULL; a device pointer as it is
         return getattr(lib, 'ginsim_loose%s_%s' % (suffix, what)), args
 
     def kernel_name(self):
@@ -631,7 +679,7 @@ class InsLooseJob(BatchJob):
         """ConsistencyResult of the last launch at cons_samples, in the caller's order: across the runs launched, the filter's
         mean P_kk next to the mean squared error of the navigation states in the filter's own coordinates, and the normalised
         errors (per state and per 3x3 block)."""
-        if self.cons is None:
+        if self.cons is None and self.consp is None:
             raise ValueError('the consistency record was not requested (cons_samples=...)')
         rec = self.ctx.download(self._bufs['cons'], (self._cons_samples.size, _lib.CONS_RECORD))
         return ConsistencyResult(rec[self._cons_back])

@@ -284,11 +284,12 @@ class _McResults(object):
             self._stats[key] = ginsim.QuantileResult(r.values.reshape(3, m, -1), r.count.reshape(3, m))
         return self._stats[key]
 
-    def consistency(self, name, samples):
+    def consistency(self, name, samples, any_family=False):
         """ginsim.ConsistencyResult of the InsLoose `name` over ALL runs of the Sim at `samples` (int64 sample indices): one more
         statistics-only launch of the filter with checkpoints (the counter RNG reproduces the same runs; nothing kept is needed),
-        merged over ranks; every rank takes the same branches."""
-        key = ('cons', name, samples.tobytes())
+        merged over ranks; every rank takes the same branches.  any_family: the launch goes through InsLooseJob(checkpoints=...),
+        which serves a filter with any of its aiding blocks."""
+        key = ('cons', name, samples.tobytes()) + (('any',) if any_family else ())
         if key not in self._stats:
             import ginsim
             from ginsim import distributed
@@ -296,7 +297,7 @@ class _McResults(object):
             if self.jobs[idx] is None:      # a rank without runs: the empty record, into the same collective
                 part = ginsim.ConsistencyResult.zero(samples.size)
             else:
-                job = self._make_cons_job(idx, samples)
+                job = self._make_cons_job(idx, samples, True) if any_family else self._make_cons_job(idx, samples)
                 job.run()
                 part = job.consistency()
                 job.release()
@@ -1103,10 +1104,11 @@ class Sim(object):
             # placed=None is kept from the parent on purpose and not yet judged: these blocks do not follow Sim(placed=)
             return jobs.fused(owners[idx], (kinds[order[idx]],), runs_, off=off, keep_traj=True, placed=None)
 
-        def make_cons_job(idx, samples):        # the filter over this rank's runs again, nothing kept, checkpoints at `samples`;
-            # the initial states of the launch run() made (the plugin's call count has moved on since)
+        def make_cons_job(idx, samples, any_family=False):  # the filter over this rank's runs again, nothing kept, checkpoints at
+            # `samples`; the initial states of the launch run() made (the plugin's call count has moved on since).  any_family: through
+            # checkpoints=, the kernel family with every block; the truth of a scale-factor state is then the Sim's odometer scale
             first = next(j for i, j, _ in loose_jobs if i == order[idx]).mc.ini_first
-            return jobs.loose(owners[idx], plan.count, False, cons_samples=samples, ini_first=first)
+            return jobs.loose(owners[idx], plan.count, False, ini_first=first, **{'checkpoints' if any_family else 'cons_samples': samples})
         names = [self.amgr.get_algo_name(i) for i in order]
         self.mc = _McResults([run.stats.get(i) for i in plan.fused] + [j for _, j, _ in loose_jobs] + [g.job for _, g in incl_groups],
                              [run.kept.get(i) for i in plan.fused] + [k for _, _, k in loose_jobs] + [g.kept for _, g in incl_groups], names,
@@ -1453,6 +1455,14 @@ class Sim(object):
             out[nm] = res
         return out
 
+    def consistency_curve_any_family(self, *, every=None, samples=None):
+        """consistency_curve for EVERY InsLoose of the Sim: with the magnetometer block, the scale-factor state, the standstill block or
+        several of them (combined=True) too, which consistency_curve refuses (InsLooseJob(checkpoints=...)).  The same
+        arguments and the same dict; a plugin with the scale-factor state gains 'scale': {'sigma', 'rms', 'ratio'}, each (m,):
+        sqrt(mean P[15][15]), the RMS of k_est - k against the Sim's odometer scale k, and their quotient.  (A method of its own and
+        not a keyword: consistency_curve keeps its signature and every refusal it has.)"""
+        return self._consistency_curve(every, samples, True)
+
     def consistency_curve(self, *, every=None, samples=None):
         """Is the covariance of the Sim's InsLoose filters honest along the run?  At each instant, across all runs: the filter's
         predicted 1 sigma next to the RMS of its actual error, state by state, and the normalised error of the position, velocity
@@ -1467,6 +1477,11 @@ class Sim(object):
         Units are the FILTER's, not the output units of ``results``: dr in m (NED metres in ref_frame 0), dv in m/s, psi in rad
         (a small rotation in the navigation frame, not Euler angles), dbg in rad/s, dba in m/s^2.  A run whose state or covariance
         is not finite, or whose P is not positive definite on a block, is left out and missing from 'count'."""
+        return self._consistency_curve(every, samples, False)
+
+    def _consistency_curve(self, every, samples, any_family):
+        """consistency_curve (any_family False: the plugins with a magnetometer, scale-factor or standstill block are refused) and
+        consistency_curve_any_family (True: they are served through InsLooseJob(checkpoints=...))."""
         if not self.sim_complete:
             print("Call Sim.run() to run the simulaltion first.")
             return None
@@ -1481,7 +1496,7 @@ class Sim(object):
         if samples is None:
             samples = np.arange(n, dtype=np.int64)
         out = {'time': t[samples], 'states': ['%s_%s' % (b, a) for b in ('dr', 'dv', 'psi', 'dbg', 'dba') for a in 'xyz']}
-        for a, (_, job, _) in zip(names, getattr(self, 'loose_jobs', ())):
+        for a, (_, job, _) in zip(names, () if any_family else getattr(self, 'loose_jobs', ())):
             if getattr(job, 'allp', None) is not None:
                 raise NotImplementedError('consistency_curve: %s runs several of the magnetometer block, the scale-factor state and the '
                                           'standstill block in one launch (InsLoose(combined=True)), and the consistency checkpoints of '
@@ -1495,9 +1510,12 @@ class Sim(object):
             if getattr(job, 'still', None) is not None:
                 raise NotImplementedError('consistency_curve: %s is aided at standstill (InsLoose(zupt=True) / InsLoose(zaru=True)), and '
                                           'the consistency checkpoints of that filter are not built' % a)
+        with_scale = {a for a, (_, job, _) in zip(names, getattr(self, 'loose_jobs', ())) if getattr(job, 'scale', None) is not None}
         for a in names:
-            c = mc.consistency(a, samples)
+            c = mc.consistency(a, samples, True) if any_family else mc.consistency(a, samples)
             out[a] = {'count': c.count, 'sigma': c.sigma, 'rms': c.rms, 'ratio': c.ratio, 'nees': c.nees}
+            if any_family and a in with_scale:
+                out[a]['scale'] = {'sigma': c.sigma_scale, 'rms': c.rms_scale, 'ratio': c.ratio_scale}
         return out
 
     def plot(self, what_to_plot, sim_idx=None, opt=None, extra_opt=''):

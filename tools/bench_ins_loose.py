@@ -9,6 +9,7 @@
     python tools/bench_ins_loose.py --odo-scale [--reps 20] [--out profiles/ins_loose_scale_timing.json]
     python tools/bench_ins_loose.py --still [--reps 20] [--out profiles/ins_loose_still_timing.json]
     python tools/bench_ins_loose.py --combined [--reps 20] [--out profiles/ins_loose_all_timing.json]
+    python tools/bench_ins_loose.py --combined-cons [--reps 20] [--out profiles/ins_loose_all_cons_timing.json]
 
 Workload: 65 536 runs x the 1000 samples of the 90-degree turn at 100 Hz (BASELINE config C2's shape) with GPS at 10 Hz, ref_frame 1,
 'mid-accuracy' IMU; statistics only (nothing but the per-run end records is written) and with everything kept (trajectory, wb, ab).
@@ -50,7 +51,12 @@ profile also each row alone; launched in turn --reps times after one warm-up eac
 launch, each single family (aid_mask 7; the magnetometer; aid_mask 7 with the scale-factor state; both standstill rows) and the
 combined launch with 15 states (aid_mask 7, magnetometer, standstill) and with 16 (and the scale-factor state), every block at every
 sample, launched in turn --reps times after one warm-up each.  Printed beside the ratios over the unaided launch: the combined
-launch's excess over the unaided launch against the sum of the excesses of the single families it replaces."""
+launch's excess over the unaided launch against the sum of the excesses of the single families it replaces.
+
+--combined-cons: the consistency checkpoints of csrc/ins_loose_all_cons.hip on --cons' case, statistics only: the
+combined 16-state launch (aid_mask 7, magnetometer, scale-factor state, standstill, every block at every sample) without checkpoints
+(loose_all_kernel), and loose_all_cons_kernel with a checkpoint every 100 samples and with one at every sample, launched in turn
+--reps times after one warm-up each.  A checkpoint's cost is printed in steps of the launch without, as --cons prints it."""
 import argparse
 import json
 import os
@@ -367,6 +373,52 @@ def time_combined(runs, reps):
     return out
 
 
+def time_combined_cons(runs, reps):
+    """{leg: {'kernel', 'checkpoints', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the combined 16-state launch without checkpoints,
+    with one every 100 samples and with one at every sample, interleaved; and what one checkpoint costs, in steps of the first."""
+    import numpy as np
+    import ginsim
+    from ginsim import workloads
+    fs, fs_gps, rf, geo = 100.0, 10.0, 1, (30.0, -3.0, 40.0)
+    ini, seg = workloads.parse_motion(workloads.profile_path('turn_90deg'))
+    raw = ginsim.pathgen(ini, seg, fs, fs_gps, workloads.HIGH_MOBILITY, rf, gps=True, geo_mag_n=geo)
+    n = int(raw['imu'].shape[0])
+    truth = {'ref_accel': np.ascontiguousarray(raw['imu'][:, 1:4]), 'ref_gyro': np.ascontiguousarray(raw['imu'][:, 4:7]),
+             'ref_pos': np.ascontiguousarray(raw['nav'][:, 1:4]), 'ref_vel': np.ascontiguousarray(raw['nav'][:, 4:7]),
+             'ref_att': np.ascontiguousarray(raw['nav'][:, 7:10]), 'ref_gps': np.ascontiguousarray(raw['gps'][:, 1:7]),
+             'gps_time': raw['gps'][:, 0] / fs, 'gps_visibility': raw['gps'][:, 7].copy(),
+             'ref_odo': np.ascontiguousarray(raw['odo'][:n, 2]), 'ref_mag': np.ascontiguousarray(raw['mag'][:n, 1:4])}
+    acc, gyr = workloads.imu_grade('mid-accuracy')
+    gps_err = {'stdp': np.array([5.0, 5.0, 7.0]), 'stdv': np.array([0.05, 0.05, 0.05])}
+    every = dict(odo_err={'scale': 0.99, 'stdv': 0.1}, aid={'odo': True, 'nhc': True, 'every': 1}, odo_scale_state={}, still={}, combined=True,
+                 mag_err={'si': np.eye(3), 'hi': np.zeros(3), 'std': np.array([0.01, 0.01, 0.01])}, geo_mag_n=geo, mag={'every': 1})
+    ctx = ginsim.Context(0)
+    out = {'device': ctx.name(), 'runs': runs, 'samples': n, 'fixes': int(truth['ref_gps'].shape[0]), 'library': os.path.basename(ginsim.LIB_PATH)}
+    legs = [('no_checkpoints', None), ('every_100_samples', np.arange(0, n, 100)), ('every_sample', np.arange(n))]
+    jobs = [(label, ginsim.InsLooseJob(ctx, fs, rf, truth, acc, gyr, gps_err, ini, runs, seed=1, keep_traj=False, checkpoints=c, **every))
+            for label, c in legs]
+    ms = {label: [] for label, _ in jobs}
+    for _, job in jobs:
+        job.run()                                       # warm-up: code object, LDS attribute
+    for _ in range(reps):
+        for label, job in jobs:
+            ctx.timer_begin()
+            job.launch()
+            ms[label].append(ctx.timer_end())
+    for (label, job), (_, c) in zip(jobs, legs):
+        t = ms[label]
+        out[label] = {'kernel': job.kernel_name(), 'checkpoints': 0 if c is None else int(c.size), 'ms_median': float(np.median(t)),
+                      'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)), 'ms_all': [float(x) for x in t]}
+        job.release()
+    step_ms = out['no_checkpoints']['ms_median'] / (n - 1)
+    for label, _ in jobs[1:]:
+        r = out[label]
+        r['over_no_checkpoints'] = r['ms_median'] / out['no_checkpoints']['ms_median']
+        r['checkpoint_cost_in_steps'] = (r['ms_median'] - out['no_checkpoints']['ms_median']) / r['checkpoints'] / step_ms
+    ctx.close()
+    return out
+
+
 def time_cons(runs, reps):
     """{leg: {'kernel', 'checkpoints', 'ms_median', 'ms_min', 'ms_max', 'ms_all'}} of the unaided launch without checkpoints, with one
     every 100 samples and with one at every sample, interleaved; and what one checkpoint costs, in steps."""
@@ -414,6 +466,7 @@ def main():
     ap.add_argument('--odo-scale', action='store_true', help='the scale-factor leg: aid_mask 7 with 15 and with 16 states, aid_every 1 and 10')
     ap.add_argument('--still', action='store_true', help='the standstill leg: unaided and ZUPT / ZARU on the 90-degree turn and on the stops profile')
     ap.add_argument('--combined', action='store_true', help='every aid in one launch, with 15 and with 16 states, beside the unaided launch and each single family, on the 90-degree turn and on the stops profile')
+    ap.add_argument('--combined-cons', action='store_true', help='the checkpoints of the combined 16-state launch: none, one every 100 samples, one at every sample')
     ap.add_argument('--runs', type=int, default=65536)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ops', type=int, default=0, help='fp64 instructions per step, instead of the count from the ISA')
@@ -423,8 +476,8 @@ def main():
         for k, (n, f, span) in sorted(isa_counts().items()):
             print('%s: %d fp64 VALU instructions (%d fused multiply-adds) in a time loop of %d lines' % (k, n, f, span))
         return
-    if a.aided or a.cons or a.mag or a.odo_scale or a.still or a.combined:
-        res = time_combined(a.runs, a.reps) if a.combined else time_still(a.runs, a.reps) if a.still else time_scale(a.runs, a.reps) if a.odo_scale else time_mag(a.runs, a.reps) if a.mag else time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
+    if a.aided or a.cons or a.mag or a.odo_scale or a.still or a.combined or a.combined_cons:
+        res = time_combined_cons(a.runs, a.reps) if a.combined_cons else time_combined(a.runs, a.reps) if a.combined else time_still(a.runs, a.reps) if a.still else time_scale(a.runs, a.reps) if a.odo_scale else time_mag(a.runs, a.reps) if a.mag else time_cons(a.runs, a.reps) if a.cons else time_aided(a.runs, a.reps, a.unaided_only)
         print(json.dumps(res))
         if a.out:
             with open(a.out, 'w') as f:
