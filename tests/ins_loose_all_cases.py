@@ -1,7 +1,9 @@
 """Shared inputs of the tests of InsLoose with all its aids in one launch (tests/test_ins_loose_all_oracle.py on the CPU,
 tests/test_gpu_ins_loose_all.py on the device): the stops profiles' truth with the magnetometer's, every block's numbers, the draw of
 the consistency test and the ratios it measures and records; and the schedule case of tests/test_ins_loose_all_schedule_oracle.py and
-tests/test_gpu_ins_loose_all_schedule.py: a period per block, the count of what fires on every sample, its standstill signal."""
+tests/test_gpu_ins_loose_all_schedule.py: a period per block, the count of what fires on every sample, its standstill signal; and the two choices of
+tests/test_gpu_ins_loose_all_cons_edges.py that tests/test_ins_loose_all_cons_oracle.py holds without a GPU: the checkpoints of the tilted
+stops profile (edge_checkpoints) and a truth of the scale factor with two non-finite entries (bad_scale_truth)."""
 import functools
 
 import numpy as np
@@ -126,6 +128,42 @@ def schedule_flags(truth, stamps, n=SCHEDULE_N):
     assert hidden.size and all(int(hidden[0]) <= j < n for j in OUTAGE_FLAGS)
     flags[list(OUTAGE_FLAGS)] = 1
     return flags
+
+
+def edge_checkpoints(ini, truth, stamps, flags, every=SCHEDULE):
+    """The checkpoints of the tilted stops profile (tests/test_gpu_ins_loose_all_cons_edges.py, held on the CPU by
+    tests/test_ins_loose_all_cons_oracle.py), each from the truth and asserted to exist: samples 0 and 1, the last flagged sample of
+    the first standstill window, the first sample at which the truth's yaw has wrapped through +-180 deg, a sample inside the GPS
+    outage at which the standstill block fires and no fix is applied, a sample at which fix, aiding, magnetometer and standstill
+    block all fire, and the last two.  Asserts the profile's preconditions: a southern latitude, |pitch| of 10 deg and more, two
+    standstill windows, one outage.  Returns the sorted list (eight samples)."""
+    n = truth['ref_accel'].shape[0]
+    att, visible, stamps = np.asarray(truth['ref_att']), np.asarray(truth['gps_visibility']), np.asarray(stamps)
+    assert ini[0] < 0.0, 'the profile lies south of the equator'
+    assert np.max(np.abs(att[:, 1])) >= np.radians(10.0)
+    win = sc.windows(flags)
+    assert len(win) == 2, win
+    hidden = np.nonzero(visible == 0)[0]
+    assert hidden.size and np.array_equal(hidden, np.arange(hidden[0], hidden[-1] + 1)) and hidden[-1] + 1 < stamps.size      # one outage
+    first, after = int(stamps[hidden[0]]), int(stamps[hidden[-1] + 1])
+    assert first <= win[1][0] and win[1][1] < after                             # the second stop lies inside it
+    wrap = np.nonzero(np.abs(np.diff(att[:, 0])) > np.pi)[0]
+    assert wrap.size
+    fires = schedule(n, every, stamps, visible, flags)
+    j = np.arange(n)
+    blind = np.nonzero((fires & STILL != 0) & (fires & FIX == 0) & (j >= first) & (j < after))[0]
+    meet = np.nonzero(fires == FIX | AID | MAG | STILL)[0]
+    assert blind.size and meet.size
+    samples = sorted({0, 1, int(win[0][1]), int(wrap[0]) + 1, int(blind[0]), int(meet[0]), n - 2, n - 1})
+    assert len(samples) == 8 and flags[win[0][1]] != 0
+    return samples
+
+
+def bad_scale_truth(runs=65):
+    """A truth of the scale factor that excludes exactly two runs from every checkpoint: NaN in run 7, +inf in run 40."""
+    truth = np.full(runs, READS)
+    truth[7], truth[40] = np.nan, np.inf
+    return truth
 
 
 def deviation(a, b):

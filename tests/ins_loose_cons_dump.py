@@ -1,5 +1,6 @@
 """The checkpoint record of an InsLoose job against the restatement of a dump (test infrastructure; no test in it, imported by tests
-only): tests/test_gpu_ins_loose_cons.py and tests/test_gpu_ins_loose_attitude.py on an ins_loose_dump.Dump that has an odometer."""
+only): tests/test_gpu_ins_loose_cons.py, tests/test_gpu_ins_loose_attitude.py and the vibration cases of
+tests/test_gpu_ins_loose_all_cons_edges.py on an ins_loose_dump.Dump that has an odometer."""
 import numpy as np
 
 import ins_loose_aided_cases as ac

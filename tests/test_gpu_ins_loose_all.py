@@ -48,14 +48,14 @@ class Dump(ins_loose_dump.Dump):
                          vib=vib, mag_errs=(('m', mag_err),), flags=sc.flags_of)
         self._restated = {}
 
-    def _case(self, which, mask, every, flags):
+    def _case(self, which, mask, every, flags, q=0.0):
         return dict(mask=mask, mag=self.mag_errs['m'] if 'mag' in which else None, scale='scale' in which, smask=3 if 'still' in which else 0,
-                    every=every, geo=self.geo, flags=flags)
+                    every=every, geo=self.geo, flags=flags, q=q)
 
-    def job(self, ctx, which=ALL, mask=ls.MASK, every=1, given=False, runs=None, flags=None, combined=True, mag_every=None, **kw):
+    def job(self, ctx, which=ALL, mask=ls.MASK, every=1, given=False, runs=None, flags=None, combined=True, mag_every=None, q=0.0, **kw):
         """which: the blocks of {'mag', 'scale', 'still'} the job holds.  flags None: the job derives the signal from the truth.
-        mag_every: the magnetometer's own period where it is not `every`."""
-        case = ls.job_kw(keep=kw.get('keep_traj', True), **self._case(which, mask, every, flags))
+        mag_every: the magnetometer's own period where it is not `every`.  q: the scale state's random walk [1/sqrt(s)]."""
+        case = ls.job_kw(keep=kw.get('keep_traj', True), **self._case(which, mask, every, flags, q))
         if mag_every is not None:
             case['mag'] = {'every': mag_every}
         if combined is not None:

@@ -43,10 +43,10 @@ def cons_name(rf, which, given=False):
     return NAME % (rf, str(given).lower(), 16 if 'scale' in which else 15)
 
 
-def restated(d, which, samples, mask=ls.MASK, every=1, flags=None, runs=None, accel=None, dtype=np.float64, scale_truth=None):
-    """The restatement's record of Dump d over `runs` (None: all) at `samples`."""
+def restated(d, which, samples, mask=ls.MASK, every=1, flags=None, runs=None, accel=None, dtype=np.float64, scale_truth=None, q=0.0):
+    """The restatement's record of Dump d over `runs` (None: all) at `samples`.  q: the scale state's random walk [1/sqrt(s)]."""
     r = np.arange(d.runs) if runs is None else np.asarray(runs)
-    kw = ls.blocks(d.model, d.fs, d.rf, **d._case(which, mask, every, d.flags if flags is None else flags))
+    kw = ls.blocks(d.model, d.fs, d.rf, **d._case(which, mask, every, d.flags if flags is None else flags, q))
     kw.update(odo=d.odo[r], mag=d.mag['m'][r] if 'mag' in which else None)
     if scale_truth is not None and np.ndim(scale_truth):
         scale_truth = np.asarray(scale_truth)[r]

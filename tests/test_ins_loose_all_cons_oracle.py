@@ -2,7 +2,9 @@
 dispatch, the build's resource reports of loose_all_cons_kernel, the job's keyword (checkpoints=, scale_truth=), the restatement
 (tests/ins_loose_all_cons_ref.py) against the restatement of the 15-state record, against a direct evaluation of the scale columns
 and against the recorded consistency ratios of the combined filter (ins_loose_all_cases.CONSISTENCY_RATIOS), which it reproduces
-in ONE run with two checkpoints where the table took two truncated runs and their kept trajectories."""
+in ONE run with two checkpoints where the table took two truncated runs and their kept trajectories; and the cases
+tests/test_gpu_ins_loose_all_cons_edges.py chooses (the tilted stops profile's checkpoints, a non-finite truth of the scale factor) on the
+restatement alone."""
 import ctypes
 import itertools
 import os
@@ -400,3 +402,65 @@ def test_one_run_with_two_checkpoints_reproduces_the_recorded_ratios_of_the_comb
     for k, tag in enumerate(('stop', 'end')):
         np.testing.assert_allclose(m['ratio'][k], ls.CONSISTENCY_RATIOS[tag][:9], rtol=0, atol=2e-3)
         np.testing.assert_allclose(m['ratio_scale'][k], ls.CONSISTENCY_RATIOS[tag][15], rtol=0, atol=2e-3)
+
+
+# ------------------------------------------------------------------------------------------------- the cases of the edges file
+def host_draw(rf, n, R, profile, geo, seed):
+    """R runs of a stops profile at 20 Hz, every sensor drawn on the host from the model (as `small`); the odometer reads ls.READS."""
+    from ginsim.ins_loose import filter_model
+    ini, truth, stamps = ls.stops_truth(20.0, rf, 2.0, n, profile, geo)
+    n = truth['ref_accel'].shape[0]
+    acc_e, gyr_e = cs.imu_errors()
+    rng = np.random.default_rng(seed)
+    accel, gyro, _, _ = ref.sample_sensors(rng, 20.0, truth['ref_accel'], truth['ref_gyro'], acc_e, gyr_e, R)
+    gps = cs.sample_gps(rng, truth, rf, R)
+    odo = ls.READS * np.asarray(truth['ref_odo'])[None] + ls.ODO_ERR['stdv'] * rng.standard_normal((R, n))
+    mag = ref.sample_mag(rng, truth['ref_mag'], mc.MAG_ERR_SKEW, R)
+    model = filter_model(20.0, acc_e, gyr_e, cs.GPS_ERR)
+    nav = np.concatenate([truth['ref_att'], truth['ref_pos'], truth['ref_vel']], axis=1)
+    return {'rf': rf, 'n': n, 'ini': ini, 'truth': truth, 'stamps': stamps, 'model': model, 'flags': sc.flags_of(truth), 'odo': odo, 'mag': mag,
+            'nav': nav, 'head': (rf, 20.0, gyro, accel, ini, model), 'tail': (gps, stamps, truth['gps_visibility'])}
+
+
+@pytest.mark.parametrize('rf', [0, 1])
+def test_the_checkpoints_of_the_tilted_stops_profile_exist_and_exclude_no_run(rf):
+    """What tests/test_gpu_ins_loose_all_cons_edges.py chooses on the tilted stops profile (41 S, parked on a slope, yaw through +-180
+    deg), without a GPU: ls.edge_checkpoints asserts the profile's preconditions and that every named sample exists; here each of them
+    is shown again from the truth, and the float64 restatement alone, on 8 host-drawn runs with every block at ls.SCHEDULE's periods,
+    includes all 8 at every one of them -- a count below the run count on the device is then the device's."""
+    ini, truth, stamps = ls.stops_truth(20.0, rf, 2.0, None, sc.TILTED_STOPS_CSV, mc.GEO_SOUTH)
+    n = truth['ref_accel'].shape[0]
+    flags = sc.flags_of(truth)
+    samples = ls.edge_checkpoints(ini, truth, stamps, flags)
+    print('tilted stops rf%d: n %d, checkpoints %s, standstill windows %s' % (rf, n, samples, sc.windows(flags)))
+    assert n == 960 and ini[0] < 0 and np.degrees(np.max(np.abs(truth['ref_att'][:, 1]))) >= 10.0
+    assert len(sc.windows(flags)) == 2 and samples[:2] == [0, 1] and samples[-2:] == [n - 2, n - 1]
+    fires = ls.schedule(n, ls.SCHEDULE, stamps, truth['gps_visibility'], flags)
+    yaw = truth['ref_att'][:, 0]
+    assert any(fires[j] == ls.FIX | ls.AID | ls.MAG | ls.STILL for j in samples)
+    assert any(fires[j] & ls.STILL and not fires[j] & ls.FIX and sc.windows(flags)[1][0] <= j <= sc.windows(flags)[1][1] for j in samples)
+    assert any(abs(yaw[j] - yaw[j - 1]) > np.pi for j in samples[1:])
+    assert sc.windows(flags)[0][1] in samples and flags[sc.windows(flags)[0][1] + 1] == 0
+    c = host_draw(rf, None, 8, sc.TILTED_STOPS_CSV, mc.GEO_SOUTH, 7)
+    kw = ls.blocks(c['model'], 20.0, rf, ls.MASK, mc.MAG_ERR_SKEW, True, 3, every=ls.SCHEDULE, geo=mc.GEO_SOUTH, flags=flags)
+    rec = acons.run(*c['head'], c['nav'], samples, *c['tail'], odo=c['odo'], mag=c['mag'], scale_truth=ls.READS, **kw)
+    assert rec.shape == (8, 43) and np.all(rec[:, 0] == 8) and np.all(np.isfinite(rec)) and np.all(rec[2:, 38] > 0)
+
+
+def test_a_non_finite_truth_of_the_scale_factor_excludes_exactly_its_two_runs():
+    """ls.bad_scale_truth (NaN in run 7, +inf in run 40) on 65 host-drawn runs of the level stops profile: the restatement alone counts
+    63 at every checkpoint of the device test's list, and its sums are those over the other 63 runs."""
+    samples = [50, 100, 101, 200, 299]
+    c = host_draw(1, 300, 65, sc.STOPS_CSV, mc.GEO, 8)
+    kw = ls.blocks(c['model'], 20.0, 1, ls.MASK, mc.MAG_ERR_SKEW, True, 3, every=2, flags=c['flags'])
+    truth = ls.bad_scale_truth(65)
+    assert np.count_nonzero(~np.isfinite(truth)) == 2
+    rec = acons.run(*c['head'], c['nav'], samples, *c['tail'], odo=c['odo'], mag=c['mag'], scale_truth=truth, **kw)
+    assert np.all(rec[:, 0] == 63) and np.all(np.isfinite(rec))
+    keep = np.setdiff1d(np.arange(65), [7, 40])
+    head = c['head'][:2] + (c['head'][2][keep], c['head'][3][keep]) + c['head'][4:]
+    part = acons.run(*head, c['nav'], samples, c['tail'][0][keep], *c['tail'][1:], odo=c['odo'][keep], mag=c['mag'][keep],
+                     scale_truth=truth[keep], **kw)
+    assert np.array_equal(part[:, 0], rec[:, 0]) and np.allclose(part, rec, rtol=1e-12, atol=0)
+    clean = acons.run(*c['head'], c['nav'], samples, *c['tail'], odo=c['odo'], mag=c['mag'], scale_truth=ls.READS, **kw)
+    assert np.all(clean[:, 0] == 65)
