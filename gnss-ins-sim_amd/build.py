@@ -95,7 +95,11 @@ SOURCES = [
     ('placed.hip', ['--offload-arch=' + ARCH]),
     ('vib_psd.hip', ['--offload-arch=' + ARCH]),
     ('selftest.hip', ['--offload-arch=' + ARCH]),
+    # the C ABI glue, host code only: the core and its three areas (api_common.hpp is what they share)
     ('ginsim_api.hip', ['--offload-arch=' + ARCH]),
+    ('api_series.hip', ['--offload-arch=' + ARCH]),
+    ('api_mc.hip', ['--offload-arch=' + ARCH]),
+    ('api_traj.hip', ['--offload-arch=' + ARCH]),
     # host-only truth generator; no fused multiply-adds (see the file header)
     ('pathgen.cpp', ['-x', 'c++', '-ffp-contract=off']),
     # RCCL behind the C ABI (host code; librccl is dlopen()ed at run time, nothing is linked)
@@ -116,14 +120,9 @@ def build(force=False, verbose=False, tag=None, defines=(), xflags=()):
         LIB = os.path.join(HERE, 'lib', 'libginsim_%s.so' % tag)
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hpp', '.h', '.inc'))]
-    deps.append(os.path.join(REPO, 'include', 'ginsim.h'))
-    deps.append(os.path.join(REPO, 'include', 'ginsim_oallan.h'))
-    deps.append(os.path.join(REPO, 'include', 'ginsim_psd.h'))
-    deps.append(os.path.join(REPO, 'include', 'ginsim_lpsd.h'))
-    deps.append(os.path.join(REPO, 'include', 'ginsim_csd.h'))
-    deps.append(os.path.join(REPO, 'include', 'ginsim_loose_all.h'))
-    deps.append(os.path.join(REPO, 'include', 'ginsim_loose_all_cons.h'))
+    # every header there is, private and public, found by pattern: a new one needs no line here to rebuild what includes it
+    deps = [os.path.join(d, f) for d, ends in ((CSRC, ('.hpp', '.h', '.inc')), (os.path.join(REPO, 'include'), ('.h',)))
+            for f in sorted(os.listdir(d)) if f.endswith(ends)]
     deps.append(os.path.abspath(__file__))
     objs = []
     for src, extra in SOURCES:

@@ -1,4 +1,4 @@
-// Launch interface of the Allan-variance kernels (allan.hip) for the C ABI glue (ginsim_api.hip).
+// Launch interface of the Allan-variance kernels (allan.hip) for the C ABI glue (api_series.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// Planning code and launch interface of the Welch cross-spectral-density kernels (csd.hip) for the C ABI glue (ginsim_api.hip).
+// Planning code and launch interface of the Welch cross-spectral-density kernels (csd.hip) for the C ABI glue (api_series.hip).
 // A pair of series is partitioned exactly as psd.hpp partitions one series -- psd_plan_shape(n, L, D), the same segs_per_part, a
 // function of (L, D) alone -- and a workgroup has psd.hip's size and LDS arrays; what differs is the record, four planes per part,
 // and the pair table that goes to the device behind the records.

@@ -25,7 +25,7 @@
 // registers.
 // What loose_aided_kernel (ins_loose_aided.hip) shares with this file -- Cov, the propagation, the correction, the time loop -- is
 // in ins_loose.hpp; the host side that launches an instantiation of either, or of loose_cons_kernel (ins_loose_cons.hip), is
-// launch_loose_family (loose_launch.hpp) on the file's trait; which family a launch takes is decided in ginsim_api.hip (launch_loose).
+// launch_loose_family (loose_launch.hpp) on the file's trait; which family a launch takes is decided in api_mc.hip (launch_loose).
 #include <hip/hip_runtime.h>
 #include "ginsim.h"
 #include "ins_loose.hpp"

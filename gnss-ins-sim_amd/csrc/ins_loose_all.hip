@@ -23,7 +23,7 @@
 
 namespace ginsim {
 
-// two or three of L.mag, L.scale and L.still are set (ginsim_api.hip checks each block as its own family does); with L.scale the
+// two or three of L.mag, L.scale and L.still are set (api_mc.hip checks each block as its own family does); with L.scale the
 // launch is ins_loose_all16.hip's
 hipError_t launch_loose_all(const LooseLaunch& L) { return L.scale ? launch_loose_all16(L) : launch_loose_all_ns<kLooseStates>(L); }
 

@@ -6,7 +6,7 @@
 
 namespace ginsim {
 
-// L.scale is set and L.b->aid_mask has bit 0 (ginsim_api.hip checks it)
+// L.scale is set and L.b->aid_mask has bit 0 (api_mc.hip checks it)
 hipError_t launch_loose_all16(const LooseLaunch& L) { return launch_loose_all_ns<kLooseScaleStates>(L); }
 
 }  // namespace ginsim

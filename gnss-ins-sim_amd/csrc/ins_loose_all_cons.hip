@@ -24,7 +24,7 @@
 
 namespace ginsim {
 
-// L.cons is set; any of L.mag, L.scale and L.still (ginsim_api.hip checks each block as its own family does); with L.scale the
+// L.cons is set; any of L.mag, L.scale and L.still (api_mc.hip checks each block as its own family does); with L.scale the
 // launch is ins_loose_all_cons16.hip's
 hipError_t launch_loose_all_cons(const LooseLaunch& L) {
     return L.scale ? launch_loose_all_cons16(L) : launch_loose_all_cons_ns<kLooseStates>(L);

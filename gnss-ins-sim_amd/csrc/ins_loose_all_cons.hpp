@@ -37,7 +37,7 @@ struct AllConsFamily {
 };
 
 // The launch, or the name, of the instantiation with NS states, then cons_final_kernel: the blocks L has one after the other, an
-// absent one all zero, as launch_loose_all_ns; L.cons->cons_m > 0 (ginsim_api.hip checks it)
+// absent one all zero, as launch_loose_all_ns; L.cons->cons_m > 0 (api_mc.hip checks it)
 template <int NS>
 hipError_t launch_loose_all_cons_ns(const LooseLaunch& L) {
     ginsim_loose_all_params g;

@@ -7,7 +7,7 @@
 
 namespace ginsim {
 
-// L.cons and L.scale are set and L.b->aid_mask has bit 0 (ginsim_api.hip checks it)
+// L.cons and L.scale are set and L.b->aid_mask has bit 0 (api_mc.hip checks it)
 hipError_t launch_loose_all_cons16(const LooseLaunch& L) { return launch_loose_all_cons_ns<kLooseScaleStates>(L); }
 
 }  // namespace ginsim

@@ -54,7 +54,7 @@ struct ConsFamily {
     template <int RF, bool GIVEN, bool VIB, bool AID> static constexpr auto kernel = &loose_cons_kernel<RF, GIVEN, VIB, AID>;
 };
 
-// L.cons->cons_m > 0 (ginsim_api.hip checks it and takes cons_m == 0 for no checkpoint block)
+// L.cons->cons_m > 0 (api_mc.hip checks it and takes cons_m == 0 for no checkpoint block)
 hipError_t launch_loose_cons(const LooseLaunch& L) {
     const ginsim_loose_cons_params& c = *L.cons;
     const hipError_t e = launch_loose_family<ConsFamily>(L, L.b->aid_mask != 0, ConsArgs{L.samples, c.cons_m, c.cons_work});

@@ -46,7 +46,7 @@ struct MagFamily {
     template <int RF, bool GIVEN, bool VIB, bool PS> static constexpr auto kernel = &loose_mag_kernel<RF, GIVEN, VIB, PS>;
 };
 
-// L.mag->mag_every > 0 (ginsim_api.hip checks it and takes mag_every == 0 for no magnetometer block)
+// L.mag->mag_every > 0 (api_mc.hip checks it and takes mag_every == 0 for no magnetometer block)
 hipError_t launch_loose_mag(const LooseLaunch& L) { return launch_loose_family<MagFamily>(L, L.b->out_proc != nullptr, *L.mag); }
 
 }  // namespace ginsim

@@ -47,7 +47,7 @@ struct ScaleFamily {
     template <int RF, bool GIVEN, bool VIB, bool PS> static constexpr auto kernel = &loose_scale_kernel<RF, GIVEN, VIB, PS>;
 };
 
-// L.b->aid_mask has bit 0 (ginsim_api.hip checks it)
+// L.b->aid_mask has bit 0 (api_mc.hip checks it)
 hipError_t launch_loose_scale(const LooseLaunch& L) { return launch_loose_family<ScaleFamily>(L, L.b->out_proc != nullptr, *L.scale); }
 
 }  // namespace ginsim

@@ -52,7 +52,7 @@ struct StillFamily {
     template <int RF, bool GIVEN, bool VIB, bool PS> static constexpr auto kernel = &loose_still_kernel<RF, GIVEN, VIB, PS>;
 };
 
-// L.still->still_mask != 0 (ginsim_api.hip checks the block and takes still_mask == 0 for no standstill block)
+// L.still->still_mask != 0 (api_mc.hip checks the block and takes still_mask == 0 for no standstill block)
 hipError_t launch_loose_still(const LooseLaunch& L) { return launch_loose_family<StillFamily>(L, L.b->out_proc != nullptr, *L.still); }
 
 }  // namespace ginsim

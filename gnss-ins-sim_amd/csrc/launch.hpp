@@ -1,6 +1,6 @@
-// The host interface between the kernel files and the C ABI glue (ginsim_api.hip): every launcher and host helper that one
-// file defines and another calls, grouped by the file that defines it, and the structs that describe a launch to them (LooseLaunch,
-// TrajView).  Every defining file includes it, and the library is linked without undefined symbols, so a signature that drifts
+// The host interface between the kernel files and the C ABI glue (ginsim_api.hip and its api_*.hip units): every launcher and
+// host helper that one file defines and another calls, grouped by the file that defines it, and the structs that describe a launch
+// to them (LooseLaunch, TrajView).  Every defining file includes it, and the library is linked without undefined symbols, so a signature that drifts
 // from its definition fails the build.  (allan.hpp, comm.hpp and placed.hpp are the same thing for their files.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,12 +32,12 @@ hipError_t launch_series(const ginsim_mc_params& p, double* carry, hipStream_t s
 hipError_t launch_incl(const ginsim_mc_params& p, const ginsim_incl_params& b, hipStream_t stream, char* name, size_t cap);
 int incl_variant(const ginsim_mc_params& p);
 
-// One launch of the loose family, as ginsim_api.hip (loose_entry) describes it to the family's launcher.
+// One launch of the loose family, as api_mc.hip (loose_entry) describes it to the family's launcher.
 struct LooseLaunch {
     const ginsim_mc_params* mc;                 // the two base blocks, checked
     const ginsim_loose_params* b;
     const ginsim_loose_cons_params* cons;       // the family blocks, checked: NULL when absent or degenerate (cons_m == 0,
-    const ginsim_loose_mag_params* mag;         // mag_every == 0); launch_loose (ginsim_api.hip) picks the family from them
+    const ginsim_loose_mag_params* mag;         // mag_every == 0); launch_loose (api_mc.hip) picks the family from them
     const ginsim_loose_scale_params* scale;
     const ginsim_loose_still_params* still;     // NULL when absent or degenerate (still_mask == 0)
     char* name; size_t cap;                     // name != NULL: report the kernel's name into name[cap], do not launch
@@ -100,6 +100,7 @@ hipError_t launch_gather_runs_f32(const float* series, int C, int64_t n, int64_t
 hipError_t launch_pattern_fill(void* p, uint64_t words, uint32_t tag, hipStream_t s);
 hipError_t launch_pattern_check(const void* p, uint64_t words, uint32_t tag, unsigned long long* out, hipStream_t s);
 hipError_t launch_digest(const void* p, uint64_t words, unsigned long long* out, hipStream_t s);
+hipError_t launch_first_xcc(uint32_t* out, hipStream_t s);
 
 // The series of the fp32 kernel hold the DISPLACEMENT from the run's initial position in their position planes
 // (ginsim_mc_params.precision), so the position of a sample is origin[run's initial state] + displacement, formed in fp64;

@@ -1,4 +1,4 @@
-// Planning code and launch interface of the decimating octave cascade (lpsd.hip) for the C ABI glue (ginsim_api.hip).
+// Planning code and launch interface of the decimating octave cascade (lpsd.hip) for the C ABI glue (api_series.hip).
 // As in psd.hpp, everything a call's shape depends on is host arithmetic in this header: ginsim_lpsd launches from lpsd_plan_levels
 // and ginsim_lpsd_plan reports it.  The Welch estimate of every level is psd.hpp's, unchanged.
 #pragma once

@@ -1,4 +1,4 @@
-// Planning code and launch interface of the Welch power-spectral-density kernels (psd.hip) for the C ABI glue (ginsim_api.hip).
+// Planning code and launch interface of the Welch power-spectral-density kernels (psd.hip) for the C ABI glue (api_series.hip).
 // Everything a call's shape depends on is host arithmetic in this header: ginsim_psd_welch launches from psd_plan_shape and
 // ginsim_psd_plan reports it, and psd.hip sizes its workgroups and LDS arrays from the same constexpr functions.
 #pragma once

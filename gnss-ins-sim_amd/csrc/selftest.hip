@@ -8,6 +8,12 @@
 #include <cstdint>
 #include "launch.hpp"
 
+// The probe of ginsim_stream_first_xcc: where the FIRST workgroup of a launch on a stream lands, the accelerator complex die (XCD)
+// of an MI300 / MI355X.  C linkage, outside the namespace: the recorded profiles and kernel traces know it by this plain name.
+extern "C" __global__ void first_xcc_kernel(uint32_t* out) {
+    if (threadIdx.x == 0) out[0] = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xf;      // HW_REG_XCC_ID, bits 3:0
+}
+
 namespace ginsim {
 
 namespace {
@@ -101,6 +107,12 @@ hipError_t launch_pattern_check(const void* p, uint64_t words, uint32_t tag, uns
 hipError_t launch_digest(const void* p, uint64_t words, unsigned long long* out, hipStream_t s) {
     hipLaunchKernelGGL(selftest_reset_kernel, dim3(1), dim3(64), 0, s, out);
     hipLaunchKernelGGL(digest_kernel, dim3(blocks_for(words)), dim3(TB), 0, s, (const uint64_t*)p, words, out);
+    return hipGetLastError();
+}
+
+// out: one device word, the die's number
+hipError_t launch_first_xcc(uint32_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(first_xcc_kernel, dim3(1), dim3(64), 0, s, out);
     return hipGetLastError();
 }
 

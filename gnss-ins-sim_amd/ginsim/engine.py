@@ -1314,15 +1314,21 @@ def allan_plan(x, n, nseries, series_stride, fs):
                       for l in lv[:nl.value]]
 
 
-def allan_var_host(ctx, series, fs):
-    """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (avar, tau)."""
+def _on_uploaded(ctx, series, call, squeeze=True):
+    """What the ``*_host`` functions of the series analyses do: series (n,) or (S, n) uploaded as rows, ``call(buf, n, S)`` on the
+    device copy, the copy freed.  With `squeeze`, the first result of a 1-D input loses its series axis."""
     a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
     buf = ctx.upload(a)
     try:
-        avar, tau = allan_var(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs)
+        res = call(buf, a.shape[1], a.shape[0])
     finally:
         buf.free()
-    return (avar[0], tau) if np.ndim(series) == 1 else (avar, tau)
+    return (res[0][0],) + tuple(res[1:]) if squeeze and np.ndim(series) == 1 else res
+
+
+def allan_var_host(ctx, series, fs):
+    """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (avar, tau)."""
+    return _on_uploaded(ctx, series, lambda buf, n, S: allan_var(ctx, buf, n, S, n, fs))
 
 
 def oallan_var(ctx, x, n, nseries, series_stride, fs, cap=128):
@@ -1356,13 +1362,7 @@ def oallan_plan(x, n, nseries, series_stride, fs):
 
 def oallan_var_host(ctx, series, fs):
     """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (oavar, tau)."""
-    a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
-    buf = ctx.upload(a)
-    try:
-        oavar, tau = oallan_var(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs)
-    finally:
-        buf.free()
-    return (oavar[0], tau) if np.ndim(series) == 1 else (oavar, tau)
+    return _on_uploaded(ctx, series, lambda buf, n, S: oallan_var(ctx, buf, n, S, n, fs))
 
 
 PSD_WINDOWS = ('boxcar', 'hann')        # ginsim_psd_welch's window 0..1
@@ -1401,13 +1401,7 @@ def welch_plan(n, nseries, series_stride, fs, nperseg, step=None):
 
 def welch_psd_host(ctx, series, fs, nperseg, step=None, window='hann', detrend=True):
     """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (psd, freq)."""
-    a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
-    buf = ctx.upload(a)
-    try:
-        psd, freq = welch_psd(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs, nperseg, step, window, detrend)
-    finally:
-        buf.free()
-    return (psd[0], freq) if np.ndim(series) == 1 else (psd, freq)
+    return _on_uploaded(ctx, series, lambda buf, n, S: welch_psd(ctx, buf, n, S, n, fs, nperseg, step, window, detrend))
 
 
 def decimate2(ctx, x, n, nseries, series_stride, y, y_stride):
@@ -1456,13 +1450,7 @@ def lpsd(ctx, x, n, nseries, series_stride, fs, nperseg, step=None, window='hann
 
 def lpsd_host(ctx, series, fs, nperseg, step=None, window='hann', detrend=True, min_segments=1):
     """Host arrays in: series (n,) or (S, n).  Uploads, runs the device kernels, returns (psd, freq, level)."""
-    a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
-    buf = ctx.upload(a)
-    try:
-        psd, freq, level = lpsd(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs, nperseg, step, window, detrend, min_segments)
-    finally:
-        buf.free()
-    return (psd[0], freq, level) if np.ndim(series) == 1 else (psd, freq, level)
+    return _on_uploaded(ctx, series, lambda buf, n, S: lpsd(ctx, buf, n, S, n, fs, nperseg, step, window, detrend, min_segments))
 
 
 class CsdResult:
@@ -1538,9 +1526,4 @@ def csd_plan(n, nseries, series_stride, fs, npairs, nperseg, step=None):
 
 def welch_csd_host(ctx, series, fs, pairs, nperseg, step=None, window='hann', detrend=True):
     """Host arrays in: series (S, n).  Uploads, runs the device kernels, returns the ``CsdResult`` of `pairs`."""
-    a = np.ascontiguousarray(np.atleast_2d(np.asarray(series, dtype=np.float64)))
-    buf = ctx.upload(a)
-    try:
-        return welch_csd(ctx, buf, a.shape[1], a.shape[0], a.shape[1], fs, pairs, nperseg, step, window, detrend)
-    finally:
-        buf.free()
+    return _on_uploaded(ctx, series, lambda buf, n, S: welch_csd(ctx, buf, n, S, n, fs, pairs, nperseg, step, window, detrend), squeeze=False)

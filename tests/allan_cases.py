@@ -4,7 +4,7 @@
 A plan is one tuple of modes per decade level, in the numbering of ginsim_allan_level.mode: L register-staged
 allan_level_kernel, P wave-pair LDS-DMA allan_pair_kernel, F0 / F1 allan_fused_kernel's two levels, T allan_tail_kernel.  The
 expected plans are written out, not computed: the constants they follow from (csrc/allan.hip: kChunk 2520, kDmaStage 2560,
-kFuseChunks 10; csrc/ginsim_api.hip: 1024 workgroups in one round, at most 16 chunks each, else total / 4096 capped at 8) are
+kFuseChunks 10; csrc/api_series.hip: 1024 workgroups in one round, at most 16 chunks each, else total / 4096 capped at 8) are
 what the table pins."""
 import numpy as np
 

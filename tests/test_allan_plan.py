@@ -1,5 +1,5 @@
 """Which kernel form an Allan call runs, without a device: ginsim_allan_plan is the planning code ginsim_allan launches from
-(csrc/ginsim_api.hip allan_plan), so this table pins the constants the GPU cases of test_gpu_allan_edges.py rely on -- kChunk
+(csrc/api_series.hip allan_plan), so this table pins the constants the GPU cases of test_gpu_allan_edges.py rely on -- kChunk
 2520, kDmaStage 2560, kFuseChunks 10, 1024 workgroups in a round, 16 chunks each, total / 4096 capped at 8, the 16-byte and
 stride-parity conditions of the LDS-DMA.  A retuned constant fails HERE, by name, and does not quietly turn a GPU case into a
 test of another kernel."""

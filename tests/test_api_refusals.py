@@ -1,5 +1,5 @@
 """CPU: what check_mc_params, check_incl_params, check_loose_params, check_loose_cons, check_loose_mag and check_loose_scale
-(csrc/ginsim_api.hip) refuse, in which order, and the dispatch table of the loose family -- through the name queries
+(csrc/api_mc.hip) refuse, in which order, and the dispatch table of the loose family -- through the name queries
 ginsim_mc_kernel_name, ginsim_incl_kernel_name, ginsim_loose_kernel_name, ginsim_loose_cons_kernel_name,
 ginsim_loose_mag_kernel_name and ginsim_loose_scale_kernel_name, which run the same checks as the launches and need no device.
 
