@@ -1,4 +1,5 @@
-"""An exact Welch cross-spectral density and the tolerance that follows from it (used by test_csd_oracle.py and test_gpu_csd.py).
+"""An exact Welch cross-spectral density and the tolerance that follows from it (used by test_csd_oracle.py and test_gpu_csd.py, and at the edges --
+the shapes of csd_edge_cases.py -- by test_csd_edges_oracle.py and test_gpu_csd_edges.py).
 
 With psd_exact's symbols, for series x and y of n samples, a segment length L (a power of two), a step D, a window w and a rate fs:
 
