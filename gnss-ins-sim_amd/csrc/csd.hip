@@ -8,7 +8,8 @@
 // then separates the two spectra per segment: with A = Z[k], B = conj(Z[L-k]), X = (A + B) / 2 and Y = (A - B) / (2i).  The four
 // sums are added from the separated X and Y -- never from |A|^2, |B|^2 and A conj(B) recombined at the end, which cancels when one
 // series is much smaller than the other.
-//   - load, balanced-tree means (one per series), cosine table, plane_slot swizzle and the radix-2 DIF stages are psd.hip's;
+//   - load, balanced-tree means (one per series), cosine table, the swizzled LDS planes (plane_slot) and the radix-2 stages but
+//     the last: welch_core.hpp, the code psd.hip runs;
 //   - the mirror bin: the transform leaves Z[k] at position rev(k) of the array.  Bins 0 .. L/2 - 1 are the EVEN positions 2j
 //     (k = rev(2j) has a clear top bit) and their mirrors L - k the odd ones; bin L/2 is position 1.  The last stage's butterfly j
 //     produces positions 2j and 2j + 1 in lane registers, so a lane keeps the even output -- its own bin -- and writes only the odd
@@ -23,78 +24,36 @@
 //   - accumulators: four per butterfly and lane in registers, and three more for bin L/2, which only thread 0 adds to.
 //   - at the end of the part the sums go to LDS by BIN (the four planes of L/2 sums fill the two planes of the transform) and
 //     from there to the record [pair][part][4][L/2 + 1] in coalesced rows.
-// Finish kernel: adds the parts' records in ascending order and scales.  No atomics: every sum has one fixed order, and a
-// pair's records depend on its two series alone.
+// Finish kernel: adds the parts' records in ascending order and scales (welch_core.hpp).  A pair's records depend on its two
+// series alone.
 #include "csd.hpp"
+#include "welch_core.hpp"
 
 namespace ginsim {
 
 namespace {
 
-__device__ inline int plane_slot(int i) { return i ^ (-((i >> 5) & 1) & 31); }
+using namespace welch;
 
 template <int L>
-struct CsdGeom {
-    static constexpr int T = csd_threads(L);
-    static constexpr int W = T / 64;
-    static constexpr int E = L / T > 1 ? L / T : 1;             // samples per lane, segment and series
-    static constexpr int B = L / 2 / T > 1 ? L / 2 / T : 1;     // butterflies per lane and stage
-};
-
-// cos(2 pi q / L) and sin(2 pi q / L) for 0 <= q <= L/2 from the quarter table
-template <int L>
-__device__ inline double table_cos(const double* C, int q) {
-    return q <= L / 4 ? C[psd_table_slot(q)] : -C[psd_table_slot(L / 2 - q)];
-}
-template <int L>
-__device__ inline double table_sin(const double* C, int q) {
-    return C[psd_table_slot(q <= L / 4 ? L / 4 - q : q - L / 4)];
-}
-
-// v[0 .. N) added as a balanced tree (N a power of two); v is left as it is
-template <int N>
-__device__ inline double tree_sum(const double (&v)[N]) {
-    if constexpr (N == 1) {
-        return v[0];
-    } else {
-        double h[N / 2];
-#pragma unroll
-        for (int i = 0; i < N / 2; ++i) h[i] = v[i] + v[i + N / 2];
-        return tree_sum(h);
-    }
-}
-
-__device__ inline double wave_tree(double a) {
-    for (int m = 32; m >= 1; m >>= 1) a += __shfl_xor(a, m, 64);
-    return a;
-}
-
-template <int L>
-__global__ void __launch_bounds__(CsdGeom<L>::T)
+__global__ void __launch_bounds__(Geom<L>::T)
 csd_part_kernel(const double* __restrict__ x, int64_t series_stride, const int32_t* __restrict__ pairs, int32_t D, int32_t window,
                 int32_t detrend, int64_t K, int32_t segs_per_part, int32_t nparts, double* __restrict__ records) {
-    using G = CsdGeom<L>;
-    constexpr int T = G::T, W = G::W, E = G::E, B = G::B, LOG2L = __builtin_ctz(L), NB = L / 2 + 1;
+    using G = Geom<L>;
+    constexpr int T = G::T, W = G::W, E = G::E, B = G::B, LOG2L = G::LOG2L, NB = L / 2 + 1;
     __shared__ double zz[2 * L];
     __shared__ double C[psd_table_doubles(L)];
     __shared__ double wave_tot[2 * W];
     double* const re = zz;
     double* const im = zz + L;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x;
     const int part = blockIdx.x;
     const int64_t pidx = blockIdx.y;
     const double* xs = x + (int64_t)pairs[2 * pidx] * series_stride;
     const double* ys = x + (int64_t)pairs[2 * pidx + 1] * series_stride;
 
-    for (int q = t; q <= L / 4; q += T) C[psd_table_slot(q)] = cospi(2.0 * (double)q / (double)L);
-    __syncthreads();
     double w[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = t + e * T;
-        w[e] = 1.0;
-        if (window == 1 && i < L) w[e] = 0.5 - 0.5 * table_cos<L>(C, i <= L / 2 ? i : L - i);
-    }
+    make_table_and_window<L>(C, window, w);
     // 4 sums per butterfly, of 2 X and 2 Y (the factor 4 leaves with the record); edge: bin L/2, thread 0 alone
     double acc[4 * B], edge[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -104,60 +63,10 @@ csd_part_kernel(const double* __restrict__ x, int64_t series_stride, const int32
     const int64_t s_begin = (int64_t)part * segs_per_part;
     const int64_t s_end = s_begin + segs_per_part < K ? s_begin + segs_per_part : K;
     for (int64_t s = s_begin; s < s_end; ++s) {
-        const double* pa = xs + s * D;                          // segment s: samples sD .. sD + L - 1 <= (K-1) D + L - 1 < n
-        const double* pb = ys + s * D;
-        double va[E], vb[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int i = t + e * T;
-            va[e] = i < L ? pa[i] : 0.0;
-            vb[e] = i < L ? pb[i] : 0.0;
-        }
-        double sa = wave_tree(tree_sum(va)), sb = wave_tree(tree_sum(vb));
-        if (W > 1) {
-            // the barrier also ends the previous segment's mirror reads of re / im
-            if (lane == 0) { wave_tot[2 * wv] = sa; wave_tot[2 * wv + 1] = sb; }
-            __syncthreads();
-            double qa[W], qb[W];
-#pragma unroll
-            for (int q = 0; q < W; ++q) { qa[q] = wave_tot[2 * q]; qb[q] = wave_tot[2 * q + 1]; }
-            sa = tree_sum(qa);
-            sb = tree_sum(qb);
-        }
-        bad = bad || !__builtin_isfinite(sa) || !__builtin_isfinite(sb);
-        const double ma = detrend ? sa * (1.0 / L) : 0.0, mb = detrend ? sb * (1.0 / L) : 0.0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int i = t + e * T;
-            if (i < L) {
-                re[plane_slot(i)] = (va[e] - ma) * w[e];
-                im[plane_slot(i)] = (vb[e] - mb) * w[e];
-            }
-        }
-        __syncthreads();
-        // the stages stay a loop, as in psd.hip: unrolled, their addresses are all hoisted and spilled
-#pragma unroll 1
-        for (int lh = LOG2L - 1; lh >= 1; --lh) {
-            const int h = 1 << lh;
-#pragma unroll
-            for (int b = 0; b < B; ++b) {
-                const int j = t + b * T;
-                if (j < L / 2) {
-                    const int pos = j & (h - 1);
-                    const int i0 = ((j - pos) << 1) + pos, i1 = i0 + h;
-                    const int p0 = plane_slot(i0), p1 = plane_slot(i1);
-                    const int q = pos << (LOG2L - 1 - lh);
-                    const double c = table_cos<L>(C, q), sn = table_sin<L>(C, q);
-                    const double ar = re[p0], ai = im[p0], br = re[p1], bi = im[p1];
-                    const double dr = ar - br, di = ai - bi;
-                    re[p0] = ar + br;
-                    im[p0] = ai + bi;
-                    re[p1] = dr * c + di * sn;                  // (dr + i di) (c - i sn)
-                    im[p1] = di * c - dr * sn;
-                }
-            }
-            __syncthreads();
-        }
+        // segment s: samples sD .. sD + L - 1 <= (K-1) D + L - 1 < n; the load's first barrier also ends the previous segment's
+        // mirror reads of re / im
+        load_rows<L>(xs + s * D, ys + s * D, true, detrend, w, re, im, wave_tot, bad);
+        dif_stages<L>(re, im, C);
         // last stage (twiddle 1): the even output Z[rev(2j)] stays here, the odd one goes back for the lane whose mirror it is
         double er[B], ei[B];
 #pragma unroll
@@ -231,41 +140,23 @@ csd_part_kernel(const double* __restrict__ x, int64_t series_stride, const int32
     }
 }
 
-// grid (ceil(4 nbins / 256), npairs): element e = plane * nbins + k of a pair
 __global__ void __launch_bounds__(256)
 csd_finish_kernel(const double* __restrict__ records, int32_t nparts, int32_t nbins, int32_t npairs, double scale, double* __restrict__ out) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= kCsdPlanes * nbins) return;
-    const int q = e / nbins, k = e - q * nbins;
-    const int64_t pidx = blockIdx.y;
-    const int64_t per = (int64_t)kCsdPlanes * nbins;
-    const double* r = records + pidx * nparts * per + e;
-    double sum = 0.0;
-    for (int p = 0; p < nparts; ++p) sum += r[(int64_t)p * per];        // parts ascending
-    out[((int64_t)q * npairs + pidx) * nbins + k] = sum * ((k == 0 || k == nbins - 1) ? scale : 2.0 * scale);
-}
-
-template <int L>
-hipError_t launch_parts(const double* x, int64_t series_stride, const int32_t* pairs, int32_t npairs, int32_t D, int32_t window,
-                        int32_t detrend, const PsdShape& s, double* records, hipStream_t st) {
-    static_assert(csd_lds_bytes(L) <= 160 * 1024, "the workgroup's LDS");
-    const int32_t nparts = (int32_t)s.nparts;                   // at most kPsdMaxParts: the glue has refused the rest
-    hipLaunchKernelGGL(csd_part_kernel<L>, dim3(nparts, npairs), dim3(CsdGeom<L>::T), 0, st, x, series_stride, pairs, D, window,
-                       detrend, s.segments, s.segs_per_part, nparts, records);
-    return hipGetLastError();
+    finish_planes<kCsdPlanes>(records, nparts, nbins, npairs, scale, out);
 }
 
 }  // namespace
 
 hipError_t launch_csd_parts(const double* x, int64_t series_stride, const int32_t* pairs, int32_t npairs, int32_t D, int32_t window,
                             int32_t detrend, const PsdShape& s, double* records, hipStream_t st) {
-    switch (s.log2L) {
-#define GINSIM_CSD_CASE(N) case N: return launch_parts<(1 << N)>(x, series_stride, pairs, npairs, D, window, detrend, s, records, st);
-        GINSIM_CSD_CASE(3) GINSIM_CSD_CASE(4) GINSIM_CSD_CASE(5) GINSIM_CSD_CASE(6) GINSIM_CSD_CASE(7) GINSIM_CSD_CASE(8)
-        GINSIM_CSD_CASE(9) GINSIM_CSD_CASE(10) GINSIM_CSD_CASE(11) GINSIM_CSD_CASE(12)
-#undef GINSIM_CSD_CASE
-    }
-    return hipErrorInvalidValue;
+    const int32_t nparts = (int32_t)s.nparts;                   // at most kPsdMaxParts: the glue has refused the rest
+    return for_segment_length<kCsdMaxLog2>(s.log2L, [&](auto length) {
+        constexpr int L = length;
+        static_assert(csd_lds_bytes(L) <= 160 * 1024, "the workgroup's LDS");
+        hipLaunchKernelGGL(csd_part_kernel<L>, dim3(nparts, npairs), dim3(Geom<L>::T), 0, st, x, series_stride, pairs, D, window,
+                           detrend, s.segments, s.segs_per_part, nparts, records);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_csd_finish(const double* records, int32_t npairs, const PsdShape& s, double scale, double* out, hipStream_t st) {

@@ -32,7 +32,7 @@ def table(stems=None):
             def g(k):
                 m = re.search(k + r': (\S+)', b)
                 return m.group(1) if m else ''
-            rows.append((f.split('.')[0], re.sub(r'\(.*$', '', name.replace('void ', '')), g('VGPRs'), g('AGPRs'), g('SGPRs'),
+            rows.append((f.split('.')[0], re.sub(r'\(.*$', '', name.replace('void ', '').replace('(anonymous namespace)::', '')), g('VGPRs'), g('AGPRs'), g('SGPRs'),
                          g(r'ScratchSize \[bytes/lane\]'), g(r'Occupancy \[waves/SIMD\]'), g(r'LDS Size \[bytes/block\]')))
     return rows
 
